@@ -2,8 +2,8 @@
 '''
 bench.py -- headline benchmark of the hot path (BASELINE.json):
   IPCS (rotational pressure-correction) time-steps/s on the Karman-vortex-street
-  channel, P2-P1 Taylor-Hood, ~10 M DoF, plus the pressure-Poisson SpMV GB/s
-  against the MI355X HBM roofline.
+  channel, P2-P1 Taylor-Hood, ~10 M DoF, plus (--full) the pressure-Poisson
+  SpMV GB/s against the MI355X HBM roofline.
 
 A "step" is one pass of the reference driver's loop body
 (tests/test_karman_vortex_street.py:219-286 of the reference): Rotational.step()
@@ -11,23 +11,32 @@ A "step" is one pass of the reference driver's loop body
 CFL step-size controller, on synthetic data (structured channel mesh pulled
 onto the cylinder: body-fitted, flow_amd/fem/mesh.py).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Everything is measured in mode 'parity' (flow_amd.navier_stokes: the
 reference's Newton path -- start from u0, exact Newton steps -- which
 reproduces the reference's iterate to < 1e-6, tests/test_full_size_parity.py).
 
-The headline `value` (round 6: the metric names a vortex street) is the mean
-over ONE SHEDDING PERIOD OF THE DEVELOPED STREET: 2400 untimed steps behind the
-settled plateau (setup), W + K steps (the window the flags ask for, reported as
-`value_developed`: it happens to sit in one of the bursts of the run), then
-`--developed-period` (400) steps timed as a whole between two barriers --
-`value`, `ms_per_step`, `headline_steps`.  The K-step window on the early
-plateau of the run (symmetric flow, one Newton iteration per step: rounds 1-5's
-`value`) is `value_plateau`.  At N = 1 the plateau window is also repeated in
-mode 'fast' (`config.fast_mode`) and with every start vector off
-(`config.zero_start`).  `--headline plateau`, or a run without the developed
-phase (`--developed 0`, sizes other than the headline's unless asked for), has
+A plain run (no --full) does what its headline needs and nothing else: setup
+(mesh, operators, the Stokes start, the settle phase below), W warm-up steps,
+K timed steps on the early plateau of the run (symmetric flow, one Newton
+iteration per step: rounds 1-5's `value`) -- `value`, `ms_per_step`,
+`value_plateau` -- and the result line; `config.headline` says what `value` is.
+`--dump-outputs DIR` writes what the last timed step handed its caller
+(velocity, pressure, clock) as DIR/<name>.npy.
+
+--full adds everything else, as every run did before it was split off: the
+developed vortex street, whose mean over ONE SHEDDING PERIOD is then `value`
+(round 6: the metric names a vortex street): 2400 untimed steps behind the
+settled plateau (setup), W + K steps (reported as `value_developed`: it happens
+to sit in one of the bursts of the run), then `--developed-period` (400) steps
+timed as a whole between two barriers -- `value`, `ms_per_step`,
+`headline_steps`; the plateau window stays `value_plateau`.  At N = 1 the
+plateau window is also repeated in mode 'fast' (`config.fast_mode`) and with
+every start vector off (`config.zero_start`); the pressure-Poisson SpMV is
+measured against the HBM roofline (`roofline`), and the CPU baselines run
+(`cpu_baseline`).  `--headline plateau`, or a run without the developed phase
+(`--developed 0`, sizes other than the headline's unless asked for), has
 `value` = the plateau window and says so in `config.headline`.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): strong scaling,
@@ -428,6 +437,36 @@ def oracle_step_timing(target_dofs=None, budget_s=25.0):
     return out, fit
 
 
+def write_outputs(path, arrays, limit=64 * 10**6, seed=0):
+    '''`arrays` (name -> 1-D float64 host array) as `path`/<name>.npy: float64
+    if all of it fits in `limit` bytes (the files' 128-byte headers included),
+    else float32; if that does not fit either, each array larger than 16
+    entries is cut to the same fixed seeded sample of its entries (sorted
+    indices, `seed`), in float32.'''
+    import numpy
+    if not os.path.isdir(path):
+        os.makedirs(path)
+    room = limit - 128 * len(arrays)
+    big = [k for k, a in arrays.items() if a.size > 16]
+    small_bytes = 8 * sum(arrays[k].size for k in arrays if k not in big)
+    n_big = sum(arrays[k].size for k in big)
+    if 8 * n_big + small_bytes <= room:
+        dtype, frac = numpy.float64, 1.0
+    else:
+        dtype = numpy.float32
+        frac = min(1.0, (room - small_bytes) / (4.0 * n_big))
+    for name, a in arrays.items():
+        if name in big:
+            if frac < 1.0:
+                k = int(frac * a.size)
+                idx = numpy.sort(numpy.random.RandomState(seed).choice(
+                    a.size, k, replace=False))
+                a = a[idx]
+            a = a.astype(dtype)
+        numpy.save(os.path.join(path, name + '.npy'),
+                   numpy.ascontiguousarray(a))
+
+
 def launch_ranks(n):
     '''`python -m torch.distributed.run --nnodes=1 --nproc-per-node n
     --master-addr 127.0.0.1 --master-port P bench.py <the same arguments>` as
@@ -487,9 +526,9 @@ def main():
                          'street -- that many untimed steps behind the settled '
                          'plateau (setup), then --warmup / --steps as for the '
                          'headline window; reported as config.developed and '
-                         'value_developed.  Default: 2400 at the headline size '
-                         '(t ~ 75: the wake sheds, a step takes two Newton '
-                         'iterations), 0 = off otherwise')
+                         'value_developed.  Default: with --full 2400 at the '
+                         'headline size (t ~ 75: the wake sheds, a step takes '
+                         'two Newton iterations), 0 = off otherwise')
     ap.add_argument('--developed-period', type=int, default=400, metavar='STEPS',
                     help='with --developed: that many further steps behind '
                          'the timed window, timed as a whole (about one '
@@ -558,8 +597,21 @@ def main():
                          'collective, first time step) may take on a rank '
                          'before that rank gives up with exit code 3 and a '
                          'line that names rank and stage')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-hbm-resident', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline window: the developed '
+                         'street (headline size), the fast-mode and zero-start '
+                         'windows, the SpMV roofline measurements, the CPU '
+                         'baselines; off: setup, --warmup, --steps, the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last step of '
+                         'the headline handed its caller (velocity, pressure, '
+                         'clock [t, dt]) as DIR/<name>.npy: float64, or '
+                         'float32 (and past that a fixed seeded sample) where '
+                         'float64 would exceed 64 MB')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='--full without the CPU baselines')
+    ap.add_argument('--no-hbm-resident', action='store_true',
+                    help='--full without the HBM-resident SpMV')
     ap.add_argument('--spmv-reps', type=int, default=100)
     args = ap.parse_args()
 
@@ -567,7 +619,8 @@ def main():
         args.initial = 'stokes' if args.velocity_degree == 2 else 'profile'
     if args.developed is None:
         args.developed = 2400 if (
-            args.nx == 2182 and args.ny is None and args.velocity_degree == 2
+            args.full and args.nx == 2182 and args.ny is None
+            and args.velocity_degree == 2
             and not args.no_settle and not args.spin_up
             and args.mode == 'parity' and args.headline == 'street') else 0
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -803,6 +856,20 @@ def main():
                 if infos[0].get('collectives_in_window') else None),
             }
 
+    def outputs():
+        '''What the caller of the timed path holds after its last step: the
+        velocity and pressure it handed back (whole fields, host copies, the
+        library's dof order) and the clock [t, dt of the next step].'''
+        got = {}
+        for name, f in (('velocity', prob.u0), ('pressure', prob.p0)):
+            data = f.data
+            if parallel.active():
+                V = f.function_space()
+                data = parallel.gather_field(_hip.clone(data), V.layout, V.dim)
+            got[name] = device.to_host(data).numpy().astype(numpy.float64)
+        got['clock'] = numpy.array([prob.t, prob.dt], dtype=numpy.float64)
+        return got
+
     # everything that is built once and cached (operators, hierarchy, ILU
     # plan, ...), then the start state: all of it setup, outside the windows
     # (development overrides first: some of them shape those structures)
@@ -823,6 +890,9 @@ def main():
     enter('plateau window')
     infos, elapsed = window(args.mode)
     head = summary(infos, elapsed)
+    # (the headline's last step, unless the developed street's period below
+    # becomes the headline; outside the clock)
+    dumped = outputs() if args.dump_outputs else None
     if settled:
         # the contract of the settle phase: plateau steps only
         dts = head['dt']
@@ -838,49 +908,95 @@ def main():
     Kbc = [v for k, v in lay._dev.items()
            if isinstance(k, tuple) and k[0] == 'K_bc'][0][0]
     n, nnz = lay.N, lay.nnz
-    bytes_alg = spmv_bytes(n, nnz)
-    # (a) as the CG runs it (on the strips: this rank's rows of the matrix),
-    # (b) back-to-back replay of the whole-matrix launch
-    t_solver, launches, t_raw, t_over = measure_spmv_in_solver(
-        prob, n, 3, args.tol)
-    t_replay = measure_spmv_replay(Kbc.apply, n, reps=args.spmv_reps)
-    bytes_solver = bytes_alg
-    if parallel.active():
-        pv = parallel.view(lay)
-        rp = lay.pattern('rowptr')
-        bytes_solver = spmv_bytes(pv.r1 - pv.r0,
-                                  int(rp[pv.r1]) - int(rp[pv.r0]))
-    if not launches:
-        t_solver, bytes_solver = t_replay, bytes_alg
-    achieved = bytes_solver / t_solver / 1e9
-    traffic = None
-    traffic_source = None
-    # (PMC summary of the same in-solver dispatches, written by
-    # profiles/run_profiles.sh from separate --pmc passes of this command: a
-    # CITATION of the newest committed summary, not something this run measures)
-    import glob
-    tfiles = sorted(glob.glob(os.path.join(
-        ROOT, 'profiles', 'spmv_traffic_r[0-9][0-9]_in_solver.json')))
-    # the committed PMC summary belongs to the headline workload only
-    if tfiles and args.nx == 2182 and args.ny is None:
-        try:
-            traffic = json.load(open(tfiles[-1])).get('hbm_bytes_per_launch')
-            traffic_source = (
-                'profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of '
-                'this bench command (profiles/run_profiles.sh), median over the '
-                'in-solver dispatches; committed with the round it names, not '
-                'measured by this run' % os.path.basename(tfiles[-1]))
-        except Exception:                              # noqa: BLE001
-            traffic = None
-    copy_ceiling, read_ceiling = measure_stream_ceilings() if world == 1 \
-        else (None, None)
-    resident = None
-    if world == 1 and not args.no_hbm_resident:
-        resident = measure_spmv_hbm_resident()
+    # (--full: the SpMV against the HBM roofline, timed in runs of its own)
+    roofline = None
+    if args.full:
+        bytes_alg = spmv_bytes(n, nnz)
+        # (a) as the CG runs it (on the strips: this rank's rows of the
+        # matrix), (b) back-to-back replay of the whole-matrix launch
+        t_solver, launches, t_raw, t_over = measure_spmv_in_solver(
+            prob, n, 3, args.tol)
+        t_replay = measure_spmv_replay(Kbc.apply, n, reps=args.spmv_reps)
+        bytes_solver = bytes_alg
+        if parallel.active():
+            pv = parallel.view(lay)
+            rp = lay.pattern('rowptr')
+            bytes_solver = spmv_bytes(pv.r1 - pv.r0,
+                                      int(rp[pv.r1]) - int(rp[pv.r0]))
+        if not launches:
+            t_solver, bytes_solver = t_replay, bytes_alg
+        achieved = bytes_solver / t_solver / 1e9
+        traffic = None
+        traffic_source = None
+        # (PMC summary of the same in-solver dispatches, written by
+        # profiles/run_profiles.sh from separate --pmc passes of this command:
+        # a CITATION of the newest committed summary, not something this run
+        # measures)
+        import glob
+        tfiles = sorted(glob.glob(os.path.join(
+            ROOT, 'profiles', 'spmv_traffic_r[0-9][0-9]_in_solver.json')))
+        # the committed PMC summary belongs to the headline workload only
+        if tfiles and args.nx == 2182 and args.ny is None:
+            try:
+                traffic = json.load(open(tfiles[-1])).get(
+                    'hbm_bytes_per_launch')
+                traffic_source = (
+                    'profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE '
+                    'passes of this bench command (profiles/run_profiles.sh), '
+                    'median over the in-solver dispatches; committed with the '
+                    'round it names, not measured by this run'
+                    % os.path.basename(tfiles[-1]))
+            except Exception:                              # noqa: BLE001
+                traffic = None
+        copy_ceiling, read_ceiling = measure_stream_ceilings() if world == 1 \
+            else (None, None)
+        resident = None
+        if world == 1 and not args.no_hbm_resident:
+            resident = measure_spmv_hbm_resident()
+        roofline = {
+            'kernel': 'spmv_stream_kernel<DOT> (pressure-Poisson CSR SpMV '
+                      'with the fused z.Az partials, fp64), as the pressure '
+                      'CG launches it inside the time steps'
+                      if launches else
+                      'spmv_stream_kernel (pressure-Poisson CSR SpMV, fp64), '
+                      'back-to-back replay',
+            'bound': 'hbm',
+            'achieved': achieved,
+            'peak': HBM_PEAK_GBPS,
+            'unit': 'GB/s',
+            'frac': achieved / HBM_PEAK_GBPS,
+            'traffic': traffic if not parallel.active() else None,
+            'traffic_source': traffic_source if not parallel.active() else None,
+            # the box's own ceilings (SURVEY 8d), timed in this run: a plain
+            # streaming copy of 1 GiB in + 1 GiB out, and a kernel that only
+            # reads 1 GiB (the SpMV is read-dominated: 8 % of its bytes are
+            # stores)
+            'copy_ceiling_GBps': copy_ceiling,
+            'read_ceiling_GBps': read_ceiling,
+            'frac_of_copy': achieved / copy_ceiling if copy_ceiling else None,
+            'frac_of_read': achieved / read_ceiling if read_ceiling else None,
+            'bytes_per_launch': bytes_solver,
+            'us_per_launch': t_solver * 1e6,
+            'launches_timed': launches,
+            'timing': 'HIP events around every in-solver launch on the launch '
+                      'stream (%.2f us per pair; the same pair around a null '
+                      'kernel reads %.2f us of dispatch latency, not '
+                      'subtracted)' % (t_raw * 1e6, t_over * 1e6),
+            'warm_replay': {
+                'us_per_launch': t_replay * 1e6,
+                'GBps': bytes_alg / t_replay / 1e9,
+                'frac': bytes_alg / t_replay / 1e9 / HBM_PEAK_GBPS,
+                'note': 'the same matrix, %d back-to-back launches: the '
+                        '114 MB working set then stays in the 256 MB '
+                        'Infinity Cache' % args.spmv_reps,
+                },
+            'hbm_resident': resident,
+            }
 
     fast = None
     zero_start = None
-    if world == 1 and args.mode == 'parity' and not args.no_fast_leg:
+    if args.full and world == 1 and args.mode == 'parity' \
+            and not args.no_fast_leg:
         f_infos, f_elapsed = window('fast')
         fast = summary(f_infos, f_elapsed)
         navsto.set_mode('parity')
@@ -976,6 +1092,8 @@ def main():
                         'without a restart: one shedding period'
                         % args.developed_period,
                 }
+            if args.dump_outputs and args.headline == 'street':
+                dumped = outputs()
         settled['state'] = plateau_state
     except StopIteration:
         pass
@@ -999,6 +1117,8 @@ def main():
     street = developed is not None and 'period' in developed \
         and args.headline == 'street'
     headline = developed['period'] if street else head
+    if dumped is not None:
+        write_outputs(args.dump_outputs, dumped)
     out = {
         'metric': 'ipcs_time_steps_per_sec',
         'value': headline['steps_per_s'],
@@ -1047,8 +1167,8 @@ def main():
                     '' if args.headline == 'plateau' else
                     ': the developed phase FAILED on the strips (%s)'
                     % developed_error if developed_error else
-                    ': the developed phase did not run (--developed 0 / not the '
-                    'headline size)')),
+                    ': the developed phase did not run (a run without --full, '
+                    '--developed 0 / not the headline size)')),
             'mode': args.mode,
             'mode_note': "headline = mode '%s'%s" % (
                 args.mode,
@@ -1103,45 +1223,6 @@ def main():
                 'ilu_sweep_vector': navsto.solver_parameters['newton'].get(
                     'ilu_vector', 'fp64')},
             },
-        'roofline': {
-            'kernel': 'spmv_stream_kernel<DOT> (pressure-Poisson CSR SpMV '
-                      'with the fused z.Az partials, fp64), as the pressure '
-                      'CG launches it inside the time steps'
-                      if launches else
-                      'spmv_stream_kernel (pressure-Poisson CSR SpMV, fp64), '
-                      'back-to-back replay',
-            'bound': 'hbm',
-            'achieved': achieved,
-            'peak': HBM_PEAK_GBPS,
-            'unit': 'GB/s',
-            'frac': achieved / HBM_PEAK_GBPS,
-            'traffic': traffic if not parallel.active() else None,
-            'traffic_source': traffic_source if not parallel.active() else None,
-            # the box's own ceilings (SURVEY 8d), timed in this run: a plain
-            # streaming copy of 1 GiB in + 1 GiB out, and a kernel that only
-            # reads 1 GiB (the SpMV is read-dominated: 8 % of its bytes are
-            # stores)
-            'copy_ceiling_GBps': copy_ceiling,
-            'read_ceiling_GBps': read_ceiling,
-            'frac_of_copy': achieved / copy_ceiling if copy_ceiling else None,
-            'frac_of_read': achieved / read_ceiling if read_ceiling else None,
-            'bytes_per_launch': bytes_solver,
-            'us_per_launch': t_solver * 1e6,
-            'launches_timed': launches,
-            'timing': 'HIP events around every in-solver launch on the launch '
-                      'stream (%.2f us per pair; the same pair around a null '
-                      'kernel reads %.2f us of dispatch latency, not '
-                      'subtracted)' % (t_raw * 1e6, t_over * 1e6),
-            'warm_replay': {
-                'us_per_launch': t_replay * 1e6,
-                'GBps': bytes_alg / t_replay / 1e9,
-                'frac': bytes_alg / t_replay / 1e9 / HBM_PEAK_GBPS,
-                'note': 'the same matrix, %d back-to-back launches: the '
-                        '114 MB working set then stays in the 256 MB '
-                        'Infinity Cache' % args.spmv_reps,
-                },
-            'hbm_resident': resident,
-            },
         }
     out['config'].update({k: v for k, v in head.items()
                           if k not in ('steps_per_s', 'ms_per_step')})
@@ -1166,7 +1247,9 @@ def main():
         "starts from u0; 40-step trajectories agree with the zero-start run to "
         "4e-10 (u) / 1.3e-9 (p), tools/linear_start_check.py; the zero-start "
         "window is reported in config.zero_start")
-    if world == 1 and not args.no_cpu_baseline:
+    if roofline is not None:
+        out['roofline'] = roofline
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the right-hand side of a real pressure solve is not kept; a fixed
         # synthetic one of the same smoothness class stands in on both sides
         dofs, _vals = collect(prob.p_bcs, n)
@@ -1193,7 +1276,7 @@ def main():
                          'iterations_per_s': sol.iterations / wall}
             if name == 'mgcg':
                 x_gpu = device.to_host(xd).numpy()
-        gpu['spmv_GBps_in_solver'] = achieved
+        gpu['spmv_GBps_in_solver'] = roofline['achieved']
         out['cpu_baseline'], x_cpu = cpu_baseline(Kbc, isbc, b, args.tol, gpu,
                                                   prob.num_dofs())
         out['cpu_baseline']['solution_rel_l2_gpu_vs_cpu'] = float(

@@ -7,6 +7,10 @@ one JSON line and the exit code (bench.py: launch_ranks).
 CPU: the launcher starts the ranks and hands their failure back (there is no
 GPU here: every rank stops at "flow_amd needs an AMD GPU", no JSON line).
 GPU (-m gpu): two gloo ranks sharing the one GPU produce the line.
+
+A plain run times its --steps and nothing else; --dump-outputs keeps what its
+last step computed (the writer is checked on the CPU); --full keeps the other
+measurements.
 '''
 import json
 import os
@@ -107,3 +111,78 @@ def test_a_stage_that_hangs_ends_the_rank_with_its_name(hip):
     err = out.stderr.decode('utf-8', 'replace')
     assert out.returncode == 3, (out.returncode, err[-2000:])
     assert "FAILED: stage 'process group (gloo)'" in err and 'rank 0/2' in err
+
+
+def test_dumped_outputs_stay_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: float64 where everything fits in the limit,
+    float32 past it, and past that a fixed seeded sample -- the same one in
+    every run -- of each large array; small arrays stay float64."""
+    import numpy
+    sys.path.insert(0, ROOT)
+    import bench
+    a = numpy.linspace(0.0, 1.0, 1000)
+    arrays = {'field': a, 'clock': numpy.array([1.5, 0.25])}
+    for limit, dtype, size in ((8272, numpy.float64, 1000),
+                               (4272, numpy.float32, 1000),
+                               (2272, numpy.float32, 500)):
+        out = tmp_path / str(limit)
+        bench.write_outputs(str(out), arrays, limit=limit)
+        f = numpy.load(str(out / 'field.npy'))
+        c = numpy.load(str(out / 'clock.npy'))
+        assert f.dtype == dtype and f.size == size
+        assert c.dtype == numpy.float64 and list(c) == [1.5, 0.25]
+        assert sum(p.stat().st_size for p in out.iterdir()) <= limit
+        assert numpy.all(numpy.isin(f, a.astype(dtype)))
+    again = tmp_path / 'again'
+    bench.write_outputs(str(again), arrays, limit=2272)
+    assert numpy.array_equal(numpy.load(str(again / 'field.npy')),
+                             numpy.load(str(tmp_path / '2272' / 'field.npy')))
+
+
+def _bench_line(args, timeout=900):
+    out = subprocess.run(
+        [sys.executable, os.path.join(ROOT, 'bench.py')] + args,
+        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+    assert out.returncode == 0, out.stderr.decode('utf-8', 'replace')[-3000:]
+    lines = [l for l in out.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_one(hip, tmp_path):
+    """A run without --full: the K timed steps are the headline (value,
+    ms_per_step), none of the --full measurements run, and --dump-outputs
+    keeps the velocity, pressure and clock of the last timed step."""
+    import numpy
+    rec = _bench_line(['--gpus', '1', '--nx', '192', '--steps', '3',
+                       '--warmup', '1', '--dump-outputs', str(tmp_path)])
+    assert rec['steps'] == 3 and len(rec['config']['dt']) == 3
+    assert rec['ms_per_step'] == rec['ms_per_step_plateau'] > 0.0
+    assert abs(rec['value'] * rec['ms_per_step'] - 1e3) < 1e-6 * rec['value']
+    assert rec['metric'] == 'ipcs_time_steps_per_sec' and rec['dtype'] == 'f64'
+    for key in ('roofline', 'cpu_baseline', 'value_developed'):
+        assert key not in rec, key
+    for key in ('fast_mode', 'zero_start', 'developed'):
+        assert key not in rec['config'], key
+    u = numpy.load(str(tmp_path / 'velocity.npy'))
+    p = numpy.load(str(tmp_path / 'pressure.npy'))
+    clock = numpy.load(str(tmp_path / 'clock.npy'))
+    assert u.dtype == p.dtype == numpy.float64
+    assert u.size + p.size == rec['config']['dofs']
+    assert numpy.isfinite(u).all() and numpy.isfinite(p).all()
+    assert numpy.abs(u).max() > 0.0
+    assert clock.shape == (2,) and clock[0] > 0.0 and clock[1] > 0.0
+
+
+@pytest.mark.gpu
+def test_full_run_keeps_the_other_measurements(hip):
+    """--full: the roofline figures and the fast-mode / zero-start windows
+    are in the line, as before the plain run was split off."""
+    rec = _bench_line(['--gpus', '1', '--nx', '192', '--steps', '3',
+                       '--warmup', '1', '--full', '--no-cpu-baseline',
+                       '--no-hbm-resident', '--spmv-reps', '5'])
+    assert rec['roofline']['achieved'] > 0.0
+    assert rec['roofline']['launches_timed'] > 0
+    assert rec['config']['fast_mode']['steps_per_s'] > 0.0
+    assert rec['config']['zero_start']['steps_per_s'] > 0.0

@@ -257,7 +257,17 @@ def _free_port():
     return port
 
 
+def _on_the_host():
+    '''The workers restate the kernels' side in numpy on host buffers: the
+    package's device is pinned to the CPU in them, also where a GPU is
+    visible (flow_amd.device.get() would pick it).'''
+    import torch
+    from flow_amd import device
+    device._DEVICE = torch.device('cpu')
+
+
 def _worker(rank, world, port, degree, out):
+    _on_the_host()
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)
@@ -381,6 +391,7 @@ class NumpyShardMass(object):
 
 
 def _mass_worker(rank, world, port, out):
+    _on_the_host()
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)
@@ -584,6 +595,7 @@ def _reference_two_level_cg(A, T, b, rtol, maxit):
 
 
 def _mgcg_worker(rank, world, port, out):
+    _on_the_host()
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)

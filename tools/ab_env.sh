@@ -5,8 +5,8 @@ set -e
 out=gpurun_out/ab
 mkdir -p $out
 run() {
-  timeout -k 10 300 python3 bench.py --nx 772 --mu 0.00565 --no-cpu-baseline > $out/proxy_$1.json 2> $out/proxy_$1.err
-  timeout -k 10 400 python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 > $out/head_$1.json 2> $out/head_$1.err
+  timeout -k 10 300 python3 bench.py --full --nx 772 --mu 0.00565 --no-cpu-baseline > $out/proxy_$1.json 2> $out/proxy_$1.err
+  timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $out/head_$1.json 2> $out/head_$1.err
 }
 run a
 export "$1"

@@ -7,7 +7,7 @@ rm -rf $out; mkdir -p $out
 for rep in 1 2; do
   for v in a b; do
     if [ $v = b ]; then export "$1"; fi
-    timeout -k 10 500 python3 bench.py --no-cpu-baseline > $out/bench_${v}_$rep.json 2> $out/bench_${v}_$rep.err
+    timeout -k 10 500 python3 bench.py --full --no-cpu-baseline > $out/bench_${v}_$rep.json 2> $out/bench_${v}_$rep.err
     if [ $v = b ]; then unset "${1%%=*}"; fi
   done
 done

@@ -4,7 +4,7 @@ set -e
 out=gpurun_out/ab
 mkdir -p $out
 run() {
-  timeout -k 10 500 python3 bench.py --no-cpu-baseline --no-hbm-resident --no-fast-leg --steps 60 --warmup 5 > $out/long_$1.json 2> $out/long_$1.err
+  timeout -k 10 500 python3 bench.py --full --no-cpu-baseline --no-hbm-resident --no-fast-leg --steps 60 --warmup 5 > $out/long_$1.json 2> $out/long_$1.err
 }
 run a
 export "$1"

@@ -7,8 +7,8 @@ rm -rf $out; mkdir -p $out
 for rep in 1 2; do
   for v in ${ORDER:-a b}; do
     if [ $v = b ]; then export "$1"; fi
-    timeout -k 10 300 python3 bench.py --nx 772 --mu 0.00565 --no-cpu-baseline --developed 0 --steps 100 --warmup 40 > $out/proxy_${v}_$rep.json 2> $out/proxy_${v}_$rep.err
-    timeout -k 10 400 python3 bench.py --no-cpu-baseline --developed 0 --steps 40 --warmup 20 > $out/head_${v}_$rep.json 2> $out/head_${v}_$rep.err
+    timeout -k 10 300 python3 bench.py --full --nx 772 --mu 0.00565 --no-cpu-baseline --developed 0 --steps 100 --warmup 40 > $out/proxy_${v}_$rep.json 2> $out/proxy_${v}_$rep.err
+    timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --developed 0 --steps 40 --warmup 20 > $out/head_${v}_$rep.json 2> $out/head_${v}_$rep.err
     if [ $v = b ]; then unset "${1%%=*}"; fi
   done
 done

@@ -6,7 +6,7 @@ mkdir -p $out
 for rep in 1 2; do
 for sites in ${SITES:-0 1 2 4}; do
   if [ $sites = 0 ]; then export FLOW_AMD_GRAPHS=0; else export FLOW_AMD_GRAPHS=1 FLOW_AMD_GRAPH_SITES=$sites; fi
-  timeout -k 10 300 python3 bench.py --nx ${NX:-772} --mu ${MU:-0.00565} --no-cpu-baseline --developed 0 > $out/sites_${sites}_$rep.json 2> $out/sites_${sites}_$rep.err
+  timeout -k 10 300 python3 bench.py --full --nx ${NX:-772} --mu ${MU:-0.00565} --no-cpu-baseline --developed 0 > $out/sites_${sites}_$rep.json 2> $out/sites_${sites}_$rep.err
 done
 done
 python3 - <<'PY'

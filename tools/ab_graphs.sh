@@ -8,11 +8,11 @@ out=gpurun_out/ab_graphs
 mkdir -p $out
 for rep in 1 2; do
   for g in 0 1; do
-    FLOW_AMD_GRAPHS=$g timeout -k 10 300 python3 bench.py --nx 772 --mu 0.00565 --no-cpu-baseline --developed 0 > $out/proxy_${g}_$rep.json 2> $out/proxy_${g}_$rep.err
+    FLOW_AMD_GRAPHS=$g timeout -k 10 300 python3 bench.py --full --nx 772 --mu 0.00565 --no-cpu-baseline --developed 0 > $out/proxy_${g}_$rep.json 2> $out/proxy_${g}_$rep.err
   done
 done
 for g in 0 1; do
-  FLOW_AMD_GRAPHS=$g timeout -k 10 400 python3 bench.py --no-cpu-baseline --developed 0 --steps 20 --warmup 5 > $out/head_$g.json 2> $out/head_$g.err
+  FLOW_AMD_GRAPHS=$g timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --developed 0 --steps 20 --warmup 5 > $out/head_$g.json 2> $out/head_$g.err
 done
 python3 - <<'PY'
 import json, glob

@@ -6,7 +6,7 @@ out=gpurun_out/ab_graphs_long
 mkdir -p $out
 for rep in 1 2; do
   for g in 0 1; do
-    FLOW_AMD_GRAPHS=$g timeout -k 10 300 python3 bench.py --nx ${NX:-772} --mu ${MU:-0.00565} --no-cpu-baseline --developed 0 --steps ${STEPS:-150} --warmup 60 > $out/nx${NX:-772}_${g}_$rep.json 2> $out/nx${NX:-772}_${g}_$rep.err
+    FLOW_AMD_GRAPHS=$g timeout -k 10 300 python3 bench.py --full --nx ${NX:-772} --mu ${MU:-0.00565} --no-cpu-baseline --developed 0 --steps ${STEPS:-150} --warmup 60 > $out/nx${NX:-772}_${g}_$rep.json 2> $out/nx${NX:-772}_${g}_$rep.err
   done
 done
 python3 - <<'PY'

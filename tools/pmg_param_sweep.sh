@@ -9,7 +9,7 @@ mkdir -p gpurun_out/pmg_sweep
 for spec in "$@"; do
   args=""
   for kv in ${spec//,/ }; do args="$args --newton pmg.$kv"; done
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-hbm-resident --no-fast-leg --steps 40 --warmup 5 \
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-hbm-resident --no-fast-leg --steps 40 --warmup 5 \
     $args > gpurun_out/pmg_sweep/$spec.json 2> gpurun_out/pmg_sweep/$spec.err
   python3 - "$spec" <<'PY'
 import json, sys
