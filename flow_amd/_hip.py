@@ -204,6 +204,37 @@ class CoefS(ctypes.Structure):
         ]
 
 
+FORM_MAX_PROGRAM = 64
+FORM_REGISTERS = 8
+FORM_MAX_CONSTANTS = 32
+FORM_MAX_FIELDS = 6
+FORM_MAX_EXPRESSIONS = 4
+FORM_MAX_POINTS = 256
+
+
+class FormS(ctypes.Structure):
+    '''flow_form (include/flow_hip.h): a compiled integrand'''
+    _fields_ = [
+        ('nprog', ctypes.c_int),
+        ('prog', ctypes.c_int * (4 * FORM_MAX_PROGRAM)),
+        ('nconst', ctypes.c_int),
+        ('consts', ctypes.c_double * FORM_MAX_CONSTANTS),
+        ('nfield', ctypes.c_int),
+        ('field', ctypes.c_void_p * FORM_MAX_FIELDS),
+        ('field_deg', ctypes.c_int * FORM_MAX_FIELDS),
+        ('cell_dofs', ctypes.c_void_p * 2),
+        ('nexpr', ctypes.c_int),
+        ('expr', ctypes.c_void_p * FORM_MAX_EXPRESSIONS),
+        ('expr_nl', ctypes.c_int * FORM_MAX_EXPRESSIONS),
+        ('expr_table', ctypes.c_int * FORM_MAX_EXPRESSIONS),
+        ('nq', ctypes.c_int),
+        ('rule', ctypes.c_void_p),
+        ('tables', ctypes.c_void_p),
+        ('ntables', ctypes.c_int),
+        ('nout', ctypes.c_int),
+        ]
+
+
 class NsParams(ctypes.Structure):
     _fields_ = [
         ('dt', ctypes.c_double), ('rho', ctypes.c_double),
@@ -387,6 +418,8 @@ SYMBOLS = {
                            _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_assemble_heat_supg_source': [_P(MeshS), _P(SpaceS), _P(SpaceS), _VP,
                                        _D, _D, _P(CoefS), _VP, _VP, _VP, _VP],
+    'flow_form_functional': [_P(MeshS), _P(FormS), _VP, _VP, _P(_D), _VP],
+    'flow_form_load_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
     }
 
 _LIB = None

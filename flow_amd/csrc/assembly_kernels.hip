@@ -70,13 +70,12 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(
   }
 }
 
-// rows [r0, r1) of the nout (r1 = 0: all); out_stride = 0: nout
-static int gather(int nout, int nplanes, const int* ptr, const int* src,
-                  const double* scratch, size_t plane_stride, double* out,
-                  hipStream_t st, size_t out_stride = 0, int r0 = 0, int r1 = 0,
-                  const double* stop = nullptr,
-                  const unsigned char* idrow = nullptr, const double* v = nullptr,
-                  size_t v_stride = 0) {
+// rows [r0, r1) of the nout (r1 = 0: all); out_stride = 0: nout (declared in
+// common.h: form_kernels.hip gathers its load vectors here too)
+int gather(int nout, int nplanes, const int* ptr, const int* src,
+           const double* scratch, size_t plane_stride, double* out,
+           hipStream_t st, size_t out_stride, int r0, int r1, const double* stop,
+           const unsigned char* idrow, const double* v, size_t v_stride) {
   const size_t os = out_stride ? out_stride : static_cast<size_t>(nout);
   const size_t ids = static_cast<size_t>(nout);     // mask: component stride n
   if (r1 > 0) {

@@ -78,6 +78,14 @@ int exchange(const flow_comm* c, int count);
 int exchange_halo(const flow_comm* C, const flow_rows* R, int ncomp, int sum_count,
                   int hoff, hipStream_t st);
 
+// assembly_kernels.hip: phase 2 of the two-phase assembly -- out[p][k] = the
+// contributions scratch[p][src[t]], t in [ptr[k], ptr[k+1]), summed in that
+// order (rows [r0, r1) only if r1 > 0; out_stride = 0: nout)
+int gather(int nout, int nplanes, const int* ptr, const int* src,
+           const double* scratch, size_t plane_stride, double* out,
+           hipStream_t st, size_t out_stride = 0, int r0 = 0, int r1 = 0,
+           const double* stop = nullptr, const unsigned char* idrow = nullptr,
+           const double* v = nullptr, size_t v_stride = 0);
 // assembly_kernels.hip: the matrix-free operator (flow_operator kind 3)
 int momentum_jvp_check(const flow_momentum_jvp* J);
 // prm_dev: the step-size dependent factors in device memory (three doubles

@@ -1,0 +1,423 @@
+// Integrals of UFL-style expressions of fields (flow_amd/fem/forms.py): one
+// kernel family that runs a host-compiled register program (include/
+// flow_hip.h, flow_form) at every quadrature point of every cell.
+//
+//   functional   assemble(f*dx): per-cell integrals to scratch[cell], then
+//                <= kRedBlocks block partials -> one finishing block
+//                (sum_partials_host), fixed order, no fp atomics: two calls
+//                give the same bits;
+//   load vector  b_i = int f phi_i (project): per-cell values to
+//                scratch[(o*nloc + i)*nc + c], then the gather of
+//                assembly_kernels.hip, as flow_assemble_source does.
+//
+// One thread per cell, a loop over the rule's points, the program inside it.
+// The program and the constants are kernel arguments: every lane reads the
+// same instruction (scalar loads, wave-uniform dispatch, no divergence).  The
+// eight registers and the field slots are NAMED values behind switches and
+// unrolled compile-time loops -- a register file indexed at run time would
+// live in scratch memory.  Scratch stays at 0 bytes per lane.
+#include "fem_device.h"
+
+namespace flow {
+
+struct FormRegs {
+  double r0, r1, r2, r3, r4, r5, r6, r7;
+};
+
+__device__ __forceinline__ double reg_get(const FormRegs& R, int i) {
+  switch (i) {
+    case 0: return R.r0;
+    case 1: return R.r1;
+    case 2: return R.r2;
+    case 3: return R.r3;
+    case 4: return R.r4;
+    case 5: return R.r5;
+    case 6: return R.r6;
+    default: return R.r7;
+  }
+}
+
+__device__ __forceinline__ void reg_set(FormRegs& R, int i, double v) {
+  switch (i) {
+    case 0: R.r0 = v; break;
+    case 1: R.r1 = v; break;
+    case 2: R.r2 = v; break;
+    case 3: R.r3 = v; break;
+    case 4: R.r4 = v; break;
+    case 5: R.r5 = v; break;
+    case 6: R.r6 = v; break;
+    default: R.r7 = v; break;
+  }
+}
+
+// sin (cos = false) or cos of x.  The library's sin / cos carry a reduction
+// for arguments of any size whose tables and constants cost the kernel ~30
+// scalar registers and made it spill them; the arguments of a form are
+// coordinates, times and field values.  Here: x = n pi/2 + r, |r| <= pi/4,
+// with a two-part pi/2 through FMAs (accurate while n pi/2 stays well inside
+// the double range of exact multiples, |x| < ~1e9), then the fdlibm minimax
+// polynomials of sin and cos on [-pi/4, pi/4] (error < 1 ulp there).
+__device__ __forceinline__ double form_sincos(double x, bool want_cos) {
+  const double n = rint(x * 0.63661977236758134308);          // 2/pi
+  double r = fma(-n, 1.5707963267948965580, x);               // pi/2, high part
+  r = fma(-n, 6.1232339957367658e-17, r);                     // pi/2 - high part
+  const double z = r * r;
+  const double sp = -1.66666666666666324348e-01 +
+      z * (8.33333333332248946124e-03 +
+      z * (-1.98412698298579493134e-04 +
+      z * (2.75573137070700676789e-06 +
+      z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10))));
+  const double cp = 4.16666666666666019037e-02 +
+      z * (-1.38888888888741095749e-03 +
+      z * (2.48015872894767294178e-05 +
+      z * (-2.75573143513906633035e-07 +
+      z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11))));
+  const double s = r + r * z * sp;
+  const double c = 1.0 - 0.5 * z + z * z * cp;
+  // quadrant of x (+1 for cos: cos x = sin(x + pi/2))
+  const double m = n + (want_cos ? 1.0 : 0.0);
+  const int quad = static_cast<int>(m - 4.0 * floor(m * 0.25));
+  const double v = (quad & 1) ? c : s;
+  return (quad & 2) ? -v : v;
+}
+
+// value (d = 0) or d/dx, d/dy (d = 1, 2) of field slot s at barycentric L
+template <int NF>
+__device__ __forceinline__ double field_at(const flow_form& F,
+                                           const double (&U)[NF][6], int s,
+                                           int d, const double L[3],
+                                           const Geom& g) {
+  double v = 0.0;
+#pragma unroll
+  for (int k = 0; k < NF; ++k) {
+    if (k != s) continue;
+    const double* u = U[k];
+    if (F.field_deg[k] == 1) {
+      if (d == 0) {
+        v = u[0] * L[0] + u[1] * L[1] + u[2] * L[2];
+      } else {
+        const int e = d - 1;
+        v = u[0] * (e == 0 ? g.gl[0][0] : g.gl[0][1]) +
+            u[1] * (e == 0 ? g.gl[1][0] : g.gl[1][1]) +
+            u[2] * (e == 0 ? g.gl[2][0] : g.gl[2][1]);
+      }
+    } else {
+      if (d == 0) {
+        v = eval_at<2>(u, L);
+      } else {
+        double gur[3];
+        ref_gradient<2>(u, L, gur);
+        const int e = d - 1;
+        v = gur[0] * (e == 0 ? g.gl[0][0] : g.gl[0][1]) +
+            gur[1] * (e == 0 ? g.gl[1][0] : g.gl[1][1]) +
+            gur[2] * (e == 0 ? g.gl[2][0] : g.gl[2][1]);
+      }
+    }
+  }
+  return v;
+}
+
+// Runs the program at every point of the rule on cell c.  TD = 0: returns
+// sum_q w_q |det J| out_0(x_q); TD = 1, 2: acc[o][i] += w_q |det J| out_o phi_i.
+template <int NF, int TD>
+__device__ __forceinline__ double form_cell(const flow_form& F, int nc,
+                                            const double* __restrict__ xy, int c,
+                                            double (&acc)[2][6]) {
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  if constexpr (NF > 0) {
+    bool p1 = false, p2 = false;
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+      p1 = p1 || F.field_deg[k] == 1;
+      p2 = p2 || F.field_deg[k] == 2;
+    }
+    int d1[3] = {0, 0, 0}, d2[6] = {0, 0, 0, 0, 0, 0};
+    if (p1) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) d1[i] = F.cell_dofs[0][i * nc + c];
+    }
+    if (p2) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) d2[i] = F.cell_dofs[1][i * nc + c];
+    }
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+      const double* f = F.field[k];
+      if (F.field_deg[k] == 1) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) U[k][i] = f[d1[i]];
+#pragma unroll
+        for (int i = 3; i < 6; ++i) U[k][i] = 0.0;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) U[k][i] = f[d2[i]];
+      }
+    }
+  }
+  double total = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
+    const double w = F.rule[3 * q + 2] * g.adet;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormRegs R = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double out0 = 0.0, out1 = 0.0;
+    for (int pc = 0; pc < F.nprog; ++pc) {
+      const int op = F.prog[4 * pc], dst = F.prog[4 * pc + 1];
+      const int a = F.prog[4 * pc + 2], b = F.prog[4 * pc + 3];
+      double v;
+      switch (op) {
+        case FLOW_FORM_OP_CONST: v = F.consts[a]; break;
+        case FLOW_FORM_OP_COORD: {
+          const double* P = a == 0 ? X : Y;
+          v = P[0] * L[0] + P[1] * L[1] + P[2] * L[2];
+          break;
+        }
+        case FLOW_FORM_OP_FIELD:
+          if constexpr (NF > 0) v = field_at<NF>(F, U, a, b, L, g);
+          else v = 0.0;
+          break;
+        case FLOW_FORM_OP_EXPR: {
+          const int nl = F.expr_nl[a];
+          const double* tab = F.tables + F.expr_table[a] + q * nl;
+          const double* e = F.expr[a];
+          double s = 0.0;
+          for (int l = 0; l < nl; ++l) s += e[static_cast<size_t>(l) * nc + c] * tab[l];
+          v = s;
+          break;
+        }
+        case FLOW_FORM_OP_MOV: v = reg_get(R, a); break;
+        case FLOW_FORM_OP_ADD: v = reg_get(R, a) + reg_get(R, b); break;
+        case FLOW_FORM_OP_SUB: v = reg_get(R, a) - reg_get(R, b); break;
+        case FLOW_FORM_OP_MUL: v = reg_get(R, a) * reg_get(R, b); break;
+        case FLOW_FORM_OP_DIV: v = reg_get(R, a) / reg_get(R, b); break;
+        case FLOW_FORM_OP_NEG: v = -reg_get(R, a); break;
+        case FLOW_FORM_OP_ABS: v = fabs(reg_get(R, a)); break;
+        case FLOW_FORM_OP_SQRT: v = sqrt(reg_get(R, a)); break;
+        // one log and one exp serve ln, exp and pow (a^b = exp(b ln a); the
+        // host sends integer exponents as multiplies and divisions, so pow
+        // only meets the exponents for which a < 0 is undefined anyway):
+        // every library routine is inlined once, which keeps the registers down
+        case FLOW_FORM_OP_POW:
+        case FLOW_FORM_OP_EXP:
+        case FLOW_FORM_OP_LN: {
+          double t = reg_get(R, a);
+          if (op != FLOW_FORM_OP_EXP) t = log(t);
+          if (op == FLOW_FORM_OP_POW) t *= reg_get(R, b);
+          v = op == FLOW_FORM_OP_LN ? t : exp(t);
+          break;
+        }
+        case FLOW_FORM_OP_SIN:
+        case FLOW_FORM_OP_COS: v = form_sincos(reg_get(R, a), op == FLOW_FORM_OP_COS); break;
+        default: {   // FLOW_FORM_OP_OUT
+          const double r = reg_get(R, a);
+          out0 = b == 0 ? r : out0;
+          out1 = b == 0 ? out1 : r;
+          continue;
+        }
+      }
+      reg_set(R, dst, v);
+    }
+    if constexpr (TD == 0) {
+      total += w * out0;
+    } else {
+      const double s0 = w * out0, s1 = w * out1;
+      if constexpr (TD == 1) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          acc[0][i] += s0 * L[i];
+          acc[1][i] += s1 * L[i];
+        }
+      } else {
+        double phi[6], dphi[6][3];
+        basis<2>(L, phi, dphi);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          acc[0][i] += s0 * phi[i];
+          acc[1][i] += s1 * phi[i];
+        }
+      }
+    }
+  }
+  return total;
+}
+
+// functional, stage 2: fixed-order sum of the per-cell integrals, one partial
+// per block
+__global__ __launch_bounds__(kBlock) void form_sum_kernel(
+    int cb, int ce, const double* __restrict__ cellv, double* __restrict__ partials) {
+  double s = 0.0;
+  for (int c = cb + blockIdx.x * blockDim.x + threadIdx.x; c < ce;
+       c += gridDim.x * blockDim.x)
+    s += cellv[c];
+  s = block_sum_once(s);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// one cell per lane.  TD = 0 (functional, stage 1): scratch[cell] = the
+// cell's integral; TD = 1, 2 (load vector): [o][i][cell] contributions for
+// the gather
+template <int NF, int TD>
+__global__ __launch_bounds__(kBlock) void form_cell_kernel(
+    int nc, int cb, int ce, const double* __restrict__ xy, const flow_form F,
+    double* __restrict__ scratch) {
+  const int c = cb + blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ce) return;
+  double acc[2][6];
+#pragma unroll
+  for (int o = 0; o < 2; ++o)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[o][i] = 0.0;
+  const double total = form_cell<NF, TD>(F, nc, xy, c, acc);
+  if constexpr (TD == 0) {
+    scratch[c] = total;
+    return;
+  }
+  constexpr int NL = TD == 1 ? 3 : 6;
+#pragma unroll
+  for (int i = 0; i < NL; ++i) scratch[static_cast<size_t>(i) * nc + c] = acc[0][i];
+  if (F.nout == 2) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i)
+      scratch[static_cast<size_t>(NL + i) * nc + c] = acc[1][i];
+  }
+}
+
+static int check_form(const flow_form* F) {
+  FLOW_REQUIRE(F, "form");
+  FLOW_REQUIRE(F->nprog >= 1 && F->nprog <= FLOW_FORM_MAX_PROGRAM,
+               "form program length");
+  FLOW_REQUIRE(F->nconst >= 0 && F->nconst <= FLOW_FORM_MAX_CONSTANTS,
+               "form constants");
+  FLOW_REQUIRE(F->nfield >= 0 && F->nfield <= FLOW_FORM_MAX_FIELDS, "form fields");
+  FLOW_REQUIRE(F->nexpr >= 0 && F->nexpr <= FLOW_FORM_MAX_EXPRESSIONS,
+               "form expressions");
+  FLOW_REQUIRE(F->nout == 1 || F->nout == 2, "form outputs");
+  FLOW_REQUIRE(F->nq >= 1 && F->nq <= FLOW_FORM_MAX_POINTS && F->rule,
+               "form quadrature rule");
+  for (int k = 0; k < F->nfield; ++k) {
+    FLOW_REQUIRE(F->field[k], "form field pointer");
+    FLOW_REQUIRE(F->field_deg[k] == 1 || F->field_deg[k] == 2, "form field degree");
+    FLOW_REQUIRE(F->cell_dofs[F->field_deg[k] - 1], "form field cell_dofs");
+  }
+  for (int k = 0; k < F->nexpr; ++k) {
+    FLOW_REQUIRE(F->expr[k] && F->expr_nl[k] >= 1 && F->expr_nl[k] <= 21,
+                 "form expression lattice");
+    FLOW_REQUIRE(F->tables && F->expr_table[k] >= 0 &&
+                     F->expr_table[k] + F->nq * F->expr_nl[k] <= F->ntables,
+                 "form expression table");
+  }
+  // every instruction: registers, operand indices and outputs in range (the
+  // kernel indexes kernel-argument arrays with them)
+  bool wrote[2] = {false, false};
+  for (int pc = 0; pc < F->nprog; ++pc) {
+    const int op = F->prog[4 * pc], dst = F->prog[4 * pc + 1];
+    const int a = F->prog[4 * pc + 2], b = F->prog[4 * pc + 3];
+    FLOW_REQUIRE(op >= FLOW_FORM_OP_CONST && op <= FLOW_FORM_OP_OUT, "form opcode");
+    const bool reg_a = op >= FLOW_FORM_OP_MOV;
+    const bool reg_b = op >= FLOW_FORM_OP_ADD && op <= FLOW_FORM_OP_POW;
+    FLOW_REQUIRE(dst >= 0 && dst < FLOW_FORM_REGISTERS, "form register");
+    FLOW_REQUIRE(!reg_a || (a >= 0 && a < FLOW_FORM_REGISTERS), "form register");
+    FLOW_REQUIRE(!reg_b || (b >= 0 && b < FLOW_FORM_REGISTERS), "form register");
+    switch (op) {
+      case FLOW_FORM_OP_CONST:
+        FLOW_REQUIRE(a >= 0 && a < F->nconst, "form constant index");
+        break;
+      case FLOW_FORM_OP_COORD:
+        FLOW_REQUIRE(a == 0 || a == 1, "form coordinate");
+        break;
+      case FLOW_FORM_OP_FIELD:
+        FLOW_REQUIRE(a >= 0 && a < F->nfield && b >= 0 && b <= 2, "form field operand");
+        break;
+      case FLOW_FORM_OP_EXPR:
+        FLOW_REQUIRE(a >= 0 && a < F->nexpr, "form expression index");
+        break;
+      case FLOW_FORM_OP_OUT:
+        FLOW_REQUIRE(b >= 0 && b < F->nout, "form output");
+        wrote[b] = true;
+        break;
+      default: break;
+    }
+  }
+  FLOW_REQUIRE(wrote[0] && (F->nout == 1 || wrote[1]), "form writes every output");
+  return FLOW_OK;
+}
+
+static int check_form_mesh(const flow_mesh* mesh) {
+  FLOW_REQUIRE(mesh && mesh->nc > 0 && mesh->xy, "mesh");
+  FLOW_REQUIRE(mesh->c1 == 0 ||
+                   (0 <= mesh->c0 && mesh->c0 < mesh->c1 && mesh->c1 <= mesh->nc),
+               "mesh cell range");
+  return FLOW_OK;
+}
+
+template <int TD>
+static int launch_cells(const flow_mesh* mesh, const flow_form* F, int cb, int ce,
+                       double* scratch, hipStream_t st) {
+  const dim3 grid((ce - cb + kBlock - 1) / kBlock);
+  switch (F->nfield) {
+#define FLOW_FORM_LOAD_CASE(NF)                                                  \
+    case NF:                                                                     \
+      hipLaunchKernelGGL((form_cell_kernel<NF, TD>), grid, dim3(kBlock), 0, st,  \
+                         mesh->nc, cb, ce, mesh->xy, *F, scratch);              \
+      break;
+    FLOW_FORM_LOAD_CASE(0)
+    FLOW_FORM_LOAD_CASE(1)
+    FLOW_FORM_LOAD_CASE(2)
+    FLOW_FORM_LOAD_CASE(3)
+    FLOW_FORM_LOAD_CASE(4)
+    FLOW_FORM_LOAD_CASE(5)
+    default:
+    FLOW_FORM_LOAD_CASE(6)
+#undef FLOW_FORM_LOAD_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+}  // namespace flow
+
+using namespace flow;
+
+extern "C" int flow_form_functional(const flow_mesh* mesh, const flow_form* form,
+                                    double* scratch, double* work,
+                                    double* result_host, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  if ((rc = check_form(form))) return rc;
+  FLOW_REQUIRE(form->nout == 1, "a functional has one output");
+  FLOW_REQUIRE(scratch && work && result_host, "pointers");
+  hipStream_t st = as_stream(stream);
+  const int cb = mesh->c1 > 0 ? mesh->c0 : 0;
+  const int ce = mesh->c1 > 0 ? mesh->c1 : mesh->nc;
+  if ((rc = launch_cells<0>(mesh, form, cb, ce, scratch, st))) return rc;
+  const int nparts = grid_for(ce - cb, kBlock, kRedBlocks);
+  hipLaunchKernelGGL(form_sum_kernel, dim3(nparts), dim3(kBlock), 0, st, cb, ce,
+                     scratch, work);
+  FLOW_CHECK_LAUNCH();
+  return sum_partials_host(work, nparts, result_host, st);
+}
+
+extern "C" int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
+                                     const flow_form* form, double* scratch,
+                                     double* b, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  if ((rc = check_form(form))) return rc;
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->vptr && V->vsrc,
+               "space");
+  FLOW_REQUIRE(V->r1 == 0 || (0 <= V->r0 && V->r0 < V->r1 && V->r1 <= V->n),
+               "space row range");
+  FLOW_REQUIRE(scratch && b, "pointers");
+  hipStream_t st = as_stream(stream);
+  const int cb = mesh->c1 > 0 ? mesh->c0 : 0;
+  const int ce = mesh->c1 > 0 ? mesh->c1 : mesh->nc;
+  rc = V->deg == 1 ? launch_cells<1>(mesh, form, cb, ce, scratch, st)
+                   : launch_cells<2>(mesh, form, cb, ce, scratch, st);
+  if (rc) return rc;
+  const int nl = V->deg == 1 ? 3 : 6;
+  return gather(V->n, form->nout, V->vptr, V->vsrc, scratch,
+                static_cast<size_t>(nl) * mesh->nc, b, st, 0, V->r0, V->r1);
+}

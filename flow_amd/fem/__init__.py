@@ -20,6 +20,11 @@ from .function import (                                         # noqa: F401
 from .bcs import DirichletBC, SubDomain                         # noqa: F401
 from .io import XDMFFile, mpi_comm_world, read_mesh             # noqa: F401
 from .space import MixedFunctionSpace                           # noqa: F401
+from .forms import (                                            # noqa: F401
+    dx, SpatialCoordinate, as_vector, sqrt, exp, ln, sin, cos, dot, inner,
+    grad, div, curl,
+    )
+from ..message import begin, end, info                          # noqa: F401
 
 DOLFIN_EPS = 3.0e-16
 triangle = 'triangle'
@@ -30,7 +35,8 @@ def __getattr__(name):
     # the operations below run on the HIP path; import them lazily so that the
     # host-only parts (meshes, spaces, BC search) work without the library
     if name in ('project', 'interpolate', 'errornorm', 'norm', 'assemble_mass',
-                'assemble_stiffness', 'integral', 'project_magnitude', 'ops'):
+                'assemble_stiffness', 'integral', 'project_magnitude', 'ops',
+                'assemble'):
         import importlib
         ops = importlib.import_module('.ops', __name__)
         return ops if name == 'ops' else getattr(ops, name)

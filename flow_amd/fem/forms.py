@@ -1,0 +1,694 @@
+# -*- coding: utf-8 -*-
+'''
+UFL-style integrands of fields: what the reference's drivers write around a
+step -- `assemble(p*dx(mesh))`, `project(sqrt(ux**2 + uy**2), Q)`,
+`project(rho(theta)*g*y, P)` with `y = SpatialCoordinate(mesh)[1]` -- built
+with operator overloading and expanded on the host into SCALAR trees (tensors
+are rank <= 2 and exist only here).  Each tree is compiled to a small register
+program (include/flow_hip.h, flow_form) that one HIP kernel family runs at the
+quadrature points of every cell (flow_amd/csrc/form_kernels.hip); the device
+calls are `ops.assemble` and `ops.project`.  Building and compiling trees is
+host-only and needs no library.
+
+Operands: Function (scalar or 2-vector, P1 or P2; `u[i]`, `u.split()`
+copies), Constant, plain numbers, Expression (through its P_k cell lattice,
+k <= 5, as `as_cell_coefficient` interpolates it: dolfin's "interpolate into
+P_degree"), SpatialCoordinate(mesh), as_vector([...]).
+Operators: + - * / unary -, ** (a non-negative integer exponent becomes
+repeated multiplies, a negative one their reciprocal, any other exponent
+pow), abs(), sqrt exp ln sin cos, dot inner grad div curl, f.dx(i).  In 2-D
+curl of a vector is the scalar dv/dx - du/dy (of a scalar s: (ds/dy, -ds/dx)).
+
+Quadrature degree: UFL's estimation rules, applied to the tensor expression
+  Function / Expression   its degree        SpatialCoordinate  1
+  Constant, number        0                 a + b, a - b       max
+  a * b, dot, inner       sum               a / b              deg a + deg b
+  a**n (int n >= 0)       n deg a           other powers       deg a + 2
+  sqrt exp ln sin cos     deg + 2           abs, unary -       unchanged
+  grad div curl .dx       max(deg - 1, 0)   as_vector, [i]     max / unchanged
+`project(f, V)` adds the test space's degree; `dx(metadata={'quadrature_degree':
+q})` or `form_compiler_parameters={'quadrature_degree': q}` replaces the
+estimate.  q <= 30.  The rules are reference.triangle_rule(q) (collapsed
+Gauss-Jacobi, exact for total degree q), not FFC's point sets: for integrands
+that are polynomials within the degree the results are dolfin's; otherwise
+they differ from dolfin's by quadrature error.
+'''
+import numbers
+
+from .function import Function, Constant, Expression
+
+MAX_QUADRATURE_DEGREE = 30
+# include/flow_hip.h
+MAX_PROGRAM = 64
+REGISTERS = 8
+MAX_CONSTANTS = 32
+MAX_FIELDS = 6
+MAX_EXPRESSIONS = 4
+OPS = {name: i for i, name in enumerate((
+    'const', 'coord', 'field', 'expr', 'mov', 'add', 'sub', 'mul', 'div', 'pow',
+    'neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos', 'out'))}
+UNARY = ('neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos')
+BINARY = ('add', 'sub', 'mul', 'div', 'pow')
+
+
+# -- scalar trees --------------------------------------------------------------
+# ('num', v) ('const', Constant, i) ('x', d) ('field', Function, i, d)
+# (d = 0 value, 1 d/dx, 2 d/dy) ('expr', Expression, i) ('powi', a, n) and
+# (op, a[, b]) for the UNARY / BINARY ops.  Objects inside compare by identity.
+ZERO = ('num', 0.0)
+ONE = ('num', 1.0)
+
+
+def _is_num(n, v=None):
+    return n[0] == 'num' and (v is None or n[1] == v)
+
+
+def s_add(a, b):
+    if _is_num(a, 0.0):
+        return b
+    if _is_num(b, 0.0):
+        return a
+    return ('add', a, b)
+
+
+def s_sub(a, b):
+    if _is_num(b, 0.0):
+        return a
+    if _is_num(a, 0.0):
+        return s_neg(b)
+    return ('sub', a, b)
+
+
+def s_mul(a, b):
+    if _is_num(a, 0.0) or _is_num(b, 0.0):
+        return ZERO
+    if _is_num(a, 1.0):
+        return b
+    if _is_num(b, 1.0):
+        return a
+    return ('mul', a, b)
+
+
+def s_div(a, b):
+    if _is_num(a, 0.0):
+        return ZERO
+    if _is_num(b, 1.0):
+        return a
+    return ('div', a, b)
+
+
+def s_neg(a):
+    if _is_num(a):
+        return ('num', -a[1])
+    return ('neg', a)
+
+
+def s_powi(a, n):
+    if n < 0:
+        return s_div(ONE, s_powi(a, -n))
+    if n == 0:
+        return ONE
+    if n == 1:
+        return a
+    return ('powi', a, n)
+
+
+def s_diff(n, d):
+    '''d n / d x_d (d = 0, 1), by the chain rule.'''
+    k = n[0]
+    if k in ('num', 'const'):
+        return ZERO
+    if k == 'x':
+        return ONE if n[1] == d else ZERO
+    if k == 'field':
+        if n[3] != 0:
+            raise NotImplementedError('second derivatives of a field')
+        return ('field', n[1], n[2], d + 1)
+    if k == 'expr':
+        raise NotImplementedError(
+            'derivatives of an Expression: interpolate it into a Function')
+    if k == 'add':
+        return s_add(s_diff(n[1], d), s_diff(n[2], d))
+    if k == 'sub':
+        return s_sub(s_diff(n[1], d), s_diff(n[2], d))
+    if k == 'neg':
+        return s_neg(s_diff(n[1], d))
+    a = n[1]
+    da = s_diff(a, d)
+    if k == 'mul':
+        return s_add(s_mul(da, n[2]), s_mul(a, s_diff(n[2], d)))
+    if k == 'div':
+        b = n[2]
+        return s_div(s_sub(s_mul(da, b), s_mul(a, s_diff(b, d))), s_powi(b, 2))
+    if k == 'powi':
+        return s_mul(s_mul(('num', float(n[2])), s_powi(a, n[2] - 1)), da)
+    if k == 'pow':
+        b = n[2]
+        return s_mul(n, s_add(s_mul(s_diff(b, d), ('ln', a)),
+                              s_div(s_mul(b, da), a)))
+    if k == 'sqrt':
+        return s_div(da, s_mul(('num', 2.0), n))
+    if k == 'exp':
+        return s_mul(n, da)
+    if k == 'ln':
+        return s_div(da, a)
+    if k == 'sin':
+        return s_mul(('cos', a), da)
+    if k == 'cos':
+        return s_neg(s_mul(('sin', a), da))
+    raise NotImplementedError('derivative of %s' % k)
+
+
+# -- tensors of scalar trees -----------------------------------------------------
+def _map(f, c, shape):
+    if len(shape) == 0:
+        return f(c)
+    return [_map(f, ci, shape[1:]) for ci in c]
+
+
+def _map2(f, a, b, shape):
+    if len(shape) == 0:
+        return f(a, b)
+    return [_map2(f, ai, bi, shape[1:]) for ai, bi in zip(a, b)]
+
+
+def _flat(c, shape):
+    if len(shape) == 0:
+        return [c]
+    return [x for ci in c for x in _flat(ci, shape[1:])]
+
+
+def _join_mesh(a, b):
+    if a is not None and b is not None and a is not b:
+        raise ValueError('the expression combines fields of two different '
+                         'meshes')
+    return a if a is not None else b
+
+
+_FORM_OPERANDS = ()     # filled below
+
+
+class FormExpr(object):
+    '''A tensor (rank <= 2, 2-D) of scalar trees with its estimated degree.
+    No __eq__ / __hash__: expressions, like the Functions inside them, compare
+    and hash by identity.'''
+    __array_ufunc__ = None          # numpy scalars defer to the operators below
+
+    def __init__(self, comps, shape, deg, mesh=None):
+        if len(shape) > 2:
+            raise ValueError('tensors of rank %d: at most rank 2 is supported'
+                             % len(shape))
+        self.comps = comps
+        self.shape = tuple(shape)
+        self.deg = int(deg)
+        self.mesh = mesh
+
+    def rank(self):
+        return len(self.shape)
+
+    def scalar_trees(self):
+        return _flat(self.comps, self.shape)
+
+    # -- arithmetic
+    def __add__(self, other):
+        return _binary('add', self, other)
+
+    def __radd__(self, other):
+        return _binary('add', other, self)
+
+    def __sub__(self, other):
+        return _binary('sub', self, other)
+
+    def __rsub__(self, other):
+        return _binary('sub', other, self)
+
+    def __mul__(self, other):
+        if isinstance(other, Measure):
+            return other.__rmul__(self)
+        return _binary('mul', self, other)
+
+    def __rmul__(self, other):
+        return _binary('mul', other, self)
+
+    def __truediv__(self, other):
+        return _binary('div', self, other)
+
+    def __rtruediv__(self, other):
+        return _binary('div', other, self)
+
+    __div__ = __truediv__
+    __rdiv__ = __rtruediv__
+
+    def __pow__(self, other):
+        return _power(self, other)
+
+    def __rpow__(self, other):
+        return _power(other, self)
+
+    def __neg__(self):
+        return FormExpr(_map(s_neg, self.comps, self.shape), self.shape,
+                        self.deg, self.mesh)
+
+    def __pos__(self):
+        return self
+
+    def __abs__(self):
+        return _function('abs', self)
+
+    def __getitem__(self, idx):
+        if not isinstance(idx, tuple):
+            idx = (idx,)
+        if len(idx) > len(self.shape):
+            raise ValueError('index %r of a tensor of shape %r'
+                             % (idx, self.shape))
+        c = self.comps
+        for i in idx:
+            if not isinstance(i, numbers.Integral):
+                raise TypeError('component indices are integers')
+            if not 0 <= i < 2:
+                raise IndexError(i)
+            c = c[i]
+        return FormExpr(c, self.shape[len(idx):], self.deg, self.mesh)
+
+    def dx(self, i):
+        if i not in (0, 1):
+            raise IndexError('dx(%r): the mesh is 2-D' % (i,))
+        return FormExpr(_map(lambda n: s_diff(n, i), self.comps, self.shape),
+                        self.shape, max(self.deg - 1, 0), self.mesh)
+
+
+def as_form(obj):
+    '''The FormExpr of an operand; TypeError if it is none.'''
+    if isinstance(obj, FormExpr):
+        return obj
+    if isinstance(obj, bool):
+        raise TypeError('not a form operand: %r' % (obj,))
+    if isinstance(obj, numbers.Real):
+        return FormExpr(('num', float(obj)), (), 0)
+    if isinstance(obj, Function):
+        V = obj.function_space()
+        if V.degree not in (1, 2):
+            raise ValueError('fields of degree 1 or 2 only')
+        if V.dim == 1:
+            return FormExpr(('field', obj, 0, 0), (), V.degree, V.mesh())
+        return FormExpr([('field', obj, i, 0) for i in range(V.dim)], (V.dim,),
+                        V.degree, V.mesh())
+    if isinstance(obj, Constant):
+        vals = obj.values()
+        if len(vals) == 1:
+            return FormExpr(('const', obj, 0), (), 0)
+        if len(vals) != 2:
+            raise ValueError('Constant with %d components' % len(vals))
+        return FormExpr([('const', obj, i) for i in range(2)], (2,), 0)
+    if isinstance(obj, Expression):
+        k = int(obj.degree)
+        if not 0 <= k <= 5:
+            raise ValueError('Expression degree must be <= 5 (got %d)' % k)
+        dim = obj.value_dim()
+        if dim == 1:
+            return FormExpr(('expr', obj, 0), (), k)
+        if dim != 2:
+            raise ValueError('Expression with %d components' % dim)
+        return FormExpr([('expr', obj, i) for i in range(2)], (2,), k)
+    raise TypeError('not a form operand: %r' % (type(obj),))
+
+
+def is_form_operand(obj):
+    return isinstance(obj, (FormExpr, Function, Constant, Expression, Measure))
+
+
+def _binary(op, a, b):
+    try:
+        a = as_form(a)
+        b = as_form(b)
+    except TypeError:
+        return NotImplemented
+    mesh = _join_mesh(a.mesh, b.mesh)
+    if op in ('add', 'sub'):
+        if a.shape != b.shape:
+            raise ValueError('%s of shapes %r and %r' % (op, a.shape, b.shape))
+        f = s_add if op == 'add' else s_sub
+        return FormExpr(_map2(f, a.comps, b.comps, a.shape), a.shape,
+                        max(a.deg, b.deg), mesh)
+    if op == 'div':
+        if b.shape:
+            raise ValueError('division by a tensor of shape %r' % (b.shape,))
+        return FormExpr(_map(lambda n: s_div(n, b.comps), a.comps, a.shape),
+                        a.shape, a.deg + b.deg, mesh)
+    # product: scalar scaling, matrix-vector or matrix-matrix
+    deg = a.deg + b.deg
+    if not a.shape:
+        return FormExpr(_map(lambda n: s_mul(a.comps, n), b.comps, b.shape),
+                        b.shape, deg, mesh)
+    if not b.shape:
+        return FormExpr(_map(lambda n: s_mul(n, b.comps), a.comps, a.shape),
+                        a.shape, deg, mesh)
+    if len(a.shape) == 2:
+        return _contract(a, b, deg, mesh)
+    raise ValueError('product of shapes %r and %r: use dot or inner'
+                     % (a.shape, b.shape))
+
+
+def _contract(a, b, deg, mesh):
+    '''a . b over the last index of a and the first of b.'''
+    def sdot(x, y):
+        return s_add(s_mul(x[0], y[0]), s_mul(x[1], y[1]))
+
+    if len(a.shape) == 1 and len(b.shape) == 1:
+        return FormExpr(sdot(a.comps, b.comps), (), deg, mesh)
+    if len(a.shape) == 2 and len(b.shape) == 1:
+        return FormExpr([sdot(a.comps[i], b.comps) for i in range(2)], (2,),
+                        deg, mesh)
+    bt = [[b.comps[0][j], b.comps[1][j]] for j in range(2)] \
+        if len(b.shape) == 2 else None
+    if len(a.shape) == 1:
+        return FormExpr([sdot(a.comps, bt[j]) for j in range(2)], (2,), deg,
+                        mesh)
+    return FormExpr([[sdot(a.comps[i], bt[j]) for j in range(2)]
+                     for i in range(2)], (2, 2), deg, mesh)
+
+
+def _power(a, p):
+    try:
+        a = as_form(a)
+    except TypeError:
+        return NotImplemented
+    if a.shape:
+        raise ValueError('power of a tensor of shape %r' % (a.shape,))
+    if isinstance(p, numbers.Integral) and not isinstance(p, bool):
+        n = int(p)
+        # (UFL: n * deg for n >= 0, else deg + 2)
+        return FormExpr(s_powi(a.comps, n), (), n * a.deg if n >= 0
+                        else a.deg + 2, a.mesh)
+    if isinstance(p, numbers.Real) and float(p).is_integer() \
+            and abs(p) <= 64:
+        # a float exponent: UFL's estimate, the exact multiplies
+        return FormExpr(s_powi(a.comps, int(p)), (), a.deg + 2, a.mesh)
+    try:
+        e = as_form(p)
+    except TypeError:
+        return NotImplemented
+    if e.shape:
+        raise ValueError('exponent of shape %r' % (e.shape,))
+    return FormExpr(('pow', a.comps, e.comps), (), a.deg + 2,
+                    _join_mesh(a.mesh, e.mesh))
+
+
+def _function(name, f):
+    f = as_form(f)
+    if f.shape:
+        raise ValueError('%s of a tensor of shape %r' % (name, f.shape))
+    return FormExpr((name, f.comps), (), f.deg if name == 'abs' else f.deg + 2,
+                    f.mesh)
+
+
+def sqrt(f):
+    return _function('sqrt', f)
+
+
+def exp(f):
+    return _function('exp', f)
+
+
+def ln(f):
+    return _function('ln', f)
+
+
+def sin(f):
+    return _function('sin', f)
+
+
+def cos(f):
+    return _function('cos', f)
+
+
+def dot(a, b):
+    a, b = as_form(a), as_form(b)
+    mesh = _join_mesh(a.mesh, b.mesh)
+    if not a.shape or not b.shape:
+        if a.shape or b.shape:
+            raise ValueError('dot of shapes %r and %r' % (a.shape, b.shape))
+        return _binary('mul', a, b)
+    return _contract(a, b, a.deg + b.deg, mesh)
+
+
+def inner(a, b):
+    a, b = as_form(a), as_form(b)
+    if a.shape != b.shape:
+        raise ValueError('inner of shapes %r and %r' % (a.shape, b.shape))
+    mesh = _join_mesh(a.mesh, b.mesh)
+    total = ZERO
+    for x, y in zip(a.scalar_trees(), b.scalar_trees()):
+        total = s_add(total, s_mul(x, y))
+    return FormExpr(total, (), a.deg + b.deg, mesh)
+
+
+def grad(f):
+    f = as_form(f)
+    if len(f.shape) == 2:
+        raise ValueError('grad of a rank-2 tensor would be rank 3: at most '
+                         'rank 2 is supported')
+    comps = _map(lambda n: [s_diff(n, 0), s_diff(n, 1)], f.comps, f.shape)
+    return FormExpr(comps, f.shape + (2,), max(f.deg - 1, 0), f.mesh)
+
+
+def div(f):
+    f = as_form(f)
+    if not f.shape:
+        raise ValueError('div of a scalar')
+    if len(f.shape) == 1:
+        c = s_add(s_diff(f.comps[0], 0), s_diff(f.comps[1], 1))
+    else:
+        c = [s_add(s_diff(f.comps[i][0], 0), s_diff(f.comps[i][1], 1))
+             for i in range(2)]
+    return FormExpr(c, f.shape[1:], max(f.deg - 1, 0), f.mesh)
+
+
+def curl(f):
+    '''2-D: of a vector v the scalar dv1/dx - dv0/dy, of a scalar s the
+    vector (ds/dy, -ds/dx).'''
+    f = as_form(f)
+    deg = max(f.deg - 1, 0)
+    if not f.shape:
+        return FormExpr([s_diff(f.comps, 1), s_neg(s_diff(f.comps, 0))], (2,),
+                        deg, f.mesh)
+    if len(f.shape) != 1:
+        raise ValueError('curl of a tensor of shape %r' % (f.shape,))
+    return FormExpr(s_sub(s_diff(f.comps[1], 0), s_diff(f.comps[0], 1)), (),
+                    deg, f.mesh)
+
+
+def as_vector(items):
+    items = list(items)
+    if len(items) != 2:
+        raise ValueError('as_vector: 2 components in 2-D, got %d' % len(items))
+    if all(isinstance(i, (list, tuple)) for i in items):
+        rows = [as_vector(i) for i in items]
+        if any(r.shape != (2,) for r in rows):
+            raise ValueError('as_vector: rows must be vectors of scalars')
+        return FormExpr([r.comps for r in rows], (2, 2),
+                        max(r.deg for r in rows),
+                        _join_mesh(rows[0].mesh, rows[1].mesh))
+    parts = [as_form(i) for i in items]
+    if any(p.shape for p in parts):
+        raise ValueError('as_vector of non-scalar components (shapes %r)'
+                         % ([p.shape for p in parts],))
+    return FormExpr([p.comps for p in parts], (2,), max(p.deg for p in parts),
+                    _join_mesh(parts[0].mesh, parts[1].mesh))
+
+
+def SpatialCoordinate(mesh):
+    return FormExpr([('x', 0), ('x', 1)], (2,), 1, mesh)
+
+
+# -- measure and forms -----------------------------------------------------------
+def _quadrature_degree(params):
+    if not params:
+        return None
+    q = params.get('quadrature_degree')
+    return None if q is None else int(q)
+
+
+class Measure(object):
+    '''`dx`, `dx(mesh)`, `dx(domain=mesh)`, `dx(metadata={...})`.'''
+
+    def __init__(self, mesh=None, metadata=None):
+        self.mesh = mesh
+        self.metadata = dict(metadata or {})
+
+    def __call__(self, domain=None, metadata=None, degree=None):
+        md = dict(self.metadata)
+        md.update(metadata or {})
+        if degree is not None:
+            md['quadrature_degree'] = degree
+        return Measure(domain if domain is not None else self.mesh, md)
+
+    def __rmul__(self, other):
+        f = as_form(other)
+        if f.shape:
+            raise ValueError('only scalar integrands can be integrated: the '
+                             'integrand has shape %r' % (f.shape,))
+        return Form(f, _join_mesh(f.mesh, self.mesh), self.metadata)
+
+
+dx = Measure()
+
+
+class Form(object):
+    '''A rank-0 form: a scalar integrand over the cells of a mesh.'''
+
+    def __init__(self, integrand, mesh, metadata):
+        self.integrand = integrand
+        self.mesh = mesh
+        self.metadata = metadata
+
+    def degree(self):
+        q = _quadrature_degree(self.metadata)
+        return self.integrand.deg if q is None else q
+
+
+def check_degree(q):
+    if not 0 <= q <= MAX_QUADRATURE_DEGREE:
+        raise ValueError('quadrature degree %d: at most %d is supported'
+                         % (q, MAX_QUADRATURE_DEGREE))
+    return q
+
+
+def projection_degree(expr, test_degree, form_compiler_parameters=None):
+    q = _quadrature_degree(form_compiler_parameters)
+    return check_degree(expr.deg + test_degree if q is None else q)
+
+
+# -- register programs -----------------------------------------------------------
+class Program(object):
+    '''Instructions (op, dst, a, b) over REGISTERS registers for a list of
+    scalar trees (output k = tree k), and the operands they load: constants
+    (('num', v) or (Constant, i)), field components (Function, i) and
+    Expression components (Expression, i), in slot order.'''
+
+    def __init__(self, trees):
+        self.code = []
+        self.consts = []
+        self.fields = []
+        self.exprs = []
+        self.nregs = 0
+        for k, t in enumerate(trees):
+            self._gen(t, 0)
+            self._emit('out', 0, 0, k)
+        if len(self.code) > MAX_PROGRAM:
+            raise ValueError('the integrand compiles to %d instructions: the '
+                             'limit is %d' % (len(self.code), MAX_PROGRAM))
+        self.nout = len(trees)
+
+    def signature(self):
+        return (tuple(self.code),
+                tuple(f.function_space().degree for f, _ in self.fields),
+                tuple(int(e.degree) for e, _ in self.exprs))
+
+    def _slot(self, table, key, limit, what):
+        for i, k in enumerate(table):
+            if k[0] is key[0] and k[1] == key[1]:
+                return i
+        if len(table) == limit:
+            raise ValueError('the integrand needs more than %d %s: the limit '
+                             'is %d' % (limit, what, limit))
+        table.append(key)
+        return len(table) - 1
+
+    def _emit(self, op, dst, a=0, b=0):
+        if op != 'out':
+            if dst >= REGISTERS:
+                raise ValueError('the integrand needs more than %d registers: '
+                                 'the limit is %d' % (REGISTERS, REGISTERS))
+            self.nregs = max(self.nregs, dst + 1)
+        self.code.append((OPS[op], dst, a, b))
+
+    def _const(self, key):
+        for i, k in enumerate(self.consts):
+            if (k[0] == 'num' and key[0] == 'num' and k[1] == key[1]) or (
+                    k[0] is key[0] and k[1] == key[1]):
+                return i
+        if len(self.consts) == MAX_CONSTANTS:
+            raise ValueError('the integrand needs more than %d constants: the '
+                             'limit is %d' % (MAX_CONSTANTS, MAX_CONSTANTS))
+        self.consts.append(key)
+        return len(self.consts) - 1
+
+    @staticmethod
+    def need(n):
+        '''Registers the tree needs (Sethi-Ullman).'''
+        k = n[0]
+        if k in ('num', 'const', 'x', 'field', 'expr'):
+            return 1
+        if k in UNARY:
+            return Program.need(n[1])
+        if k == 'powi':
+            m = n[2]
+            na = Program.need(n[1])
+            return na if m & (m - 1) == 0 else max(na, 2)
+        la, lb = Program.need(n[1]), Program.need(n[2])
+        return la + 1 if la == lb else max(la, lb)
+
+    def _gen(self, n, base):
+        k = n[0]
+        if k == 'num':
+            self._emit('const', base, self._const(('num', n[1])))
+        elif k == 'const':
+            self._emit('const', base, self._const((n[1], n[2])))
+        elif k == 'x':
+            self._emit('coord', base, n[1])
+        elif k == 'field':
+            self._emit('field', base, self._slot(
+                self.fields, (n[1], n[2]), MAX_FIELDS, 'field components'),
+                n[3])
+        elif k == 'expr':
+            self._emit('expr', base, self._slot(
+                self.exprs, (n[1], n[2]), MAX_EXPRESSIONS,
+                'Expression components'))
+        elif k in UNARY:
+            self._gen(n[1], base)
+            self._emit(k, base, base)
+        elif k == 'powi':
+            m = n[2]
+            self._gen(n[1], base)
+            if m & (m - 1) == 0:            # a power of two: square in place
+                while m > 1:
+                    self._emit('mul', base, base, base)
+                    m >>= 1
+            else:                           # left-to-right binary powering
+                self._emit('mov', base + 1, base)
+                for bit in bin(m)[3:]:
+                    self._emit('mul', base + 1, base + 1, base + 1)
+                    if bit == '1':
+                        self._emit('mul', base + 1, base + 1, base)
+                self._emit('mov', base, base + 1)
+        else:
+            a, b = n[1], n[2]
+            if self.need(a) >= self.need(b):
+                self._gen(a, base)
+                self._gen(b, base + 1)
+                self._emit(k, base, base, base + 1)
+            else:
+                self._gen(b, base)
+                self._gen(a, base + 1)
+                self._emit(k, base, base + 1, base)
+
+    def constant_values(self):
+        '''The constants' current values (Constants may be re-assigned
+        between calls: they travel with every launch).'''
+        out = []
+        for k in self.consts:
+            if isinstance(k[0], str):
+                out.append(k[1])
+            else:
+                out.append(float(k[0].values()[k[1]]))
+        return out
+
+
+def form_mesh(expr, mesh=None):
+    '''The mesh an expression lives on (ValueError if it has none).'''
+    m = _join_mesh(expr.mesh, mesh)
+    if m is None:
+        raise ValueError('the integrand carries no mesh: integrate over '
+                         'dx(mesh)')
+    return m

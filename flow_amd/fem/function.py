@@ -19,7 +19,43 @@ from .. import _hip
 from .. import device
 
 
-class Constant(object):
+def _form_op(name):
+    '''The operator `name` of flow_amd.fem.forms.FormExpr on the form of self:
+    arithmetic on Functions, Constants and Expressions builds integrands.'''
+    def op(self, *args):
+        from . import forms
+        return getattr(forms.FormExpr, name)(forms.as_form(self), *args)
+    op.__name__ = name
+    return op
+
+
+class _FormOperand(object):
+    '''Operators that build UFL-style integrands (flow_amd/fem/forms.py).
+    No __eq__ / __hash__: the identity hash of Functions, Constants and
+    Expressions (held in dicts and caches) stays.'''
+    __array_ufunc__ = None          # numpy scalars defer to these operators
+    __add__ = _form_op('__add__')
+    __radd__ = _form_op('__radd__')
+    __sub__ = _form_op('__sub__')
+    __rsub__ = _form_op('__rsub__')
+    __mul__ = _form_op('__mul__')
+    __rmul__ = _form_op('__rmul__')
+    __truediv__ = _form_op('__truediv__')
+    __rtruediv__ = _form_op('__rtruediv__')
+    __pow__ = _form_op('__pow__')
+    __rpow__ = _form_op('__rpow__')
+    __neg__ = _form_op('__neg__')
+    __abs__ = _form_op('__abs__')
+    __getitem__ = _form_op('__getitem__')
+    dx = _form_op('dx')
+
+
+def _is_form_operand(obj):
+    from . import forms
+    return forms.is_form_operand(obj)
+
+
+class Constant(_FormOperand):
     def __init__(self, value):
         self._values = numpy.atleast_1d(numpy.asarray(value, dtype=float))
         return
@@ -39,12 +75,21 @@ class Constant(object):
         assert len(self._values) == 1
         return float(self._values[0])
 
+    # Constant * number and Constant / number stay Constants; with a field,
+    # an Expression or a measure they build an integrand
     def __mul__(self, other):
+        if _is_form_operand(other):
+            return _FormOperand.__mul__(self, other)
         return Constant(self._values * float(other))
 
-    __rmul__ = __mul__
+    def __rmul__(self, other):
+        if _is_form_operand(other):
+            return _FormOperand.__rmul__(self, other)
+        return Constant(self._values * float(other))
 
     def __truediv__(self, other):
+        if _is_form_operand(other):
+            return _FormOperand.__truediv__(self, other)
         return Constant(self._values / float(other))
 
 
@@ -65,7 +110,7 @@ _NAMESPACE = {
     }
 
 
-class Expression(object):
+class Expression(_FormOperand):
     '''`Expression(code, degree=k, **params)`.
 
     `code` is a Python callable f(x) (x has shape (2, n); returns an array or a
@@ -232,7 +277,7 @@ class _VectorSlice(object):
         return self.vec.get_local()
 
 
-class Function(object):
+class Function(_FormOperand):
     def __init__(self, V, data=None):
         assert isinstance(V, FunctionSpace)
         assert V.component is None, 'Function on a sub-space view'

@@ -637,10 +637,17 @@ def assemble_source(V, f):
     return b
 
 
-def project(f, V, tol=1.0e-14):
+def project(f, V, tol=1.0e-14, form_compiler_parameters=None):
     '''L2 projection (dolfin.project): mass solve per component, CG + Jacobi on
-    the device.'''
-    b = assemble_source(V, f)
+    the device.  f: Constant / Expression / Function / NodalExpression, or an
+    integrand built from them (flow_amd/fem/forms.py: its load vector comes
+    from the form kernels; form_compiler_parameters={'quadrature_degree': q}
+    replaces the estimated degree).'''
+    from .forms import FormExpr
+    if isinstance(f, FormExpr):
+        b = form_load_vector(f, V, form_compiler_parameters)
+    else:
+        b = assemble_source(V, f)
     M = assemble_mass(V)
     dinv = M.diag_inv()
     out = Function(V)
@@ -781,3 +788,143 @@ def errornorm(exact, uh, degree_rise=3):
     Mk = reference.mass_matrix(k)
     detj = 2.0 * mesh.cell_areas()
     return float(numpy.sqrt(numpy.einsum('acl,lm,acm,c->', e, Mk, e, detj)))
+
+
+# -- forms (flow_amd/fem/forms.py, csrc/form_kernels.hip) ---------------------
+_FORM_TABLES = {}
+
+
+def _form_tables(q, expr_degrees):
+    '''Rule (nq x 3: xi, eta, weight) and the P_k basis tables of the
+    Expression operands at its points, uploaded once per (degree, lattice
+    degrees): an upload drains the stream, and time loops integrate the same
+    forms every step.  (The program and the constants need no upload: they
+    travel with the launch.)'''
+    key = (q, expr_degrees, str(device.get()))
+    held = _FORM_TABLES.get(key)
+    if held is None:
+        pts, wts = reference.triangle_rule(q)
+        if len(wts) > _hip.FORM_MAX_POINTS:
+            raise ValueError('quadrature degree %d: %d points, the limit is %d'
+                             % (q, len(wts), _hip.FORM_MAX_POINTS))
+        rule = numpy.concatenate([pts, wts[:, None]], axis=1)
+        offsets = []
+        tabs = [numpy.zeros(1)]
+        off = 1
+        for k in expr_degrees:
+            t = reference.tabulate(k, pts)              # (nq, nl)
+            offsets.append(off)
+            tabs.append(t.reshape(-1))
+            off += t.size
+        tables = numpy.concatenate(tabs)
+        held = (device.to_device(rule.reshape(-1).copy()),
+                device.to_device(tables), offsets, len(wts), int(tables.size))
+        if len(_FORM_TABLES) >= 64:
+            _FORM_TABLES.clear()
+        _FORM_TABLES[key] = held
+    return held
+
+
+def _form_struct(prog, mesh, q):
+    '''flow_form of a compiled forms.Program on `mesh` with the degree-q
+    rule.  Returns (struct, keepalive).'''
+    fs = _hip.FormS()
+    fs.nprog = len(prog.code)
+    for i, ins in enumerate(prog.code):
+        for j in range(4):
+            fs.prog[4 * i + j] = int(ins[j])
+    vals = prog.constant_values()
+    fs.nconst = len(vals)
+    for i, v in enumerate(vals):
+        fs.consts[i] = v
+    keep = []
+    nc = mesh.num_cells()
+    fs.nfield = len(prog.fields)
+    for i, (f, comp) in enumerate(prog.fields):
+        W = f.function_space()
+        if W.mesh() is not mesh:
+            raise ValueError('a field of the integrand lives on another mesh')
+        lay = W.layout
+        base = _hip.f64(f.data, W.size(), 'field of the integrand').value
+        fs.field[i] = base + 8 * comp * lay.N
+        fs.field_deg[i] = lay.degree
+        fs.cell_dofs[lay.degree - 1] = _hip.i32(
+            lay.dev('cell_dofs'), lay.nloc * nc, 'cell_dofs').value
+        keep.append(f.data)
+    expr_degrees = tuple(int(e.degree) for e, _ in prog.exprs)
+    rule, tables, offsets, nq, ntables = _form_tables(q, expr_degrees)
+    fs.nexpr = len(prog.exprs)
+    coefs = {}
+    for i, (e, comp) in enumerate(prog.exprs):
+        if id(e) not in coefs:
+            coefs[id(e)] = as_cell_coefficient(e, mesh, e.value_dim())
+        coef = coefs[id(e)]
+        n = coef.nl * nc
+        base = _hip.f64(coef.values, coef.dim * n, 'Expression lattice').value
+        fs.expr[i] = base + 8 * comp * n
+        fs.expr_nl[i] = coef.nl
+        fs.expr_table[i] = offsets[i]
+        keep.append(coef.values)
+    fs.nq = nq
+    fs.rule = _hip.f64(rule, 3 * nq, 'rule').value
+    fs.tables = _hip.f64(tables, ntables, 'tables').value
+    fs.ntables = ntables
+    fs.nout = prog.nout
+    return fs, (keep, rule, tables)
+
+
+def _no_strips(what):
+    from .. import parallel
+    if parallel.active():
+        raise NotImplementedError(
+            '%s on strips is not implemented (project_magnitude is the path '
+            'there)' % what)
+
+
+def assemble(form):
+    '''assemble(f*dx): the integral of a scalar integrand over the mesh, a
+    float.  Fixed-order reduction on the device: the same bits on every
+    call.'''
+    from . import forms
+    if not isinstance(form, forms.Form):
+        raise TypeError('assemble takes a rank-0 form f*dx (got %r): forms '
+                        'of test and trial functions are not supported'
+                        % (type(form),))
+    _no_strips('assemble')
+    lib = _hip.lib()
+    mesh = forms.form_mesh(form.integrand, form.mesh)
+    q = forms.check_degree(form.degree())
+    prog = forms.Program([form.integrand.comps])
+    fs, keep = _form_struct(prog, mesh, q)
+    res = ctypes.c_double(0.0)
+    _hip.check(lib.flow_form_functional(
+        ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs),
+        _hip.f64(scratch(mesh, mesh.num_cells())),
+        _hip.f64(work(_hip.REDUCE_WORK)), ctypes.byref(res), _hip.stream()
+        ))
+    del keep
+    return res.value
+
+
+def form_load_vector(expr, V, form_compiler_parameters=None):
+    '''b_(a,i) = int expr_a phi_i over the test functions of V: the load
+    vector of project(expr, V).'''
+    from . import forms
+    if expr.shape != (() if V.dim == 1 else (V.dim,)):
+        raise ValueError('projecting an expression of shape %r into a space '
+                         'with %d components' % (expr.shape, V.dim))
+    _no_strips('project of an expression')
+    lib = _hip.lib()
+    mesh = forms.form_mesh(expr, V.mesh())
+    q = forms.projection_degree(expr, V.degree, form_compiler_parameters)
+    prog = forms.Program(expr.scalar_trees())
+    fs, keep = _form_struct(prog, mesh, q)
+    lay = V.layout
+    b = device.empty(V.size())
+    buf = scratch(mesh, V.dim * lay.nloc * mesh.num_cells())
+    _hip.check(lib.flow_form_load_vector(
+        ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay)),
+        ctypes.byref(fs), _hip.f64(buf), _hip.f64(b), _hip.stream()
+        ))
+    del keep
+    return b

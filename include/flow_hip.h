@@ -1085,6 +1085,79 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
                             const double* u, double* scratch, double* b,
                             void* stream);
 
+/* ---- forms: integrals of expressions of fields (flow_amd/fem/forms.py) -----
+ * The host expands a UFL-style integrand into scalar trees and compiles each
+ * to a register program: at most FLOW_FORM_MAX_PROGRAM instructions
+ * (op, dst, a, b) over FLOW_FORM_REGISTERS fp64 registers r[0..7].  A cell
+ * kernel runs the program at every point of the quadrature rule; `out` ops
+ * hand a register to output 0 or 1.
+ *   const  r[dst] = consts[a]          coord  r[dst] = x_a at the point
+ *   field  r[dst] = field a (b = 0), d/dx (b = 1) or d/dy (b = 2)
+ *   expr   r[dst] = sum_l expr[a][l][c] * tables[expr_table[a] + q*nl + l]
+ *   mov    r[dst] = r[a]               add sub mul div pow  r[dst] = r[a] o r[b]
+ *   neg abs sqrt exp ln sin cos  r[dst] = f(r[a])
+ *   out    output b = r[a]
+ * The program and the constants travel by value with the launch (constants
+ * may change from call to call at no cost); rule and tables are device
+ * arrays, uploaded once per program signature and degree by the host. */
+#define FLOW_FORM_MAX_PROGRAM 64
+#define FLOW_FORM_REGISTERS 8
+#define FLOW_FORM_MAX_CONSTANTS 32
+#define FLOW_FORM_MAX_FIELDS 6
+#define FLOW_FORM_MAX_EXPRESSIONS 4
+#define FLOW_FORM_MAX_POINTS 256
+#define FLOW_FORM_OP_CONST 0
+#define FLOW_FORM_OP_COORD 1
+#define FLOW_FORM_OP_FIELD 2
+#define FLOW_FORM_OP_EXPR 3
+#define FLOW_FORM_OP_MOV 4
+#define FLOW_FORM_OP_ADD 5
+#define FLOW_FORM_OP_SUB 6
+#define FLOW_FORM_OP_MUL 7
+#define FLOW_FORM_OP_DIV 8
+#define FLOW_FORM_OP_POW 9
+#define FLOW_FORM_OP_NEG 10
+#define FLOW_FORM_OP_ABS 11
+#define FLOW_FORM_OP_SQRT 12
+#define FLOW_FORM_OP_EXP 13
+#define FLOW_FORM_OP_LN 14
+#define FLOW_FORM_OP_SIN 15
+#define FLOW_FORM_OP_COS 16
+#define FLOW_FORM_OP_OUT 17
+typedef struct {
+  int nprog;
+  int prog[4 * FLOW_FORM_MAX_PROGRAM];     /* (op, dst, a, b) per instruction */
+  int nconst;
+  double consts[FLOW_FORM_MAX_CONSTANTS];
+  int nfield;                              /* scalar field components */
+  const double* field[FLOW_FORM_MAX_FIELDS];   /* n dofs each */
+  int field_deg[FLOW_FORM_MAX_FIELDS];     /* 1 | 2 */
+  const int* cell_dofs[2];                 /* (nloc, nc) of the P1 | P2 layout */
+  int nexpr;                               /* Expression components */
+  const double* expr[FLOW_FORM_MAX_EXPRESSIONS];   /* P_k lattice (nl, nc) */
+  int expr_nl[FLOW_FORM_MAX_EXPRESSIONS];  /* nl <= 21 (k <= 5) */
+  int expr_table[FLOW_FORM_MAX_EXPRESSIONS];
+  int nq;                                  /* <= FLOW_FORM_MAX_POINTS */
+  const double* rule;                      /* nq x 3: xi, eta, weight (sum 1/2) */
+  const double* tables;                    /* P_k basis at the rule's points */
+  int ntables;                             /* doubles in tables */
+  int nout;                                /* 1 | 2 */
+} flow_form;
+
+/* assemble(f*dx): the integral of output 0 over the cells of `mesh`, to the
+ * host.  Fixed-order reduction (per-cell integrals, <= 1024 block partials,
+ * one finishing block): bitwise reproducible.  scratch: nc doubles; work:
+ * FLOW_REDUCE_WORK doubles. */
+int flow_form_functional(const flow_mesh* mesh, const flow_form* form,
+                         double* scratch, double* work, double* result_host,
+                         void* stream);
+
+/* Load vector b_(o,i) = int out_o phi_i for o < form->nout (the right-hand
+ * side of project(f, V)); V: test space (deg 1|2).  scratch: nout*nloc*nc. */
+int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
+                          const flow_form* form, double* scratch, double* b,
+                          void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
