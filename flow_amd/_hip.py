@@ -420,6 +420,8 @@ SYMBOLS = {
                                        _D, _D, _P(CoefS), _VP, _VP, _VP, _VP],
     'flow_form_functional': [_P(MeshS), _P(FormS), _VP, _VP, _P(_D), _VP],
     'flow_form_load_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
+    'flow_form_facet_functional': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP,
+                                   _P(_D), _VP],
     }
 
 _LIB = None

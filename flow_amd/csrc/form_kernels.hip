@@ -6,6 +6,8 @@
 //                <= kRedBlocks block partials -> one finishing block
 //                (sum_partials_host), fixed order, no fp atomics: two calls
 //                give the same bits;
+//   facets       assemble(f*ds): one lane per listed exterior facet, the
+//                per-facet integrals to scratch[k], then the same reduction;
 //   load vector  b_i = int f phi_i (project): per-cell values to
 //                scratch[(o*nloc + i)*nc + c], then the gather of
 //                assembly_kernels.hip, as flow_assemble_source does.
@@ -117,16 +119,84 @@ __device__ __forceinline__ double field_at(const flow_form& F,
   return v;
 }
 
-// Runs the program at every point of the rule on cell c.  TD = 0: returns
-// sum_q w_q |det J| out_0(x_q); TD = 1, 2: acc[o][i] += w_q |det J| out_o phi_i.
-template <int NF, int TD>
-__device__ __forceinline__ double form_cell(const flow_form& F, int nc,
-                                            const double* __restrict__ xy, int c,
-                                            double (&acc)[2][6]) {
-  const Geom g = load_geom(xy, nc, c);
-  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
-  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
-  double U[NF > 0 ? NF : 1][6];
+// The program at one point: L its barycentric coordinates on cell c, row its
+// row of the rule (and of the Expression tables).  FACET: the point lies on a
+// facet whose outward unit normal is (n0, n1); the cell kernels pass
+// FACET = false, their programs never hold NORMAL (check_form).
+template <int NF, bool FACET>
+__device__ __forceinline__ void form_point(const flow_form& F,
+                                           const double (&U)[NF > 0 ? NF : 1][6],
+                                           const double X[3], const double Y[3],
+                                           const Geom& g, const double L[3], int row,
+                                           int nc, int c, double n0, double n1,
+                                           double& out0, double& out1) {
+  FormRegs R = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int pc = 0; pc < F.nprog; ++pc) {
+    const int op = F.prog[4 * pc], dst = F.prog[4 * pc + 1];
+    const int a = F.prog[4 * pc + 2], b = F.prog[4 * pc + 3];
+    double v;
+    switch (op) {
+      case FLOW_FORM_OP_CONST: v = F.consts[a]; break;
+      case FLOW_FORM_OP_COORD: {
+        const double* P = a == 0 ? X : Y;
+        v = P[0] * L[0] + P[1] * L[1] + P[2] * L[2];
+        break;
+      }
+      case FLOW_FORM_OP_FIELD:
+        if constexpr (NF > 0) v = field_at<NF>(F, U, a, b, L, g);
+        else v = 0.0;
+        break;
+      case FLOW_FORM_OP_EXPR: {
+        const int nl = F.expr_nl[a];
+        const double* tab = F.tables + F.expr_table[a] + row * nl;
+        const double* e = F.expr[a];
+        double s = 0.0;
+        for (int l = 0; l < nl; ++l) s += e[static_cast<size_t>(l) * nc + c] * tab[l];
+        v = s;
+        break;
+      }
+      case FLOW_FORM_OP_NORMAL:
+        if constexpr (FACET) v = a == 0 ? n0 : n1;
+        else v = 0.0;
+        break;
+      case FLOW_FORM_OP_MOV: v = reg_get(R, a); break;
+      case FLOW_FORM_OP_ADD: v = reg_get(R, a) + reg_get(R, b); break;
+      case FLOW_FORM_OP_SUB: v = reg_get(R, a) - reg_get(R, b); break;
+      case FLOW_FORM_OP_MUL: v = reg_get(R, a) * reg_get(R, b); break;
+      case FLOW_FORM_OP_DIV: v = reg_get(R, a) / reg_get(R, b); break;
+      case FLOW_FORM_OP_NEG: v = -reg_get(R, a); break;
+      case FLOW_FORM_OP_ABS: v = fabs(reg_get(R, a)); break;
+      case FLOW_FORM_OP_SQRT: v = sqrt(reg_get(R, a)); break;
+      // one log and one exp serve ln, exp and pow (a^b = exp(b ln a); the
+      // host sends integer exponents as multiplies and divisions, so pow
+      // only meets the exponents for which a < 0 is undefined anyway):
+      // every library routine is inlined once, which keeps the registers down
+      case FLOW_FORM_OP_POW:
+      case FLOW_FORM_OP_EXP:
+      case FLOW_FORM_OP_LN: {
+        double t = reg_get(R, a);
+        if (op != FLOW_FORM_OP_EXP) t = log(t);
+        if (op == FLOW_FORM_OP_POW) t *= reg_get(R, b);
+        v = op == FLOW_FORM_OP_LN ? t : exp(t);
+        break;
+      }
+      case FLOW_FORM_OP_SIN:
+      case FLOW_FORM_OP_COS: v = form_sincos(reg_get(R, a), op == FLOW_FORM_OP_COS); break;
+      default: {   // FLOW_FORM_OP_OUT
+        const double r = reg_get(R, a);
+        out0 = b == 0 ? r : out0;
+        out1 = b == 0 ? out1 : r;
+        continue;
+      }
+    }
+    reg_set(R, dst, v);
+  }
+}
+
+// the local values of the form's fields on cell c
+template <int NF>
+__device__ __forceinline__ void load_form_fields(const flow_form& F, int nc, int c,
+                                                 double (&U)[NF > 0 ? NF : 1][6]) {
   if constexpr (NF > 0) {
     bool p1 = false, p2 = false;
 #pragma unroll
@@ -157,69 +227,26 @@ __device__ __forceinline__ double form_cell(const flow_form& F, int nc,
       }
     }
   }
+}
+
+// Runs the program at every point of the rule on cell c.  TD = 0: returns
+// sum_q w_q |det J| out_0(x_q); TD = 1, 2: acc[o][i] += w_q |det J| out_o phi_i.
+template <int NF, int TD>
+__device__ __forceinline__ double form_cell(const flow_form& F, int nc,
+                                            const double* __restrict__ xy, int c,
+                                            double (&acc)[2][6]) {
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
   double total = 0.0;
   for (int q = 0; q < F.nq; ++q) {
     const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
     const double w = F.rule[3 * q + 2] * g.adet;
     const double L[3] = {1.0 - xi - eta, xi, eta};
-    FormRegs R = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     double out0 = 0.0, out1 = 0.0;
-    for (int pc = 0; pc < F.nprog; ++pc) {
-      const int op = F.prog[4 * pc], dst = F.prog[4 * pc + 1];
-      const int a = F.prog[4 * pc + 2], b = F.prog[4 * pc + 3];
-      double v;
-      switch (op) {
-        case FLOW_FORM_OP_CONST: v = F.consts[a]; break;
-        case FLOW_FORM_OP_COORD: {
-          const double* P = a == 0 ? X : Y;
-          v = P[0] * L[0] + P[1] * L[1] + P[2] * L[2];
-          break;
-        }
-        case FLOW_FORM_OP_FIELD:
-          if constexpr (NF > 0) v = field_at<NF>(F, U, a, b, L, g);
-          else v = 0.0;
-          break;
-        case FLOW_FORM_OP_EXPR: {
-          const int nl = F.expr_nl[a];
-          const double* tab = F.tables + F.expr_table[a] + q * nl;
-          const double* e = F.expr[a];
-          double s = 0.0;
-          for (int l = 0; l < nl; ++l) s += e[static_cast<size_t>(l) * nc + c] * tab[l];
-          v = s;
-          break;
-        }
-        case FLOW_FORM_OP_MOV: v = reg_get(R, a); break;
-        case FLOW_FORM_OP_ADD: v = reg_get(R, a) + reg_get(R, b); break;
-        case FLOW_FORM_OP_SUB: v = reg_get(R, a) - reg_get(R, b); break;
-        case FLOW_FORM_OP_MUL: v = reg_get(R, a) * reg_get(R, b); break;
-        case FLOW_FORM_OP_DIV: v = reg_get(R, a) / reg_get(R, b); break;
-        case FLOW_FORM_OP_NEG: v = -reg_get(R, a); break;
-        case FLOW_FORM_OP_ABS: v = fabs(reg_get(R, a)); break;
-        case FLOW_FORM_OP_SQRT: v = sqrt(reg_get(R, a)); break;
-        // one log and one exp serve ln, exp and pow (a^b = exp(b ln a); the
-        // host sends integer exponents as multiplies and divisions, so pow
-        // only meets the exponents for which a < 0 is undefined anyway):
-        // every library routine is inlined once, which keeps the registers down
-        case FLOW_FORM_OP_POW:
-        case FLOW_FORM_OP_EXP:
-        case FLOW_FORM_OP_LN: {
-          double t = reg_get(R, a);
-          if (op != FLOW_FORM_OP_EXP) t = log(t);
-          if (op == FLOW_FORM_OP_POW) t *= reg_get(R, b);
-          v = op == FLOW_FORM_OP_LN ? t : exp(t);
-          break;
-        }
-        case FLOW_FORM_OP_SIN:
-        case FLOW_FORM_OP_COS: v = form_sincos(reg_get(R, a), op == FLOW_FORM_OP_COS); break;
-        default: {   // FLOW_FORM_OP_OUT
-          const double r = reg_get(R, a);
-          out0 = b == 0 ? r : out0;
-          out1 = b == 0 ? out1 : r;
-          continue;
-        }
-      }
-      reg_set(R, dst, v);
-    }
+    form_point<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out0, out1);
     if constexpr (TD == 0) {
       total += w * out0;
     } else {
@@ -240,6 +267,37 @@ __device__ __forceinline__ double form_cell(const flow_form& F, int nc,
         }
       }
     }
+  }
+  return total;
+}
+
+// The integral of output 0 over local facet lf of cell c: the rule's rows
+// lf*nq .. lf*nq + nq - 1 (reference coordinates on that facet, weights
+// summing to 1) scaled by the facet's length |det J| |grad lambda_lf|; the
+// outward unit normal is -grad(lambda_lf) / |grad lambda_lf|.
+template <int NF>
+__device__ __forceinline__ double form_facet(const flow_form& F, int nc,
+                                             const double* __restrict__ xy, int c,
+                                             int lf) {
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
+  // (selects, not g.gl[lf]: a run-time index would put g in scratch memory)
+  const double gx = lf == 0 ? g.gl[0][0] : (lf == 1 ? g.gl[1][0] : g.gl[2][0]);
+  const double gy = lf == 0 ? g.gl[0][1] : (lf == 1 ? g.gl[1][1] : g.gl[2][1]);
+  const double gn = sqrt(gx * gx + gy * gy);
+  const double n0 = -gx / gn, n1 = -gy / gn;
+  const double len = g.adet * gn;
+  double total = 0.0;
+  for (int j = 0; j < F.nq; ++j) {
+    const int row = lf * F.nq + j;
+    const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    double out0 = 0.0, out1 = 0.0;
+    form_point<NF, true>(F, U, X, Y, g, L, row, nc, c, n0, n1, out0, out1);
+    total += F.rule[3 * row + 2] * len * out0;
   }
   return total;
 }
@@ -285,7 +343,26 @@ __global__ __launch_bounds__(kBlock) void form_cell_kernel(
   }
 }
 
-static int check_form(const flow_form* F) {
+// one facet per lane: scratch[k] = the integral over facet k of the list
+// (cell, local facet); a facet outside the mesh gives NaN, not a stray read
+template <int NF>
+__global__ __launch_bounds__(kBlock) void form_facet_kernel(
+    int nc, int nfacets, const int* __restrict__ fcell,
+    const int* __restrict__ flocal, const double* __restrict__ xy,
+    const flow_form F, double* __restrict__ scratch) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nfacets) return;
+  const int c = fcell[k], lf = flocal[k];
+  if (c < 0 || c >= nc || lf < 0 || lf > 2) {
+    scratch[k] = __builtin_nan("");
+    return;
+  }
+  scratch[k] = form_facet<NF>(F, nc, xy, c, lf);
+}
+
+// rows: the rule holds rows * nq points (1: cells; 3: the three local
+// facets); facet: NORMAL is legal
+static int check_form(const flow_form* F, int rows = 1, bool facet = false) {
   FLOW_REQUIRE(F, "form");
   FLOW_REQUIRE(F->nprog >= 1 && F->nprog <= FLOW_FORM_MAX_PROGRAM,
                "form program length");
@@ -295,7 +372,7 @@ static int check_form(const flow_form* F) {
   FLOW_REQUIRE(F->nexpr >= 0 && F->nexpr <= FLOW_FORM_MAX_EXPRESSIONS,
                "form expressions");
   FLOW_REQUIRE(F->nout == 1 || F->nout == 2, "form outputs");
-  FLOW_REQUIRE(F->nq >= 1 && F->nq <= FLOW_FORM_MAX_POINTS && F->rule,
+  FLOW_REQUIRE(F->nq >= 1 && rows * F->nq <= FLOW_FORM_MAX_POINTS && F->rule,
                "form quadrature rule");
   for (int k = 0; k < F->nfield; ++k) {
     FLOW_REQUIRE(F->field[k], "form field pointer");
@@ -306,7 +383,7 @@ static int check_form(const flow_form* F) {
     FLOW_REQUIRE(F->expr[k] && F->expr_nl[k] >= 1 && F->expr_nl[k] <= 21,
                  "form expression lattice");
     FLOW_REQUIRE(F->tables && F->expr_table[k] >= 0 &&
-                     F->expr_table[k] + F->nq * F->expr_nl[k] <= F->ntables,
+                     F->expr_table[k] + rows * F->nq * F->expr_nl[k] <= F->ntables,
                  "form expression table");
   }
   // every instruction: registers, operand indices and outputs in range (the
@@ -315,8 +392,10 @@ static int check_form(const flow_form* F) {
   for (int pc = 0; pc < F->nprog; ++pc) {
     const int op = F->prog[4 * pc], dst = F->prog[4 * pc + 1];
     const int a = F->prog[4 * pc + 2], b = F->prog[4 * pc + 3];
-    FLOW_REQUIRE(op >= FLOW_FORM_OP_CONST && op <= FLOW_FORM_OP_OUT, "form opcode");
-    const bool reg_a = op >= FLOW_FORM_OP_MOV;
+    FLOW_REQUIRE((op >= FLOW_FORM_OP_CONST && op <= FLOW_FORM_OP_OUT) ||
+                     (facet && op == FLOW_FORM_OP_NORMAL),
+                 facet ? "form opcode" : "form opcode (NORMAL: facet integrals only)");
+    const bool reg_a = op >= FLOW_FORM_OP_MOV && op <= FLOW_FORM_OP_OUT;
     const bool reg_b = op >= FLOW_FORM_OP_ADD && op <= FLOW_FORM_OP_POW;
     FLOW_REQUIRE(dst >= 0 && dst < FLOW_FORM_REGISTERS, "form register");
     FLOW_REQUIRE(!reg_a || (a >= 0 && a < FLOW_FORM_REGISTERS), "form register");
@@ -333,6 +412,9 @@ static int check_form(const flow_form* F) {
         break;
       case FLOW_FORM_OP_EXPR:
         FLOW_REQUIRE(a >= 0 && a < F->nexpr, "form expression index");
+        break;
+      case FLOW_FORM_OP_NORMAL:
+        FLOW_REQUIRE(a == 0 || a == 1, "form normal component");
         break;
       case FLOW_FORM_OP_OUT:
         FLOW_REQUIRE(b >= 0 && b < F->nout, "form output");
@@ -372,6 +454,30 @@ static int launch_cells(const flow_mesh* mesh, const flow_form* F, int cb, int c
     default:
     FLOW_FORM_LOAD_CASE(6)
 #undef FLOW_FORM_LOAD_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+static int launch_facets(const flow_mesh* mesh, const flow_form* F, int nfacets,
+                         const int* fcell, const int* flocal, double* scratch,
+                         hipStream_t st) {
+  const dim3 grid((nfacets + kBlock - 1) / kBlock);
+  switch (F->nfield) {
+#define FLOW_FORM_FACET_CASE(NF)                                                 \
+    case NF:                                                                     \
+      hipLaunchKernelGGL((form_facet_kernel<NF>), grid, dim3(kBlock), 0, st,     \
+                         mesh->nc, nfacets, fcell, flocal, mesh->xy, *F, scratch); \
+      break;
+    FLOW_FORM_FACET_CASE(0)
+    FLOW_FORM_FACET_CASE(1)
+    FLOW_FORM_FACET_CASE(2)
+    FLOW_FORM_FACET_CASE(3)
+    FLOW_FORM_FACET_CASE(4)
+    FLOW_FORM_FACET_CASE(5)
+    default:
+    FLOW_FORM_FACET_CASE(6)
+#undef FLOW_FORM_FACET_CASE
   }
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
@@ -420,4 +526,31 @@ extern "C" int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
   const int nl = V->deg == 1 ? 3 : 6;
   return gather(V->n, form->nout, V->vptr, V->vsrc, scratch,
                 static_cast<size_t>(nl) * mesh->nc, b, st, 0, V->r0, V->r1);
+}
+
+extern "C" int flow_form_facet_functional(const flow_mesh* mesh, const flow_form* form,
+                                          int nfacets, const int* facet_cell,
+                                          const int* facet_local, double* scratch,
+                                          double* work, double* result_host,
+                                          void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "facet integrals on strips");
+  if ((rc = check_form(form, 3, true))) return rc;
+  FLOW_REQUIRE(form->nout == 1, "a functional has one output");
+  FLOW_REQUIRE(nfacets >= 0 && result_host, "facet count / result pointer");
+  if (nfacets == 0) {
+    *result_host = 0.0;
+    return FLOW_OK;
+  }
+  FLOW_REQUIRE(facet_cell && facet_local, "facet lists");
+  FLOW_REQUIRE(scratch && work, "pointers");
+  hipStream_t st = as_stream(stream);
+  if ((rc = launch_facets(mesh, form, nfacets, facet_cell, facet_local, scratch, st)))
+    return rc;
+  const int nparts = grid_for(nfacets, kBlock, kRedBlocks);
+  hipLaunchKernelGGL(form_sum_kernel, dim3(nparts), dim3(kBlock), 0, st, 0, nfacets,
+                     scratch, work);
+  FLOW_CHECK_LAUNCH();
+  return sum_partials_host(work, nparts, result_host, st);
 }

@@ -9,6 +9,7 @@ GPU box, so the counterpart drivers import these names from here instead.
 from .mesh import (                                             # noqa: F401
     Mesh, Point, RectangleMesh, UnitSquareMesh, rectangle_with_hole,
     karman_channel, karman_channel_graded, heater_box, heater_box_coarse,
+    MeshFunction, FacetFunction,
     )
 from .space import (                                            # noqa: F401
     FunctionSpace, VectorFunctionSpace, FiniteElement, VectorElement,
@@ -21,8 +22,8 @@ from .bcs import DirichletBC, SubDomain                         # noqa: F401
 from .io import XDMFFile, mpi_comm_world, read_mesh             # noqa: F401
 from .space import MixedFunctionSpace                           # noqa: F401
 from .forms import (                                            # noqa: F401
-    dx, SpatialCoordinate, as_vector, sqrt, exp, ln, sin, cos, dot, inner,
-    grad, div, curl,
+    dx, ds, Measure, FacetNormal, SpatialCoordinate, as_vector, sqrt, exp,
+    ln, sin, cos, dot, inner, grad, div, curl,
     )
 from ..message import begin, end, info                          # noqa: F401
 

@@ -21,21 +21,53 @@ class SubDomain(object):
     def inside(self, x, on_boundary):   # pragma: no cover - user overrides
         raise NotImplementedError
 
+    def mark(self, markers, value):
+        '''Set `value` on the facets of a facet MeshFunction where `inside`
+        holds at both vertices and the midpoint (facet_marked): on_boundary
+        is True on the exterior facets and False on the interior ones.'''
+        mesh = markers.mesh
+        sel = numpy.zeros(mesh.num_edges(), dtype=bool)
+        bf = mesh.bfacets
+        interior = numpy.ones(mesh.num_edges(), dtype=bool)
+        interior[bf] = False
+        interior = numpy.nonzero(interior)[0]
+        sel[bf] = facet_marked(self, mesh, bf, True)
+        sel[interior] = facet_marked(self, mesh, interior, False)
+        markers.set_where(sel, value)
+        return
 
-def _eval_inside(where, x):
+
+def _eval_inside(where, x, on_boundary=True):
     '''x: (n, 2) -> bool (n,).  Tries a vectorised call first (x[0], x[1] are
     arrays), falls back to point-by-point evaluation.'''
     n = len(x)
     if isinstance(where, str):
         assert where == 'on_boundary'
-        return numpy.ones(n, dtype=bool)
+        return numpy.full(n, bool(on_boundary))
     fun = where.inside if hasattr(where, 'inside') else where
     try:
-        res = fun(x.T, True)
+        res = fun(x.T, on_boundary)
         res = numpy.broadcast_to(numpy.asarray(res, dtype=bool), (n,))
         return res.copy()
     except (ValueError, TypeError):
-        return numpy.array([bool(fun(xi, True)) for xi in x], dtype=bool)
+        return numpy.array([bool(fun(xi, on_boundary)) for xi in x], dtype=bool)
+
+
+def facet_marked(where, mesh, facets, on_boundary):
+    '''The facet test of DOLFIN's topological search, shared by DirichletBC
+    and SubDomain.mark: `inside(x, on_boundary)` holds at both vertices and
+    the midpoint of each facet (edge ids `facets`).  Bool per facet.'''
+    facets = numpy.asarray(facets)
+    if len(facets) == 0:
+        return numpy.zeros(0, dtype=bool)
+    ev = mesh.edges[facets]                             # (m, 2)
+    p0 = mesh.points[ev[:, 0]]
+    p1 = mesh.points[ev[:, 1]]
+    return (
+        _eval_inside(where, p0, on_boundary)
+        & _eval_inside(where, p1, on_boundary)
+        & _eval_inside(where, 0.5 * (p0 + p1), on_boundary)
+        )
 
 
 class DirichletBC(object):
@@ -83,15 +115,8 @@ class DirichletBC(object):
             mesh = self.space.mesh()
             layout = self.space.layout
             bf = mesh.bfacets
-            ev = mesh.edges[bf]                         # (Nb, 2)
-            p0 = mesh.points[ev[:, 0]]
-            p1 = mesh.points[ev[:, 1]]
-            marked = (
-                _eval_inside(self.where, p0)
-                & _eval_inside(self.where, p1)
-                & _eval_inside(self.where, 0.5 * (p0 + p1))
-                )
-            ev = ev[marked]
+            marked = facet_marked(self.where, mesh, bf, True)
+            ev = mesh.edges[bf][marked]                 # (m, 2)
             dofs = [layout.vertex_dofs[ev.ravel()]]
             if layout.degree == 2:
                 dofs.append(layout.edge_dofs[bf[marked]])

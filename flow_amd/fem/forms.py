@@ -32,6 +32,17 @@ estimate.  q <= 30.  The rules are reference.triangle_rule(q) (collapsed
 Gauss-Jacobi, exact for total degree q), not FFC's point sets: for integrands
 that are polynomials within the degree the results are dolfin's; otherwise
 they differ from dolfin's by quadrature error.
+
+Exterior facets: `f*ds` integrates over the boundary edges of the mesh, with
+dolfin-2017's spellings -- ds(mesh), ds(domain=mesh), ds(1),
+ds(subdomain_id=1), ds(metadata={...}), ds(degree=q) and
+Measure('ds', domain=mesh, subdomain_data=markers) then ds(k), where markers
+is a MeshFunction('size_t', mesh, 1) (or FacetFunction) filled by
+SubDomain.mark.  FacetNormal(mesh) (the outward unit normal, degree 0) is
+legal only in ds integrands.  The rule is reference.line_rule(q) on each
+edge (Gauss-Legendre, exact for degree q).  Rank-0 forms add and subtract:
+assemble(f*dx + g*ds(1) - h*ds(2)) sums the parts in the order written.
+No interior facets (dS), no facet integrals on strips.
 '''
 import numbers
 
@@ -46,15 +57,16 @@ MAX_FIELDS = 6
 MAX_EXPRESSIONS = 4
 OPS = {name: i for i, name in enumerate((
     'const', 'coord', 'field', 'expr', 'mov', 'add', 'sub', 'mul', 'div', 'pow',
-    'neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos', 'out'))}
+    'neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos', 'out', 'normal'))}
 UNARY = ('neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos')
 BINARY = ('add', 'sub', 'mul', 'div', 'pow')
 
 
 # -- scalar trees --------------------------------------------------------------
 # ('num', v) ('const', Constant, i) ('x', d) ('field', Function, i, d)
-# (d = 0 value, 1 d/dx, 2 d/dy) ('expr', Expression, i) ('powi', a, n) and
-# (op, a[, b]) for the UNARY / BINARY ops.  Objects inside compare by identity.
+# (d = 0 value, 1 d/dx, 2 d/dy) ('expr', Expression, i) ('n', d) (component
+# d of the outward unit normal, ds only) ('powi', a, n) and (op, a[, b]) for
+# the UNARY / BINARY ops.  Objects inside compare by identity.
 ZERO = ('num', 0.0)
 ONE = ('num', 1.0)
 
@@ -116,7 +128,7 @@ def s_powi(a, n):
 def s_diff(n, d):
     '''d n / d x_d (d = 0, 1), by the chain rule.'''
     k = n[0]
-    if k in ('num', 'const'):
+    if k in ('num', 'const', 'n'):      # (the normal: constant on a facet)
         return ZERO
     if k == 'x':
         return ONE if n[1] == d else ZERO
@@ -501,6 +513,26 @@ def SpatialCoordinate(mesh):
     return FormExpr([('x', 0), ('x', 1)], (2,), 1, mesh)
 
 
+def FacetNormal(mesh):
+    '''The outward unit normal of the domain: ds integrands only (constant on
+    every facet of an affine mesh, degree 0).'''
+    return FormExpr([('n', 0), ('n', 1)], (2,), 0, mesh)
+
+
+def has_normal(n):
+    '''Whether a scalar tree reads the facet normal.'''
+    if n[0] == 'n':
+        return True
+    return n[0] in UNARY + BINARY + ('powi',) and any(
+        has_normal(c) for c in n[1:] if isinstance(c, tuple))
+
+
+def check_no_normal(expr, where):
+    if any(has_normal(t) for t in expr.scalar_trees()):
+        raise ValueError('FacetNormal is defined on exterior facets only: it '
+                         'cannot be used in %s' % where)
+
+
 # -- measure and forms -----------------------------------------------------------
 def _quadrature_degree(params):
     if not params:
@@ -509,42 +541,126 @@ def _quadrature_degree(params):
     return None if q is None else int(q)
 
 
+_INTEGRAL_TYPES = {'dx': 'cell', 'cell': 'cell', 'ds': 'exterior_facet',
+                   'exterior_facet': 'exterior_facet'}
+
+
+def _is_mesh(obj):
+    return hasattr(obj, 'num_cells') and hasattr(obj, 'bfacets')
+
+
 class Measure(object):
-    '''`dx`, `dx(mesh)`, `dx(domain=mesh)`, `dx(metadata={...})`.'''
+    '''`dx` over the cells, `ds` over the exterior facets (UFL's
+    Measure(integral_type, domain, subdomain_id, metadata, subdomain_data)).
+    Calls: `dx(mesh)`, `dx(domain=mesh)`, `dx(metadata={...})`, `dx(degree=q)`;
+    `ds` also takes a subdomain id, `ds(1)` / `ds(subdomain_id=1)`, which
+    selects the facets its subdomain_data (a facet MeshFunction) marks 1.'''
 
-    def __init__(self, mesh=None, metadata=None):
-        self.mesh = mesh
+    def __init__(self, integral_type='dx', domain=None,
+                 subdomain_id='everywhere', metadata=None, subdomain_data=None):
+        if integral_type not in _INTEGRAL_TYPES:
+            raise NotImplementedError(
+                'integral type %r: only dx (cells) and ds (exterior facets) '
+                'are supported' % (integral_type,))
+        self.integral_type = _INTEGRAL_TYPES[integral_type]
+        self.mesh = domain
+        self.subdomain_id = subdomain_id
         self.metadata = dict(metadata or {})
+        self.subdomain_data = subdomain_data
+        if self.integral_type == 'cell' and (
+                subdomain_id != 'everywhere' or subdomain_data is not None):
+            raise NotImplementedError('cell subdomains: dx integrates over '
+                                      'the whole mesh')
 
-    def __call__(self, domain=None, metadata=None, degree=None):
+    def __call__(self, subdomain_id=None, metadata=None, domain=None,
+                 subdomain_data=None, degree=None):
+        if _is_mesh(subdomain_id):          # ds(mesh), dx(mesh)
+            subdomain_id, domain = None, subdomain_id
         md = dict(self.metadata)
         md.update(metadata or {})
         if degree is not None:
             md['quadrature_degree'] = degree
-        return Measure(domain if domain is not None else self.mesh, md)
+        return Measure(
+            'dx' if self.integral_type == 'cell' else 'ds',
+            domain if domain is not None else self.mesh,
+            self.subdomain_id if subdomain_id is None else subdomain_id, md,
+            self.subdomain_data if subdomain_data is None else subdomain_data)
 
     def __rmul__(self, other):
         f = as_form(other)
         if f.shape:
             raise ValueError('only scalar integrands can be integrated: the '
                              'integrand has shape %r' % (f.shape,))
-        return Form(f, _join_mesh(f.mesh, self.mesh), self.metadata)
+        if self.integral_type == 'cell':
+            check_no_normal(f, 'a dx integral')
+            return Form(f, _join_mesh(f.mesh, self.mesh), self.metadata)
+        mesh = _join_mesh(f.mesh, self.mesh)
+        if self.subdomain_data is not None:
+            mesh = _join_mesh(mesh, self.subdomain_data.mesh)
+        return Form(f, mesh, self.metadata, 'exterior_facet',
+                    self.subdomain_id, self.subdomain_data)
 
 
-dx = Measure()
+dx = Measure('dx')
+ds = Measure('ds')
 
 
 class Form(object):
-    '''A rank-0 form: a scalar integrand over the cells of a mesh.'''
+    '''A rank-0 form: a scalar integrand over the cells of a mesh
+    (integral_type 'cell') or over its exterior facets ('exterior_facet':
+    all of them for subdomain_id 'everywhere', else those whose
+    subdomain_data marker equals subdomain_id).  Forms add and subtract
+    into a FormSum.'''
 
-    def __init__(self, integrand, mesh, metadata):
+    def __init__(self, integrand, mesh, metadata, integral_type='cell',
+                 subdomain_id='everywhere', subdomain_data=None):
         self.integrand = integrand
         self.mesh = mesh
         self.metadata = metadata
+        self.integral_type = integral_type
+        self.subdomain_id = subdomain_id
+        self.subdomain_data = subdomain_data
 
     def degree(self):
         q = _quadrature_degree(self.metadata)
         return self.integrand.deg if q is None else q
+
+    def terms(self):
+        return [(1.0, self)]
+
+    def __add__(self, other):
+        return FormSum.of(self, other, 1.0)
+
+    def __radd__(self, other):
+        if isinstance(other, numbers.Real) and other == 0:     # sum([...])
+            return FormSum(self.terms())
+        return NotImplemented
+
+    def __sub__(self, other):
+        return FormSum.of(self, other, -1.0)
+
+    def __neg__(self):
+        return FormSum([(-s, f) for s, f in self.terms()])
+
+
+class FormSum(Form):
+    '''A signed sum of rank-0 forms; assemble() adds the parts in the order
+    they were written.'''
+
+    def __init__(self, terms):
+        self._terms = list(terms)
+
+    @staticmethod
+    def of(a, b, sign):
+        if not isinstance(b, Form):
+            return NotImplemented
+        return FormSum(a.terms() + [(sign * s, f) for s, f in b.terms()])
+
+    def terms(self):
+        return list(self._terms)
+
+    def degree(self):
+        raise TypeError('a sum of forms has one degree per part')
 
 
 def check_degree(q):
@@ -566,7 +682,12 @@ class Program(object):
     (('num', v) or (Constant, i)), field components (Function, i) and
     Expression components (Expression, i), in slot order.'''
 
-    def __init__(self, trees):
+    def __init__(self, trees, facet=False):
+        '''facet: the program runs on exterior facets, where the normal
+        exists (ValueError if a tree reads it otherwise).'''
+        if not facet and any(has_normal(t) for t in trees):
+            raise ValueError('FacetNormal is defined on exterior facets only: '
+                             'integrate over ds')
         self.code = []
         self.consts = []
         self.fields = []
@@ -618,7 +739,7 @@ class Program(object):
     def need(n):
         '''Registers the tree needs (Sethi-Ullman).'''
         k = n[0]
-        if k in ('num', 'const', 'x', 'field', 'expr'):
+        if k in ('num', 'const', 'x', 'field', 'expr', 'n'):
             return 1
         if k in UNARY:
             return Program.need(n[1])
@@ -637,6 +758,8 @@ class Program(object):
             self._emit('const', base, self._const((n[1], n[2])))
         elif k == 'x':
             self._emit('coord', base, n[1])
+        elif k == 'n':
+            self._emit('normal', base, n[1])
         elif k == 'field':
             self._emit('field', base, self._slot(
                 self.fields, (n[1], n[2]), MAX_FIELDS, 'field components'),
@@ -690,5 +813,5 @@ def form_mesh(expr, mesh=None):
     m = _join_mesh(expr.mesh, mesh)
     if m is None:
         raise ValueError('the integrand carries no mesh: integrate over '
-                         'dx(mesh)')
+                         'dx(mesh) or ds(mesh)')
     return m

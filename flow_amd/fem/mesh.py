@@ -202,6 +202,61 @@ class Mesh(object):
         return mask
 
 
+_MESH_FUNCTION_TYPES = {'size_t': numpy.uintp, 'int': numpy.intc,
+                        'bool': numpy.bool_, 'double': numpy.float64}
+
+
+class MeshFunction(object):
+    '''dolfin's MeshFunction(value_type, mesh, dim, value) for facets
+    (dim = 1): one value per edge, in `mesh.edges` order.  SubDomain.mark
+    fills it; `ds` reads it as subdomain_data.  `array()` is a read-only view:
+    changes go through set_all / mark / item assignment, which bump
+    `version` (the device facet lists of ops.assemble are cached against it).'''
+
+    def __init__(self, value_type, mesh, dim, value=0):
+        if value_type not in _MESH_FUNCTION_TYPES:
+            raise ValueError('MeshFunction value type %r: one of %s'
+                             % (value_type, sorted(_MESH_FUNCTION_TYPES)))
+        if dim != 1:
+            raise NotImplementedError('MeshFunction of dimension %r: only '
+                                      'facet markers (dim 1)' % (dim,))
+        self.mesh = mesh
+        self.dim = dim
+        self.value_type = value_type
+        self._values = numpy.full(mesh.num_edges(), value,
+                                  dtype=_MESH_FUNCTION_TYPES[value_type])
+        self.version = 0
+
+    def size(self):
+        return len(self._values)
+
+    def array(self):
+        view = self._values.view()
+        view.flags.writeable = False
+        return view
+
+    def set_all(self, value):
+        self._values[:] = value
+        self.version += 1
+
+    def __getitem__(self, i):
+        return self._values[i]
+
+    def __setitem__(self, i, value):
+        self._values[i] = value
+        self.version += 1
+
+    def set_where(self, mask, value):
+        '''Set `value` on the facets of a boolean mask over the edges.'''
+        self._values[mask] = value
+        self.version += 1
+
+
+def FacetFunction(value_type, mesh, value=0):
+    '''MeshFunction(value_type, mesh, 1, value) under its older name.'''
+    return MeshFunction(value_type, mesh, 1, value)
+
+
 def _quad_cells(nx, ny, diagonal, vid, mid=None):
     '''Triangles of a structured nx x ny quad grid.  vid(ix, iy) -> vertex id
     arrays; mid(ix, iy) -> centre-vertex ids for 'crossed'.

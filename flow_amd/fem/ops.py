@@ -794,40 +794,48 @@ def errornorm(exact, uh, degree_rise=3):
 _FORM_TABLES = {}
 
 
-def _form_tables(q, expr_degrees):
-    '''Rule (nq x 3: xi, eta, weight) and the P_k basis tables of the
-    Expression operands at its points, uploaded once per (degree, lattice
-    degrees): an upload drains the stream, and time loops integrate the same
-    forms every step.  (The program and the constants need no upload: they
-    travel with the launch.)'''
-    key = (q, expr_degrees, str(device.get()))
+def _form_tables(q, expr_degrees, facet=False):
+    '''Rule (nq x 3: xi, eta, weight; on facets 3*nq rows, the points of
+    local facets 0, 1, 2: reference.facet_rule) and the P_k basis tables of
+    the Expression operands at its points, uploaded once per (degree, lattice
+    degrees, cells | facets): an upload drains the stream, and time loops
+    integrate the same forms every step.  (The program and the constants
+    need no upload: they travel with the launch.)  Returns (rule, tables,
+    table offsets, nq per cell or facet, doubles in tables).'''
+    key = (q, expr_degrees, facet, str(device.get()))
     held = _FORM_TABLES.get(key)
     if held is None:
-        pts, wts = reference.triangle_rule(q)
-        if len(wts) > _hip.FORM_MAX_POINTS:
+        if facet:
+            rule = reference.facet_rule(q)
+            pts = rule[:, :2]
+            nq = len(rule) // 3
+        else:
+            pts, wts = reference.triangle_rule(q)
+            rule = numpy.concatenate([pts, wts[:, None]], axis=1)
+            nq = len(wts)
+        if len(rule) > _hip.FORM_MAX_POINTS:
             raise ValueError('quadrature degree %d: %d points, the limit is %d'
-                             % (q, len(wts), _hip.FORM_MAX_POINTS))
-        rule = numpy.concatenate([pts, wts[:, None]], axis=1)
+                             % (q, len(rule), _hip.FORM_MAX_POINTS))
         offsets = []
         tabs = [numpy.zeros(1)]
         off = 1
         for k in expr_degrees:
-            t = reference.tabulate(k, pts)              # (nq, nl)
+            t = reference.tabulate(k, pts)              # (points, nl)
             offsets.append(off)
             tabs.append(t.reshape(-1))
             off += t.size
         tables = numpy.concatenate(tabs)
         held = (device.to_device(rule.reshape(-1).copy()),
-                device.to_device(tables), offsets, len(wts), int(tables.size))
+                device.to_device(tables), offsets, nq, int(tables.size))
         if len(_FORM_TABLES) >= 64:
             _FORM_TABLES.clear()
         _FORM_TABLES[key] = held
     return held
 
 
-def _form_struct(prog, mesh, q):
+def _form_struct(prog, mesh, q, facet=False):
     '''flow_form of a compiled forms.Program on `mesh` with the degree-q
-    rule.  Returns (struct, keepalive).'''
+    rule of the cells, or of the facets.  Returns (struct, keepalive).'''
     fs = _hip.FormS()
     fs.nprog = len(prog.code)
     for i, ins in enumerate(prog.code):
@@ -852,7 +860,7 @@ def _form_struct(prog, mesh, q):
             lay.dev('cell_dofs'), lay.nloc * nc, 'cell_dofs').value
         keep.append(f.data)
     expr_degrees = tuple(int(e.degree) for e, _ in prog.exprs)
-    rule, tables, offsets, nq, ntables = _form_tables(q, expr_degrees)
+    rule, tables, offsets, nq, ntables = _form_tables(q, expr_degrees, facet)
     fs.nexpr = len(prog.exprs)
     coefs = {}
     for i, (e, comp) in enumerate(prog.exprs):
@@ -866,7 +874,7 @@ def _form_struct(prog, mesh, q):
         fs.expr_table[i] = offsets[i]
         keep.append(coef.values)
     fs.nq = nq
-    fs.rule = _hip.f64(rule, 3 * nq, 'rule').value
+    fs.rule = _hip.f64(rule, (9 if facet else 3) * nq, 'rule').value
     fs.tables = _hip.f64(tables, ntables, 'tables').value
     fs.ntables = ntables
     fs.nout = prog.nout
@@ -882,28 +890,85 @@ def _no_strips(what):
 
 
 def assemble(form):
-    '''assemble(f*dx): the integral of a scalar integrand over the mesh, a
-    float.  Fixed-order reduction on the device: the same bits on every
-    call.'''
+    '''assemble(f*dx), assemble(f*ds(k)), and signed sums of such forms: the
+    integral of a scalar integrand over the cells or the exterior facets of
+    the mesh, a float.  Fixed-order reductions on the device and the parts of
+    a sum added in the order written: the same bits on every call.'''
     from . import forms
     if not isinstance(form, forms.Form):
         raise TypeError('assemble takes a rank-0 form f*dx (got %r): forms '
                         'of test and trial functions are not supported'
                         % (type(form),))
     _no_strips('assemble')
+    if isinstance(form, forms.FormSum):
+        total = 0.0
+        for sign, part in form.terms():
+            total += sign * assemble(part)
+        return total
     lib = _hip.lib()
     mesh = forms.form_mesh(form.integrand, form.mesh)
     q = forms.check_degree(form.degree())
-    prog = forms.Program([form.integrand.comps])
-    fs, keep = _form_struct(prog, mesh, q)
+    facet = form.integral_type == 'exterior_facet'
+    prog = forms.Program([form.integrand.comps], facet=facet)
+    fs, keep = _form_struct(prog, mesh, q, facet)
     res = ctypes.c_double(0.0)
-    _hip.check(lib.flow_form_functional(
-        ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs),
-        _hip.f64(scratch(mesh, mesh.num_cells())),
-        _hip.f64(work(_hip.REDUCE_WORK)), ctypes.byref(res), _hip.stream()
-        ))
+    if facet:
+        cells, local, nf = facet_lists(mesh, form.subdomain_data,
+                                       form.subdomain_id)
+        _hip.check(lib.flow_form_facet_functional(
+            ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs), nf,
+            _hip.i32(cells, nf, 'facet cells'),
+            _hip.i32(local, nf, 'facet local indices'),
+            _hip.f64(scratch(mesh, max(nf, 1))),
+            _hip.f64(work(_hip.REDUCE_WORK)), ctypes.byref(res), _hip.stream()
+            ))
+    else:
+        _hip.check(lib.flow_form_functional(
+            ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs),
+            _hip.f64(scratch(mesh, mesh.num_cells())),
+            _hip.f64(work(_hip.REDUCE_WORK)), ctypes.byref(res), _hip.stream()
+            ))
     del keep
     return res.value
+
+
+def facet_lists(mesh, markers=None, subdomain_id='everywhere'):
+    '''The exterior facets a ds integral runs over, as device int32 arrays
+    (owning cell, local facet index) and their count: every boundary facet
+    for subdomain_id 'everywhere', else those whose marker equals
+    subdomain_id, in boundary-facet order.  Cached on the mesh against the
+    markers' version: a time loop uploads nothing, re-marking re-selects.'''
+    everywhere = subdomain_id in (None, 'everywhere')
+    if markers is None and not everywhere:
+        raise ValueError('ds(%r) needs markers: Measure(\'ds\', domain=mesh, '
+                         'subdomain_data=markers)' % (subdomain_id,))
+    if markers is not None and markers.mesh is not mesh:
+        raise ValueError('the facet markers belong to another mesh')
+    cache = mesh._cache.setdefault('facet_lists', {})
+    key = (None if everywhere else id(markers),
+           None if everywhere else subdomain_id, str(device.get()))
+    version = None if everywhere else markers.version
+    held = cache.get(key)
+    if held is not None and held[0] is (None if everywhere else markers) \
+            and held[1] == version:
+        return held[2:]
+    if everywhere:
+        sel = numpy.arange(len(mesh.bfacets))
+    else:
+        sel = numpy.nonzero(markers.array()[mesh.bfacets] == subdomain_id)[0]
+    cells = mesh.bfacet_cell[sel].astype(numpy.int32)
+    local = mesh.bfacet_local[sel].astype(numpy.int32)
+    nf = len(sel)
+    if nf:
+        cells, local = device.to_device(cells), device.to_device(local)
+    else:
+        cells = local = None
+    if len(cache) >= 32:
+        cache.clear()
+    # (the markers are kept alive with the entry: their id stays unique)
+    held = (None if everywhere else markers, version, cells, local, nf)
+    cache[key] = held
+    return held[2:]
 
 
 def form_load_vector(expr, V, form_compiler_parameters=None):
@@ -913,6 +978,7 @@ def form_load_vector(expr, V, form_compiler_parameters=None):
     if expr.shape != (() if V.dim == 1 else (V.dim,)):
         raise ValueError('projecting an expression of shape %r into a space '
                          'with %d components' % (expr.shape, V.dim))
+    forms.check_no_normal(expr, 'project')
     _no_strips('project of an expression')
     lib = _hip.lib()
     mesh = forms.form_mesh(expr, V.mesh())

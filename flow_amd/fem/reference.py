@@ -103,6 +103,35 @@ def triangle_rule(degree):
 
 
 @functools.lru_cache(maxsize=None)
+def line_rule(degree):
+    '''Gauss-Legendre rule on [0, 1], exact for degree <= `degree`.
+    Returns (points (nq,), weights (nq,)), weights sum to 1.'''
+    x, w = numpy.polynomial.legendre.leggauss(degree // 2 + 1)
+    return 0.5 * (x + 1.0), 0.5 * w
+
+
+# local facet i is the edge opposite vertex i, from vertex FACET_VERTICES[i][0]
+# to FACET_VERTICES[i][1] (fem_device.h: facet_v0 / facet_v1)
+FACET_VERTICES = ((1, 2), (0, 2), (0, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def facet_rule(degree):
+    '''line_rule(degree) laid out on the three local facets of the reference
+    triangle: rows (xi, eta, weight), the nq points of facet 0, then 1, then
+    2; point s of facet i has barycentric l_v0 = 1 - s, l_v1 = s.  Weights
+    sum to 1 per facet (the kernel scales them by the facet's length).'''
+    s, w = line_rule(degree)
+    rows = []
+    for v0, v1 in FACET_VERTICES:
+        L = numpy.zeros((len(s), 3))
+        L[:, v0] = 1.0 - s
+        L[:, v1] = s
+        rows.append(numpy.stack([L[:, 1], L[:, 2], w], axis=1))
+    return numpy.concatenate(rows)
+
+
+@functools.lru_cache(maxsize=None)
 def source_matrix(k, deg):
     '''G[l][i] = int_ref psi_l^(k) phi_i^(deg)  (reference area 1/2 included).
     A coefficient given by its P_k lattice values F_l on a cell contributes

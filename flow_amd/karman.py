@@ -235,6 +235,37 @@ class KarmanProblem(object):
     def reynolds(self):
         return ENTRANCE_VELOCITY * 0.04 * self.rho / self.mu
 
+    def forces(self):
+        '''Drag and lift on the obstacle for the current (u0, p0):
+            F = -int_Gamma sigma(u, p) n ds,  sigma = mu (grad u + grad u^T) - p I
+        (the stress of the reference's weak form, 2 mu eps(u):eps(v) - p div v),
+        n the outward normal of the fluid (into the obstacle on Gamma), so F is
+        the force the fluid exerts on the body.  Returns dict(drag=F_x,
+        lift=F_y, c_drag, c_lift) with the coefficients 2 F / (rho U^2 D),
+        D = 0.04 the cylinder's diameter and U = ENTRANCE_VELOCITY (the U of
+        reynolds()).  Two facet integrals over the obstacle's facets (marked
+        once, ObstacleBoundary); not on strips.'''
+        from .fem import forms
+        if getattr(self, '_obstacle_ds', None) is None:
+            markers = fem.MeshFunction('size_t', self.mesh, 1, 0)
+            ObstacleBoundary(self.length).mark(markers, 1)
+            self._obstacle_ds = fem.Measure('ds', domain=self.mesh,
+                                            subdomain_data=markers)(1)
+        n = fem.FacetNormal(self.mesh)
+        gu = forms.grad(self.u0)                # gu[a, b] = d u_a / d x_b
+        p, mu = self.p0, self.mu
+
+        def traction(a):
+            # (sigma n)_a = mu sum_b (d_b u_a + d_a u_b) n_b - p n_a
+            return mu * ((gu[a, 0] + gu[0, a]) * n[0]
+                         + (gu[a, 1] + gu[1, a]) * n[1]) - p * n[a]
+
+        drag = -fem.assemble(traction(0) * self._obstacle_ds)
+        lift = -fem.assemble(traction(1) * self._obstacle_ds)
+        scale = 2.0 / (self.rho * ENTRANCE_VELOCITY**2 * 0.04)
+        return dict(drag=drag, lift=lift, c_drag=scale * drag,
+                    c_lift=scale * lift)
+
     def step(self, tol=1.0e-10, adapt=True):
         '''One pass of the reference's time loop body (:219-286).'''
         u1, p1 = self.stepper.step(

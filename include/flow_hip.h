@@ -1097,6 +1097,8 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
  *   mov    r[dst] = r[a]               add sub mul div pow  r[dst] = r[a] o r[b]
  *   neg abs sqrt exp ln sin cos  r[dst] = f(r[a])
  *   out    output b = r[a]
+ *   normal r[dst] = component a of the outward unit normal (facet
+ *          integrals only: the cell entry points refuse it)
  * The program and the constants travel by value with the launch (constants
  * may change from call to call at no cost); rule and tables are device
  * arrays, uploaded once per program signature and degree by the host. */
@@ -1124,6 +1126,7 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
 #define FLOW_FORM_OP_SIN 15
 #define FLOW_FORM_OP_COS 16
 #define FLOW_FORM_OP_OUT 17
+#define FLOW_FORM_OP_NORMAL 18
 typedef struct {
   int nprog;
   int prog[4 * FLOW_FORM_MAX_PROGRAM];     /* (op, dst, a, b) per instruction */
@@ -1151,6 +1154,20 @@ typedef struct {
 int flow_form_functional(const flow_mesh* mesh, const flow_form* form,
                          double* scratch, double* work, double* result_host,
                          void* stream);
+
+/* assemble(f*ds): the integral of output 0 over a list of exterior facets,
+ * facet k being local facet facet_local[k] (the edge opposite that vertex)
+ * of cell facet_cell[k] (device int32 arrays of nfacets entries).  The rule
+ * holds 3*nq rows: the nq points of local facet 0, then 1, then 2, in
+ * reference coordinates, weights summing to 1 per facet (scaled by the
+ * facet's length); the Expression tables hold 3*nq rows to match.  Fixed-order
+ * reduction as flow_form_functional: bitwise reproducible.  nfacets == 0:
+ * 0.0, nothing launched.  Not on strips.  scratch: nfacets doubles; work:
+ * FLOW_REDUCE_WORK doubles. */
+int flow_form_facet_functional(const flow_mesh* mesh, const flow_form* form,
+                               int nfacets, const int* facet_cell,
+                               const int* facet_local, double* scratch,
+                               double* work, double* result_host, void* stream);
 
 /* Load vector b_(o,i) = int out_o phi_i for o < form->nout (the right-hand
  * side of project(f, V)); V: test space (deg 1|2).  scratch: nout*nloc*nc. */
