@@ -235,6 +235,17 @@ class FormS(ctypes.Structure):
         ]
 
 
+class PointGridS(ctypes.Structure):
+    '''flow_point_grid (include/flow_hip.h): the bucket grid of point location'''
+    _fields_ = [
+        ('nx', ctypes.c_int), ('ny', ctypes.c_int),
+        ('x0', ctypes.c_double), ('y0', ctypes.c_double),
+        ('hx_inv', ctypes.c_double), ('hy_inv', ctypes.c_double),
+        ('start', ctypes.c_void_p),
+        ('cells', ctypes.c_void_p),
+        ]
+
+
 class NsParams(ctypes.Structure):
     _fields_ = [
         ('dt', ctypes.c_double), ('rho', ctypes.c_double),
@@ -422,6 +433,8 @@ SYMBOLS = {
     'flow_form_load_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
     'flow_form_facet_functional': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP,
                                    _P(_D), _VP],
+    'flow_locate_points': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _VP, _VP],
+    'flow_form_points': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP],
     }
 
 _LIB = None

@@ -10,7 +10,11 @@
 //                per-facet integrals to scratch[k], then the same reduction;
 //   load vector  b_i = int f phi_i (project): per-cell values to
 //                scratch[(o*nloc + i)*nc + c], then the gather of
-//                assembly_kernels.hip, as flow_assemble_source does.
+//                assembly_kernels.hip, as flow_assemble_source does;
+//   points       u(x), Probes: one lane per located point, the program at
+//                its barycentric coordinates (flow_locate_points finds the
+//                cell: the bucket grid's candidates in ascending order, the
+//                first cell that holds the point).
 //
 // One thread per cell, a loop over the rule's points, the program inside it.
 // The program and the constants are kernel arguments: every lane reads the
@@ -18,9 +22,15 @@
 // eight registers and the field slots are NAMED values behind switches and
 // unrolled compile-time loops -- a register file indexed at run time would
 // live in scratch memory.  Scratch stays at 0 bytes per lane.
+#include <cmath>
+
 #include "fem_device.h"
 
 namespace flow {
+
+// flow_locate_points: a point lies in a cell when all three barycentric
+// coordinates are >= this (include/flow_hip.h)
+constexpr double kPointTol = -1.0e-12;
 
 struct FormRegs {
   double r0, r1, r2, r3, r4, r5, r6, r7;
@@ -360,9 +370,93 @@ __global__ __launch_bounds__(kBlock) void form_facet_kernel(
   scratch[k] = form_facet<NF>(F, nc, xy, c, lf);
 }
 
+// The point of the mesh's cell c at barycentric (l0, l1, l2): the test of
+// flow_locate_points.  Contraction stays off, so that the host's numpy
+// evaluation of the same expressions (flow_amd/fem/points.py) gives the same
+// bits: which cell a point on an edge belongs to is then decided alike.
+__device__ __forceinline__ bool point_in_cell(const double* __restrict__ xy, int nc,
+                                              int c, double px, double py,
+                                              double& l0, double& l1, double& l2) {
+#pragma clang fp contract(off)
+  const double x0 = xy[0 * nc + c], x1 = xy[1 * nc + c], x2 = xy[2 * nc + c];
+  const double y0 = xy[3 * nc + c], y1 = xy[4 * nc + c], y2 = xy[5 * nc + c];
+  const double j00 = x1 - x0, j01 = x2 - x0, j10 = y1 - y0, j11 = y2 - y0;
+  const double det = j00 * j11 - j01 * j10;
+  const double dx = px - x0, dy = py - y0;
+  l1 = (j11 * dx - j01 * dy) / det;
+  l2 = (j00 * dy - j10 * dx) / det;
+  l0 = 1.0 - l1 - l2;
+  return l0 >= kPointTol && l1 >= kPointTol && l2 >= kPointTol;
+}
+
+// one point per lane: its bucket's candidates in ascending cell order, the
+// first that holds it
+__global__ __launch_bounds__(kBlock) void locate_points_kernel(
+    int nc, const double* __restrict__ xy, const flow_point_grid G, int n,
+    const double* __restrict__ pts, int* __restrict__ cell,
+    double* __restrict__ bary) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double px = pts[i], py = pts[static_cast<size_t>(n) + i];
+  // (clamped as doubles: a NaN or a far point never becomes an int out of
+  // range; NaN fails every test below)
+  double tx = (px - G.x0) * G.hx_inv, ty = (py - G.y0) * G.hy_inv;
+  tx = tx >= 0.0 ? (tx <= G.nx - 1.0 ? tx : G.nx - 1.0) : 0.0;
+  ty = ty >= 0.0 ? (ty <= G.ny - 1.0 ? ty : G.ny - 1.0) : 0.0;
+  const int b = static_cast<int>(floor(ty)) * G.nx + static_cast<int>(floor(tx));
+  int found = -1;
+  double l0 = __builtin_nan(""), l1 = l0, l2 = l0;
+  for (int k = G.start[b], e = G.start[b + 1]; k < e; ++k) {
+    const int c = G.cells[k];
+    if (c < 0 || c >= nc) continue;
+    double m0, m1, m2;
+    if (point_in_cell(xy, nc, c, px, py, m0, m1, m2)) {
+      found = c;
+      l0 = m0;
+      l1 = m1;
+      l2 = m2;
+      break;
+    }
+  }
+  cell[i] = found;
+  bary[i] = l0;
+  bary[static_cast<size_t>(n) + i] = l1;
+  bary[2 * static_cast<size_t>(n) + i] = l2;
+}
+
+// one located point per lane: the program at its barycentric coordinates,
+// out[o][i]; NaN for a point in no cell
+template <int NF>
+__global__ __launch_bounds__(kBlock) void form_points_kernel(
+    int nc, const double* __restrict__ xy, const flow_form F, int n,
+    const int* __restrict__ cell, const double* __restrict__ bary,
+    double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int c = cell[i];
+  double out0 = __builtin_nan(""), out1 = out0;
+  if (c >= 0 && c < nc) {
+    const Geom g = load_geom(xy, nc, c);
+    const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+    const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+    double U[NF > 0 ? NF : 1][6];
+    load_form_fields<NF>(F, nc, c, U);
+    const double L[3] = {bary[i], bary[static_cast<size_t>(n) + i],
+                         bary[2 * static_cast<size_t>(n) + i]};
+    out0 = 0.0;
+    out1 = 0.0;
+    form_point<NF, false>(F, U, X, Y, g, L, 0, nc, c, 0.0, 0.0, out0, out1);
+  }
+  out[i] = out0;
+  if (F.nout == 2) out[static_cast<size_t>(n) + i] = out1;
+}
+
 // rows: the rule holds rows * nq points (1: cells; 3: the three local
-// facets); facet: NORMAL is legal
-static int check_form(const flow_form* F, int rows = 1, bool facet = false) {
+// facets); facet: NORMAL is legal; points: the program runs at located
+// points -- no rule, no Expression lattices (they are tabulated at the
+// rule's rows), no normal
+static int check_form(const flow_form* F, int rows = 1, bool facet = false,
+                      bool points = false) {
   FLOW_REQUIRE(F, "form");
   FLOW_REQUIRE(F->nprog >= 1 && F->nprog <= FLOW_FORM_MAX_PROGRAM,
                "form program length");
@@ -372,8 +466,10 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false) {
   FLOW_REQUIRE(F->nexpr >= 0 && F->nexpr <= FLOW_FORM_MAX_EXPRESSIONS,
                "form expressions");
   FLOW_REQUIRE(F->nout == 1 || F->nout == 2, "form outputs");
-  FLOW_REQUIRE(F->nq >= 1 && rows * F->nq <= FLOW_FORM_MAX_POINTS && F->rule,
+  FLOW_REQUIRE(points || (F->nq >= 1 && rows * F->nq <= FLOW_FORM_MAX_POINTS && F->rule),
                "form quadrature rule");
+  FLOW_REQUIRE(!points || F->nexpr == 0,
+               "form expression (Expression leaves cannot be evaluated at points)");
   for (int k = 0; k < F->nfield; ++k) {
     FLOW_REQUIRE(F->field[k], "form field pointer");
     FLOW_REQUIRE(F->field_deg[k] == 1 || F->field_deg[k] == 2, "form field degree");
@@ -395,6 +491,8 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false) {
     FLOW_REQUIRE((op >= FLOW_FORM_OP_CONST && op <= FLOW_FORM_OP_OUT) ||
                      (facet && op == FLOW_FORM_OP_NORMAL),
                  facet ? "form opcode" : "form opcode (NORMAL: facet integrals only)");
+    FLOW_REQUIRE(!points || op != FLOW_FORM_OP_EXPR,
+                 "form opcode (EXPR: not at points)");
     const bool reg_a = op >= FLOW_FORM_OP_MOV && op <= FLOW_FORM_OP_OUT;
     const bool reg_b = op >= FLOW_FORM_OP_ADD && op <= FLOW_FORM_OP_POW;
     FLOW_REQUIRE(dst >= 0 && dst < FLOW_FORM_REGISTERS, "form register");
@@ -483,6 +581,30 @@ static int launch_facets(const flow_mesh* mesh, const flow_form* F, int nfacets,
   return FLOW_OK;
 }
 
+static int launch_points(const flow_mesh* mesh, const flow_form* F, int n,
+                         const int* cell, const double* bary, double* out,
+                         hipStream_t st) {
+  const dim3 grid((n + kBlock - 1) / kBlock);
+  switch (F->nfield) {
+#define FLOW_FORM_POINTS_CASE(NF)                                                \
+    case NF:                                                                     \
+      hipLaunchKernelGGL((form_points_kernel<NF>), grid, dim3(kBlock), 0, st,    \
+                         mesh->nc, mesh->xy, *F, n, cell, bary, out);           \
+      break;
+    FLOW_FORM_POINTS_CASE(0)
+    FLOW_FORM_POINTS_CASE(1)
+    FLOW_FORM_POINTS_CASE(2)
+    FLOW_FORM_POINTS_CASE(3)
+    FLOW_FORM_POINTS_CASE(4)
+    FLOW_FORM_POINTS_CASE(5)
+    default:
+    FLOW_FORM_POINTS_CASE(6)
+#undef FLOW_FORM_POINTS_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
 }  // namespace flow
 
 using namespace flow;
@@ -553,4 +675,39 @@ extern "C" int flow_form_facet_functional(const flow_mesh* mesh, const flow_form
                      scratch, work);
   FLOW_CHECK_LAUNCH();
   return sum_partials_host(work, nparts, result_host, st);
+}
+
+extern "C" int flow_locate_points(const flow_mesh* mesh, const flow_point_grid* grid,
+                                  int n, const double* xy, int* cell, double* bary,
+                                  void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(grid && grid->nx >= 1 && grid->ny >= 1 &&
+                   static_cast<long long>(grid->nx) * grid->ny < (1LL << 31) - 1,
+               "point grid size");
+  FLOW_REQUIRE(grid->hx_inv > 0.0 && grid->hy_inv > 0.0 && std::isfinite(grid->hx_inv) &&
+                   std::isfinite(grid->hy_inv) && std::isfinite(grid->x0) && std::isfinite(grid->y0),
+               "point grid geometry");
+  FLOW_REQUIRE(grid->start && grid->cells, "point grid arrays");
+  FLOW_REQUIRE(n >= 0, "point count");
+  if (n == 0) return FLOW_OK;
+  FLOW_REQUIRE(xy && cell && bary, "pointers");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(locate_points_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock),
+                     0, st, mesh->nc, mesh->xy, *grid, n, xy, cell, bary);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+extern "C" int flow_form_points(const flow_mesh* mesh, const flow_form* form, int n,
+                                const int* cell, const double* bary, double* out,
+                                void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "point evaluation on strips");
+  if ((rc = check_form(form, 1, false, true))) return rc;
+  FLOW_REQUIRE(n >= 0, "point count");
+  if (n == 0) return FLOW_OK;
+  FLOW_REQUIRE(cell && bary && out, "pointers");
+  return launch_points(mesh, form, n, cell, bary, out, as_stream(stream));
 }

@@ -25,6 +25,7 @@ from .forms import (                                            # noqa: F401
     dx, ds, Measure, FacetNormal, SpatialCoordinate, as_vector, sqrt, exp,
     ln, sin, cos, dot, inner, grad, div, curl,
     )
+from .points import Probes                                      # noqa: F401
 from ..message import begin, end, info                          # noqa: F401
 
 DOLFIN_EPS = 3.0e-16

@@ -527,6 +527,26 @@ def has_normal(n):
         has_normal(c) for c in n[1:] if isinstance(c, tuple))
 
 
+def has_leaf(n, kind):
+    '''Whether a scalar tree holds a leaf of `kind` ('n', 'expr', ...).'''
+    if n[0] == kind:
+        return True
+    return n[0] in UNARY + BINARY + ('powi',) and any(
+        has_leaf(c, kind) for c in n[1:] if isinstance(c, tuple))
+
+
+def point_program(expr):
+    '''The register program of a rank <= 1 expression at points (Probes,
+    u(x)): one output per component.  ValueError for rank 2, Expression
+    leaves and FacetNormal.'''
+    expr = as_form(expr)
+    if len(expr.shape) > 1:
+        raise ValueError('point evaluation of a tensor of shape %r: evaluate '
+                         'its rows or components, e.g. f[0] or f[0, 1]'
+                         % (expr.shape,))
+    return Program(expr.scalar_trees(), point=True)
+
+
 def check_no_normal(expr, where):
     if any(has_normal(t) for t in expr.scalar_trees()):
         raise ValueError('FacetNormal is defined on exterior facets only: it '
@@ -682,9 +702,18 @@ class Program(object):
     (('num', v) or (Constant, i)), field components (Function, i) and
     Expression components (Expression, i), in slot order.'''
 
-    def __init__(self, trees, facet=False):
+    def __init__(self, trees, facet=False, point=False):
         '''facet: the program runs on exterior facets, where the normal
-        exists (ValueError if a tree reads it otherwise).'''
+        exists (ValueError if a tree reads it otherwise).  point: it runs at
+        located points (Probes, u(x)), where neither the normal nor
+        Expression leaves exist (their lattices are tabulated at the rule's
+        points only).'''
+        if point and any(has_leaf(t, 'n') for t in trees):
+            raise ValueError('FacetNormal is defined on exterior facets only: '
+                             'it cannot be evaluated at points')
+        if point and any(has_leaf(t, 'expr') for t in trees):
+            raise ValueError('Expression leaves cannot be evaluated at points: '
+                             'interpolate the Expression into a Function')
         if not facet and any(has_normal(t) for t in trees):
             raise ValueError('FacetNormal is defined on exterior facets only: '
                              'integrate over ds')

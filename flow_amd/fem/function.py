@@ -344,6 +344,14 @@ class Function(_FormOperand):
     def value_dim(self):
         return self._V.dim
 
+    def __call__(self, *x):
+        '''The value at a point, as dolfin's `u(x, y)`, `u(Point(x, y))`,
+        `u((x, y))`, `u(numpy.array([x, y]))`: a float for a scalar field, a
+        numpy (2,) array for a vector field; RuntimeError outside the mesh.
+        Through fem.Probes (flow_amd/fem/points.py), on the GPU.'''
+        from .points import evaluate_function
+        return evaluate_function(self, x)
+
     def __bool__(self):
         # `if p0:` is always true for a Function
         # (flow/navier_stokes/pressure_correction.py:308)

@@ -54,6 +54,9 @@ class Mesh(object):
         assert self.cell_vertices.max() < len(self.points)
         self._topology = None
         self._cache = {}
+        # (cx, cy, radius) of the circle a body-fitted hole was pulled onto
+        # (rectangle_with_fitted_hole), else None
+        self.hole = None
         return
 
     # -- numbering -------------------------------------------------------------
@@ -86,6 +89,7 @@ class Mesh(object):
         corigin = corder if self.cell_origin is None \
             else numpy.asarray(self.cell_origin)[corder]
         out.cell_origin = corigin.astype(numpy.int64)
+        out.hole = self.hole
         return out
 
     def bandwidth(self):
@@ -390,7 +394,8 @@ def rectangle_with_fitted_hole(
     cell order are those of `rectangle_with_hole`; the boundary is a polygon
     with its vertices ON the circle (O(h^2) from it, where the staircase is
     O(h) and leaves one-cell notches).  The circle's centre moves to the
-    nearest grid vertex (< h/2).'''
+    nearest grid vertex (< h/2); the returned mesh records the circle it
+    fitted as `mesh.hole = (cx, cy, radius)`.'''
     hx, hy = (x1 - x0) / nx, (y1 - y0) / ny
     ic = int(round((centre[0] - x0) / hx))
     jc = int(round((centre[1] - y0) / hy))
@@ -441,7 +446,9 @@ def rectangle_with_fitted_hole(
     used = numpy.zeros(len(pts), dtype=bool)
     used[cells.ravel()] = True
     new_id = numpy.cumsum(used) - 1
-    return Mesh(pts[used], new_id[cells])
+    out = Mesh(pts[used], new_id[cells])
+    out.hole = (cx, cy, radius)
+    return out
 
 
 def karman_channel(nx, ny=None, diagonal='right', fitted=False, length=0.6):

@@ -266,6 +266,25 @@ class KarmanProblem(object):
         return dict(drag=drag, lift=lift, c_drag=scale * drag,
                     c_lift=scale * lift)
 
+    def pressure_difference(self):
+        '''p(cx - r, cy) - p(cx + r, cy) for the current p0: the pressure
+        drop across the obstacle from its front to its back point, (cx, cy,
+        r) the circle the body-fitted mesh was pulled onto (`mesh.hole`;
+        both points are mesh vertices on the obstacle's boundary).  The
+        probes are located once.  ValueError on a staircase obstacle, whose
+        nominal circle is not the fluid's boundary; not on strips.'''
+        if getattr(self, '_dp_probes', None) is None:
+            hole = getattr(self.mesh, 'hole', None)
+            if hole is None:
+                raise ValueError(
+                    'pressure_difference needs the body-fitted obstacle '
+                    '(fitted=True): on a staircase mesh the points on the '
+                    'circle are not in the fluid')
+            cx, cy, r = hole
+            self._dp_probes = fem.Probes(self.mesh, [(cx - r, cy), (cx + r, cy)])
+        front, back = self._dp_probes(self.p0)
+        return float(front - back)
+
     def step(self, tol=1.0e-10, adapt=True):
         '''One pass of the reference's time loop body (:219-286).'''
         u1, p1 = self.stepper.step(

@@ -1175,6 +1175,37 @@ int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
                           const flow_form* form, double* scratch, double* b,
                           void* stream);
 
+/* ---- point evaluation (flow_amd/fem/points.py): u(x), Probes ---------------
+ * A uniform bucket grid over the mesh's bounding box, built on the host once
+ * per mesh: bucket (ix, iy) = (floor((x - x0) * hx_inv), floor((y - y0) *
+ * hy_inv)) clamped to [0, nx-1] x [0, ny-1], id iy*nx + ix; its candidate
+ * cells are cells[start[b] .. start[b+1]), every cell whose (padded)
+ * bounding box overlaps the bucket, in ascending cell index. */
+typedef struct {
+  int nx, ny;              /* buckets per axis */
+  double x0, y0;           /* lower-left corner of the grid */
+  double hx_inv, hy_inv;   /* 1 / bucket width, 1 / bucket height */
+  const int* start;        /* nx*ny + 1 */
+  const int* cells;        /* start[nx*ny] candidate cells */
+} flow_point_grid;
+
+/* Point location, one lane per point.  xy: (2, n) SoA fp64.  Point i belongs
+ * to the LOWEST-index cell c whose barycentric coordinates all satisfy
+ * lambda_k >= -1e-12, or to none: cell[i] = c or -1 (int32), bary[k*n + i] =
+ * lambda_k on that cell ((3, n) fp64; NaN for -1).  The grid only narrows the
+ * candidates; the answer does not depend on it, nor on the order or number of
+ * the points.  n == 0: nothing launched. */
+int flow_locate_points(const flow_mesh* mesh, const flow_point_grid* grid, int n,
+                       const double* xy, int* cell, double* bary, void* stream);
+
+/* The form's program at located points, one lane per point: out[o*n + i] =
+ * output o (< form->nout) at barycentric bary[., i] of cell[i]; NaN where
+ * cell[i] == -1.  The rule and tables are unused; programs holding expr or
+ * normal are refused.  Not on strips.  n == 0: nothing launched. */
+int flow_form_points(const flow_mesh* mesh, const flow_form* form, int n,
+                     const int* cell, const double* bary, double* out,
+                     void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
