@@ -133,13 +133,46 @@ __device__ __forceinline__ double field_at(const flow_form& F,
 // row of the rule (and of the Expression tables).  FACET: the point lies on a
 // facet whose outward unit normal is (n0, n1); the cell kernels pass
 // FACET = false, their programs never hold NORMAL (check_form).
-template <int NF, bool FACET>
-__device__ __forceinline__ void form_point(const flow_form& F,
-                                           const double (&U)[NF > 0 ? NF : 1][6],
-                                           const double X[3], const double Y[3],
-                                           const Geom& g, const double L[3], int row,
-                                           int nc, int c, double n0, double n1,
-                                           double& out0, double& out1) {
+//
+// OUT receives the `out` instructions: FormOut2 for the functionals, load
+// vectors and points, FormSlots<9> / <3> for the coefficient tables of rank-2
+// / rank-1 forms.  Like the registers, the outputs are named values.
+struct FormOut2 {
+  double& out0;
+  double& out1;
+  __device__ __forceinline__ void set(int b, double r) {
+    out0 = b == 0 ? r : out0;
+    out1 = b == 0 ? out1 : r;
+  }
+};
+
+template <int N>
+struct FormSlots {
+  double v[N];
+  // (a wave-uniform switch, as reg_set: N selects would hold N lane masks in
+  // scalar registers at once)
+  __device__ __forceinline__ void set(int b, double r) {
+    switch (b) {
+      case 0: v[0] = r; break;
+      case 1: v[1 < N ? 1 : 0] = r; break;
+      case 2: v[2 < N ? 2 : 0] = r; break;
+      case 3: v[3 < N ? 3 : 0] = r; break;
+      case 4: v[4 < N ? 4 : 0] = r; break;
+      case 5: v[5 < N ? 5 : 0] = r; break;
+      case 6: v[6 < N ? 6 : 0] = r; break;
+      case 7: v[7 < N ? 7 : 0] = r; break;
+      default: v[N - 1] = r; break;
+    }
+  }
+};
+
+template <int NF, bool FACET, class OUT>
+__device__ __forceinline__ void form_point_n(const flow_form& F,
+                                             const double (&U)[NF > 0 ? NF : 1][6],
+                                             const double X[3], const double Y[3],
+                                             const Geom& g, const double L[3], int row,
+                                             int nc, int c, double n0, double n1,
+                                             OUT& out) {
   FormRegs R = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int pc = 0; pc < F.nprog; ++pc) {
     const int op = F.prog[4 * pc], dst = F.prog[4 * pc + 1];
@@ -193,14 +226,24 @@ __device__ __forceinline__ void form_point(const flow_form& F,
       case FLOW_FORM_OP_SIN:
       case FLOW_FORM_OP_COS: v = form_sincos(reg_get(R, a), op == FLOW_FORM_OP_COS); break;
       default: {   // FLOW_FORM_OP_OUT
-        const double r = reg_get(R, a);
-        out0 = b == 0 ? r : out0;
-        out1 = b == 0 ? out1 : r;
+        out.set(b, reg_get(R, a));
         continue;
       }
     }
     reg_set(R, dst, v);
   }
+}
+
+// the two-output program of the functionals, load vectors and points
+template <int NF, bool FACET>
+__device__ __forceinline__ void form_point(const flow_form& F,
+                                           const double (&U)[NF > 0 ? NF : 1][6],
+                                           const double X[3], const double Y[3],
+                                           const Geom& g, const double L[3], int row,
+                                           int nc, int c, double n0, double n1,
+                                           double& out0, double& out1) {
+  FormOut2 out = {out0, out1};
+  form_point_n<NF, FACET>(F, U, X, Y, g, L, row, nc, c, n0, n1, out);
 }
 
 // the local values of the form's fields on cell c
@@ -451,12 +494,138 @@ __global__ __launch_bounds__(kBlock) void form_points_kernel(
   if (F.nout == 2) out[static_cast<size_t>(n) + i] = out1;
 }
 
+// ---------------------------------------------------------------------------
+// Forms of test and trial functions (forms.py, extract_arguments): the host
+// rewrites a rank-2 integrand as sum_(b,a) c_ba D_a u D_b v and a rank-1
+// integrand as sum_b c_b D_b v (D_0 value, D_1 d/dx, D_2 d/dy), and compiles
+// the argument-free coefficients c into ONE program whose output slot is fixed
+// by the term: 3 b + a (rank 2), b (rank 1).  `live` holds one bit per slot
+// the program writes; it is a kernel argument, so a term that is absent costs
+// a wave-uniform branch and nothing else.
+// ---------------------------------------------------------------------------
+// D_a of basis function t (a is a compile-time value in the unrolled callers)
+template <int NL>
+__device__ __forceinline__ double arg_basis(int a, const double (&phi)[NL],
+                                            const double (&gphi)[NL][2], int t) {
+  return a == 0 ? phi[t] : gphi[t][a == 2 ? 1 : 0];
+}
+
+// Ke[i][j] = sum_q w_q |det J| sum_ba c_ba(x_q) D_a phi_j D_b phi_i, to
+// scratch[(i*NL + j)*nc + c] (the layout of scalar_matrix_kernel: the gather
+// over cptr / csrc sums it into a value plane).  All NL*NL entries are held
+// in one pass over the rule (measured faster than a row or three
+// at a time with the program re-run per pass).  Per point and test derivative
+// b, t_j = sum_a w c_ba D_a phi_j first, then Ke[i][j] += D_b phi_i t_j.
+template <int NF, int DEG>
+__global__ __launch_bounds__(kBlock) void form_matrix_kernel(
+    int nc, const double* __restrict__ xy, const flow_form F, int live,
+    double* __restrict__ scratch) {
+  constexpr int NL = Elem<DEG>::NL;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  // (the lane's own address: the base pointer need not stay in scalar
+  // registers across the interpreter loop, which is short of them)
+  double* const dst = scratch + c;
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
+  double Ke[NL][NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i)
+#pragma unroll
+    for (int j = 0; j < NL; ++j) Ke[i][j] = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
+    const double w = F.rule[3 * q + 2] * g.adet;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlots<FLOW_FORM_SLOTS> out;
+#pragma unroll
+    for (int k = 0; k < FLOW_FORM_SLOTS; ++k) out.v[k] = 0.0;
+    form_point_n<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    double phi[NL], dphi[NL][3], gphi[NL][2];
+    basis<DEG>(L, phi, dphi);
+    phys_grad<NL>(g, dphi, gphi);
+    // (the mask through an empty asm: otherwise the twelve tests below are
+    // hoisted out of the loop and their results held in scalar registers
+    // across the interpreter, which then spills two of its own)
+    int m = live;
+    asm volatile("" : "+s"(m));
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (((m >> (3 * b)) & 7) == 0) continue;
+      double t[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) t[j] = 0.0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (((m >> (3 * b + a)) & 1) == 0) continue;
+        const double s = w * out.v[3 * b + a];
+#pragma unroll
+        for (int j = 0; j < NL; ++j) t[j] += s * arg_basis<NL>(a, phi, gphi, j);
+      }
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const double di = arg_basis<NL>(b, phi, gphi, i);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) Ke[i][j] += di * t[j];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NL; ++i)
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+      dst[static_cast<size_t>(i * NL + j) * nc] = Ke[i][j];
+}
+
+// be[i] = sum_q w_q |det J| sum_b c_b(x_q) D_b phi_i, to scratch[i*nc + c]
+// (the gather over vptr / vsrc sums it into the vector)
+template <int NF, int DEG>
+__global__ __launch_bounds__(kBlock) void form_vector_kernel(
+    int nc, const double* __restrict__ xy, const flow_form F, int live,
+    double* __restrict__ scratch) {
+  constexpr int NL = Elem<DEG>::NL;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
+  double be[NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i) be[i] = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
+    const double w = F.rule[3 * q + 2] * g.adet;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlots<3> out = {{0.0, 0.0, 0.0}};
+    form_point_n<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    double phi[NL], dphi[NL][3], gphi[NL][2];
+    basis<DEG>(L, phi, dphi);
+    phys_grad<NL>(g, dphi, gphi);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (((live >> b) & 1) == 0) continue;
+      const double s = w * out.v[b];
+#pragma unroll
+      for (int i = 0; i < NL; ++i) be[i] += s * arg_basis<NL>(b, phi, gphi, i);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NL; ++i) scratch[static_cast<size_t>(i) * nc + c] = be[i];
+}
+
 // rows: the rule holds rows * nq points (1: cells; 3: the three local
 // facets); facet: NORMAL is legal; points: the program runs at located
 // points -- no rule, no Expression lattices (they are tabulated at the
-// rule's rows), no normal
+// rule's rows), no normal; slots = 0: one or two outputs, each written; 9 | 3:
+// the coefficient table of a rank-2 | rank-1 form -- nout == slots, *live =
+// one bit per slot the program writes (at least one, none twice)
 static int check_form(const flow_form* F, int rows = 1, bool facet = false,
-                      bool points = false) {
+                      bool points = false, int slots = 0, int* live = nullptr) {
   FLOW_REQUIRE(F, "form");
   FLOW_REQUIRE(F->nprog >= 1 && F->nprog <= FLOW_FORM_MAX_PROGRAM,
                "form program length");
@@ -465,7 +634,8 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
   FLOW_REQUIRE(F->nfield >= 0 && F->nfield <= FLOW_FORM_MAX_FIELDS, "form fields");
   FLOW_REQUIRE(F->nexpr >= 0 && F->nexpr <= FLOW_FORM_MAX_EXPRESSIONS,
                "form expressions");
-  FLOW_REQUIRE(F->nout == 1 || F->nout == 2, "form outputs");
+  FLOW_REQUIRE(slots == 0 ? (F->nout == 1 || F->nout == 2) : (F->nout == slots && live),
+               "form outputs");
   FLOW_REQUIRE(points || (F->nq >= 1 && rows * F->nq <= FLOW_FORM_MAX_POINTS && F->rule),
                "form quadrature rule");
   FLOW_REQUIRE(!points || F->nexpr == 0,
@@ -484,7 +654,7 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
   }
   // every instruction: registers, operand indices and outputs in range (the
   // kernel indexes kernel-argument arrays with them)
-  bool wrote[2] = {false, false};
+  int wrote = 0;
   for (int pc = 0; pc < F->nprog; ++pc) {
     const int op = F->prog[4 * pc], dst = F->prog[4 * pc + 1];
     const int a = F->prog[4 * pc + 2], b = F->prog[4 * pc + 3];
@@ -516,12 +686,17 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
         break;
       case FLOW_FORM_OP_OUT:
         FLOW_REQUIRE(b >= 0 && b < F->nout, "form output");
-        wrote[b] = true;
+        FLOW_REQUIRE(slots == 0 || !((wrote >> b) & 1), "form output slot written twice");
+        wrote |= 1 << b;
         break;
       default: break;
     }
   }
-  FLOW_REQUIRE(wrote[0] && (F->nout == 1 || wrote[1]), "form writes every output");
+  if (slots == 0)
+    FLOW_REQUIRE(wrote == (1 << F->nout) - 1, "form writes every output");
+  else
+    FLOW_REQUIRE(wrote != 0, "form writes no coefficient slot");
+  if (live) *live = wrote;
   return FLOW_OK;
 }
 
@@ -600,6 +775,54 @@ static int launch_points(const flow_mesh* mesh, const flow_form* F, int n,
     default:
     FLOW_FORM_POINTS_CASE(6)
 #undef FLOW_FORM_POINTS_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+template <int DEG>
+static int launch_matrix(const flow_mesh* mesh, const flow_form* F, int live,
+                         double* scratch, hipStream_t st) {
+  const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
+  switch (F->nfield) {
+#define FLOW_FORM_MATRIX_CASE(NF)                                                \
+    case NF:                                                                     \
+      hipLaunchKernelGGL((form_matrix_kernel<NF, DEG>), grid, dim3(kBlock),      \
+                         0, st, mesh->nc, mesh->xy, *F, live, scratch);         \
+      break;
+    FLOW_FORM_MATRIX_CASE(0)
+    FLOW_FORM_MATRIX_CASE(1)
+    FLOW_FORM_MATRIX_CASE(2)
+    FLOW_FORM_MATRIX_CASE(3)
+    FLOW_FORM_MATRIX_CASE(4)
+    FLOW_FORM_MATRIX_CASE(5)
+    default:
+    FLOW_FORM_MATRIX_CASE(6)
+#undef FLOW_FORM_MATRIX_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+template <int DEG>
+static int launch_vector(const flow_mesh* mesh, const flow_form* F, int live,
+                         double* scratch, hipStream_t st) {
+  const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
+  switch (F->nfield) {
+#define FLOW_FORM_VECTOR_CASE(NF)                                                \
+    case NF:                                                                     \
+      hipLaunchKernelGGL((form_vector_kernel<NF, DEG>), grid, dim3(kBlock), 0,   \
+                         st, mesh->nc, mesh->xy, *F, live, scratch);            \
+      break;
+    FLOW_FORM_VECTOR_CASE(0)
+    FLOW_FORM_VECTOR_CASE(1)
+    FLOW_FORM_VECTOR_CASE(2)
+    FLOW_FORM_VECTOR_CASE(3)
+    FLOW_FORM_VECTOR_CASE(4)
+    FLOW_FORM_VECTOR_CASE(5)
+    default:
+    FLOW_FORM_VECTOR_CASE(6)
+#undef FLOW_FORM_VECTOR_CASE
   }
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
@@ -710,4 +933,44 @@ extern "C" int flow_form_points(const flow_mesh* mesh, const flow_form* form, in
   if (n == 0) return FLOW_OK;
   FLOW_REQUIRE(cell && bary && out, "pointers");
   return launch_points(mesh, form, n, cell, bary, out, as_stream(stream));
+}
+
+extern "C" int flow_form_matrix(const flow_mesh* mesh, const flow_space* V,
+                                const flow_form* form, double* scratch,
+                                double* vals, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  int live = 0;
+  if ((rc = check_form(form, 1, false, false, FLOW_FORM_SLOTS, &live))) return rc;
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->nnz > 0 &&
+                   V->cptr && V->csrc,
+               "space");
+  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(scratch && vals, "pointers");
+  hipStream_t st = as_stream(stream);
+  rc = V->deg == 1 ? launch_matrix<1>(mesh, form, live, scratch, st)
+                   : launch_matrix<2>(mesh, form, live, scratch, st);
+  if (rc) return rc;
+  return gather(V->nnz, 1, V->cptr, V->csrc, scratch, 0, vals, st);
+}
+
+extern "C" int flow_form_vector(const flow_mesh* mesh, const flow_space* V,
+                                const flow_form* form, double* scratch, double* b,
+                                void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  int live = 0;
+  if ((rc = check_form(form, 1, false, false, 3, &live))) return rc;
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->vptr && V->vsrc,
+               "space");
+  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(scratch && b, "pointers");
+  hipStream_t st = as_stream(stream);
+  rc = V->deg == 1 ? launch_vector<1>(mesh, form, live, scratch, st)
+                   : launch_vector<2>(mesh, form, live, scratch, st);
+  if (rc) return rc;
+  return gather(V->n, 1, V->vptr, V->vsrc, scratch,
+                static_cast<size_t>(V->deg == 1 ? 3 : 6) * mesh->nc, b, st);
 }

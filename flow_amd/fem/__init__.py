@@ -23,7 +23,8 @@ from .io import XDMFFile, mpi_comm_world, read_mesh             # noqa: F401
 from .space import MixedFunctionSpace                           # noqa: F401
 from .forms import (                                            # noqa: F401
     dx, ds, Measure, FacetNormal, SpatialCoordinate, as_vector, sqrt, exp,
-    ln, sin, cos, dot, inner, grad, div, curl,
+    ln, sin, cos, dot, inner, grad, div, curl, TestFunction, TrialFunction,
+    lhs, rhs, system, dS, derivative, action, adjoint,
     )
 from .points import Probes                                      # noqa: F401
 from ..message import begin, end, info                          # noqa: F401
@@ -38,7 +39,7 @@ def __getattr__(name):
     # host-only parts (meshes, spaces, BC search) work without the library
     if name in ('project', 'interpolate', 'errornorm', 'norm', 'assemble_mass',
                 'assemble_stiffness', 'integral', 'project_magnitude', 'ops',
-                'assemble'):
+                'assemble', 'assemble_system', 'solve'):
         import importlib
         ops = importlib.import_module('.ops', __name__)
         return ops if name == 'ops' else getattr(ops, name)

@@ -109,6 +109,23 @@ class DirichletBC(object):
             pass
         return None
 
+    def apply(self, *args):
+        '''bc.apply(A), bc.apply(b), bc.apply(A, b) (flow/heat.py:113-114):
+        the rows of the condition's dofs become identity rows of the Matrix
+        A, the entries of the Vector b the condition's values; the columns
+        stay (assemble_system eliminates symmetrically).'''
+        from . import ops
+        A = b = None
+        for arg in args:
+            if isinstance(arg, ops.Matrix):
+                A = arg
+            else:
+                b = arg
+        if len(args) not in (1, 2) or (len(args) == 2 and (
+                A is None or b is None)):
+            raise TypeError('apply(A), apply(b) or apply(A, b)')
+        ops.apply_identity_rows(self, A, b)
+
     def _scalar_dofs(self):
         '''Scalar dof ids on the marked boundary facets (sorted, unique).'''
         if self._facet_cache is None:

@@ -43,6 +43,25 @@ legal only in ds integrands.  The rule is reference.line_rule(q) on each
 edge (Gauss-Legendre, exact for degree q).  Rank-0 forms add and subtract:
 assemble(f*dx + g*ds(1) - h*ds(2)) sums the parts in the order written.
 No interior facets (dS), no facet integrals on strips.
+
+Arguments: `v = TestFunction(V)`, `u = TrialFunction(V)` on a scalar P1 / P2
+space are operands like any other (degree = the space's), so `grad`, `dot`,
+`inner`, `.dx(i)`, `v/c` and products with coefficients work unchanged.  A
+form's rank is the number of distinct arguments in it: `assemble` gives a float
+(0), a Vector (1) or a Matrix (2); `lhs` / `rhs` / `system` split a signed sum
+of forms, `a == L` is an Equation for `solve`.  On the host the integrand of a
+rank-2 form is rewritten by linearity as sum_(b,a) c[b][a] D_a u D_b v, of a
+rank-1 form as sum_b c[b] D_b v (D_0 value, D_1 d/dx, D_2 d/dy;
+`extract_arguments`): + - and unary - distribute, * multiplies the two sides'
+tables, / needs an argument-free denominator, anything else applied to an
+argument is a ValueError.  The coefficients c are argument-free scalar trees;
+they compile to one Program with one output slot per term (3 b + a, or b).
+`form_compiler_parameters={'quadrature_rule': 'vertex'}` integrates with the
+cell vertices and weights |T|/3 (the lumped mass matrix of u*v*dx).
+Not supported (NotImplementedError): arguments on vector or mixed spaces, test
+and trial functions of different spaces, arguments under ds (Neumann / Robin
+terms: the facet gather needs a contribution map that does not exist yet),
+dS, derivative / action / adjoint.
 '''
 import numbers
 
@@ -65,8 +84,10 @@ BINARY = ('add', 'sub', 'mul', 'div', 'pow')
 # -- scalar trees --------------------------------------------------------------
 # ('num', v) ('const', Constant, i) ('x', d) ('field', Function, i, d)
 # (d = 0 value, 1 d/dx, 2 d/dy) ('expr', Expression, i) ('n', d) (component
-# d of the outward unit normal, ds only) ('powi', a, n) and (op, a[, b]) for
-# the UNARY / BINARY ops.  Objects inside compare by identity.
+# d of the outward unit normal, ds only) ('arg', number, d, V) (number 0 the
+# test, 1 the trial function of the space V; d as for fields) ('powi', a, n)
+# and (op, a[, b]) for the UNARY / BINARY ops.  Objects inside compare by
+# identity.
 ZERO = ('num', 0.0)
 ONE = ('num', 1.0)
 
@@ -139,6 +160,11 @@ def s_diff(n, d):
     if k == 'expr':
         raise NotImplementedError(
             'derivatives of an Expression: interpolate it into a Function')
+    if k == 'arg':
+        if n[2] != 0:
+            raise NotImplementedError('second derivatives of a test or trial '
+                                      'function')
+        return ('arg', n[1], d + 1, n[3])
     if k == 'add':
         return s_add(s_diff(n[1], d), s_diff(n[2], d))
     if k == 'sub':
@@ -195,6 +221,18 @@ def _join_mesh(a, b):
         raise ValueError('the expression combines fields of two different '
                          'meshes')
     return a if a is not None else b
+
+
+def _join(a, b):
+    '''The mesh of a combination of two FormExprs.  Fields of two meshes
+    are a ValueError (_join_mesh); a test and a trial function of two meshes
+    are out of scope like those of two spaces: NotImplementedError.'''
+    if a.mesh is not None and b.mesh is not None and a.mesh is not b.mesh \
+            and all(any(has_leaf(t, 'arg') for t in e.scalar_trees())
+                    for e in (a, b)):
+        raise NotImplementedError(
+            'test and trial functions on different meshes')
+    return _join_mesh(a.mesh, b.mesh)
 
 
 _FORM_OPERANDS = ()     # filled below
@@ -335,7 +373,7 @@ def _binary(op, a, b):
         b = as_form(b)
     except TypeError:
         return NotImplemented
-    mesh = _join_mesh(a.mesh, b.mesh)
+    mesh = _join(a, b)
     if op in ('add', 'sub'):
         if a.shape != b.shape:
             raise ValueError('%s of shapes %r and %r' % (op, a.shape, b.shape))
@@ -436,7 +474,7 @@ def cos(f):
 
 def dot(a, b):
     a, b = as_form(a), as_form(b)
-    mesh = _join_mesh(a.mesh, b.mesh)
+    mesh = _join(a, b)
     if not a.shape or not b.shape:
         if a.shape or b.shape:
             raise ValueError('dot of shapes %r and %r' % (a.shape, b.shape))
@@ -448,7 +486,7 @@ def inner(a, b):
     a, b = as_form(a), as_form(b)
     if a.shape != b.shape:
         raise ValueError('inner of shapes %r and %r' % (a.shape, b.shape))
-    mesh = _join_mesh(a.mesh, b.mesh)
+    mesh = _join(a, b)
     total = ZERO
     for x, y in zip(a.scalar_trees(), b.scalar_trees()):
         total = s_add(total, s_mul(x, y))
@@ -519,6 +557,125 @@ def FacetNormal(mesh):
     return FormExpr([('n', 0), ('n', 1)], (2,), 0, mesh)
 
 
+def _argument(V, number):
+    name = ('TestFunction', 'TrialFunction')[number]
+    if not hasattr(V, 'layout') or not hasattr(V, 'dim'):
+        raise NotImplementedError(
+            '%s on a mixed space: only scalar P1 / P2 spaces carry arguments'
+            % name)
+    if V.dim != 1 or V.component is not None:
+        raise NotImplementedError(
+            '%s on a vector space or a component view: only scalar P1 / P2 '
+            'spaces carry arguments' % name)
+    if V.degree not in (1, 2):
+        raise ValueError('%s: spaces of degree 1 or 2 only' % name)
+    return FormExpr(('arg', number, 0, V), (), V.degree, V.mesh())
+
+
+def TestFunction(V):
+    '''The test function of the scalar space V (argument number 0).'''
+    return _argument(V, 0)
+
+
+def TrialFunction(V):
+    '''The trial function of the scalar space V (argument number 1).'''
+    return _argument(V, 1)
+
+
+def arguments(n, found=None):
+    '''{number: space} of the argument leaves of a scalar tree.'''
+    found = {} if found is None else found
+    if n[0] == 'arg':
+        V = found.setdefault(n[1], n[3])
+        if V is not n[3] and not V.same_as(n[3]):
+            raise NotImplementedError(
+                'two %s functions of different spaces in one form'
+                % ('test', 'trial')[n[1]])
+    elif n[0] in UNARY + BINARY + ('powi',):
+        for c in n[1:]:
+            if isinstance(c, tuple):
+                arguments(c, found)
+    return found
+
+
+_OP_NAMES = {'powi': '**', 'pow': '**', 'div': '/', 'mul': '*'}
+
+
+def extract_arguments(n):
+    '''The integrand tree n, linear in its arguments, as a table
+    {(b, a): c}: n = sum c D_a u D_b v with argument-free trees c; b (test)
+    and a (trial) are 0 value, 1 d/dx, 2 d/dy, or None where that argument is
+    absent.  Entries whose coefficient folds to zero are dropped.  ValueError,
+    naming the operation, where n is not linear in an argument.'''
+    k = n[0]
+    if k == 'arg':
+        return {((n[2], None) if n[1] == 0 else (None, n[2])): ONE}
+    if not has_leaf(n, 'arg'):
+        return {} if _is_num(n, 0.0) else {(None, None): n}
+    if k in ('add', 'sub'):
+        out = dict(extract_arguments(n[1]))
+        for key, c in extract_arguments(n[2]).items():
+            if key in out:
+                out[key] = (s_add if k == 'add' else s_sub)(out[key], c)
+            else:
+                out[key] = c if k == 'add' else s_neg(c)
+        return out
+    if k == 'neg':
+        return {key: s_neg(c) for key, c in extract_arguments(n[1]).items()}
+    if k == 'mul':
+        out = {}
+        tb = extract_arguments(n[2])
+        for (b1, a1), c1 in extract_arguments(n[1]).items():
+            for (b2, a2), c2 in tb.items():
+                if (b1 is not None and b2 is not None) or (
+                        a1 is not None and a2 is not None):
+                    raise ValueError(
+                        'the form is not linear: the %s function appears twice '
+                        'in a product (*)'
+                        % ('test' if b1 is not None and b2 is not None
+                           else 'trial'))
+                key = (b1 if b2 is None else b2, a1 if a2 is None else a2)
+                c = s_mul(c1, c2)
+                out[key] = s_add(out[key], c) if key in out else c
+        return {key: c for key, c in out.items() if not _is_num(c, 0.0)}
+    if k == 'div':
+        if has_leaf(n[2], 'arg'):
+            raise ValueError('the form is not linear: division (/) by an '
+                             'expression of a test or trial function')
+        return {key: s_div(c, n[2])
+                for key, c in extract_arguments(n[1]).items()}
+    raise ValueError('the form is not linear: a test or trial function under '
+                     '%s' % _OP_NAMES.get(k, k))
+
+
+def argument_table(integrand):
+    '''(rank, table) of a scalar integrand: table[b][a] (rank 2) or table[b]
+    (rank 1) of coefficient trees, None where the term is absent.'''
+    tab = {key: c for key, c in extract_arguments(integrand).items()
+           if not _is_num(c, 0.0)}
+    kinds = set((b is not None, a is not None) for b, a in tab)
+    if (False, True) in kinds:
+        raise ValueError('a term of the form holds the trial function without '
+                         'the test function')
+    if len(kinds) > 1:
+        raise ValueError(
+            'the terms of the integrand differ in rank (the test function '
+            'without the trial function, or neither, in a sum that elsewhere '
+            'has both): write the parts as separate forms and split them '
+            'with lhs() / rhs()')
+    if not kinds or kinds == {(False, False)}:
+        return 0, None
+    if kinds == {(True, False)}:
+        return 1, [tab.get((b, None)) for b in range(3)]
+    return 2, [[tab.get((b, a)) for a in range(3)] for b in range(3)]
+
+
+def is_symmetric_table(table):
+    '''Structural symmetry of a rank-2 table: c[b][a] and c[a][b] are the same
+    tree for every (a, b).'''
+    return all(table[b][a] == table[a][b] for b in range(3) for a in range(b))
+
+
 def has_normal(n):
     '''Whether a scalar tree reads the facet normal.'''
     if n[0] == 'n':
@@ -559,6 +716,20 @@ def _quadrature_degree(params):
         return None
     q = params.get('quadrature_degree')
     return None if q is None else int(q)
+
+
+def quadrature_scheme(*params):
+    '''The 'quadrature_rule' of the first of the parameter dicts (form compiler
+    parameters, then the measure's metadata) that names one: 'default' or
+    'vertex'.'''
+    for p in params:
+        rule = (p or {}).get('quadrature_rule')
+        if rule is not None:
+            if rule not in ('default', 'vertex'):
+                raise ValueError("quadrature_rule %r: 'default' or 'vertex'"
+                                 % (rule,))
+            return rule
+    return 'default'
 
 
 _INTEGRAL_TYPES = {'dx': 'cell', 'cell': 'cell', 'ds': 'exterior_facet',
@@ -614,6 +785,11 @@ class Measure(object):
         if self.integral_type == 'cell':
             check_no_normal(f, 'a dx integral')
             return Form(f, _join_mesh(f.mesh, self.mesh), self.metadata)
+        if has_leaf(f.comps, 'arg'):
+            raise NotImplementedError(
+                'test and trial functions under ds (Neumann and Robin terms): '
+                'the facet gather needs a contribution map that does not '
+                'exist yet')
         mesh = _join_mesh(f.mesh, self.mesh)
         if self.subdomain_data is not None:
             mesh = _join_mesh(mesh, self.subdomain_data.mesh)
@@ -625,12 +801,27 @@ dx = Measure('dx')
 ds = Measure('ds')
 
 
+class _InteriorFacets(object):
+    '''dS: interior-facet integrals are not supported.'''
+
+    def _refuse(self, *args, **kwargs):
+        raise NotImplementedError('dS: interior-facet integrals are not '
+                                  'supported (dx and ds are)')
+
+    __call__ = __rmul__ = _refuse
+
+
+dS = _InteriorFacets()
+
+
 class Form(object):
-    '''A rank-0 form: a scalar integrand over the cells of a mesh
-    (integral_type 'cell') or over its exterior facets ('exterior_facet':
-    all of them for subdomain_id 'everywhere', else those whose
-    subdomain_data marker equals subdomain_id).  Forms add and subtract
-    into a FormSum.'''
+    '''A form: a scalar integrand over the cells of a mesh (integral_type
+    'cell') or over its exterior facets ('exterior_facet': all of them for
+    subdomain_id 'everywhere', else those whose subdomain_data marker equals
+    subdomain_id).  `rank` counts its arguments: 0 a functional, 1 linear in
+    a test function, 2 bilinear in a trial and a test function.  Forms add
+    and subtract into a FormSum; `a == L` is an Equation when a side has
+    arguments.'''
 
     def __init__(self, integrand, mesh, metadata, integral_type='cell',
                  subdomain_id='everywhere', subdomain_data=None):
@@ -648,6 +839,40 @@ class Form(object):
     def terms(self):
         return [(1.0, self)]
 
+    def arguments(self):
+        '''{number: space} of the test (0) and trial (1) functions.'''
+        if getattr(self, '_arguments', None) is None:
+            found = arguments(self.integrand.comps)
+            if 0 in found and 1 in found and not found[0].same_as(found[1]):
+                raise NotImplementedError(
+                    'test and trial functions of different spaces or meshes')
+            self._arguments = found
+        return self._arguments
+
+    def argument_table(self):
+        '''(rank, coefficient table) of the integrand: argument_table().'''
+        if getattr(self, '_table', None) is None:
+            self.arguments()
+            self._table = argument_table(self.integrand.comps)
+        return self._table
+
+    @property
+    def rank(self):
+        if not has_leaf(self.integrand.comps, 'arg'):
+            return 0
+        return self.argument_table()[0]
+
+    def function_space(self):
+        '''The space of the test function (None for a functional).'''
+        return self.arguments().get(0)
+
+    def __eq__(self, other):
+        if isinstance(other, Form) and (_sum_rank(self) or _sum_rank(other)):
+            return Equation(self, other)
+        return NotImplemented
+
+    __hash__ = object.__hash__
+
     def __add__(self, other):
         return FormSum.of(self, other, 1.0)
 
@@ -664,8 +889,9 @@ class Form(object):
 
 
 class FormSum(Form):
-    '''A signed sum of rank-0 forms; assemble() adds the parts in the order
-    they were written.'''
+    '''A signed sum of forms; assemble() adds the parts in the order they
+    were written.  The parts of an assembled sum have one rank; lhs() / rhs()
+    split a sum that mixes ranks 1 and 2.'''
 
     def __init__(self, terms):
         self._terms = list(terms)
@@ -681,6 +907,91 @@ class FormSum(Form):
 
     def degree(self):
         raise TypeError('a sum of forms has one degree per part')
+
+    def arguments(self):
+        found = {}
+        for _, f in self._terms:
+            for number, V in f.arguments().items():
+                W = found.setdefault(number, V)
+                if not W.same_as(V):
+                    raise NotImplementedError(
+                        'test and trial functions of different spaces or '
+                        'meshes')
+        return found
+
+    @property
+    def rank(self):
+        ranks = set(f.rank for _, f in self._terms)
+        if len(ranks) > 1:
+            raise ValueError('the parts of the sum have ranks %s: split it '
+                             'with lhs() and rhs()' % sorted(ranks))
+        return ranks.pop() if ranks else 0
+
+    def argument_table(self):
+        raise TypeError('a sum of forms has one table per part')
+
+
+def _sum_rank(form):
+    '''The highest rank among the parts of a form or sum.'''
+    return max([f.rank for _, f in form.terms()] or [0])
+
+
+class Equation(object):
+    '''`a == L`: what solve() takes.'''
+
+    def __init__(self, lhs, rhs):
+        self.lhs = lhs
+        self.rhs = rhs
+
+    def __bool__(self):
+        # (as UFL: `if a == L` asks whether the two are the same object)
+        return self.lhs is self.rhs
+
+    __nonzero__ = __bool__
+
+
+def _parts_of_rank(form, rank, sign):
+    if not isinstance(form, Form):
+        raise TypeError('lhs / rhs / system take a form (got %r)'
+                        % (type(form),))
+    parts = []
+    for s, f in form.terms():
+        if f.rank == 0:
+            raise ValueError('lhs / rhs / system: a part of the sum has no '
+                             'test function')
+        if f.rank == rank:
+            parts.append((sign * s, f))
+    return FormSum(parts)
+
+
+def lhs(F):
+    '''The bilinear parts of a signed sum of forms F (as UFL's lhs).'''
+    return _parts_of_rank(F, 2, 1.0)
+
+
+def rhs(F):
+    '''The linear parts of F, NEGATED (as UFL's rhs: F = a - L = 0).'''
+    return _parts_of_rank(F, 1, -1.0)
+
+
+def system(F):
+    return lhs(F), rhs(F)
+
+
+def derivative(*args, **kwargs):
+    raise NotImplementedError('derivative(): forms are not differentiated '
+                              'here; write the linearised form by hand')
+
+
+def action(*args, **kwargs):
+    raise NotImplementedError('action(): assemble the form and multiply, '
+                              'A * u, or write u in place of the trial '
+                              'function')
+
+
+def adjoint(*args, **kwargs):
+    raise NotImplementedError('adjoint(): swap the test and trial functions '
+                              'in the form by hand')
 
 
 def check_degree(q):
@@ -702,12 +1013,15 @@ class Program(object):
     (('num', v) or (Constant, i)), field components (Function, i) and
     Expression components (Expression, i), in slot order.'''
 
-    def __init__(self, trees, facet=False, point=False):
+    def __init__(self, trees, facet=False, point=False, slots=None,
+                 nout=None):
         '''facet: the program runs on exterior facets, where the normal
         exists (ValueError if a tree reads it otherwise).  point: it runs at
         located points (Probes, u(x)), where neither the normal nor
         Expression leaves exist (their lattices are tabulated at the rule's
-        points only).'''
+        points only).  slots: the output slot of every tree out of nout
+        (default: tree k -> output k of len(trees)); the coefficient tables
+        of forms of arguments use it (argument_program).'''
         if point and any(has_leaf(t, 'n') for t in trees):
             raise ValueError('FacetNormal is defined on exterior facets only: '
                              'it cannot be evaluated at points')
@@ -717,18 +1031,24 @@ class Program(object):
         if not facet and any(has_normal(t) for t in trees):
             raise ValueError('FacetNormal is defined on exterior facets only: '
                              'integrate over ds')
+        if any(has_leaf(t, 'arg') for t in trees):
+            raise ValueError('test and trial functions are not evaluated: only '
+                             'their coefficients compile (argument_table)')
+        if slots is None:
+            slots = list(range(len(trees)))
         self.code = []
         self.consts = []
         self.fields = []
         self.exprs = []
         self.nregs = 0
-        for k, t in enumerate(trees):
+        for k, t in zip(slots, trees):
             self._gen(t, 0)
             self._emit('out', 0, 0, k)
         if len(self.code) > MAX_PROGRAM:
             raise ValueError('the integrand compiles to %d instructions: the '
                              'limit is %d' % (len(self.code), MAX_PROGRAM))
-        self.nout = len(trees)
+        self.slots = list(slots)
+        self.nout = len(trees) if nout is None else nout
 
     def signature(self):
         return (tuple(self.code),
@@ -835,6 +1155,18 @@ class Program(object):
             else:
                 out.append(float(k[0].values()[k[1]]))
         return out
+
+
+def argument_program(table, rank):
+    '''The Program of a coefficient table (argument_table): rank 2, slot
+    3 b + a of 9; rank 1, slot b of 3; absent terms have no instruction.'''
+    if rank == 2:
+        items = [(3 * b + a, table[b][a]) for b in range(3) for a in range(3)]
+    else:
+        items = list(enumerate(table))
+    items = [(k, t) for k, t in items if t is not None]
+    return Program([t for _, t in items], slots=[k for k, _ in items],
+                   nout=9 if rank == 2 else 3)
 
 
 def form_mesh(expr, mesh=None):

@@ -185,8 +185,25 @@ class Matrix(object):
             ))
         return out
 
+    def __mul__(self, x):
+        '''A * x for a Vector or a Function: a new Vector (one apply).  Not
+        on strips, where a rank holds its own rows only.'''
+        from .function import Vector
+        _no_strips('Matrix * vector')
+        data = x.data if isinstance(x, (Vector, Function)) else None
+        if data is None:
+            return NotImplemented
+        if data.numel() != self.size:
+            raise ValueError('matrix of size %d times a vector of %d entries'
+                             % (self.size, data.numel()))
+        return Vector(self.apply(data, device.empty(self.size)))
+
+    __matmul__ = __mul__
+
     def to_scipy(self):
-        '''Host copy (tests / debugging only).'''
+        '''Host copy as a scipy.sparse CSR matrix: the way to inspect an
+        assembled matrix (entries, symmetry, a direct solve in a test).  Not
+        for hot paths: it copies every value plane to the host.'''
         import scipy.sparse as sp
         lay = self.layout
         rp = lay.pattern('rowptr')
@@ -794,18 +811,29 @@ def errornorm(exact, uh, degree_rise=3):
 _FORM_TABLES = {}
 
 
-def _form_tables(q, expr_degrees, facet=False):
+def _form_tables(q, expr_degrees, facet=False, scheme='default'):
     '''Rule (nq x 3: xi, eta, weight; on facets 3*nq rows, the points of
     local facets 0, 1, 2: reference.facet_rule) and the P_k basis tables of
     the Expression operands at its points, uploaded once per (degree, lattice
     degrees, cells | facets): an upload drains the stream, and time loops
     integrate the same forms every step.  (The program and the constants
     need no upload: they travel with the launch.)  Returns (rule, tables,
-    table offsets, nq per cell or facet, doubles in tables).'''
+    table offsets, nq per cell or facet, doubles in tables).  scheme
+    'vertex' (cells only): the cell vertices with weights |T|/3, whatever
+    q.'''
+    if scheme == 'vertex':
+        if facet:
+            raise ValueError('the vertex quadrature rule is defined on cells')
+        q = None
     key = (q, expr_degrees, facet, str(device.get()))
     held = _FORM_TABLES.get(key)
     if held is None:
-        if facet:
+        if scheme == 'vertex':
+            pts = numpy.array([[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]])
+            rule = numpy.concatenate([pts, numpy.full((3, 1), 1.0 / 6.0)],
+                                     axis=1)
+            nq = 3
+        elif facet:
             rule = reference.facet_rule(q)
             pts = rule[:, :2]
             nq = len(rule) // 3
@@ -833,9 +861,10 @@ def _form_tables(q, expr_degrees, facet=False):
     return held
 
 
-def _form_struct(prog, mesh, q, facet=False):
+def _form_struct(prog, mesh, q, facet=False, scheme='default'):
     '''flow_form of a compiled forms.Program on `mesh` with the degree-q
-    rule of the cells, or of the facets.  Returns (struct, keepalive).'''
+    rule of the cells, or of the facets (scheme 'vertex': the vertex rule of
+    the cells).  Returns (struct, keepalive).'''
     fs = _hip.FormS()
     fs.nprog = len(prog.code)
     for i, ins in enumerate(prog.code):
@@ -860,7 +889,8 @@ def _form_struct(prog, mesh, q, facet=False):
             lay.dev('cell_dofs'), lay.nloc * nc, 'cell_dofs').value
         keep.append(f.data)
     expr_degrees = tuple(int(e.degree) for e, _ in prog.exprs)
-    rule, tables, offsets, nq, ntables = _form_tables(q, expr_degrees, facet)
+    rule, tables, offsets, nq, ntables = _form_tables(q, expr_degrees, facet,
+                                                      scheme)
     fs.nexpr = len(prog.exprs)
     coefs = {}
     for i, (e, comp) in enumerate(prog.exprs):
@@ -889,25 +919,37 @@ def _no_strips(what):
             'there)' % what)
 
 
-def assemble(form):
-    '''assemble(f*dx), assemble(f*ds(k)), and signed sums of such forms: the
-    integral of a scalar integrand over the cells or the exterior facets of
-    the mesh, a float.  Fixed-order reductions on the device and the parts of
-    a sum added in the order written: the same bits on every call.'''
+def assemble(form, form_compiler_parameters=None):
+    '''By the rank of the form.  0: assemble(f*dx), assemble(f*ds(k)) and
+    signed sums of such forms -- the integral of a scalar integrand over the
+    cells or the exterior facets of the mesh, a float.  1: forms of a
+    TestFunction, a Vector.  2: forms of a TrialFunction and a TestFunction
+    (over dx), a Matrix of kind 0 on the space's pattern.  The parts of a sum
+    are assembled one by one, each at its own degree, and added in the order
+    written; fixed-order reductions and gathers on the device: the same bits
+    on every call.  form_compiler_parameters: 'quadrature_degree' replaces
+    the estimate (a measure's own metadata comes first), 'quadrature_rule':
+    'vertex' selects the vertex rule for ranks 1 and 2 (functionals do not
+    read that key).'''
     from . import forms
     if not isinstance(form, forms.Form):
-        raise TypeError('assemble takes a rank-0 form f*dx (got %r): forms '
-                        'of test and trial functions are not supported'
+        raise TypeError('assemble takes a form, f*dx or f*ds (got %r)'
                         % (type(form),))
     _no_strips('assemble')
+    rank = form.rank
+    if rank > 0:
+        return _assemble_arguments(form, rank, form_compiler_parameters)
     if isinstance(form, forms.FormSum):
         total = 0.0
         for sign, part in form.terms():
-            total += sign * assemble(part)
+            total += sign * assemble(part, form_compiler_parameters)
         return total
+    q = forms._quadrature_degree(form.metadata)
+    if q is None:
+        q = forms._quadrature_degree(form_compiler_parameters)
+    q = forms.check_degree(form.degree() if q is None else q)
     lib = _hip.lib()
     mesh = forms.form_mesh(form.integrand, form.mesh)
-    q = forms.check_degree(form.degree())
     facet = form.integral_type == 'exterior_facet'
     prog = forms.Program([form.integrand.comps], facet=facet)
     fs, keep = _form_struct(prog, mesh, q, facet)
@@ -930,6 +972,208 @@ def assemble(form):
             ))
     del keep
     return res.value
+
+
+def _assemble_arguments(form, rank, form_compiler_parameters=None):
+    '''assemble() of a form, or of a signed sum of forms, of rank 1 (a
+    Vector) or 2 (a Matrix): flow_form_vector / flow_form_matrix per part.'''
+    from . import forms
+    from .function import Vector
+    lib = _hip.lib()
+    V = form.arguments()[0]
+    lay = V.layout
+    mesh = V.mesh()
+    nc = mesh.num_cells()
+    total = None
+    for sign, part in form.terms():
+        if part.integral_type != 'cell':
+            raise NotImplementedError('test and trial functions under ds')
+        if forms.form_mesh(part.integrand, part.mesh) is not mesh:
+            raise ValueError('the form is integrated over another mesh than '
+                             'the one of its arguments')
+        _, table = part.argument_table()
+        q = forms._quadrature_degree(part.metadata)
+        if q is None:
+            q = forms._quadrature_degree(form_compiler_parameters)
+        q = forms.check_degree(part.degree() if q is None else q)
+        scheme = forms.quadrature_scheme(form_compiler_parameters,
+                                         part.metadata)
+        prog = forms.argument_program(table, rank)
+        fs, keep = _form_struct(prog, mesh, q, scheme=scheme)
+        if rank == 2:
+            out = value_plane(lay)
+            buf = scratch(mesh, lay.nloc**2 * nc)
+            _hip.check(lib.flow_form_matrix(
+                ctypes.byref(mesh_struct(mesh)),
+                ctypes.byref(space_struct(lay)), ctypes.byref(fs),
+                _hip.f64(buf, lay.nloc**2 * nc, 'scratch'),
+                _hip.f64(out, lay.nnz, 'vals'), _hip.stream()
+                ))
+        else:
+            out = device.empty(lay.N)
+            buf = scratch(mesh, lay.nloc * nc)
+            _hip.check(lib.flow_form_vector(
+                ctypes.byref(mesh_struct(mesh)),
+                ctypes.byref(space_struct(lay)), ctypes.byref(fs),
+                _hip.f64(buf, lay.nloc * nc, 'scratch'),
+                _hip.f64(out, lay.N, 'b'), _hip.stream()
+                ))
+        del keep
+        if total is None and sign == 1.0:
+            total = out
+        else:
+            if total is None:
+                total = _hip.fill(device.empty(out.numel()), 0.0)
+            axpby(sign, out, 1.0, total)
+    if total is None:
+        raise ValueError('an empty sum of forms has no rank')
+    return Matrix(lay, 0, total) if rank == 2 else Vector(total)
+
+
+def _scalar_bcs(bcs, V):
+    '''(dofs, values) on the device and the byte mask of the Dirichlet dofs
+    of conditions on the scalar space V (None, None, None without any).'''
+    from .bcs import collect
+    if bcs is None:
+        bcs = []
+    if not isinstance(bcs, (list, tuple)):
+        bcs = [bcs]
+    for bc in bcs:
+        W = bc.function_space()
+        if W.component is not None or not W.same_as(V):
+            raise ValueError('a Dirichlet condition lives on another space '
+                             'than the form')
+    dofs, vals = collect(list(bcs), V.size())
+    if len(dofs) == 0:
+        return None, None, None
+    mask = numpy.zeros(V.N, dtype=numpy.uint8)
+    mask[dofs] = 1
+    return (device.to_device(dofs), device.to_device(vals),
+            device.to_device(mask))
+
+
+def _set_values(dofs, vals, x):
+    _hip.check(_hip.lib().flow_bc_set_values(
+        dofs.numel(), _hip.i32(dofs), _hip.f64(vals, dofs.numel()),
+        _hip.f64(x), _hip.stream()))
+
+
+def _form_space(a):
+    found = a.arguments()
+    if a.rank != 2:
+        raise ValueError('the left-hand side must be a bilinear form (rank 2)')
+    return found[0]
+
+
+def assemble_system(a, L, bcs=None, form_compiler_parameters=None):
+    '''(A, b) of the bilinear form a and the linear form L (None or an empty
+    sum: zero) with dolfin's symmetric elimination of the Dirichlet
+    conditions: rows and columns of their dofs are zeroed, the diagonal is 1,
+    b is lifted by the eliminated columns and b[dof] = g.'''
+    from . import forms
+    from .function import Vector
+    _no_strips('assemble_system')
+    V = _form_space(a)
+    A0 = assemble(a, form_compiler_parameters)
+    if L is None or (isinstance(L, forms.FormSum) and not L.terms()):
+        b = Vector(device.zeros(V.N))
+    else:
+        if L.rank != 1:
+            raise ValueError('the right-hand side must be a linear form '
+                             '(rank 1)')
+        if not L.arguments()[0].same_as(V):
+            raise NotImplementedError('test functions of different spaces or '
+                                      'meshes on the two sides')
+        b = assemble(L, form_compiler_parameters)
+    dofs, vals, mask = _scalar_bcs(bcs, V)
+    if dofs is None:
+        return A0, b
+    g = device.zeros(V.N)
+    _set_values(dofs, vals, g)
+    lift = A0.apply(g, device.empty(V.N))
+    axpby(-1.0, lift, 1.0, b.data)
+    _set_values(dofs, vals, b.data)
+    return symmetric_bc_matrix(A0, mask), b
+
+
+def apply_identity_rows(bc, A=None, b=None):
+    '''DirichletBC.apply: the rows of the condition's dofs of A become
+    identity rows, the entries of b its values (no column elimination).
+    Not on strips (the steppers apply their conditions themselves there).'''
+    _no_strips('DirichletBC.apply')
+    V = bc.function_space()
+    dofs, vals, _ = _scalar_bcs([bc], V)
+    if dofs is None:
+        return
+    if A is not None:
+        if A.kind != 0 or A.layout is not V.layout:
+            raise ValueError('the matrix does not belong to the space of the '
+                             'condition')
+        _hip.check(_hip.lib().flow_bc_identity_rows(
+            ctypes.byref(A.operator()), _hip.f64(A.vals),
+            _hip.i32(V.layout.dev('diag_idx')), dofs.numel(), _hip.i32(dofs),
+            _hip.stream()))
+    if b is not None:
+        data = b.data if hasattr(b, 'data') else b
+        if data.numel() != V.N:
+            raise ValueError('the vector does not belong to the space of the '
+                             'condition')
+        _set_values(dofs, vals, data)
+
+
+_KRYLOV_METHODS = ('cg', 'gmres', 'bicgstab')
+
+
+def solve(equation, u, bcs=None, solver_parameters=None,
+          form_compiler_parameters=None):
+    '''solve(a == L, u, bcs): assemble_system, then a Krylov solve on the
+    device that starts from u's values and writes into u.  Returns the
+    SolveInfo.  The form counts as symmetric where every part of a is
+    structurally symmetric, or where solver_parameters['symmetric'] is True.
+    solver_parameters: 'linear_solver' 'cg' | 'gmres' | 'bicgstab'; absent,
+    'default' or 'iterative': CG for a symmetric form, else GMRES.  The
+    preconditioner follows one rule, whether the method was chosen or
+    defaulted: ILU(0) iff the method is not CG and the form is not symmetric,
+    Jacobi otherwise -- so 'gmres' or 'bicgstab' on a symmetric form run with
+    Jacobi, and 'cg' on a non-symmetric form is run as asked, with Jacobi and
+    without a warning (it may not converge: NotConverged).  'krylov_solver':
+    'relative_tolerance' (1e-12), 'absolute_tolerance' (0),
+    'maximum_iterations' (1000).  There is no direct solver.  A pure Neumann
+    problem is singular: pin a value.  Raises _hip.NotConverged (a
+    RuntimeError).  Not on strips.'''
+    from . import forms
+    _no_strips('solve')
+    if not isinstance(equation, forms.Equation):
+        raise TypeError('solve takes an equation a == L of a bilinear and a '
+                        'linear form (got %r)' % (type(equation),))
+    prm = dict(solver_parameters or {})
+    method = prm.get('linear_solver', 'default')
+    if method not in _KRYLOV_METHODS + ('default', 'iterative'):
+        raise ValueError(
+            'linear_solver %r: there is no direct solver here; the choices '
+            'are %s' % (method, ', '.join(_KRYLOV_METHODS + ('default',))))
+    a, L = equation.lhs, equation.rhs
+    V = _form_space(a)
+    if not isinstance(u, Function) or not u.function_space().same_as(V):
+        raise ValueError('solve writes into a Function of the space of the '
+                         'trial function')
+    symmetric = prm.get('symmetric') is True or all(
+        forms.is_symmetric_table(part.argument_table()[1])
+        for _, part in a.terms())
+    if method in ('default', 'iterative'):
+        method = 'cg' if symmetric else 'gmres'
+    ks = dict(prm.get('krylov_solver') or {})
+    A, b = assemble_system(a, L, bcs, form_compiler_parameters)
+    ilu = None
+    if method != 'cg' and not symmetric:
+        from .ilu import Ilu0
+        ilu = Ilu0(A)
+    info = krylov_solve(
+        method, A, b.data, u.data, ks.get('relative_tolerance', 1.0e-12),
+        atol=ks.get('absolute_tolerance', 0.0),
+        maxit=int(ks.get('maximum_iterations', 1000)), ilu=ilu,
+        check_every=10)
+    return info
 
 
 def facet_lists(mesh, markers=None, subdomain_id='everywhere'):

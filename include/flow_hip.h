@@ -1090,7 +1090,8 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
  * to a register program: at most FLOW_FORM_MAX_PROGRAM instructions
  * (op, dst, a, b) over FLOW_FORM_REGISTERS fp64 registers r[0..7].  A cell
  * kernel runs the program at every point of the quadrature rule; `out` ops
- * hand a register to output 0 or 1.
+ * hand a register to output 0 or 1 (to a coefficient slot in the programs of
+ * flow_form_matrix / flow_form_vector).
  *   const  r[dst] = consts[a]          coord  r[dst] = x_a at the point
  *   field  r[dst] = field a (b = 0), d/dx (b = 1) or d/dy (b = 2)
  *   expr   r[dst] = sum_l expr[a][l][c] * tables[expr_table[a] + q*nl + l]
@@ -1108,6 +1109,7 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
 #define FLOW_FORM_MAX_FIELDS 6
 #define FLOW_FORM_MAX_EXPRESSIONS 4
 #define FLOW_FORM_MAX_POINTS 256
+#define FLOW_FORM_SLOTS 9     /* coefficient slots of a rank-2 form */
 #define FLOW_FORM_OP_CONST 0
 #define FLOW_FORM_OP_COORD 1
 #define FLOW_FORM_OP_FIELD 2
@@ -1144,7 +1146,8 @@ typedef struct {
   const double* rule;                      /* nq x 3: xi, eta, weight (sum 1/2) */
   const double* tables;                    /* P_k basis at the rule's points */
   int ntables;                             /* doubles in tables */
-  int nout;                                /* 1 | 2 */
+  int nout;                                /* 1 | 2; flow_form_matrix: 9,
+                                              flow_form_vector: 3 */
 } flow_form;
 
 /* assemble(f*dx): the integral of output 0 over the cells of `mesh`, to the
@@ -1174,6 +1177,27 @@ int flow_form_facet_functional(const flow_mesh* mesh, const flow_form* form,
 int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
                           const flow_form* form, double* scratch, double* b,
                           void* stream);
+
+/* Forms of a test function v and a trial function u of the scalar space V
+ * (TestFunction / TrialFunction of forms.py).  The host rewrites the integrand
+ * by linearity as  sum_(b,a) c_ba D_a u D_b v  (rank 2) or  sum_b c_b D_b v
+ * (rank 1), D_0 the value, D_1 d/dx, D_2 d/dy, and compiles the argument-free
+ * coefficients into one program: `out` slot 3 b + a holds c_ba (nout =
+ * FLOW_FORM_SLOTS), slot b holds c_b (nout = 3).  Slots the program does not
+ * write are absent terms (a bit mask of the written ones travels with the
+ * launch); at least one must be written, none twice; NORMAL is refused.
+ *   flow_form_matrix: Ke[i][j] = sum_q w_q |det J| sum_ba c_ba(x_q) D_a phi_j
+ *     D_b phi_i per cell, summed over cptr / csrc into `vals`, one value plane
+ *     (nnz doubles) of a kind-0 operator on V's pattern.  scratch: nloc^2 * nc.
+ *   flow_form_vector: b_i = sum_q w_q |det J| sum_b c_b(x_q) D_b phi_i, summed
+ *     over vptr / vsrc into b (n doubles).  scratch: nloc * nc.
+ * No floating-point atomics: two calls give the same bits.  Not on strips. */
+int flow_form_matrix(const flow_mesh* mesh, const flow_space* V,
+                     const flow_form* form, double* scratch, double* vals,
+                     void* stream);
+int flow_form_vector(const flow_mesh* mesh, const flow_space* V,
+                     const flow_form* form, double* scratch, double* b,
+                     void* stream);
 
 /* ---- point evaluation (flow_amd/fem/points.py): u(x), Probes ---------------
  * A uniform bucket grid over the mesh's bounding box, built on the host once
