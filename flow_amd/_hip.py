@@ -211,6 +211,7 @@ FORM_MAX_FIELDS = 6
 FORM_MAX_EXPRESSIONS = 4
 FORM_MAX_POINTS = 256
 FORM_SLOTS = 9
+FORM_NEWTON_SLOTS = 12
 
 
 class FormS(ctypes.Structure):
@@ -434,6 +435,8 @@ SYMBOLS = {
     'flow_form_load_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
     'flow_form_matrix': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
     'flow_form_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
+    'flow_form_newton': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP,
+                         _VP],
     'flow_form_facet_functional': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP,
                                    _P(_D), _VP],
     'flow_locate_points': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _VP, _VP],

@@ -166,6 +166,29 @@ struct FormSlots {
   }
 };
 
+// the 12 slots of form_newton_kernel: 3 b + a of the Jacobian's table, then
+// 9 + b of the residual's (a set of its own: FormSlots<9> / <3> and the code
+// of the kernels that use them stay as they are)
+struct FormSlotsNewton {
+  double v[FLOW_FORM_NEWTON_SLOTS];
+  __device__ __forceinline__ void set(int b, double r) {
+    switch (b) {
+      case 0: v[0] = r; break;
+      case 1: v[1] = r; break;
+      case 2: v[2] = r; break;
+      case 3: v[3] = r; break;
+      case 4: v[4] = r; break;
+      case 5: v[5] = r; break;
+      case 6: v[6] = r; break;
+      case 7: v[7] = r; break;
+      case 8: v[8] = r; break;
+      case 9: v[9] = r; break;
+      case 10: v[10] = r; break;
+      default: v[11] = r; break;
+    }
+  }
+};
+
 template <int NF, bool FACET, class OUT>
 __device__ __forceinline__ void form_point_n(const flow_form& F,
                                              const double (&U)[NF > 0 ? NF : 1][6],
@@ -618,12 +641,94 @@ __global__ __launch_bounds__(kBlock) void form_vector_kernel(
   for (int i = 0; i < NL; ++i) scratch[static_cast<size_t>(i) * nc + c] = be[i];
 }
 
+// Jacobian and residual of a Newton iteration in one pass (forms.py,
+// newton_program): ONE program writes the 9 slots of the Jacobian's table and,
+// at 9 + b, the 3 of the residual's; geometry, field values, basis tables and
+// the subtrees the two tables share are loaded / computed once per point.  Ke
+// and be are accumulated with the arithmetic of form_matrix_kernel and
+// form_vector_kernel, in their order; Ke goes to scratch[(i*NL + j)*nc + c],
+// be behind it to scratch[(NL*NL + i)*nc + c].  live: bits 0..8 the Jacobian's
+// slots, 9..11 the residual's.
+template <int NF, int DEG>
+__global__ __launch_bounds__(kBlock) void form_newton_kernel(
+    int nc, const double* __restrict__ xy, const flow_form F, int live,
+    double* __restrict__ scratch) {
+  constexpr int NL = Elem<DEG>::NL;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  double* const dst = scratch + c;
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
+  double Ke[NL][NL], be[NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i) {
+    be[i] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) Ke[i][j] = 0.0;
+  }
+  for (int q = 0; q < F.nq; ++q) {
+    const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
+    const double w = F.rule[3 * q + 2] * g.adet;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlotsNewton out;
+#pragma unroll
+    for (int k = 0; k < FLOW_FORM_NEWTON_SLOTS; ++k) out.v[k] = 0.0;
+    form_point_n<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    double phi[NL], dphi[NL][3], gphi[NL][2];
+    basis<DEG>(L, phi, dphi);
+    phys_grad<NL>(g, dphi, gphi);
+    // (the mask through an empty asm, as in form_matrix_kernel)
+    int m = live;
+    asm volatile("" : "+s"(m));
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (((m >> (3 * b)) & 7) == 0) continue;
+      double t[NL];
+#pragma unroll
+      for (int j = 0; j < NL; ++j) t[j] = 0.0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (((m >> (3 * b + a)) & 1) == 0) continue;
+        const double s = w * out.v[3 * b + a];
+#pragma unroll
+        for (int j = 0; j < NL; ++j) t[j] += s * arg_basis<NL>(a, phi, gphi, j);
+      }
+#pragma unroll
+      for (int i = 0; i < NL; ++i) {
+        const double di = arg_basis<NL>(b, phi, gphi, i);
+#pragma unroll
+        for (int j = 0; j < NL; ++j) Ke[i][j] += di * t[j];
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (((m >> (FLOW_FORM_SLOTS + b)) & 1) == 0) continue;
+      const double s = w * out.v[FLOW_FORM_SLOTS + b];
+#pragma unroll
+      for (int i = 0; i < NL; ++i) be[i] += s * arg_basis<NL>(b, phi, gphi, i);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NL; ++i)
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+      dst[static_cast<size_t>(i * NL + j) * nc] = Ke[i][j];
+#pragma unroll
+  for (int i = 0; i < NL; ++i)
+    dst[static_cast<size_t>(NL * NL + i) * nc] = be[i];
+}
+
 // rows: the rule holds rows * nq points (1: cells; 3: the three local
 // facets); facet: NORMAL is legal; points: the program runs at located
 // points -- no rule, no Expression lattices (they are tabulated at the
 // rule's rows), no normal; slots = 0: one or two outputs, each written; 9 | 3:
-// the coefficient table of a rank-2 | rank-1 form -- nout == slots, *live =
-// one bit per slot the program writes (at least one, none twice)
+// the coefficient table of a rank-2 | rank-1 form, 12: the two tables of
+// flow_form_newton behind one another -- nout == slots, *live = one bit per
+// slot the program writes (at least one, none twice; 12: at least one of the
+// first 9 and one of the last 3)
 static int check_form(const flow_form* F, int rows = 1, bool facet = false,
                       bool points = false, int slots = 0, int* live = nullptr) {
   FLOW_REQUIRE(F, "form");
@@ -696,6 +801,9 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
     FLOW_REQUIRE(wrote == (1 << F->nout) - 1, "form writes every output");
   else
     FLOW_REQUIRE(wrote != 0, "form writes no coefficient slot");
+  if (slots == FLOW_FORM_NEWTON_SLOTS)
+    FLOW_REQUIRE((wrote & ((1 << FLOW_FORM_SLOTS) - 1)) != 0 && (wrote >> FLOW_FORM_SLOTS) != 0,
+                 "form writes no Jacobian slot or no residual slot");
   if (live) *live = wrote;
   return FLOW_OK;
 }
@@ -823,6 +931,30 @@ static int launch_vector(const flow_mesh* mesh, const flow_form* F, int live,
     default:
     FLOW_FORM_VECTOR_CASE(6)
 #undef FLOW_FORM_VECTOR_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+template <int DEG>
+static int launch_newton(const flow_mesh* mesh, const flow_form* F, int live,
+                         double* scratch, hipStream_t st) {
+  const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
+  switch (F->nfield) {
+#define FLOW_FORM_NEWTON_CASE(NF)                                                \
+    case NF:                                                                     \
+      hipLaunchKernelGGL((form_newton_kernel<NF, DEG>), grid, dim3(kBlock),      \
+                         0, st, mesh->nc, mesh->xy, *F, live, scratch);         \
+      break;
+    FLOW_FORM_NEWTON_CASE(0)
+    FLOW_FORM_NEWTON_CASE(1)
+    FLOW_FORM_NEWTON_CASE(2)
+    FLOW_FORM_NEWTON_CASE(3)
+    FLOW_FORM_NEWTON_CASE(4)
+    FLOW_FORM_NEWTON_CASE(5)
+    default:
+    FLOW_FORM_NEWTON_CASE(6)
+#undef FLOW_FORM_NEWTON_CASE
   }
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
@@ -973,4 +1105,28 @@ extern "C" int flow_form_vector(const flow_mesh* mesh, const flow_space* V,
   if (rc) return rc;
   return gather(V->n, 1, V->vptr, V->vsrc, scratch,
                 static_cast<size_t>(V->deg == 1 ? 3 : 6) * mesh->nc, b, st);
+}
+
+extern "C" int flow_form_newton(const flow_mesh* mesh, const flow_space* V,
+                                const flow_form* form, double* scratch, double* vals,
+                                double* b, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  int live = 0;
+  if ((rc = check_form(form, 1, false, false, FLOW_FORM_NEWTON_SLOTS, &live))) return rc;
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->nnz > 0 &&
+                   V->cptr && V->csrc && V->vptr && V->vsrc,
+               "space");
+  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(scratch && vals && b, "pointers");
+  hipStream_t st = as_stream(stream);
+  rc = V->deg == 1 ? launch_newton<1>(mesh, form, live, scratch, st)
+                   : launch_newton<2>(mesh, form, live, scratch, st);
+  if (rc) return rc;
+  const int nl = V->deg == 1 ? 3 : 6;
+  if ((rc = gather(V->nnz, 1, V->cptr, V->csrc, scratch, 0, vals, st))) return rc;
+  return gather(V->n, 1, V->vptr, V->vsrc,
+                scratch + static_cast<size_t>(nl) * nl * mesh->nc,
+                static_cast<size_t>(nl) * mesh->nc, b, st);
 }

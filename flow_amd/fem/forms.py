@@ -61,7 +61,32 @@ cell vertices and weights |T|/3 (the lumped mass matrix of u*v*dx).
 Not supported (NotImplementedError): arguments on vector or mixed spaces, test
 and trial functions of different spaces, arguments under ds (Neumann / Robin
 terms: the facet gather needs a contribution map that does not exist yet),
-dS, derivative / action / adjoint.
+dS, action / adjoint.
+
+Derivatives: `derivative(F, u, du=None)` is the Gateaux derivative of a form
+(or signed sum) of rank 0 or 1 with respect to a scalar P1 / P2 Function u,
+taken on the scalar trees like s_diff's spatial chain rule (s_gateaux): the
+leaf ('field', u, 0, d) becomes ('arg', k, d, V), V = u.function_space(), k =
+the number of arguments F already has (a functional gives a form in the test
+function, a residual one in the trial function); every other leaf is zero;
+add sub neg mul div powi pow sqrt exp ln sin cos abs follow the usual rules
+(abs(a): a/abs(a) da), zeros fold away, and the new argument only ever lands
+in numerators and products, so the result passes extract_arguments as it is.
+It works part by part (sign, measure, metadata and mesh are kept; parts that
+do not depend on u vanish), twice on an energy functional it gives the
+bilinear form.  A derived part keeps the quadrature degree of the part it
+came from (unless metadata fixes one): for integrands polynomial in u that IS
+UFL's estimate -- replacing a factor u by du of the same space leaves the sum
+of degrees unchanged --, for the others it differs from dolfin's by
+quadrature error, like the estimates above.  Refused: a rank-2 form (the
+result would be a rank-3 form), u on a vector, component or mixed space,
+rank-0 ds parts (the argument would land under ds), a form that does not
+depend on u, u of another space than the form's arguments.  `F == 0` is the
+Equation of the nonlinear solve(F == 0, u, bcs, J=...) (ops.solve: Newton);
+a form of any rank compared with the number 0 gives one (solve refuses what
+is not a residual), any other number is a ValueError.
+newton_program() compiles the tables of J and F into one Program (slots
+3 b + a and 9 + b of 12) that computes the subtrees the two share once.
 '''
 import numbers
 
@@ -74,6 +99,7 @@ REGISTERS = 8
 MAX_CONSTANTS = 32
 MAX_FIELDS = 6
 MAX_EXPRESSIONS = 4
+NEWTON_SLOTS = 12       # 9 of the Jacobian's table, 3 of the residual's
 OPS = {name: i for i, name in enumerate((
     'const', 'coord', 'field', 'expr', 'mov', 'add', 'sub', 'mul', 'div', 'pow',
     'neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos', 'out', 'normal'))}
@@ -86,8 +112,9 @@ BINARY = ('add', 'sub', 'mul', 'div', 'pow')
 # (d = 0 value, 1 d/dx, 2 d/dy) ('expr', Expression, i) ('n', d) (component
 # d of the outward unit normal, ds only) ('arg', number, d, V) (number 0 the
 # test, 1 the trial function of the space V; d as for fields) ('powi', a, n)
-# and (op, a[, b]) for the UNARY / BINARY ops.  Objects inside compare by
-# identity.
+# and (op, a[, b]) for the UNARY / BINARY ops; ('reg', r) (register r of the
+# program, holding a subtree computed up front: newton_program only).  Objects
+# inside compare by identity.
 ZERO = ('num', 0.0)
 ONE = ('num', 1.0)
 
@@ -195,6 +222,51 @@ def s_diff(n, d):
     if k == 'cos':
         return s_neg(s_mul(('sin', a), da))
     raise NotImplementedError('derivative of %s' % k)
+
+
+def s_gateaux(n, u, k, V):
+    '''d n / d u in the direction of argument number k of V = the space of the
+    scalar Function u: s_diff's chain rule with another leaf rule.'''
+    op = n[0]
+    if op == 'field':
+        if n[1] is u and n[2] == 0:
+            return ('arg', k, n[3], V)
+        return ZERO
+    if op in ('num', 'const', 'x', 'expr', 'n', 'arg'):
+        return ZERO
+    a = n[1]
+    da = s_gateaux(a, u, k, V)
+    if op == 'neg':
+        return s_neg(da)
+    if op == 'powi':
+        return s_mul(s_mul(('num', float(n[2])), s_powi(a, n[2] - 1)), da)
+    if op == 'sqrt':
+        return s_div(da, s_mul(('num', 2.0), n))
+    if op == 'exp':
+        return s_mul(n, da)
+    if op == 'ln':
+        return s_div(da, a)
+    if op == 'sin':
+        return s_mul(('cos', a), da)
+    if op == 'cos':
+        return s_neg(s_mul(('sin', a), da))
+    if op == 'abs':
+        return s_mul(s_div(a, n), da)
+    if op not in BINARY:
+        raise NotImplementedError('derivative of %s' % op)
+    b = n[2]
+    db = s_gateaux(b, u, k, V)
+    if op == 'add':
+        return s_add(da, db)
+    if op == 'sub':
+        return s_sub(da, db)
+    if op == 'mul':
+        return s_add(s_mul(da, b), s_mul(a, db))
+    if op == 'div':
+        # (da / b - a db / b^2: the argument stays in the numerators)
+        return s_sub(s_div(da, b), s_div(s_mul(a, db), s_powi(b, 2)))
+    # pow
+    return s_mul(n, s_add(s_mul(db, ('ln', a)), s_div(s_mul(b, da), a)))
 
 
 # -- tensors of scalar trees -----------------------------------------------------
@@ -869,6 +941,11 @@ class Form(object):
     def __eq__(self, other):
         if isinstance(other, Form) and (_sum_rank(self) or _sum_rank(other)):
             return Equation(self, other)
+        if isinstance(other, numbers.Real) and not isinstance(other, bool):
+            if other != 0:
+                raise ValueError('F == %r: a form equals another form (a == L) '
+                                 'or 0 (the nonlinear F == 0)' % (other,))
+            return Equation(self, 0)
         return NotImplemented
 
     __hash__ = object.__hash__
@@ -937,7 +1014,7 @@ def _sum_rank(form):
 
 
 class Equation(object):
-    '''`a == L`: what solve() takes.'''
+    '''`a == L`, or `F == 0` (rhs the number 0): what solve() takes.'''
 
     def __init__(self, lhs, rhs):
         self.lhs = lhs
@@ -978,9 +1055,67 @@ def system(F):
     return lhs(F), rhs(F)
 
 
-def derivative(*args, **kwargs):
-    raise NotImplementedError('derivative(): forms are not differentiated '
-                              'here; write the linearised form by hand')
+def derivative(F, u, du=None):
+    '''The Gateaux derivative of the form (or signed sum) F of rank 0 or 1
+    with respect to the scalar P1 / P2 Function u, part by part: a form of
+    rank + 1 whose new argument has the number of arguments F already has (0:
+    the test, 1: the trial function of u's space).  du: that argument, given
+    explicitly.  See the module docstring for the rules and the refusals.'''
+    if not isinstance(F, Form):
+        raise TypeError('derivative takes a form (got %r)' % (type(F),))
+    if _sum_rank(F) >= 2:
+        raise NotImplementedError(
+            'derivative of a bilinear form would be a rank-3 form')
+    if not isinstance(u, Function):
+        raise TypeError('derivative with respect to a Function (got %r)'
+                        % (type(u),))
+    V = u.function_space()
+    if not hasattr(V, 'layout') or not hasattr(V, 'dim') or V.dim != 1 \
+            or V.component is not None:
+        raise NotImplementedError(
+            'derivative with respect to a Function of a vector, component or '
+            'mixed space: only scalar P1 / P2 spaces carry arguments')
+    if V.degree not in (1, 2):
+        raise ValueError('derivative: spaces of degree 1 or 2 only')
+    found = F.arguments()
+    k = len(found)
+    if sorted(found) != list(range(k)):
+        raise ValueError('derivative: the form holds a trial function without '
+                         'a test function')
+    for W in found.values():
+        if not W.same_as(V):
+            raise ValueError(
+                'derivative: u and the arguments of the form live on '
+                'different spaces or meshes')
+    if du is not None:
+        t = du.comps if isinstance(du, FormExpr) else None
+        if not (isinstance(t, tuple) and t[0] == 'arg' and t[1] == k
+                and t[2] == 0 and t[3].same_as(V)):
+            raise ValueError(
+                'derivative: du must be the %s(V) of the space of u'
+                % ('TestFunction', 'TrialFunction')[k])
+    parts = []
+    for sign, part in F.terms():
+        tree = s_gateaux(part.integrand.comps, u, k, V)
+        if _is_num(tree, 0.0):
+            continue
+        if part.integral_type != 'cell':
+            raise NotImplementedError(
+                'derivative of a ds part: test and trial functions under ds '
+                '(Neumann and Robin terms): the facet gather needs a '
+                'contribution map that does not exist yet')
+        mesh = _join_mesh(_join_mesh(part.integrand.mesh, part.mesh),
+                          V.mesh())
+        # (the degree of the part it came from: see the module docstring)
+        derived = Form(FormExpr(tree, (), part.integrand.deg, mesh), mesh,
+                       part.metadata)
+        derived.derived_from = part
+        parts.append((sign, derived))
+    if not parts:
+        raise ValueError('derivative: the form does not depend on u')
+    if len(parts) == 1 and parts[0][0] == 1.0 and not isinstance(F, FormSum):
+        return parts[0][1]
+    return FormSum(parts)
 
 
 def action(*args, **kwargs):
@@ -1014,14 +1149,18 @@ class Program(object):
     Expression components (Expression, i), in slot order.'''
 
     def __init__(self, trees, facet=False, point=False, slots=None,
-                 nout=None):
+                 nout=None, shared=()):
         '''facet: the program runs on exterior facets, where the normal
         exists (ValueError if a tree reads it otherwise).  point: it runs at
         located points (Probes, u(x)), where neither the normal nor
         Expression leaves exist (their lattices are tabulated at the rule's
         points only).  slots: the output slot of every tree out of nout
         (default: tree k -> output k of len(trees)); the coefficient tables
-        of forms of arguments use it (argument_program).'''
+        of forms of arguments use it (argument_program).  shared: (register,
+        tree) pairs computed first, in that order, into registers the output
+        trees then read through ('reg', r) leaves (newton_program).'''
+        trees = list(trees)
+        shared = list(shared)
         if point and any(has_leaf(t, 'n') for t in trees):
             raise ValueError('FacetNormal is defined on exterior facets only: '
                              'it cannot be evaluated at points')
@@ -1041,6 +1180,9 @@ class Program(object):
         self.fields = []
         self.exprs = []
         self.nregs = 0
+        for r, t in shared:
+            self._gen(t, 0)
+            self._emit('mov', r, 0)
         for k, t in zip(slots, trees):
             self._gen(t, 0)
             self._emit('out', 0, 0, k)
@@ -1088,7 +1230,7 @@ class Program(object):
     def need(n):
         '''Registers the tree needs (Sethi-Ullman).'''
         k = n[0]
-        if k in ('num', 'const', 'x', 'field', 'expr', 'n'):
+        if k in ('num', 'const', 'x', 'field', 'expr', 'n', 'reg'):
             return 1
         if k in UNARY:
             return Program.need(n[1])
@@ -1109,6 +1251,8 @@ class Program(object):
             self._emit('coord', base, n[1])
         elif k == 'n':
             self._emit('normal', base, n[1])
+        elif k == 'reg':
+            self._emit('mov', base, n[1])
         elif k == 'field':
             self._emit('field', base, self._slot(
                 self.fields, (n[1], n[2]), MAX_FIELDS, 'field components'),
@@ -1167,6 +1311,156 @@ def argument_program(table, rank):
     items = [(k, t) for k, t in items if t is not None]
     return Program([t for _, t in items], slots=[k for k, _ in items],
                    nout=9 if rank == 2 else 3)
+
+
+def _count(n):
+    '''Instructions Program._gen emits for the tree n.'''
+    k = n[0]
+    if k in UNARY:
+        return _count(n[1]) + 1
+    if k == 'powi':
+        m = n[2]
+        if m & (m - 1) == 0:
+            return _count(n[1]) + m.bit_length() - 1
+        return _count(n[1]) + 2 + sum(2 if b == '1' else 1 for b in bin(m)[3:])
+    if k in BINARY:
+        return _count(n[1]) + _count(n[2]) + 1
+    return 1
+
+
+def _subtrees(n, found):
+    '''The non-leaf subtrees of n, into the set `found`.'''
+    if n[0] in UNARY + BINARY + ('powi',):
+        found.add(n)
+        for c in n[1:]:
+            if isinstance(c, tuple):
+                _subtrees(c, found)
+    return found
+
+
+def _substitute(n, old, new):
+    if n == old:
+        return new
+    if n[0] in UNARY + BINARY + ('powi',):
+        return (n[0],) + tuple(_substitute(c, old, new)
+                               if isinstance(c, tuple) else c for c in n[1:])
+    return n
+
+
+def share_subtrees(trees):
+    '''Common-subtree sharing for the output trees of one program: (shared,
+    trees) with shared = [(register, tree)] in the order to compute them and
+    the output trees rewritten to read them through ('reg', r) leaves.
+    Candidates are the structurally equal (==; objects inside by identity)
+    non-leaf subtrees that occur in two or more trees, the largest first;
+    each taken one gets the highest free register; one is taken where that
+    saves instructions and still leaves every output tree, and every shared
+    subtree, its Sethi-Ullman need below the reserved registers.'''
+    trees = list(trees)
+    seen = {}
+    order = []
+    for t in trees:
+        for c in _subtrees(t, set()):
+            if c not in seen:
+                seen[c] = 0
+                order.append(c)
+            seen[c] += 1
+    cands = [c for c in order if seen[c] >= 2]
+    # (largest first; ties by the instruction stream they would emit, which
+    # is the same from run to run)
+    cands.sort(key=lambda c: (-_count(c), repr(_strip(c))))
+    defs = []           # (register, original tree, tree as it is computed)
+    for c in cands:
+        users = [t for t in trees + [d[2] for d in defs]
+                 if c in _subtrees(t, set())]
+        m = len(users)
+        if m < 2 or _count(c) + 1 + m >= m * _count(c):
+            continue
+        r = REGISTERS - 1 - len(defs)
+        leaf = ('reg', r)
+        new_trees = [_substitute(t, c, leaf) for t in trees]
+        new_defs = [(d[0], d[1], _substitute(d[2], c, leaf)) for d in defs] \
+            + [(r, c, c)]
+        free = REGISTERS - len(new_defs)
+        if all(Program.need(t) <= free for t in new_trees) and all(
+                Program.need(d[2]) <= free for d in new_defs):
+            trees, defs = new_trees, new_defs
+    # (a subtree of a larger shared one was taken after it: compute it first)
+    defs.sort(key=lambda d: _count(d[1]))
+    return [(d[0], d[2]) for d in defs], trees
+
+
+def _strip(n):
+    '''The tree with the objects inside replaced by their kinds (sort key).'''
+    return tuple(_strip(c) if isinstance(c, tuple) else
+                 (c if isinstance(c, (str, int, float)) else type(c).__name__)
+                 for c in n)
+
+
+def newton_program(tableJ, tableF, share=True):
+    '''ONE Program for the coefficient tables of a Jacobian (rank 2) and of a
+    residual (rank 1) at the same state: slot 3 b + a of the first, 9 + b of
+    the second, nout = 12.  The subtrees the two tables share (u, grad u and
+    the nonlinearity appear in both) are computed once (share_subtrees;
+    share=False: every tree on its own, as argument_program compiles them).
+    ValueError where the combined program exceeds a limit of flow_form: the
+    caller then runs the two programs one after the other.'''
+    items = [(3 * b + a, tableJ[b][a]) for b in range(3) for a in range(3)]
+    items += [(9 + b, tableF[b]) for b in range(3)]
+    items = [(k, t) for k, t in items if t is not None]
+    trees = [t for _, t in items]
+    shared = ()
+    if share:
+        shared, trees = share_subtrees(trees)
+    return Program(trees, slots=[k for k, _ in items], nout=NEWTON_SLOTS,
+                   shared=shared)
+
+
+def argument_programs(table, rank):
+    '''The coefficient table as a list of Programs whose cell tensors add up
+    to the form's: [argument_program(table, rank)] where that fits the
+    limits of flow_form; else the slots are dealt, in order, to as few
+    programs as fit (each with its common subtrees computed once, as
+    newton_program's), and the caller sums what they assemble.  ValueError
+    where one coefficient alone exceeds a limit.'''
+    try:
+        return [argument_program(table, rank)]
+    except ValueError:
+        pass
+    if rank == 2:
+        items = [(3 * b + a, table[b][a]) for b in range(3) for a in range(3)]
+    else:
+        items = list(enumerate(table))
+    items = [(k, t) for k, t in items if t is not None]
+    nout = 9 if rank == 2 else 3
+
+    def build(chunk):
+        shared, trees = share_subtrees([t for _, t in chunk])
+        return Program(trees, slots=[k for k, _ in chunk], nout=nout,
+                       shared=shared)
+
+    progs, chunk = [], []
+    for item in items:
+        try:
+            prog = build(chunk + [item])
+            chunk.append(item)
+        except ValueError:
+            if not chunk:
+                raise
+            progs.append(held)
+            chunk = [item]
+            prog = build(chunk)         # (ValueError: one slot is too long)
+        held = prog
+    progs.append(held)
+    return progs
+
+
+def depends_on(n, u):
+    '''Whether the scalar tree n reads the Function u.'''
+    if n[0] == 'field':
+        return n[1] is u
+    return n[0] in UNARY + BINARY + ('powi',) and any(
+        depends_on(c, u) for c in n[1:] if isinstance(c, tuple))
 
 
 def form_mesh(expr, mesh=None):

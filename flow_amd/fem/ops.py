@@ -3,12 +3,17 @@
 Host-side operations that run on the HIP path: matrices over a space's CSR
 pattern, Krylov solves, norms, and the callers' utilities `project`,
 `interpolate`, `errornorm`, `norm` (tests/test_navier_stokes.py:296-308, 333;
-tests/test_karman_vortex_street.py:262-268; tests/test_boussinesq.py:85).
+tests/test_karman_vortex_street.py:262-268; tests/test_boussinesq.py:85),
+`assemble` / `assemble_system` / `solve` of forms (flow_amd/fem/forms.py):
+`solve(a == L, u, bcs)` a Krylov solve, `solve(F == 0, u, bcs, J)` Newton's
+method with the Jacobian and the residual assembled in one pass
+(newton_solve, NewtonAssembler, flow_form_newton).
 
 Everything numerical is a call into libflow_hip.so (flow_amd/_hip.py); torch
 only owns the HBM buffers.
 '''
 import ctypes
+import numbers
 
 import numpy
 import torch
@@ -350,11 +355,13 @@ def assemble_stiffness(V):
     return assemble_scalar_matrix(V.layout, STIFFNESS)
 
 
-def symmetric_bc_matrix(A, isbc):
-    '''assemble_system-style symmetric elimination of one scalar plane.'''
+def symmetric_bc_matrix(A, isbc, out=None):
+    '''assemble_system-style symmetric elimination of one scalar plane
+    (out: a Matrix of the same layout to write into).'''
     lib = _hip.lib()
     lay = A.layout
-    out = Matrix(lay, 0)
+    if out is None:
+        out = Matrix(lay, 0)
     _hip.check(lib.flow_bc_symmetric_matrix(
         lay.N, _hip.i32(lay.dev('rowptr')), _hip.i32(lay.dev('cols')),
         _hip.f64(A.vals, lay.nnz), _hip.u8(isbc, lay.N, 'isbc'),
@@ -976,7 +983,8 @@ def assemble(form, form_compiler_parameters=None):
 
 def _assemble_arguments(form, rank, form_compiler_parameters=None):
     '''assemble() of a form, or of a signed sum of forms, of rank 1 (a
-    Vector) or 2 (a Matrix): flow_form_vector / flow_form_matrix per part.'''
+    Vector) or 2 (a Matrix): flow_form_vector / flow_form_matrix per part
+    (per program of a part whose table needs several).'''
     from . import forms
     from .function import Vector
     lib = _hip.lib()
@@ -998,33 +1006,35 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
         q = forms.check_degree(part.degree() if q is None else q)
         scheme = forms.quadrature_scheme(form_compiler_parameters,
                                          part.metadata)
-        prog = forms.argument_program(table, rank)
-        fs, keep = _form_struct(prog, mesh, q, scheme=scheme)
-        if rank == 2:
-            out = value_plane(lay)
-            buf = scratch(mesh, lay.nloc**2 * nc)
-            _hip.check(lib.flow_form_matrix(
-                ctypes.byref(mesh_struct(mesh)),
-                ctypes.byref(space_struct(lay)), ctypes.byref(fs),
-                _hip.f64(buf, lay.nloc**2 * nc, 'scratch'),
-                _hip.f64(out, lay.nnz, 'vals'), _hip.stream()
-                ))
-        else:
-            out = device.empty(lay.N)
-            buf = scratch(mesh, lay.nloc * nc)
-            _hip.check(lib.flow_form_vector(
-                ctypes.byref(mesh_struct(mesh)),
-                ctypes.byref(space_struct(lay)), ctypes.byref(fs),
-                _hip.f64(buf, lay.nloc * nc, 'scratch'),
-                _hip.f64(out, lay.N, 'b'), _hip.stream()
-                ))
-        del keep
-        if total is None and sign == 1.0:
-            total = out
-        else:
-            if total is None:
-                total = _hip.fill(device.empty(out.numel()), 0.0)
-            axpby(sign, out, 1.0, total)
+        # (one program, or several whose results add up where the table
+        # exceeds the limits of flow_form: forms.argument_programs)
+        for prog in forms.argument_programs(table, rank):
+            fs, keep = _form_struct(prog, mesh, q, scheme=scheme)
+            if rank == 2:
+                out = value_plane(lay)
+                buf = scratch(mesh, lay.nloc**2 * nc)
+                _hip.check(lib.flow_form_matrix(
+                    ctypes.byref(mesh_struct(mesh)),
+                    ctypes.byref(space_struct(lay)), ctypes.byref(fs),
+                    _hip.f64(buf, lay.nloc**2 * nc, 'scratch'),
+                    _hip.f64(out, lay.nnz, 'vals'), _hip.stream()
+                    ))
+            else:
+                out = device.empty(lay.N)
+                buf = scratch(mesh, lay.nloc * nc)
+                _hip.check(lib.flow_form_vector(
+                    ctypes.byref(mesh_struct(mesh)),
+                    ctypes.byref(space_struct(lay)), ctypes.byref(fs),
+                    _hip.f64(buf, lay.nloc * nc, 'scratch'),
+                    _hip.f64(out, lay.N, 'b'), _hip.stream()
+                    ))
+            del keep
+            if total is None and sign == 1.0:
+                total = out
+            else:
+                if total is None:
+                    total = _hip.fill(device.empty(out.numel()), 0.0)
+                axpby(sign, out, 1.0, total)
     if total is None:
         raise ValueError('an empty sum of forms has no rank')
     return Matrix(lay, 0, total) if rank == 2 else Vector(total)
@@ -1124,9 +1134,12 @@ def apply_identity_rows(bc, A=None, b=None):
 _KRYLOV_METHODS = ('cg', 'gmres', 'bicgstab')
 
 
-def solve(equation, u, bcs=None, solver_parameters=None,
+def solve(equation, u, bcs=None, J=None, solver_parameters=None,
           form_compiler_parameters=None):
-    '''solve(a == L, u, bcs): assemble_system, then a Krylov solve on the
+    '''solve(F == 0, u, bcs, J=None): Newton's method, newton_solve below
+    (J: the Jacobian, derivative(F, u) by default; for a linear equation it
+    must stay None).
+    solve(a == L, u, bcs): assemble_system, then a Krylov solve on the
     device that starts from u's values and writes into u.  Returns the
     SolveInfo.  The form counts as symmetric where every part of a is
     structurally symmetric, or where solver_parameters['symmetric'] is True.
@@ -1146,6 +1159,11 @@ def solve(equation, u, bcs=None, solver_parameters=None,
     if not isinstance(equation, forms.Equation):
         raise TypeError('solve takes an equation a == L of a bilinear and a '
                         'linear form (got %r)' % (type(equation),))
+    if isinstance(equation.rhs, numbers.Real):
+        return newton_solve(equation.lhs, u, bcs, J, solver_parameters,
+                            form_compiler_parameters)
+    if J is not None:
+        raise ValueError('J= belongs to the nonlinear solve(F == 0, u, ...)')
     prm = dict(solver_parameters or {})
     method = prm.get('linear_solver', 'default')
     if method not in _KRYLOV_METHODS + ('default', 'iterative'):
@@ -1174,6 +1192,318 @@ def solve(equation, u, bcs=None, solver_parameters=None,
         maxit=int(ks.get('maximum_iterations', 1000)), ilu=ilu,
         check_every=10)
     return info
+
+
+# -- Newton's method: solve(F == 0, u, bcs, J) ----------------------------------
+NEWTON_DEFAULTS = {
+    'maximum_iterations': 50, 'relative_tolerance': 1.0e-9,
+    'absolute_tolerance': 1.0e-10, 'relaxation_parameter': 1.0,
+    'error_on_nonconvergence': True, 'convergence_criterion': 'residual',
+    'report': False, 'linear_solver': 'default', 'krylov_solver': None,
+    }
+
+
+def newton_parameters(solver_parameters):
+    '''(newton_solver dict with dolfin's defaults filled in, symmetric flag)
+    of the solver_parameters of solve(F == 0, ...); ValueError for what is
+    not built ('snes', the 'incremental' criterion, direct solvers) and for
+    unknown keys.  Needs no device.'''
+    prm = dict(solver_parameters or {})
+    unknown = set(prm) - {'nonlinear_solver', 'newton_solver', 'symmetric'}
+    if unknown:
+        raise ValueError('solver_parameters of a nonlinear solve: unknown '
+                         'keys %s' % sorted(unknown))
+    if prm.get('nonlinear_solver', 'newton') != 'newton':
+        raise ValueError("nonlinear_solver %r: only 'newton' is built"
+                         % (prm['nonlinear_solver'],))
+    given = dict(prm.get('newton_solver') or {})
+    unknown = set(given) - set(NEWTON_DEFAULTS)
+    if unknown:
+        raise ValueError('newton_solver: unknown keys %s' % sorted(unknown))
+    ns = dict(NEWTON_DEFAULTS)
+    ns.update(given)
+    if ns['convergence_criterion'] != 'residual':
+        raise ValueError("convergence_criterion %r: only 'residual' is built"
+                         % (ns['convergence_criterion'],))
+    if ns['linear_solver'] not in _KRYLOV_METHODS + ('default', 'iterative'):
+        raise ValueError(
+            'linear_solver %r: there is no direct solver here; the choices '
+            'are %s' % (ns['linear_solver'],
+                        ', '.join(_KRYLOV_METHODS + ('default',))))
+    ns['krylov_solver'] = dict(ns['krylov_solver'] or {})
+    return ns, prm.get('symmetric') is True
+
+
+class NewtonInfo(object):
+    '''What solve(F == 0, ...) returns: `iterations` (linear solves done),
+    `converged`, `residuals` (|F|_2 before the first and after every
+    iteration), `linear_iterations` (of every linear solve), `fused` (every
+    part of the Jacobian was assembled together with a part of the residual
+    by flow_form_newton), `method` (of the linear solves).'''
+
+    def __init__(self, fused, method):
+        self.iterations = 0
+        self.converged = False
+        self.residuals = []
+        self.linear_iterations = []
+        self.fused = fused
+        self.method = method
+
+    def __repr__(self):
+        return 'newton (%s, %s): %d iterations, |F| = %.3e, %s' % (
+            self.method, 'fused' if self.fused else 'pair', self.iterations,
+            self.residuals[-1] if self.residuals else float('nan'),
+            'converged' if self.converged else 'NOT converged')
+
+
+def _part_rule(part, form_compiler_parameters):
+    '''(degree, scheme) a part of a form of arguments is integrated with.'''
+    from . import forms
+    q = forms._quadrature_degree(part.metadata)
+    if q is None:
+        q = forms._quadrature_degree(form_compiler_parameters)
+    q = forms.check_degree(part.degree() if q is None else q)
+    return q, forms.quadrature_scheme(form_compiler_parameters, part.metadata)
+
+
+def _fusable(tj, fparts, rules, used, rule, origin):
+    '''(index of the part of F to fuse a part of J with, their Program): the
+    first unused part of the same rule, the one J's part was derived from
+    first, whose combined program fits the limits of flow_form; (None, None)
+    without one.'''
+    from . import forms
+    for i in sorted(range(len(fparts)),
+                    key=lambda i: fparts[i][1] is not origin):
+        if used[i] or rules[i] != rule:
+            continue
+        try:
+            return i, forms.newton_program(
+                tj, fparts[i][1].argument_table()[1])
+        except ValueError:          # over a limit of flow_form
+            continue
+    return None, None
+
+
+def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
+    '''The launches that assemble (J, F) at one state, as a list of
+    (kind, sign of the matrix part, sign of the vector part, Program,
+    degree, scheme), kind 'newton' | 'matrix' | 'vector'.  A part of J is
+    fused with a part of F of the same degree and rule (the one it was
+    derived from first) where forms.newton_program fits the limits of
+    flow_form; what is left goes through flow_form_matrix / flow_form_vector
+    part by part (program by program where a table needs several:
+    forms.argument_programs).  Host only.'''
+    from . import forms
+    fparts = F.terms()
+    rules = [_part_rule(p, form_compiler_parameters) for _, p in fparts]
+    used = [False] * len(fparts)
+    jobs = []
+    for sj, pj in J.terms():
+        rule = _part_rule(pj, form_compiler_parameters)
+        tj = pj.argument_table()[1]
+        i, prog = _fusable(tj, fparts, rules, used, rule,
+                           getattr(pj, 'derived_from', None)) \
+            if fuse else (None, None)
+        if prog is not None:
+            used[i] = True
+            jobs.append(('newton', sj, fparts[i][0], prog) + rule)
+        else:
+            jobs.extend(('matrix', sj, 0.0, prog) + rule
+                        for prog in forms.argument_programs(tj, 2))
+    for i, (sf, pf) in enumerate(fparts):
+        if not used[i]:
+            jobs.extend(('vector', 0.0, sf, prog) + rules[i]
+                        for prog in forms.argument_programs(
+                            pf.argument_table()[1], 1))
+    return jobs
+
+
+class NewtonAssembler(object):
+    '''(J, F) at the current values of the fields, into buffers that live as
+    long as the object: the value plane `A.vals`, the vector `b`, one more of
+    each where a sum of parts needs it, and the mesh's scratch.  `fused`:
+    every part of J goes through flow_form_newton.'''
+
+    def __init__(self, J, F, V, form_compiler_parameters=None, fuse=True):
+        from . import forms
+        self.V = V
+        self.mesh = V.mesh()
+        for _, part in J.terms() + F.terms():
+            if part.integral_type != 'cell':
+                raise NotImplementedError('test and trial functions under ds')
+            if forms.form_mesh(part.integrand, part.mesh) is not self.mesh:
+                raise ValueError('the form is integrated over another mesh '
+                                 'than the one of its arguments')
+        self.jobs = newton_jobs(J, F, form_compiler_parameters, fuse)
+        self.fused = all(j[0] != 'matrix' for j in self.jobs)
+        lay = V.layout
+        self.A = Matrix(lay, 0, value_plane(lay))
+        self.b = device.empty(lay.N)
+        self._plane = self._vector = None
+        # (the structs hold pointers to the fields' data, which Newton updates
+        # in place; the constants' values are refreshed by every assemble())
+        self.structs = [_form_struct(j[3], self.mesh, j[4], scheme=j[5])
+                        for j in self.jobs]
+
+    def assemble(self):
+        lib = _hip.lib()
+        lay, mesh = self.V.layout, self.mesh
+        nc = mesh.num_cells()
+        nl = lay.nloc
+        ms, ss = ctypes.byref(mesh_struct(mesh)), ctypes.byref(
+            space_struct(lay))
+        first_m = first_v = True
+        for (kind, sm, sv, prog, _, _), (fs, _) in zip(self.jobs,
+                                                       self.structs):
+            for i, value in enumerate(prog.constant_values()):
+                fs.consts[i] = value
+            vals = vec = None
+            if kind != 'vector':
+                vals = self.A.vals if first_m and sm == 1.0 else self._tmp(0)
+            if kind != 'matrix':
+                vec = self.b if first_v and sv == 1.0 else self._tmp(1)
+            if kind == 'newton':
+                n = (nl * nl + nl) * nc
+                _hip.check(lib.flow_form_newton(
+                    ms, ss, ctypes.byref(fs),
+                    _hip.f64(scratch(mesh, n), n, 'scratch'),
+                    _hip.f64(vals, lay.nnz, 'vals'), _hip.f64(vec, lay.N, 'b'),
+                    _hip.stream()))
+            elif kind == 'matrix':
+                n = nl * nl * nc
+                _hip.check(lib.flow_form_matrix(
+                    ms, ss, ctypes.byref(fs),
+                    _hip.f64(scratch(mesh, n), n, 'scratch'),
+                    _hip.f64(vals, lay.nnz, 'vals'), _hip.stream()))
+            else:
+                n = nl * nc
+                _hip.check(lib.flow_form_vector(
+                    ms, ss, ctypes.byref(fs),
+                    _hip.f64(scratch(mesh, n), n, 'scratch'),
+                    _hip.f64(vec, lay.N, 'b'), _hip.stream()))
+            if vals is not None:
+                self._add(first_m, sm, vals, self.A.vals)
+                first_m = False
+            if vec is not None:
+                self._add(first_v, sv, vec, self.b)
+                first_v = False
+        if first_m or first_v:
+            raise ValueError('an empty sum of forms has no rank')
+        return self.A, self.b
+
+    def _tmp(self, which):
+        if which == 0:
+            if self._plane is None:
+                self._plane = value_plane(self.V.layout)
+            return self._plane
+        if self._vector is None:
+            self._vector = device.empty(self.V.N)
+        return self._vector
+
+    @staticmethod
+    def _add(first, sign, out, total):
+        if out is total:
+            return
+        if first:
+            _hip.fill(total, 0.0)
+        axpby(sign, out, 1.0, total)
+
+
+def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
+                 form_compiler_parameters=None):
+    '''solve(F == 0, u, bcs, J): dolfin's NewtonSolver on the device.  F: a
+    form of rank 1 in TestFunction(V) that holds the Function u of V; J: its
+    Jacobian, derivative(F, u) by default.  u[dof] = g first; then, per
+    iteration: (J, F) at u in one pass where the parts pair up
+    (flow_form_newton; `fused` of the returned NewtonInfo tells), the
+    conditions applied homogeneously (the symmetric elimination of
+    assemble_system, F[dof] = 0), r = |F|_2 -- the one read-back of an
+    iteration besides those of the Krylov solve --, stop where r <
+    absolute_tolerance or r / r0 < relative_tolerance, else J delta = F from
+    a zero start with the method and preconditioner rule of the linear solve
+    (CG + Jacobi for symmetric tables or solver_parameters['symmetric'],
+    else GMRES + ILU(0)) and u -= relaxation_parameter * delta.
+    solver_parameters: 'nonlinear_solver' 'newton'; 'newton_solver' with
+    dolfin's keys and defaults (NEWTON_DEFAULTS; 'linear_solver' and
+    'krylov_solver' as for the linear solve; 'report' prints a line per
+    iteration through message.info).  Raises _hip.NotConverged unless
+    'error_on_nonconvergence' is False.  Not on strips.'''
+    from . import forms
+    from ..message import info as say
+    ns, symmetric = newton_parameters(solver_parameters)
+    if not isinstance(F, forms.Form) or F.rank != 1:
+        raise ValueError('solve(F == 0, u): F must be a form of rank 1, '
+                         'linear in a test function')
+    V = F.arguments()[0]
+    if not isinstance(u, Function) or not u.function_space().same_as(V):
+        raise ValueError('solve writes into a Function of the space of the '
+                         'test function')
+    if not any(forms.depends_on(p.integrand.comps, u) for _, p in F.terms()):
+        raise ValueError('solve(F == 0, u): the form does not depend on u')
+    if J is None:
+        J = forms.derivative(F, u)
+    elif not isinstance(J, forms.Form) or J.rank != 2 \
+            or not J.arguments()[0].same_as(V):
+        raise ValueError('J must be a bilinear form (rank 2) on the space of '
+                         'u')
+    symmetric = symmetric or all(
+        forms.is_symmetric_table(part.argument_table()[1])
+        for _, part in J.terms())
+    method = ns['linear_solver']
+    if method in ('default', 'iterative'):
+        method = 'cg' if symmetric else 'gmres'
+    asm = NewtonAssembler(J, F, V, form_compiler_parameters)
+    ks = ns['krylov_solver']
+    dofs, vals, mask = _scalar_bcs(bcs, V)
+    if dofs is not None:
+        _set_values(dofs, vals, u.data)
+        zero = device.zeros(dofs.numel())
+        Abc = Matrix(V.layout, 0)
+    delta = device.empty(V.N)
+    ilu = None
+    out = NewtonInfo(asm.fused, method)
+    rtol, atol = ns['relative_tolerance'], ns['absolute_tolerance']
+    maxit = int(ns['maximum_iterations'])
+    r0 = None
+    while True:
+        A, b = asm.assemble()
+        if dofs is not None:
+            A = symmetric_bc_matrix(A, mask, Abc)
+            _set_values(dofs, zero, b)
+        r = vector_norm(b)
+        r0 = r if r0 is None else r0
+        out.residuals.append(r)
+        rel = r / r0 if r0 > 0.0 else 0.0
+        if ns['report']:
+            say('Newton iteration %d: r (abs) = %.3e (tol = %.3e) r (rel) = '
+                '%.3e (tol = %.3e)' % (out.iterations, r, atol, rel, rtol))
+        if r < atol or rel < rtol:
+            out.converged = True
+            break
+        if out.iterations >= maxit:
+            break
+        if method != 'cg' and not symmetric:
+            if ilu is None:
+                from .ilu import Ilu0
+                ilu = Ilu0(A)
+            else:
+                ilu.refactor(A)
+        _hip.fill(delta, 0.0)
+        kinfo = krylov_solve(
+            method, A, b, delta, ks.get('relative_tolerance', 1.0e-12),
+            atol=ks.get('absolute_tolerance', 0.0),
+            maxit=int(ks.get('maximum_iterations', 1000)), ilu=ilu,
+            check_every=10, x_is_zero=True)
+        out.method = kinfo.method
+        out.linear_iterations.append(kinfo.iterations)
+        axpby(-float(ns['relaxation_parameter']), delta, 1.0, u.data)
+        out.iterations += 1
+    if not out.converged and ns['error_on_nonconvergence']:
+        raise _hip.NotConverged(
+            'Newton solver did not converge: %d iterations, |F| = %.3e '
+            '(absolute tolerance %.3e), |F| / |F0| = %.3e (relative '
+            'tolerance %.3e)' % (out.iterations, r, atol, rel, rtol))
+    return out
 
 
 def facet_lists(mesh, markers=None, subdomain_id='everywhere'):

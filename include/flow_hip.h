@@ -1110,6 +1110,7 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
 #define FLOW_FORM_MAX_EXPRESSIONS 4
 #define FLOW_FORM_MAX_POINTS 256
 #define FLOW_FORM_SLOTS 9     /* coefficient slots of a rank-2 form */
+#define FLOW_FORM_NEWTON_SLOTS 12   /* those, then the 3 of a rank-1 form */
 #define FLOW_FORM_OP_CONST 0
 #define FLOW_FORM_OP_COORD 1
 #define FLOW_FORM_OP_FIELD 2
@@ -1147,7 +1148,8 @@ typedef struct {
   const double* tables;                    /* P_k basis at the rule's points */
   int ntables;                             /* doubles in tables */
   int nout;                                /* 1 | 2; flow_form_matrix: 9,
-                                              flow_form_vector: 3 */
+                                              flow_form_vector: 3,
+                                              flow_form_newton: 12 */
 } flow_form;
 
 /* assemble(f*dx): the integral of output 0 over the cells of `mesh`, to the
@@ -1198,6 +1200,20 @@ int flow_form_matrix(const flow_mesh* mesh, const flow_space* V,
 int flow_form_vector(const flow_mesh* mesh, const flow_space* V,
                      const flow_form* form, double* scratch, double* b,
                      void* stream);
+
+/* The Jacobian J(u) and the residual F(u) of a Newton iteration in one pass
+ * over the cells: ONE program holds both coefficient tables, slot 3 b + a the
+ * Jacobian's c_ba and slot FLOW_FORM_SLOTS + b the residual's c_b (nout =
+ * FLOW_FORM_NEWTON_SLOTS; at least one slot of each must be written, none
+ * twice), so geometry, field values, basis tables and the subexpressions the
+ * two tables share are loaded and computed once per quadrature point.  Ke and
+ * be are accumulated as flow_form_matrix and flow_form_vector accumulate them
+ * and gathered over cptr / csrc into `vals` (nnz doubles) and over vptr / vsrc
+ * into b (n doubles).  No floating-point atomics: two calls give the same
+ * bits.  Not on strips.  scratch: (nloc^2 + nloc) * nc. */
+int flow_form_newton(const flow_mesh* mesh, const flow_space* V,
+                     const flow_form* form, double* scratch, double* vals,
+                     double* b, void* stream);
 
 /* ---- point evaluation (flow_amd/fem/points.py): u(x), Probes ---------------
  * A uniform bucket grid over the mesh's bounding box, built on the host once
