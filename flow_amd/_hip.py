@@ -429,6 +429,7 @@ SYMBOLS = {
     'flow_bc_symmetric_matrix': [_I, _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_assemble_heat': [_P(MeshS), _P(SpaceS), _P(SpaceS), _VP, _D, _D, _I,
                            _VP, _VP, _VP, _VP, _VP, _VP],
+    'flow_supg_tau': [_P(MeshS), _P(SpaceS), _VP, _D, _I, _VP, _VP, _VP],
     'flow_assemble_heat_supg_source': [_P(MeshS), _P(SpaceS), _P(SpaceS), _VP,
                                        _D, _D, _P(CoefS), _VP, _VP, _VP, _VP],
     'flow_form_functional': [_P(MeshS), _P(FormS), _VP, _VP, _P(_D), _VP],

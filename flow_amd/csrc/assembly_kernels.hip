@@ -918,6 +918,28 @@ __device__ __forceinline__ double supg_tau(const double px[3], const double py[3
   return tau;
 }
 
+// tau alone: one cell per lane, tau at the three vertices to tau[m*nc + c] (the
+// P1 cell lattice a form's `expr` operand reads), the convection at vertex m
+// being its vertex dof value as in heat_kernel (the first three local dofs
+// of a P1 or P2 space).  No matrix, no scratch.
+__global__ __launch_bounds__(kBlock) void supg_tau_kernel(
+    int nc, const double* __restrict__ xy, const int* __restrict__ cdw, int nw,
+    const double* __restrict__ conv, double kappa, int p,
+    double* __restrict__ tau, int* __restrict__ status) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const Geom g = load_geom(xy, nc, c);
+  const double px[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double py[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    const int d = cdw[m * nc + c];
+    tau[static_cast<size_t>(m) * nc + c] =
+        supg_tau(px, py, 0.5 * g.adet, conv[d], conv[static_cast<size_t>(nw) + d],
+                 kappa, p, status);
+  }
+}
+
 template <int DEGQ, int DEGW, bool SUPG>
 __global__ __launch_bounds__(kBlock) void heat_kernel(
     int nc, int cb, int ce, const double* __restrict__ xy,
@@ -1552,6 +1574,22 @@ extern "C" int flow_assemble_heat(const flow_mesh* mesh, const flow_space* Q,
   if (supg)
     return gather(Q->nnz, 1, Q->cptr, Q->csrc, scratch + plane, 0, Msupg_vals, st,
                   0, k0, k1);
+  return FLOW_OK;
+}
+
+extern "C" int flow_supg_tau(const flow_mesh* mesh, const flow_space* W,
+                             const double* conv, double kappa, int p, double* tau,
+                             int* status_dev, void* stream) {
+  int rc = check_mesh_space(mesh, W);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "tau on strips");
+  FLOW_REQUIRE(conv && tau && status_dev, "pointers");
+  FLOW_REQUIRE(kappa > 0.0 && (p == 1 || p == 2), "coefficients");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(supg_tau_kernel, cell_grid(mesh->nc), dim3(kBlock), 0, st,
+                     mesh->nc, mesh->xy, W->cell_dofs, W->n, conv, kappa, p, tau,
+                     status_dev);
+  FLOW_CHECK_LAUNCH();
   return FLOW_OK;
 }
 

@@ -189,7 +189,52 @@ struct FormSlotsNewton {
   }
 };
 
-template <int NF, bool FACET, class OUT>
+// tanh x from e = exp(-2|x|), which the interpreter's one exp computed: for
+// |x| >= 1/2, (1 - e) / (1 + e) with e <= 0.37 (no cancellation; e -> 0 gives
+// +-1, never inf/inf); below, x P(x^2) / Q(x^2), the [7/6] Pade approximant
+// from the continued fraction x / (1 + x^2 / (3 + x^2 / (5 + ...))) (error <
+// 1e-17 relative there, exact to first order at 0).  One division.
+__device__ __forceinline__ double form_tanh(double x, double e) {
+  const double z = x * x;
+  const bool small = z < 0.25;
+  const double pn = x * (135135.0 + z * (17325.0 + z * (378.0 + z)));
+  const double pd = 135135.0 + z * (62370.0 + z * (3150.0 + z * 28.0));
+  return (small ? pn : copysign(1.0 - e, x)) / (small ? pd : 1.0 + e);
+}
+
+// The extended opcodes (FLOW_FORM_OP_LT and up) but tanh.  They are compiled
+// into instances of their own (EXT = true, chosen on the host where the
+// program holds one): the instances every other program runs keep the
+// registers and the occupancy they had.
+__device__ __forceinline__ double form_ext_op(int op, int a, double ra, double rb,
+                                              double rd, const double X[3],
+                                              const double Y[3], const Geom& g) {
+  switch (op) {
+    case FLOW_FORM_OP_LT: return ra < rb ? 1.0 : 0.0;
+    case FLOW_FORM_OP_LE: return ra <= rb ? 1.0 : 0.0;
+    case FLOW_FORM_OP_EQ: return ra == rb ? 1.0 : 0.0;
+    case FLOW_FORM_OP_NE: return ra != rb ? 1.0 : 0.0;
+    // a real select: the value not taken is never combined with the result
+    case FLOW_FORM_OP_SELECT: return ra != 0.0 ? rb : rd;
+    // (fmin / fmax return the other operand where one is NaN; sign returns
+    // +-0 and NaN as they are: include/flow_hip.h)
+    case FLOW_FORM_OP_MIN: return fmin(ra, rb);
+    case FLOW_FORM_OP_MAX: return fmax(ra, rb);
+    case FLOW_FORM_OP_SIGN: return ra > 0.0 ? 1.0 : (ra < 0.0 ? -1.0 : ra);
+    default: {   // FLOW_FORM_OP_CELL
+      // from the vertex coordinates the lane holds (no load): squared edge
+      // lengths, then |T| = |det J| / 2, the circumradius abc / (4 |T|) or
+      // the largest vertex distance
+      const double e0 = (X[1] - X[0]) * (X[1] - X[0]) + (Y[1] - Y[0]) * (Y[1] - Y[0]);
+      const double e1 = (X[2] - X[1]) * (X[2] - X[1]) + (Y[2] - Y[1]) * (Y[2] - Y[1]);
+      const double e2 = (X[0] - X[2]) * (X[0] - X[2]) + (Y[0] - Y[2]) * (Y[0] - Y[2]);
+      const double s = sqrt(a == 1 ? e0 * e1 * e2 : fmax(e0, fmax(e1, e2)));
+      return a == 0 ? 0.5 * g.adet : (a == 1 ? s / (2.0 * g.adet) : s);
+    }
+  }
+}
+
+template <int NF, bool FACET, bool EXT, class OUT>
 __device__ __forceinline__ void form_point_n(const flow_form& F,
                                              const double (&U)[NF > 0 ? NF : 1][6],
                                              const double X[3], const double Y[3],
@@ -198,9 +243,25 @@ __device__ __forceinline__ void form_point_n(const flow_form& F,
                                              OUT& out) {
   FormRegs R = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int pc = 0; pc < F.nprog; ++pc) {
-    const int op = F.prog[4 * pc], dst = F.prog[4 * pc + 1];
+    int op = F.prog[4 * pc];
+    const int dst = F.prog[4 * pc + 1];
     const int a = F.prog[4 * pc + 2], b = F.prog[4 * pc + 3];
     double v;
+    bool tanh_op = false;
+    if constexpr (EXT) {
+      // tanh goes through the exp below; the others have a switch of their own
+      tanh_op = op == FLOW_FORM_OP_TANH;
+      if (tanh_op) {
+        op = FLOW_FORM_OP_EXP;
+      } else if (op >= FLOW_FORM_OP_LT) {
+        const bool two = op <= FLOW_FORM_OP_MAX;
+        reg_set(R, dst,
+                form_ext_op(op, a, op == FLOW_FORM_OP_CELL ? 0.0 : reg_get(R, a),
+                            two ? reg_get(R, b) : 0.0,
+                            op == FLOW_FORM_OP_SELECT ? reg_get(R, dst) : 0.0, X, Y, g));
+        continue;
+      }
+    }
     switch (op) {
       case FLOW_FORM_OP_CONST: v = F.consts[a]; break;
       case FLOW_FORM_OP_COORD: {
@@ -241,9 +302,15 @@ __device__ __forceinline__ void form_point_n(const flow_form& F,
       case FLOW_FORM_OP_EXP:
       case FLOW_FORM_OP_LN: {
         double t = reg_get(R, a);
+        if constexpr (EXT) {
+          if (tanh_op) t = -2.0 * fabs(t);
+        }
         if (op != FLOW_FORM_OP_EXP) t = log(t);
         if (op == FLOW_FORM_OP_POW) t *= reg_get(R, b);
         v = op == FLOW_FORM_OP_LN ? t : exp(t);
+        if constexpr (EXT) {
+          if (tanh_op) v = form_tanh(reg_get(R, a), v);
+        }
         break;
       }
       case FLOW_FORM_OP_SIN:
@@ -258,7 +325,7 @@ __device__ __forceinline__ void form_point_n(const flow_form& F,
 }
 
 // the two-output program of the functionals, load vectors and points
-template <int NF, bool FACET>
+template <int NF, bool FACET, bool EXT>
 __device__ __forceinline__ void form_point(const flow_form& F,
                                            const double (&U)[NF > 0 ? NF : 1][6],
                                            const double X[3], const double Y[3],
@@ -266,7 +333,7 @@ __device__ __forceinline__ void form_point(const flow_form& F,
                                            int nc, int c, double n0, double n1,
                                            double& out0, double& out1) {
   FormOut2 out = {out0, out1};
-  form_point_n<NF, FACET>(F, U, X, Y, g, L, row, nc, c, n0, n1, out);
+  form_point_n<NF, FACET, EXT>(F, U, X, Y, g, L, row, nc, c, n0, n1, out);
 }
 
 // the local values of the form's fields on cell c
@@ -307,7 +374,7 @@ __device__ __forceinline__ void load_form_fields(const flow_form& F, int nc, int
 
 // Runs the program at every point of the rule on cell c.  TD = 0: returns
 // sum_q w_q |det J| out_0(x_q); TD = 1, 2: acc[o][i] += w_q |det J| out_o phi_i.
-template <int NF, int TD>
+template <int NF, int TD, bool EXT>
 __device__ __forceinline__ double form_cell(const flow_form& F, int nc,
                                             const double* __restrict__ xy, int c,
                                             double (&acc)[2][6]) {
@@ -322,7 +389,7 @@ __device__ __forceinline__ double form_cell(const flow_form& F, int nc,
     const double w = F.rule[3 * q + 2] * g.adet;
     const double L[3] = {1.0 - xi - eta, xi, eta};
     double out0 = 0.0, out1 = 0.0;
-    form_point<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out0, out1);
+    form_point<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out0, out1);
     if constexpr (TD == 0) {
       total += w * out0;
     } else {
@@ -351,7 +418,7 @@ __device__ __forceinline__ double form_cell(const flow_form& F, int nc,
 // lf*nq .. lf*nq + nq - 1 (reference coordinates on that facet, weights
 // summing to 1) scaled by the facet's length |det J| |grad lambda_lf|; the
 // outward unit normal is -grad(lambda_lf) / |grad lambda_lf|.
-template <int NF>
+template <int NF, bool EXT>
 __device__ __forceinline__ double form_facet(const flow_form& F, int nc,
                                              const double* __restrict__ xy, int c,
                                              int lf) {
@@ -372,7 +439,7 @@ __device__ __forceinline__ double form_facet(const flow_form& F, int nc,
     const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
     const double L[3] = {1.0 - xi - eta, xi, eta};
     double out0 = 0.0, out1 = 0.0;
-    form_point<NF, true>(F, U, X, Y, g, L, row, nc, c, n0, n1, out0, out1);
+    form_point<NF, true, EXT>(F, U, X, Y, g, L, row, nc, c, n0, n1, out0, out1);
     total += F.rule[3 * row + 2] * len * out0;
   }
   return total;
@@ -393,7 +460,7 @@ __global__ __launch_bounds__(kBlock) void form_sum_kernel(
 // one cell per lane.  TD = 0 (functional, stage 1): scratch[cell] = the
 // cell's integral; TD = 1, 2 (load vector): [o][i][cell] contributions for
 // the gather
-template <int NF, int TD>
+template <int NF, int TD, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_cell_kernel(
     int nc, int cb, int ce, const double* __restrict__ xy, const flow_form F,
     double* __restrict__ scratch) {
@@ -404,7 +471,7 @@ __global__ __launch_bounds__(kBlock) void form_cell_kernel(
   for (int o = 0; o < 2; ++o)
 #pragma unroll
     for (int i = 0; i < 6; ++i) acc[o][i] = 0.0;
-  const double total = form_cell<NF, TD>(F, nc, xy, c, acc);
+  const double total = form_cell<NF, TD, EXT>(F, nc, xy, c, acc);
   if constexpr (TD == 0) {
     scratch[c] = total;
     return;
@@ -421,7 +488,7 @@ __global__ __launch_bounds__(kBlock) void form_cell_kernel(
 
 // one facet per lane: scratch[k] = the integral over facet k of the list
 // (cell, local facet); a facet outside the mesh gives NaN, not a stray read
-template <int NF>
+template <int NF, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_facet_kernel(
     int nc, int nfacets, const int* __restrict__ fcell,
     const int* __restrict__ flocal, const double* __restrict__ xy,
@@ -433,7 +500,7 @@ __global__ __launch_bounds__(kBlock) void form_facet_kernel(
     scratch[k] = __builtin_nan("");
     return;
   }
-  scratch[k] = form_facet<NF>(F, nc, xy, c, lf);
+  scratch[k] = form_facet<NF, EXT>(F, nc, xy, c, lf);
 }
 
 // The point of the mesh's cell c at barycentric (l0, l1, l2): the test of
@@ -492,7 +559,7 @@ __global__ __launch_bounds__(kBlock) void locate_points_kernel(
 
 // one located point per lane: the program at its barycentric coordinates,
 // out[o][i]; NaN for a point in no cell
-template <int NF>
+template <int NF, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_points_kernel(
     int nc, const double* __restrict__ xy, const flow_form F, int n,
     const int* __restrict__ cell, const double* __restrict__ bary,
@@ -511,7 +578,7 @@ __global__ __launch_bounds__(kBlock) void form_points_kernel(
                          bary[2 * static_cast<size_t>(n) + i]};
     out0 = 0.0;
     out1 = 0.0;
-    form_point<NF, false>(F, U, X, Y, g, L, 0, nc, c, 0.0, 0.0, out0, out1);
+    form_point<NF, false, EXT>(F, U, X, Y, g, L, 0, nc, c, 0.0, 0.0, out0, out1);
   }
   out[i] = out0;
   if (F.nout == 2) out[static_cast<size_t>(n) + i] = out1;
@@ -539,7 +606,7 @@ __device__ __forceinline__ double arg_basis(int a, const double (&phi)[NL],
 // in one pass over the rule (measured faster than a row or three
 // at a time with the program re-run per pass).  Per point and test derivative
 // b, t_j = sum_a w c_ba D_a phi_j first, then Ke[i][j] += D_b phi_i t_j.
-template <int NF, int DEG>
+template <int NF, int DEG, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_matrix_kernel(
     int nc, const double* __restrict__ xy, const flow_form F, int live,
     double* __restrict__ scratch) {
@@ -566,7 +633,7 @@ __global__ __launch_bounds__(kBlock) void form_matrix_kernel(
     FormSlots<FLOW_FORM_SLOTS> out;
 #pragma unroll
     for (int k = 0; k < FLOW_FORM_SLOTS; ++k) out.v[k] = 0.0;
-    form_point_n<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    form_point_n<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
     double phi[NL], dphi[NL][3], gphi[NL][2];
     basis<DEG>(L, phi, dphi);
     phys_grad<NL>(g, dphi, gphi);
@@ -605,7 +672,7 @@ __global__ __launch_bounds__(kBlock) void form_matrix_kernel(
 
 // be[i] = sum_q w_q |det J| sum_b c_b(x_q) D_b phi_i, to scratch[i*nc + c]
 // (the gather over vptr / vsrc sums it into the vector)
-template <int NF, int DEG>
+template <int NF, int DEG, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_vector_kernel(
     int nc, const double* __restrict__ xy, const flow_form F, int live,
     double* __restrict__ scratch) {
@@ -625,13 +692,17 @@ __global__ __launch_bounds__(kBlock) void form_vector_kernel(
     const double w = F.rule[3 * q + 2] * g.adet;
     const double L[3] = {1.0 - xi - eta, xi, eta};
     FormSlots<3> out = {{0.0, 0.0, 0.0}};
-    form_point_n<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    form_point_n<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
     double phi[NL], dphi[NL][3], gphi[NL][2];
     basis<DEG>(L, phi, dphi);
     phys_grad<NL>(g, dphi, gphi);
+    // (EXT: the mask through an empty asm, as in form_matrix_kernel -- the
+    // larger interpreter has no scalar registers left for the hoisted tests)
+    int m = live;
+    if constexpr (EXT) asm volatile("" : "+s"(m));
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
-      if (((live >> b) & 1) == 0) continue;
+      if (((m >> b) & 1) == 0) continue;
       const double s = w * out.v[b];
 #pragma unroll
       for (int i = 0; i < NL; ++i) be[i] += s * arg_basis<NL>(b, phi, gphi, i);
@@ -649,7 +720,7 @@ __global__ __launch_bounds__(kBlock) void form_vector_kernel(
 // form_vector_kernel, in their order; Ke goes to scratch[(i*NL + j)*nc + c],
 // be behind it to scratch[(NL*NL + i)*nc + c].  live: bits 0..8 the Jacobian's
 // slots, 9..11 the residual's.
-template <int NF, int DEG>
+template <int NF, int DEG, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_newton_kernel(
     int nc, const double* __restrict__ xy, const flow_form F, int live,
     double* __restrict__ scratch) {
@@ -676,7 +747,7 @@ __global__ __launch_bounds__(kBlock) void form_newton_kernel(
     FormSlotsNewton out;
 #pragma unroll
     for (int k = 0; k < FLOW_FORM_NEWTON_SLOTS; ++k) out.v[k] = 0.0;
-    form_point_n<NF, false>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    form_point_n<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
     double phi[NL], dphi[NL][3], gphi[NL][2];
     basis<DEG>(L, phi, dphi);
     phys_grad<NL>(g, dphi, gphi);
@@ -764,12 +835,15 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
     const int op = F->prog[4 * pc], dst = F->prog[4 * pc + 1];
     const int a = F->prog[4 * pc + 2], b = F->prog[4 * pc + 3];
     FLOW_REQUIRE((op >= FLOW_FORM_OP_CONST && op <= FLOW_FORM_OP_OUT) ||
-                     (facet && op == FLOW_FORM_OP_NORMAL),
+                     (facet && op == FLOW_FORM_OP_NORMAL) ||
+                     (op >= FLOW_FORM_OP_LT && op <= FLOW_FORM_OP_CELL),
                  facet ? "form opcode" : "form opcode (NORMAL: facet integrals only)");
     FLOW_REQUIRE(!points || op != FLOW_FORM_OP_EXPR,
                  "form opcode (EXPR: not at points)");
-    const bool reg_a = op >= FLOW_FORM_OP_MOV && op <= FLOW_FORM_OP_OUT;
-    const bool reg_b = op >= FLOW_FORM_OP_ADD && op <= FLOW_FORM_OP_POW;
+    const bool reg_a = (op >= FLOW_FORM_OP_MOV && op <= FLOW_FORM_OP_OUT) ||
+                       (op >= FLOW_FORM_OP_LT && op <= FLOW_FORM_OP_TANH);
+    const bool reg_b = (op >= FLOW_FORM_OP_ADD && op <= FLOW_FORM_OP_POW) ||
+                       (op >= FLOW_FORM_OP_LT && op <= FLOW_FORM_OP_MAX);
     FLOW_REQUIRE(dst >= 0 && dst < FLOW_FORM_REGISTERS, "form register");
     FLOW_REQUIRE(!reg_a || (a >= 0 && a < FLOW_FORM_REGISTERS), "form register");
     FLOW_REQUIRE(!reg_b || (b >= 0 && b < FLOW_FORM_REGISTERS), "form register");
@@ -788,6 +862,9 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
         break;
       case FLOW_FORM_OP_NORMAL:
         FLOW_REQUIRE(a == 0 || a == 1, "form normal component");
+        break;
+      case FLOW_FORM_OP_CELL:
+        FLOW_REQUIRE(a >= 0 && a <= 2, "form cell quantity");
         break;
       case FLOW_FORM_OP_OUT:
         FLOW_REQUIRE(b >= 0 && b < F->nout, "form output");
@@ -808,6 +885,14 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
   return FLOW_OK;
 }
 
+// whether the program holds an extended opcode: it then runs on the EXT
+// instance of its kernel
+static bool form_is_extended(const flow_form* F) {
+  for (int pc = 0; pc < F->nprog; ++pc)
+    if (F->prog[4 * pc] >= FLOW_FORM_OP_LT) return true;
+  return false;
+}
+
 static int check_form_mesh(const flow_mesh* mesh) {
   FLOW_REQUIRE(mesh && mesh->nc > 0 && mesh->xy, "mesh");
   FLOW_REQUIRE(mesh->c1 == 0 ||
@@ -820,11 +905,16 @@ template <int TD>
 static int launch_cells(const flow_mesh* mesh, const flow_form* F, int cb, int ce,
                        double* scratch, hipStream_t st) {
   const dim3 grid((ce - cb + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
   switch (F->nfield) {
 #define FLOW_FORM_LOAD_CASE(NF)                                                  \
     case NF:                                                                     \
-      hipLaunchKernelGGL((form_cell_kernel<NF, TD>), grid, dim3(kBlock), 0, st,  \
-                         mesh->nc, cb, ce, mesh->xy, *F, scratch);              \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_cell_kernel<NF, TD, true>), grid, dim3(kBlock), \
+                           0, st, mesh->nc, cb, ce, mesh->xy, *F, scratch);     \
+      else                                                                       \
+        hipLaunchKernelGGL((form_cell_kernel<NF, TD, false>), grid, dim3(kBlock),\
+                           0, st, mesh->nc, cb, ce, mesh->xy, *F, scratch);     \
       break;
     FLOW_FORM_LOAD_CASE(0)
     FLOW_FORM_LOAD_CASE(1)
@@ -844,11 +934,18 @@ static int launch_facets(const flow_mesh* mesh, const flow_form* F, int nfacets,
                          const int* fcell, const int* flocal, double* scratch,
                          hipStream_t st) {
   const dim3 grid((nfacets + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
   switch (F->nfield) {
 #define FLOW_FORM_FACET_CASE(NF)                                                 \
     case NF:                                                                     \
-      hipLaunchKernelGGL((form_facet_kernel<NF>), grid, dim3(kBlock), 0, st,     \
-                         mesh->nc, nfacets, fcell, flocal, mesh->xy, *F, scratch); \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_facet_kernel<NF, true>), grid, dim3(kBlock), 0, \
+                           st, mesh->nc, nfacets, fcell, flocal, mesh->xy, *F,  \
+                           scratch);                                             \
+      else                                                                       \
+        hipLaunchKernelGGL((form_facet_kernel<NF, false>), grid, dim3(kBlock), 0,\
+                           st, mesh->nc, nfacets, fcell, flocal, mesh->xy, *F,  \
+                           scratch);                                             \
       break;
     FLOW_FORM_FACET_CASE(0)
     FLOW_FORM_FACET_CASE(1)
@@ -868,11 +965,16 @@ static int launch_points(const flow_mesh* mesh, const flow_form* F, int n,
                          const int* cell, const double* bary, double* out,
                          hipStream_t st) {
   const dim3 grid((n + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
   switch (F->nfield) {
 #define FLOW_FORM_POINTS_CASE(NF)                                                \
     case NF:                                                                     \
-      hipLaunchKernelGGL((form_points_kernel<NF>), grid, dim3(kBlock), 0, st,    \
-                         mesh->nc, mesh->xy, *F, n, cell, bary, out);           \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_points_kernel<NF, true>), grid, dim3(kBlock), 0,\
+                           st, mesh->nc, mesh->xy, *F, n, cell, bary, out);     \
+      else                                                                       \
+        hipLaunchKernelGGL((form_points_kernel<NF, false>), grid, dim3(kBlock),  \
+                           0, st, mesh->nc, mesh->xy, *F, n, cell, bary, out);  \
       break;
     FLOW_FORM_POINTS_CASE(0)
     FLOW_FORM_POINTS_CASE(1)
@@ -892,11 +994,18 @@ template <int DEG>
 static int launch_matrix(const flow_mesh* mesh, const flow_form* F, int live,
                          double* scratch, hipStream_t st) {
   const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
   switch (F->nfield) {
 #define FLOW_FORM_MATRIX_CASE(NF)                                                \
     case NF:                                                                     \
-      hipLaunchKernelGGL((form_matrix_kernel<NF, DEG>), grid, dim3(kBlock),      \
-                         0, st, mesh->nc, mesh->xy, *F, live, scratch);         \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_matrix_kernel<NF, DEG, true>), grid,            \
+                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
+                           scratch);                                             \
+      else                                                                       \
+        hipLaunchKernelGGL((form_matrix_kernel<NF, DEG, false>), grid,           \
+                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
+                           scratch);                                             \
       break;
     FLOW_FORM_MATRIX_CASE(0)
     FLOW_FORM_MATRIX_CASE(1)
@@ -916,11 +1025,18 @@ template <int DEG>
 static int launch_vector(const flow_mesh* mesh, const flow_form* F, int live,
                          double* scratch, hipStream_t st) {
   const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
   switch (F->nfield) {
 #define FLOW_FORM_VECTOR_CASE(NF)                                                \
     case NF:                                                                     \
-      hipLaunchKernelGGL((form_vector_kernel<NF, DEG>), grid, dim3(kBlock), 0,   \
-                         st, mesh->nc, mesh->xy, *F, live, scratch);            \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_vector_kernel<NF, DEG, true>), grid,            \
+                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
+                           scratch);                                             \
+      else                                                                       \
+        hipLaunchKernelGGL((form_vector_kernel<NF, DEG, false>), grid,           \
+                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
+                           scratch);                                             \
       break;
     FLOW_FORM_VECTOR_CASE(0)
     FLOW_FORM_VECTOR_CASE(1)
@@ -940,11 +1056,18 @@ template <int DEG>
 static int launch_newton(const flow_mesh* mesh, const flow_form* F, int live,
                          double* scratch, hipStream_t st) {
   const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
   switch (F->nfield) {
 #define FLOW_FORM_NEWTON_CASE(NF)                                                \
     case NF:                                                                     \
-      hipLaunchKernelGGL((form_newton_kernel<NF, DEG>), grid, dim3(kBlock),      \
-                         0, st, mesh->nc, mesh->xy, *F, live, scratch);         \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_newton_kernel<NF, DEG, true>), grid,            \
+                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
+                           scratch);                                             \
+      else                                                                       \
+        hipLaunchKernelGGL((form_newton_kernel<NF, DEG, false>), grid,           \
+                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
+                           scratch);                                             \
       break;
     FLOW_FORM_NEWTON_CASE(0)
     FLOW_FORM_NEWTON_CASE(1)

@@ -25,6 +25,8 @@ from .forms import (                                            # noqa: F401
     dx, ds, Measure, FacetNormal, SpatialCoordinate, as_vector, sqrt, exp,
     ln, sin, cos, dot, inner, grad, div, curl, TestFunction, TrialFunction,
     lhs, rhs, system, dS, derivative, action, adjoint,
+    conditional, lt, le, gt, ge, eq, ne, And, Or, Not, max_value, min_value,
+    sign, tanh, CellVolume, Circumradius, CellDiameter,
     )
 from .points import Probes                                      # noqa: F401
 from ..message import begin, end, info                          # noqa: F401

@@ -61,7 +61,10 @@ cell vertices and weights |T|/3 (the lumped mass matrix of u*v*dx).
 Not supported (NotImplementedError): arguments on vector or mixed spaces, test
 and trial functions of different spaces, arguments under ds (Neumann / Robin
 terms: the facet gather needs a contribution map that does not exist yet),
-dS, action / adjoint.
+dS, action / adjoint.  lhs / rhs also split ONE integrand that holds terms of
+both ranks, (source - dot(conv, grad(u))) * tau * dot(conv, grad(v)) * dx, by
+linearity, as UFL does; assembling such an integrand unsplit stays a
+ValueError.
 
 Derivatives: `derivative(F, u, du=None)` is the Gateaux derivative of a form
 (or signed sum) of rank 0 or 1 with respect to a scalar P1 / P2 Function u,
@@ -87,6 +90,44 @@ a form of any rank compared with the number 0 gives one (solve refuses what
 is not a residual), any other number is a ValueError.
 newton_program() compiles the tables of J and F into one Program (slots
 3 b + a and 9 + b of 12) that computes the subtrees the two share once.
+
+Branches, clips and cell geometry (UFL's spellings):
+  operand / operator                   degree            d/dx and Gateaux
+  conditional(c, t, f)                 max(deg t, deg f) conditional(c, t', f')
+  max_value(a, b)                      max               conditional(gt(a, b), a', b')
+  min_value(a, b)                      max               conditional(lt(a, b), a', b')
+  sign(a)                              deg a             0
+  tanh(a)                              deg a + 2         (1 - tanh(a)^2) a'
+  CellVolume Circumradius CellDiameter 0                 0
+  stabilization.supg(...) (SUPG tau)   1                 Gateaux 0; d/dx refused
+Conditions are lt le gt ge eq ne of two scalars (also a < b, a <= b, ...) and
+And Or Not of conditions.  A condition is NOT a scalar operand: arithmetic with
+one is a TypeError, a number in its place too; it is never differentiated and
+does not count in the degree.  t and f are scalars or tensors of one shape
+(component by component).  conditional is a SELECT: both branches are
+computed and the value of the untaken one never reaches the result, so
+conditional(gt(Pe, 1e-5), (1/tanh(Pe) - 1/Pe)/Pe, 1/3 - Pe**2/45) is 1/3 at
+Pe == 0 although the other branch is inf - inf there.  On the device a
+condition is 1.0 or 0.0 (opcodes lt le eq ne; gt and ge swap their operands;
+And is the product, Or the larger, Not 1 - c) and `select` is R[dst] = R[a]
+!= 0 ? R[b] : R[dst]; Program.need counts its three live values.  The
+geometry operands are cell-wise constants that carry their mesh (the owning
+cell under ds and at points): CellVolume |T|, Circumradius abc / (4 |T|),
+CellDiameter the largest vertex distance, computed on the device from the
+vertex coordinates a lane holds.  An argument may sit in the BRANCHES of a
+conditional: extract_arguments distributes it over the two branches' tables,
+c[b][a] = conditional(cond, c_t, c_f) with zero where a branch lacks the
+term; an argument in a condition or under max_value / min_value / sign /
+tanh is the "not linear" ValueError.  The SUPG tau is the values at the three
+vertices of each cell, linear inside, discontinuous across cells: an 'expr'
+leaf whose lattice flow_supg_tau computes at every launch from the convection
+field as it then is; legal under dx and ds, not at points.  sinh, cosh and
+atan are not provided: each needs an inlined routine of its own in the
+interpreter (tanh shares the one exp), and the interpreter's instances are at
+their register limits.  Programs with an opcode from 19 up run on
+instances of the kernels compiled for them; every other program launches the
+instances it always did.  compile_trees() computes subtrees that repeat
+within an integrand once where the plain program exceeds a limit of flow_form.
 '''
 import numbers
 
@@ -102,9 +143,19 @@ MAX_EXPRESSIONS = 4
 NEWTON_SLOTS = 12       # 9 of the Jacobian's table, 3 of the residual's
 OPS = {name: i for i, name in enumerate((
     'const', 'coord', 'field', 'expr', 'mov', 'add', 'sub', 'mul', 'div', 'pow',
-    'neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos', 'out', 'normal'))}
+    'neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos', 'out', 'normal',
+    # 19 up: conditions (1.0 | 0.0), the select, clips, tanh, cell geometry
+    'lt', 'le', 'eq', 'ne', 'select', 'min', 'max', 'sign', 'tanh', 'cell'))}
 UNARY = ('neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos')
 BINARY = ('add', 'sub', 'mul', 'div', 'pow')
+# the extended vocabulary: nodes like the above that no argument may sit under
+UNARY_EXT = ('sign', 'tanh')
+BINARY_EXT = ('max', 'min')
+COMPARE = ('lt', 'le', 'gt', 'ge', 'eq', 'ne')
+# every node with subtrees: (op, a[, b]), ('powi', a, n), ('cond', c, t, f)
+NONLEAF = UNARY + BINARY + ('powi',) + UNARY_EXT + BINARY_EXT + COMPARE \
+    + ('cond',)
+CELL_QUANTITIES = ('volume', 'circumradius', 'diameter')
 
 
 # -- scalar trees --------------------------------------------------------------
@@ -113,8 +164,12 @@ BINARY = ('add', 'sub', 'mul', 'div', 'pow')
 # d of the outward unit normal, ds only) ('arg', number, d, V) (number 0 the
 # test, 1 the trial function of the space V; d as for fields) ('powi', a, n)
 # and (op, a[, b]) for the UNARY / BINARY ops; ('reg', r) (register r of the
-# program, holding a subtree computed up front: newton_program only).  Objects
-# inside compare by identity.
+# program, holding a subtree computed up front: newton_program only);
+# ('cell', mesh, k) (k = 0 |T|, 1 the circumradius, 2 the diameter of the cell);
+# (op, a[, b]) for UNARY_EXT / BINARY_EXT; (op, a, b) for COMPARE, worth 1.0
+# or 0.0 (And = mul, Or = max, Not = 1 - c of those); ('cond', c, t, f), t
+# where c != 0 and f elsewhere -- a select, the untaken value is not read.
+# Objects inside compare by identity.
 ZERO = ('num', 0.0)
 ONE = ('num', 1.0)
 
@@ -173,11 +228,24 @@ def s_powi(a, n):
     return ('powi', a, n)
 
 
+def s_cond(c, t, f):
+    '''t where c holds, f elsewhere; equal branches need no condition.'''
+    if t == f:
+        return t
+    return ('cond', c, t, f)
+
+
 def s_diff(n, d):
     '''d n / d x_d (d = 0, 1), by the chain rule.'''
     k = n[0]
-    if k in ('num', 'const', 'n'):      # (the normal: constant on a facet)
+    if k in ('num', 'const', 'n', 'cell', 'sign'):
+        # (the normal: constant on a facet; cell geometry: on a cell)
         return ZERO
+    if k == 'cond':                     # (the condition is not differentiated)
+        return s_cond(n[1], s_diff(n[2], d), s_diff(n[3], d))
+    if k in ('max', 'min'):
+        return s_cond(('gt' if k == 'max' else 'lt', n[1], n[2]),
+                      s_diff(n[1], d), s_diff(n[2], d))
     if k == 'x':
         return ONE if n[1] == d else ZERO
     if k == 'field':
@@ -185,6 +253,11 @@ def s_diff(n, d):
             raise NotImplementedError('second derivatives of a field')
         return ('field', n[1], n[2], d + 1)
     if k == 'expr':
+        if _has_lattice(n[1]):
+            raise NotImplementedError(
+                'spatial derivatives of the SUPG tau (a cell-wise linear, '
+                'discontinuous coefficient given by its vertex values) are '
+                'not supported')
         raise NotImplementedError(
             'derivatives of an Expression: interpolate it into a Function')
     if k == 'arg':
@@ -221,6 +294,8 @@ def s_diff(n, d):
         return s_mul(('cos', a), da)
     if k == 'cos':
         return s_neg(s_mul(('sin', a), da))
+    if k == 'tanh':
+        return s_mul(s_sub(ONE, s_powi(n, 2)), da)
     raise NotImplementedError('derivative of %s' % k)
 
 
@@ -232,12 +307,19 @@ def s_gateaux(n, u, k, V):
         if n[1] is u and n[2] == 0:
             return ('arg', k, n[3], V)
         return ZERO
-    if op in ('num', 'const', 'x', 'expr', 'n', 'arg'):
+    if op in ('num', 'const', 'x', 'expr', 'n', 'arg', 'cell', 'sign'):
         return ZERO
+    if op == 'cond':
+        return s_cond(n[1], s_gateaux(n[2], u, k, V), s_gateaux(n[3], u, k, V))
+    if op in ('max', 'min'):
+        return s_cond(('gt' if op == 'max' else 'lt', n[1], n[2]),
+                      s_gateaux(n[1], u, k, V), s_gateaux(n[2], u, k, V))
     a = n[1]
     da = s_gateaux(a, u, k, V)
     if op == 'neg':
         return s_neg(da)
+    if op == 'tanh':
+        return s_mul(s_sub(ONE, s_powi(n, 2)), da)
     if op == 'powi':
         return s_mul(s_mul(('num', float(n[2])), s_powi(a, n[2] - 1)), da)
     if op == 'sqrt':
@@ -377,6 +459,19 @@ class FormExpr(object):
     def __abs__(self):
         return _function('abs', self)
 
+    # (UFL: a < b is lt(a, b); == and != stay identity, use eq() and ne())
+    def __lt__(self, other):
+        return lt(self, other)
+
+    def __le__(self, other):
+        return le(self, other)
+
+    def __gt__(self, other):
+        return gt(self, other)
+
+    def __ge__(self, other):
+        return ge(self, other)
+
     def __getitem__(self, idx):
         if not isinstance(idx, tuple):
             idx = (idx,)
@@ -405,6 +500,8 @@ def as_form(obj):
         return obj
     if isinstance(obj, bool):
         raise TypeError('not a form operand: %r' % (obj,))
+    if isinstance(obj, Condition):
+        raise TypeError(Condition.REFUSAL)
     if isinstance(obj, numbers.Real):
         return FormExpr(('num', float(obj)), (), 0)
     if isinstance(obj, Function):
@@ -432,11 +529,22 @@ def as_form(obj):
         if dim != 2:
             raise ValueError('Expression with %d components' % dim)
         return FormExpr([('expr', obj, i) for i in range(2)], (2,), k)
+    if _has_lattice(obj):
+        return FormExpr(('expr', obj, 0), (), int(obj.degree), obj.mesh)
     raise TypeError('not a form operand: %r' % (type(obj),))
 
 
+def _has_lattice(obj):
+    '''A scalar coefficient that computes its own P_degree cell lattice on
+    the device (stabilization.SupgTau: the values at the cell vertices, linear
+    inside a cell, discontinuous across cells): an 'expr' leaf that carries
+    its mesh; ops._form_struct calls obj.form_lattice(mesh) at every launch.'''
+    return hasattr(obj, 'form_lattice') and hasattr(obj, 'degree')
+
+
 def is_form_operand(obj):
-    return isinstance(obj, (FormExpr, Function, Constant, Expression, Measure))
+    return isinstance(obj, (FormExpr, Function, Constant, Expression, Measure,
+                            Condition)) or _has_lattice(obj)
 
 
 def _binary(op, a, b):
@@ -520,8 +628,8 @@ def _function(name, f):
     f = as_form(f)
     if f.shape:
         raise ValueError('%s of a tensor of shape %r' % (name, f.shape))
-    return FormExpr((name, f.comps), (), f.deg if name == 'abs' else f.deg + 2,
-                    f.mesh)
+    return FormExpr((name, f.comps), (),
+                    f.deg if name in ('abs', 'sign') else f.deg + 2, f.mesh)
 
 
 def sqrt(f):
@@ -542,6 +650,154 @@ def sin(f):
 
 def cos(f):
     return _function('cos', f)
+
+
+def tanh(f):
+    return _function('tanh', f)
+
+
+def sign(f):
+    '''-1, 0 or 1 (degree unchanged, derivative 0).'''
+    return _function('sign', f)
+
+
+def _clip(name, a, b):
+    a, b = as_form(a), as_form(b)
+    if a.shape or b.shape:
+        raise ValueError('%s_value of tensors of shapes %r and %r'
+                         % (name, a.shape, b.shape))
+    return FormExpr((name, a.comps, b.comps), (), max(a.deg, b.deg),
+                    _join(a, b))
+
+
+def max_value(a, b):
+    return _clip('max', a, b)
+
+
+def min_value(a, b):
+    return _clip('min', a, b)
+
+
+class Condition(object):
+    '''lt(a, b) ... ne(a, b) and their And / Or / Not: what conditional()
+    branches on.  Its tree is worth 1.0 or 0.0 on the device, but a condition
+    is not a scalar operand: arithmetic with it is a TypeError.'''
+    REFUSAL = ('a condition (lt, le, gt, ge, eq, ne, And, Or, Not) is not a '
+               'scalar operand: use it as the first argument of conditional()')
+
+    def __init__(self, tree, mesh):
+        self.tree = tree
+        self.mesh = mesh
+
+    def _refuse(self, *args, **kwargs):
+        raise TypeError(Condition.REFUSAL)
+
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = _refuse
+    __truediv__ = __rtruediv__ = __div__ = __rdiv__ = _refuse
+    __pow__ = __rpow__ = __neg__ = __pos__ = __abs__ = __float__ = _refuse
+    __getitem__ = _refuse
+
+    def __bool__(self):
+        raise TypeError('a condition has no truth value on the host: it is '
+                        'evaluated at the quadrature points (conditional())')
+
+    __nonzero__ = __bool__
+
+
+def _compare(name, a, b):
+    a, b = as_form(a), as_form(b)
+    if a.shape or b.shape:
+        raise ValueError('%s of tensors of shapes %r and %r: conditions '
+                         'compare scalars' % (name, a.shape, b.shape))
+    return Condition((name, a.comps, b.comps), _join(a, b))
+
+
+def lt(a, b):
+    return _compare('lt', a, b)
+
+
+def le(a, b):
+    return _compare('le', a, b)
+
+
+def gt(a, b):
+    return _compare('gt', a, b)
+
+
+def ge(a, b):
+    return _compare('ge', a, b)
+
+
+def eq(a, b):
+    return _compare('eq', a, b)
+
+
+def ne(a, b):
+    return _compare('ne', a, b)
+
+
+def _condition(c):
+    if not isinstance(c, Condition):
+        raise TypeError('a condition is expected: lt, le, gt, ge, eq, ne of '
+                        'two scalars or And, Or, Not of conditions (got %r)'
+                        % (type(c),))
+    return c
+
+
+def And(a, b):
+    '''Both: the product of the two 0-1 values.'''
+    a, b = _condition(a), _condition(b)
+    return Condition(('mul', a.tree, b.tree), _join_mesh(a.mesh, b.mesh))
+
+
+def Or(a, b):
+    '''Either: the larger of the two 0-1 values.'''
+    a, b = _condition(a), _condition(b)
+    return Condition(('max', a.tree, b.tree), _join_mesh(a.mesh, b.mesh))
+
+
+def Not(a):
+    a = _condition(a)
+    return Condition(('sub', ONE, a.tree), a.mesh)
+
+
+def conditional(cond, t, f):
+    '''t where cond holds, f elsewhere; tensors of equal shape component by
+    component.  Degree: the larger of the branches'.  Both branches are
+    computed, the result is SELECTED: a value of the untaken branch (inf,
+    NaN) never reaches it.'''
+    cond = _condition(cond)
+    t, f = as_form(t), as_form(f)
+    if t.shape != f.shape:
+        raise ValueError('conditional of shapes %r and %r'
+                         % (t.shape, f.shape))
+    mesh = _join_mesh(cond.mesh, _join(t, f))
+    return FormExpr(_map2(lambda x, y: s_cond(cond.tree, x, y), t.comps,
+                          f.comps, t.shape), t.shape, max(t.deg, f.deg), mesh)
+
+
+def _cell_quantity(mesh, k):
+    if not _is_mesh(mesh):
+        raise TypeError('%s takes a mesh (got %r)'
+                        % (('CellVolume', 'Circumradius', 'CellDiameter')[k],
+                           type(mesh)))
+    return FormExpr(('cell', mesh, k), (), 0, mesh)
+
+
+def CellVolume(mesh):
+    '''|T| of the cell (of the owning cell under ds and at points): a
+    cell-wise constant, degree 0, derivatives zero.'''
+    return _cell_quantity(mesh, 0)
+
+
+def Circumradius(mesh):
+    '''abc / (4 |T|) of the cell's edge lengths a, b, c.'''
+    return _cell_quantity(mesh, 1)
+
+
+def CellDiameter(mesh):
+    '''The largest distance between two vertices of the cell.'''
+    return _cell_quantity(mesh, 2)
 
 
 def dot(a, b):
@@ -663,14 +919,18 @@ def arguments(n, found=None):
             raise NotImplementedError(
                 'two %s functions of different spaces in one form'
                 % ('test', 'trial')[n[1]])
-    elif n[0] in UNARY + BINARY + ('powi',):
+    elif n[0] in NONLEAF:
         for c in n[1:]:
             if isinstance(c, tuple):
                 arguments(c, found)
     return found
 
 
-_OP_NAMES = {'powi': '**', 'pow': '**', 'div': '/', 'mul': '*'}
+_OP_NAMES = {'powi': '**', 'pow': '**', 'div': '/', 'mul': '*',
+             'max': 'max_value', 'min': 'min_value', 'cond': 'conditional',
+             'lt': 'a condition (lt)', 'le': 'a condition (le)',
+             'gt': 'a condition (gt)', 'ge': 'a condition (ge)',
+             'eq': 'a condition (eq)', 'ne': 'a condition (ne)'}
 
 
 def extract_arguments(n):
@@ -716,6 +976,19 @@ def extract_arguments(n):
                              'expression of a test or trial function')
         return {key: s_div(c, n[2])
                 for key, c in extract_arguments(n[1]).items()}
+    if k == 'cond':
+        # the conditional distributes over the two branches' tables: zero
+        # where a branch lacks the term
+        if has_leaf(n[1], 'arg'):
+            raise ValueError('the form is not linear: a test or trial '
+                             'function in the condition of a conditional')
+        tt, tf = extract_arguments(n[2]), extract_arguments(n[3])
+        out = {}
+        for key in list(tt) + [key for key in tf if key not in tt]:
+            c = s_cond(n[1], tt.get(key, ZERO), tf.get(key, ZERO))
+            if not _is_num(c, 0.0):
+                out[key] = c
+        return out
     raise ValueError('the form is not linear: a test or trial function under '
                      '%s' % _OP_NAMES.get(k, k))
 
@@ -752,7 +1025,7 @@ def has_normal(n):
     '''Whether a scalar tree reads the facet normal.'''
     if n[0] == 'n':
         return True
-    return n[0] in UNARY + BINARY + ('powi',) and any(
+    return n[0] in NONLEAF and any(
         has_normal(c) for c in n[1:] if isinstance(c, tuple))
 
 
@@ -760,7 +1033,7 @@ def has_leaf(n, kind):
     '''Whether a scalar tree holds a leaf of `kind` ('n', 'expr', ...).'''
     if n[0] == kind:
         return True
-    return n[0] in UNARY + BINARY + ('powi',) and any(
+    return n[0] in NONLEAF and any(
         has_leaf(c, kind) for c in n[1:] if isinstance(c, tuple))
 
 
@@ -773,7 +1046,7 @@ def point_program(expr):
         raise ValueError('point evaluation of a tensor of shape %r: evaluate '
                          'its rows or components, e.g. f[0] or f[0, 1]'
                          % (expr.shape,))
-    return Program(expr.scalar_trees(), point=True)
+    return compile_trees(expr.scalar_trees(), point=True)
 
 
 def check_no_normal(expr, where):
@@ -1033,11 +1306,43 @@ def _parts_of_rank(form, rank, sign):
                         % (type(form),))
     parts = []
     for s, f in form.terms():
-        if f.rank == 0:
+        if not has_leaf(f.integrand.comps, 'arg'):
             raise ValueError('lhs / rhs / system: a part of the sum has no '
                              'test function')
-        if f.rank == rank:
-            parts.append((sign * s, f))
+        f.arguments()
+        tab = {key: c for key, c in
+               extract_arguments(f.integrand.comps).items()
+               if not _is_num(c, 0.0)}
+        ranks = set((b is not None) + (a is not None) for b, a in tab)
+        if len(ranks) <= 1 or 0 in ranks \
+                or any(b is None for b, a in tab):
+            # one rank (or an integrand argument_table refuses, with its
+            # message): the part as it was written
+            if f.rank == 0:
+                raise ValueError('lhs / rhs / system: a part of the sum has '
+                                 'no test function')
+            if f.rank == rank:
+                parts.append((sign * s, f))
+            continue
+        # an integrand of both ranks, as the reference's SUPG term (R2 holds
+        # the trial function and the source): split by linearity, as UFL does.
+        # The terms of the wanted rank, c D_a u D_b v, at the degree of the
+        # integrand they came from
+        found = f.arguments()
+        tree = ZERO
+        for (b, a), c in tab.items():
+            if (a is not None) + 1 != rank:
+                continue
+            term = s_mul(c, ('arg', 0, b, found[0]))
+            if a is not None:
+                term = s_mul(term, ('arg', 1, a, found[1]))
+            tree = s_add(tree, term)
+        if _is_num(tree, 0.0):
+            continue
+        split = Form(FormExpr(tree, (), f.integrand.deg, f.integrand.mesh),
+                     f.mesh, f.metadata, f.integral_type, f.subdomain_id,
+                     f.subdomain_data)
+        parts.append((sign * s, split))
     return FormSum(parts)
 
 
@@ -1142,6 +1447,13 @@ def projection_degree(expr, test_degree, form_compiler_parameters=None):
 
 
 # -- register programs -----------------------------------------------------------
+class ProgramLimit(ValueError):
+    '''The trees exceed a limit of flow_form (instructions, registers,
+    constants, field or Expression slots): what the callers with a fallback
+    (compile_trees, argument_programs, the Newton assembler) catch.  A
+    ValueError, as it always was.'''
+
+
 class Program(object):
     '''Instructions (op, dst, a, b) over REGISTERS registers for a list of
     scalar trees (output k = tree k), and the operands they load: constants
@@ -1187,7 +1499,7 @@ class Program(object):
             self._gen(t, 0)
             self._emit('out', 0, 0, k)
         if len(self.code) > MAX_PROGRAM:
-            raise ValueError('the integrand compiles to %d instructions: the '
+            raise ProgramLimit('the integrand compiles to %d instructions: the '
                              'limit is %d' % (len(self.code), MAX_PROGRAM))
         self.slots = list(slots)
         self.nout = len(trees) if nout is None else nout
@@ -1202,7 +1514,7 @@ class Program(object):
             if k[0] is key[0] and k[1] == key[1]:
                 return i
         if len(table) == limit:
-            raise ValueError('the integrand needs more than %d %s: the limit '
+            raise ProgramLimit('the integrand needs more than %d %s: the limit '
                              'is %d' % (limit, what, limit))
         table.append(key)
         return len(table) - 1
@@ -1210,7 +1522,7 @@ class Program(object):
     def _emit(self, op, dst, a=0, b=0):
         if op != 'out':
             if dst >= REGISTERS:
-                raise ValueError('the integrand needs more than %d registers: '
+                raise ProgramLimit('the integrand needs more than %d registers: '
                                  'the limit is %d' % (REGISTERS, REGISTERS))
             self.nregs = max(self.nregs, dst + 1)
         self.code.append((OPS[op], dst, a, b))
@@ -1221,7 +1533,7 @@ class Program(object):
                     k[0] is key[0] and k[1] == key[1]):
                 return i
         if len(self.consts) == MAX_CONSTANTS:
-            raise ValueError('the integrand needs more than %d constants: the '
+            raise ProgramLimit('the integrand needs more than %d constants: the '
                              'limit is %d' % (MAX_CONSTANTS, MAX_CONSTANTS))
         self.consts.append(key)
         return len(self.consts) - 1
@@ -1230,10 +1542,14 @@ class Program(object):
     def need(n):
         '''Registers the tree needs (Sethi-Ullman).'''
         k = n[0]
-        if k in ('num', 'const', 'x', 'field', 'expr', 'n', 'reg'):
+        if k in ('num', 'const', 'x', 'field', 'expr', 'n', 'reg', 'cell'):
             return 1
-        if k in UNARY:
+        if k in UNARY + UNARY_EXT:
             return Program.need(n[1])
+        if k == 'cond':
+            # three live values: the k-th computed holds k registers below it
+            return max(Program.need(c) + i
+                       for i, c in enumerate(_select_order(n)))
         if k == 'powi':
             m = n[2]
             na = Program.need(n[1])
@@ -1261,9 +1577,21 @@ class Program(object):
             self._emit('expr', base, self._slot(
                 self.exprs, (n[1], n[2]), MAX_EXPRESSIONS,
                 'Expression components'))
-        elif k in UNARY:
+        elif k == 'cell':
+            self._emit('cell', base, n[2])
+        elif k in UNARY + UNARY_EXT:
             self._gen(n[1], base)
             self._emit(k, base, base)
+        elif k == 'cond':
+            # R[dst] = R[a] != 0 ? R[b] : R[dst]: dst holds the else-value
+            order = _select_order(n)
+            for i, c in enumerate(order):
+                self._gen(c, base + i)
+            rc, rt, rf = [base + [j for j in range(3) if order[j] is c][0]
+                          for c in n[1:]]
+            self._emit('select', rf, rc, rt)
+            if rf != base:
+                self._emit('mov', base, rf)
         elif k == 'powi':
             m = n[2]
             self._gen(n[1], base)
@@ -1280,6 +1608,8 @@ class Program(object):
                 self._emit('mov', base, base + 1)
         else:
             a, b = n[1], n[2]
+            if k in ('gt', 'ge'):           # a > b is b < a
+                k, a, b = {'gt': 'lt', 'ge': 'le'}[k], b, a
             if self.need(a) >= self.need(b):
                 self._gen(a, base)
                 self._gen(b, base + 1)
@@ -1313,24 +1643,34 @@ def argument_program(table, rank):
                    nout=9 if rank == 2 else 3)
 
 
+def _select_order(n):
+    '''The order in which the condition and the two branches of ('cond', c,
+    t, f) are computed into registers base, base + 1, base + 2: the largest
+    register need first (else-value, condition, then-value among equals).'''
+    return sorted((n[3], n[1], n[2]), key=lambda c: -Program.need(c))
+
+
 def _count(n):
     '''Instructions Program._gen emits for the tree n.'''
     k = n[0]
-    if k in UNARY:
+    if k in UNARY + UNARY_EXT:
         return _count(n[1]) + 1
+    if k == 'cond':
+        return sum(_count(c) for c in n[1:]) + (
+            1 if _select_order(n)[0] is n[3] else 2)
     if k == 'powi':
         m = n[2]
         if m & (m - 1) == 0:
             return _count(n[1]) + m.bit_length() - 1
         return _count(n[1]) + 2 + sum(2 if b == '1' else 1 for b in bin(m)[3:])
-    if k in BINARY:
+    if k in BINARY + BINARY_EXT + COMPARE:
         return _count(n[1]) + _count(n[2]) + 1
     return 1
 
 
 def _subtrees(n, found):
     '''The non-leaf subtrees of n, into the set `found`.'''
-    if n[0] in UNARY + BINARY + ('powi',):
+    if n[0] in NONLEAF:
         found.add(n)
         for c in n[1:]:
             if isinstance(c, tuple):
@@ -1341,20 +1681,30 @@ def _subtrees(n, found):
 def _substitute(n, old, new):
     if n == old:
         return new
-    if n[0] in UNARY + BINARY + ('powi',):
+    if n[0] in NONLEAF:
         return (n[0],) + tuple(_substitute(c, old, new)
                                if isinstance(c, tuple) else c for c in n[1:])
     return n
 
 
-def share_subtrees(trees):
+def _occurrences(n, c):
+    """How often the subtree c occurs in the tree n."""
+    if n == c:
+        return 1
+    if n[0] in NONLEAF:
+        return sum(_occurrences(m, c) for m in n[1:] if isinstance(m, tuple))
+    return 0
+
+
+def share_subtrees(trees, within=False):
     '''Common-subtree sharing for the output trees of one program: (shared,
     trees) with shared = [(register, tree)] in the order to compute them and
     the output trees rewritten to read them through ('reg', r) leaves.
     Candidates are the structurally equal (==; objects inside by identity)
-    non-leaf subtrees that occur in two or more trees, the largest first;
-    each taken one gets the highest free register; one is taken where that
-    saves instructions and still leaves every output tree, and every shared
+    non-leaf subtrees that occur in two or more trees (within=True: two or
+    more times, in one tree or several), the largest first; each taken one
+    gets the highest free register; one is taken where that saves
+    instructions and still leaves every output tree, and every shared
     subtree, its Sethi-Ullman need below the reserved registers.'''
     trees = list(trees)
     seen = {}
@@ -1364,7 +1714,7 @@ def share_subtrees(trees):
             if c not in seen:
                 seen[c] = 0
                 order.append(c)
-            seen[c] += 1
+            seen[c] += _occurrences(t, c) if within else 1
     cands = [c for c in order if seen[c] >= 2]
     # (largest first; ties by the instruction stream they would emit, which
     # is the same from run to run)
@@ -1373,7 +1723,7 @@ def share_subtrees(trees):
     for c in cands:
         users = [t for t in trees + [d[2] for d in defs]
                  if c in _subtrees(t, set())]
-        m = len(users)
+        m = sum(_occurrences(t, c) for t in users) if within else len(users)
         if m < 2 or _count(c) + 1 + m >= m * _count(c):
             continue
         r = REGISTERS - 1 - len(defs)
@@ -1388,6 +1738,24 @@ def share_subtrees(trees):
     # (a subtree of a larger shared one was taken after it: compute it first)
     defs.sort(key=lambda d: _count(d[1]))
     return [(d[0], d[2]) for d in defs], trees
+
+
+def compile_trees(trees, **kwargs):
+    '''Program(trees, ...) as it always was where that fits the limits of
+    flow_form; else with the subtrees that repeat, inside one tree or across
+    them, computed once (share_subtrees, within=True) -- xi(Pe) names Pe five
+    times.  The first ValueError where sharing does not help.'''
+    trees = list(trees)
+    try:
+        return Program(trees, **kwargs)
+    except ProgramLimit as e:
+        shared, new = share_subtrees(trees, within=True)
+        if not shared:
+            raise
+        try:
+            return Program(new, shared=shared, **kwargs)
+        except ProgramLimit:
+            raise e
 
 
 def _strip(n):
@@ -1435,9 +1803,14 @@ def argument_programs(table, rank):
     nout = 9 if rank == 2 else 3
 
     def build(chunk):
-        shared, trees = share_subtrees([t for _, t in chunk])
-        return Program(trees, slots=[k for k, _ in chunk], nout=nout,
-                       shared=shared)
+        try:
+            shared, trees = share_subtrees([t for _, t in chunk])
+            return Program(trees, slots=[k for k, _ in chunk], nout=nout,
+                           shared=shared)
+        except ProgramLimit:
+            # (subtrees that repeat inside one coefficient, too)
+            return compile_trees([t for _, t in chunk],
+                                 slots=[k for k, _ in chunk], nout=nout)
 
     progs, chunk = [], []
     for item in items:
@@ -1459,7 +1832,7 @@ def depends_on(n, u):
     '''Whether the scalar tree n reads the Function u.'''
     if n[0] == 'field':
         return n[1] is u
-    return n[0] in UNARY + BINARY + ('powi',) and any(
+    return n[0] in NONLEAF and any(
         depends_on(c, u) for c in n[1:] if isinstance(c, tuple))
 
 

@@ -902,7 +902,10 @@ def _form_struct(prog, mesh, q, facet=False, scheme='default'):
     coefs = {}
     for i, (e, comp) in enumerate(prog.exprs):
         if id(e) not in coefs:
-            coefs[id(e)] = as_cell_coefficient(e, mesh, e.value_dim())
+            # (a coefficient with a lattice of its own, stabilization.SupgTau:
+            # computed on the device now, from its field's current values)
+            coefs[id(e)] = e.form_lattice(mesh) if hasattr(e, 'form_lattice') \
+                else as_cell_coefficient(e, mesh, e.value_dim())
         coef = coefs[id(e)]
         n = coef.nl * nc
         base = _hip.f64(coef.values, coef.dim * n, 'Expression lattice').value
@@ -958,7 +961,7 @@ def assemble(form, form_compiler_parameters=None):
     lib = _hip.lib()
     mesh = forms.form_mesh(form.integrand, form.mesh)
     facet = form.integral_type == 'exterior_facet'
-    prog = forms.Program([form.integrand.comps], facet=facet)
+    prog = forms.compile_trees([form.integrand.comps], facet=facet)
     fs, keep = _form_struct(prog, mesh, q, facet)
     res = ctypes.c_double(0.0)
     if facet:
@@ -1557,7 +1560,7 @@ def form_load_vector(expr, V, form_compiler_parameters=None):
     lib = _hip.lib()
     mesh = forms.form_mesh(expr, V.mesh())
     q = forms.projection_degree(expr, V.degree, form_compiler_parameters)
-    prog = forms.Program(expr.scalar_trees())
+    prog = forms.compile_trees(expr.scalar_trees())
     fs, keep = _form_struct(prog, mesh, q)
     lay = V.layout
     b = device.empty(V.size())

@@ -13,6 +13,17 @@ tau is a device function of the heat assembly kernel
     h   = 4 |b| area / sum_edges |e_y b_x - e_x b_y|      (directed diameter),
     xi  = (coth Pe - 1/Pe)/Pe  for Pe > 1e-5, else 1/3 - Pe^2/45 + 2 Pe^4/945,
     tau = 0 for |b| < 1e-10;  tau > 1e3 is an error (the reference throws).
+
+The handle `supg()` returns is also an operand of the generic forms
+(flow_amd/fem/forms.py), with the reference's meaning: the values at the
+three vertices of each cell, interpolated linearly inside the cell,
+discontinuous across cells -- `assemble(u * tau * dot(conv, grad(v)) * dx)`.
+Its lattice comes from a kernel of its own (`flow_supg_tau`: one cell per
+lane, no matrix) at EVERY launch of a form that holds it: the convection
+field may have changed, through set_array or through a kernel that wrote its
+data, and nothing on the host sees the second.  derivative() with respect to
+any Function treats tau as a coefficient (derivative zero), as dolfin treats
+an Expression.
 '''
 import ctypes
 
@@ -34,6 +45,37 @@ class SupgTau(object):
         self.epsilon = float(epsilon)
         self.p = int(p)
         self.degree = 1
+
+    def value_dim(self):
+        return 1
+
+    def form_lattice(self, mesh=None):
+        '''The P1 cell lattice of tau on the device, (1, 3, Nc) with the cell
+        index fastest, from the convection field as it is now
+        (flow_supg_tau).  RuntimeError where tau > 1e3.'''
+        from .fem.function import CellCoefficient
+        if mesh is not None and mesh is not self.mesh:
+            raise ValueError('the SUPG tau of the integrand lives on another '
+                             'mesh')
+        lib = _hip.lib()
+        W = self.convection.function_space()
+        if W.mesh() is not self.mesh:
+            raise ValueError('SUPG: the convection field lives on another '
+                             'mesh')
+        if self.epsilon <= 0.0 or self.p not in (1, 2):
+            raise ValueError('SUPG: diffusion > 0 and element degree 1 or 2')
+        nc = self.mesh.num_cells()
+        tau = device.empty(3 * nc)
+        status = device.zeros(1, dtype=torch.int32)
+        _hip.check(lib.flow_supg_tau(
+            ctypes.byref(ops.mesh_struct(self.mesh)),
+            ctypes.byref(ops.space_struct(W.layout)),
+            _hip.f64(self.convection.data, W.size()), self.epsilon, self.p,
+            _hip.f64(tau, 3 * nc), _hip.i32(status), _hip.stream()
+            ))
+        if int(device.to_host(status).item()) != 0:
+            raise RuntimeError('SUPG: tau > 1e3')
+        return CellCoefficient(1, 1, tau, 1)
 
     def cell_vertex_values(self):
         '''tau at the three vertices of every cell, (Nc, 3) numpy array,

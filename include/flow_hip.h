@@ -1100,6 +1100,18 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
  *   out    output b = r[a]
  *   normal r[dst] = component a of the outward unit normal (facet
  *          integrals only: the cell entry points refuse it)
+ *   lt le eq ne  r[dst] = r[a] o r[b] ? 1.0 : 0.0
+ *   select r[dst] = r[a] != 0 ? r[b] : r[dst]   (the value not selected is
+ *          not read: an inf or NaN in it does not reach the result)
+ *   min max  r[dst] = the smaller | larger of r[a], r[b] (fmin / fmax: where
+ *          one operand is NaN the OTHER is returned -- numpy.minimum /
+ *          maximum and UFL's conditional-based definition give NaN there;
+ *          `Or` of two conditions is max of their 0-1 values, never NaN)
+ *   sign   r[dst] = -1, 0, 1 by the sign of r[a]; +-0 and NaN are returned as
+ *          they are                                   tanh  r[dst] = tanh r[a]
+ *   cell   r[dst] = a = 0: |T|, 1: the circumradius, 2: the diameter (largest
+ *          vertex distance) of the cell (of the owning cell on facets and at
+ *          points), from the vertex coordinates the kernels hold
  * The program and the constants travel by value with the launch (constants
  * may change from call to call at no cost); rule and tables are device
  * arrays, uploaded once per program signature and degree by the host. */
@@ -1130,6 +1142,16 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
 #define FLOW_FORM_OP_COS 16
 #define FLOW_FORM_OP_OUT 17
 #define FLOW_FORM_OP_NORMAL 18
+#define FLOW_FORM_OP_LT 19
+#define FLOW_FORM_OP_LE 20
+#define FLOW_FORM_OP_EQ 21
+#define FLOW_FORM_OP_NE 22
+#define FLOW_FORM_OP_SELECT 23
+#define FLOW_FORM_OP_MIN 24
+#define FLOW_FORM_OP_MAX 25
+#define FLOW_FORM_OP_SIGN 26
+#define FLOW_FORM_OP_TANH 27
+#define FLOW_FORM_OP_CELL 28
 typedef struct {
   int nprog;
   int prog[4 * FLOW_FORM_MAX_PROGRAM];     /* (op, dst, a, b) per instruction */
@@ -1277,6 +1299,13 @@ int flow_assemble_heat(const flow_mesh* mesh, const flow_space* Q,
                        double rho_cp, int supg, double* scratch, double* Avals,
                        double* Msupg_vals, double* tau_out, int* status_dev,
                        void* stream);
+
+/* tau alone, one cell per lane: tau (3*nc) at the three vertices of every
+ * cell -- the P1 cell lattice an `expr` operand of a form reads -- with the
+ * arithmetic of flow_assemble_heat's tau_out; p: the degree of the space tau
+ * stabilises (1|2).  No scratch, no matrix.  status_dev as above. */
+int flow_supg_tau(const flow_mesh* mesh, const flow_space* W, const double* conv,
+                  double kappa, int p, double* tau, int* status_dev, void* stream);
 
 /* SUPG part of the heat load vector with a non-zero source (heat.py:79-86:
  * the `source / rho_cp` term of R2 times tau conv.grad(v)):
