@@ -442,6 +442,8 @@ SYMBOLS = {
                                    _P(_D), _VP],
     'flow_locate_points': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _VP, _VP],
     'flow_form_points': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP],
+    'flow_advect_points': [_P(MeshS), _P(PointGridS), _P(SpaceS), _VP, _VP, _I,
+                           _VP, _VP, _VP, _D, _I, _I, _VP],
     }
 
 _LIB = None

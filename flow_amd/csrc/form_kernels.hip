@@ -522,15 +522,13 @@ __device__ __forceinline__ bool point_in_cell(const double* __restrict__ xy, int
   return l0 >= kPointTol && l1 >= kPointTol && l2 >= kPointTol;
 }
 
-// one point per lane: its bucket's candidates in ascending cell order, the
-// first that holds it
-__global__ __launch_bounds__(kBlock) void locate_points_kernel(
-    int nc, const double* __restrict__ xy, const flow_point_grid G, int n,
-    const double* __restrict__ pts, int* __restrict__ cell,
-    double* __restrict__ bary) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double px = pts[i], py = pts[static_cast<size_t>(n) + i];
+// The cell of the point (px, py) and its barycentric coordinates there: its
+// bucket's candidates in ascending cell order, the first that holds it (the
+// lowest-index rule); -1 and NaN for a point in no cell.
+__device__ __forceinline__ int locate_point(const double* __restrict__ xy, int nc,
+                                            const flow_point_grid& G, double px,
+                                            double py, double& l0, double& l1,
+                                            double& l2) {
   // (clamped as doubles: a NaN or a far point never becomes an int out of
   // range; NaN fails every test below)
   double tx = (px - G.x0) * G.hx_inv, ty = (py - G.y0) * G.hy_inv;
@@ -538,7 +536,7 @@ __global__ __launch_bounds__(kBlock) void locate_points_kernel(
   ty = ty >= 0.0 ? (ty <= G.ny - 1.0 ? ty : G.ny - 1.0) : 0.0;
   const int b = static_cast<int>(floor(ty)) * G.nx + static_cast<int>(floor(tx));
   int found = -1;
-  double l0 = __builtin_nan(""), l1 = l0, l2 = l0;
+  l0 = l1 = l2 = __builtin_nan("");
   for (int k = G.start[b], e = G.start[b + 1]; k < e; ++k) {
     const int c = G.cells[k];
     if (c < 0 || c >= nc) continue;
@@ -551,7 +549,144 @@ __global__ __launch_bounds__(kBlock) void locate_points_kernel(
       break;
     }
   }
-  cell[i] = found;
+  return found;
+}
+
+// one point per lane
+__global__ __launch_bounds__(kBlock) void locate_points_kernel(
+    int nc, const double* __restrict__ xy, const flow_point_grid G, int n,
+    const double* __restrict__ pts, int* __restrict__ cell,
+    double* __restrict__ bary) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double px = pts[i], py = pts[static_cast<size_t>(n) + i];
+  double l0, l1, l2;
+  cell[i] = locate_point(xy, nc, G, px, py, l0, l1, l2);
+  bary[i] = l0;
+  bary[static_cast<size_t>(n) + i] = l1;
+  bary[2 * static_cast<size_t>(n) + i] = l2;
+}
+
+// ---------------------------------------------------------------------------
+// Tracer particles (flow_amd/fem/tracers.py, flow_advect_points): one particle
+// per lane; its position, cell and barycentric coordinates stay in registers
+// over all `steps` substeps of an explicit Runge-Kutta scheme (SCHEME 1: Euler,
+// 2: midpoint, 4: classical RK4).  Every stage point is located with
+// locate_point -- the exact lowest-index scan, so a stage's velocity is a
+// function of the point alone and steps = k equals k calls of steps = 1 bit
+// for bit -- and the P1 / P2 velocity is evaluated there from the cell's dofs.
+// NEXT: the velocity at fraction theta of the call's time steps * dt is
+// (1 - theta) u + theta u_next.  A substep one of whose stage points, or whose
+// end point, lies in no cell loses the particle: it keeps the position it had
+// at the start of that substep, its cell becomes -1 and the lane stops
+// loading.  The end point of an accepted substep is the first stage point of
+// the next one, so a substep of s stages costs s locations.  No atomics, no
+// LDS, no reductions; the only divergence is the bucket scan and the loss.
+// ---------------------------------------------------------------------------
+template <int DEG, bool NEXT>
+__device__ __forceinline__ void tracer_velocity(
+    int nc, int c, double l0, double l1, double l2,
+    const int* __restrict__ cell_dofs, int ndof, const double* __restrict__ u,
+    const double* __restrict__ u_next, double theta, double& vx, double& vy) {
+  constexpr int NL = Elem<DEG>::NL;
+  const double L[3] = {l0, l1, l2};
+  int d[NL];
+#pragma unroll
+  for (int j = 0; j < NL; ++j) d[j] = cell_dofs[j * nc + c];
+  double U[2][NL];
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    U[0][j] = u[d[j]];
+    U[1][j] = u[static_cast<size_t>(ndof) + d[j]];
+  }
+  vx = eval_at<DEG>(U[0], L);
+  vy = eval_at<DEG>(U[1], L);
+  if constexpr (NEXT) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      U[0][j] = u_next[d[j]];
+      U[1][j] = u_next[static_cast<size_t>(ndof) + d[j]];
+    }
+    vx = (1.0 - theta) * vx + theta * eval_at<DEG>(U[0], L);
+    vy = (1.0 - theta) * vy + theta * eval_at<DEG>(U[1], L);
+  }
+}
+
+template <int DEG, int SCHEME, bool NEXT>
+__global__ __launch_bounds__(kBlock) void advect_points_kernel(
+    int nc, const double* __restrict__ xy, const flow_point_grid G,
+    const int* __restrict__ cell_dofs, int ndof, const double* __restrict__ u,
+    const double* __restrict__ u_next, int n, double* __restrict__ pts,
+    int* __restrict__ cell, double* __restrict__ bary, double dt, int steps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int c = cell[i];
+  if (c < 0 || c >= nc) return;          // lost: left alone
+  double px = pts[i], py = pts[static_cast<size_t>(n) + i];
+  double l0 = bary[i], l1 = bary[static_cast<size_t>(n) + i],
+         l2 = bary[2 * static_cast<size_t>(n) + i];
+  const double inv_steps = 1.0 / steps;
+  for (int s = 0; s < steps; ++s) {
+    // (cs, m) the cell and the barycentrics of a stage point, (ex, ey) the
+    // end point
+    double k1x, k1y, ex = px, ey = py;
+    tracer_velocity<DEG, NEXT>(nc, c, l0, l1, l2, cell_dofs, ndof, u, u_next,
+                               s * inv_steps, k1x, k1y);
+    bool ok = true;
+    if constexpr (SCHEME == 1) {
+      ex = px + dt * k1x;
+      ey = py + dt * k1y;
+    } else {
+      const double th = (s + 0.5) * inv_steps;
+      double m0, m1, m2, k2x, k2y;
+      int cs = locate_point(xy, nc, G, px + (0.5 * dt) * k1x, py + (0.5 * dt) * k1y,
+                            m0, m1, m2);
+      ok = cs >= 0;
+      if (ok) {
+        tracer_velocity<DEG, NEXT>(nc, cs, m0, m1, m2, cell_dofs, ndof, u, u_next,
+                                   th, k2x, k2y);
+        if constexpr (SCHEME == 2) {
+          ex = px + dt * k2x;
+          ey = py + dt * k2y;
+        } else {
+          double k3x, k3y, k4x, k4y;
+          cs = locate_point(xy, nc, G, px + (0.5 * dt) * k2x,
+                            py + (0.5 * dt) * k2y, m0, m1, m2);
+          ok = cs >= 0;
+          if (ok) {
+            tracer_velocity<DEG, NEXT>(nc, cs, m0, m1, m2, cell_dofs, ndof, u,
+                                       u_next, th, k3x, k3y);
+            cs = locate_point(xy, nc, G, px + dt * k3x, py + dt * k3y, m0, m1, m2);
+            ok = cs >= 0;
+          }
+          if (ok) {
+            tracer_velocity<DEG, NEXT>(nc, cs, m0, m1, m2, cell_dofs, ndof, u,
+                                       u_next, (s + 1) * inv_steps, k4x, k4y);
+            ex = px + (dt / 6.0) * (k1x + 2.0 * k2x + 2.0 * k3x + k4x);
+            ey = py + (dt / 6.0) * (k1y + 2.0 * k2y + 2.0 * k3y + k4y);
+          }
+        }
+      }
+    }
+    int ce = -1;
+    double e0, e1, e2;
+    if (ok) ce = locate_point(xy, nc, G, ex, ey, e0, e1, e2);
+    if (ce < 0) {
+      // lost: the position of the start of this substep stays
+      c = -1;
+      l0 = l1 = l2 = __builtin_nan("");
+      break;
+    }
+    px = ex;
+    py = ey;
+    c = ce;
+    l0 = e0;
+    l1 = e1;
+    l2 = e2;
+  }
+  pts[i] = px;
+  pts[static_cast<size_t>(n) + i] = py;
+  cell[i] = c;
   bary[i] = l0;
   bary[static_cast<size_t>(n) + i] = l1;
   bary[2 * static_cast<size_t>(n) + i] = l2;
@@ -1155,11 +1290,7 @@ extern "C" int flow_form_facet_functional(const flow_mesh* mesh, const flow_form
   return sum_partials_host(work, nparts, result_host, st);
 }
 
-extern "C" int flow_locate_points(const flow_mesh* mesh, const flow_point_grid* grid,
-                                  int n, const double* xy, int* cell, double* bary,
-                                  void* stream) {
-  int rc = check_form_mesh(mesh);
-  if (rc) return rc;
+static int check_point_grid(const flow_point_grid* grid) {
   FLOW_REQUIRE(grid && grid->nx >= 1 && grid->ny >= 1 &&
                    static_cast<long long>(grid->nx) * grid->ny < (1LL << 31) - 1,
                "point grid size");
@@ -1167,12 +1298,74 @@ extern "C" int flow_locate_points(const flow_mesh* mesh, const flow_point_grid* 
                    std::isfinite(grid->hy_inv) && std::isfinite(grid->x0) && std::isfinite(grid->y0),
                "point grid geometry");
   FLOW_REQUIRE(grid->start && grid->cells, "point grid arrays");
+  return FLOW_OK;
+}
+
+extern "C" int flow_locate_points(const flow_mesh* mesh, const flow_point_grid* grid,
+                                  int n, const double* xy, int* cell, double* bary,
+                                  void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  if ((rc = check_point_grid(grid))) return rc;
   FLOW_REQUIRE(n >= 0, "point count");
   if (n == 0) return FLOW_OK;
   FLOW_REQUIRE(xy && cell && bary, "pointers");
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(locate_points_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock),
                      0, st, mesh->nc, mesh->xy, *grid, n, xy, cell, bary);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+template <int DEG, int SCHEME>
+static void launch_advect(const flow_mesh* mesh, const flow_point_grid* grid,
+                          const flow_space* W, const double* u, const double* u_next,
+                          int n, double* xy, int* cell, double* bary, double dt,
+                          int steps, hipStream_t st) {
+  const dim3 blocks((n + kBlock - 1) / kBlock);
+  if (u_next)
+    hipLaunchKernelGGL((advect_points_kernel<DEG, SCHEME, true>), blocks, dim3(kBlock),
+                       0, st, mesh->nc, mesh->xy, *grid, W->cell_dofs, W->n, u, u_next,
+                       n, xy, cell, bary, dt, steps);
+  else
+    hipLaunchKernelGGL((advect_points_kernel<DEG, SCHEME, false>), blocks, dim3(kBlock),
+                       0, st, mesh->nc, mesh->xy, *grid, W->cell_dofs, W->n, u, u_next,
+                       n, xy, cell, bary, dt, steps);
+}
+
+extern "C" int flow_advect_points(const flow_mesh* mesh, const flow_point_grid* grid,
+                                  const flow_space* W, const double* u,
+                                  const double* u_next, int n, double* xy, int* cell,
+                                  double* bary, double dt, int steps, int scheme,
+                                  void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "tracer particles on strips");
+  if ((rc = check_point_grid(grid))) return rc;
+  FLOW_REQUIRE(W && (W->deg == 1 || W->deg == 2) && W->n >= 1 && W->cell_dofs,
+               "velocity space");
+  FLOW_REQUIRE(u, "velocity");
+  FLOW_REQUIRE(scheme == FLOW_ADVECT_EULER || scheme == FLOW_ADVECT_RK2 ||
+                   scheme == FLOW_ADVECT_RK4,
+               "scheme");
+  FLOW_REQUIRE(steps >= 1, "substeps");
+  FLOW_REQUIRE(std::isfinite(dt), "time step");
+  FLOW_REQUIRE(n >= 0, "point count");
+  if (n == 0) return FLOW_OK;
+  FLOW_REQUIRE(xy && cell && bary, "pointers");
+  hipStream_t st = as_stream(stream);
+#define FLOW_ADVECT(DEG, SCHEME)                                                   \
+  launch_advect<DEG, SCHEME>(mesh, grid, W, u, u_next, n, xy, cell, bary, dt, steps, st)
+  if (W->deg == 1) {
+    if (scheme == FLOW_ADVECT_EULER) FLOW_ADVECT(1, 1);
+    else if (scheme == FLOW_ADVECT_RK2) FLOW_ADVECT(1, 2);
+    else FLOW_ADVECT(1, 4);
+  } else {
+    if (scheme == FLOW_ADVECT_EULER) FLOW_ADVECT(2, 1);
+    else if (scheme == FLOW_ADVECT_RK2) FLOW_ADVECT(2, 2);
+    else FLOW_ADVECT(2, 4);
+  }
+#undef FLOW_ADVECT
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
 }

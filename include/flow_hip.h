@@ -1268,6 +1268,29 @@ int flow_form_points(const flow_mesh* mesh, const flow_form* form, int n,
                      const int* cell, const double* bary, double* out,
                      void* stream);
 
+/* Tracer particles (flow_amd/fem/tracers.py): `steps` substeps of size dt of
+ * an explicit Runge-Kutta scheme for dx/dt = u(x, t), one lane per particle,
+ * one launch.  W: the scalar space of the velocity's components (deg 1 | 2,
+ * cell_dofs read); u, u_next: 2 * W->n doubles, component-major; u_next NULL:
+ * the field is frozen, else the velocity at fraction theta in [0, 1] of the
+ * call's time steps * dt is (1 - theta) u + theta u_next, at each stage's own
+ * time.  xy (2, n), cell (n,), bary (3, n): the state in the layout of
+ * flow_locate_points, updated in place; on entry cell / bary must be what
+ * flow_locate_points gives for xy, and they are again on return.  Every stage
+ * point is located by the lowest-index rule.  A substep one of whose stage
+ * points, or whose end point, lies in no cell loses the particle: xy keeps
+ * the start of that substep, cell = -1, bary = NaN; particles with cell -1
+ * are left alone.  dt may be negative.  Two calls give the same bits; steps =
+ * k equals k calls of steps = 1 on a frozen field.  Not on strips.  n == 0:
+ * nothing launched. */
+#define FLOW_ADVECT_EULER 1
+#define FLOW_ADVECT_RK2 2      /* midpoint */
+#define FLOW_ADVECT_RK4 4      /* classical */
+int flow_advect_points(const flow_mesh* mesh, const flow_point_grid* grid,
+                       const flow_space* W, const double* u, const double* u_next,
+                       int n, double* xy, int* cell, double* bary, double dt,
+                       int steps, int scheme, void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
