@@ -444,6 +444,9 @@ SYMBOLS = {
     'flow_form_points': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP],
     'flow_advect_points': [_P(MeshS), _P(PointGridS), _P(SpaceS), _VP, _VP, _I,
                            _VP, _VP, _VP, _D, _I, _I, _VP],
+    'flow_nearest_cells': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _I, _VP,
+                           _VP, _VP, _VP, _VP],
+    'flow_transfer_apply': [_P(SpaceS), _I, _I, _VP, _VP, _VP, _VP, _VP],
     }
 
 _LIB = None

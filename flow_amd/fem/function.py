@@ -318,6 +318,22 @@ class Function(_FormOperand):
         else:
             raise TypeError('cannot assign %r' % type(other))
 
+    def interpolate(self, other):
+        '''dolfin's w.interpolate(u): a Function of another space or mesh
+        through fem.Transfer (flow_amd/fem/transfer.py), on the GPU; a
+        Constant or an Expression at the dof coordinates.'''
+        if isinstance(other, Function):
+            from .transfer import interpolate_function
+            interpolate_function(other, self._V, out=self)
+        elif isinstance(other, Constant):
+            self.assign(other)
+        elif isinstance(other, Expression):
+            vals = other.eval(self._V.layout.dof_coords.T)
+            assert vals.shape[0] == self._V.dim
+            self.set_array(vals.reshape(-1))
+        else:
+            raise TypeError('cannot interpolate %r' % type(other))
+
     def copy(self, deepcopy=True):
         assert deepcopy
         return Function(self._V, _hip.clone(self.data))

@@ -752,6 +752,12 @@ def project_magnitude(u, mode=0, tol=1.0e-12, initial_guess=None):
 
 
 def interpolate(f, V):
+    '''f in V: a Function of another space or mesh through fem.Transfer
+    (flow_amd/fem/transfer.py), on the GPU; a Constant or an Expression at
+    the dof coordinates.'''
+    if isinstance(f, Function):
+        from .transfer import interpolate_function
+        return interpolate_function(f, V)
     out = Function(V)
     if isinstance(f, Constant):
         out.assign(f)

@@ -1291,6 +1291,37 @@ int flow_advect_points(const flow_mesh* mesh, const flow_point_grid* grid,
                        int n, double* xy, int* cell, double* bary, double dt,
                        int steps, int scheme, void* stream);
 
+/* ---- field transfer (flow_amd/fem/transfer.py): fem.Transfer -----------------
+ * Nearest point of the mesh for points in no cell, one lane per point.  Every
+ * point with cell[i] == -1 on entry (what flow_locate_points gives it) gets
+ * the nearest point of the mesh's boundary: the boundary facet f with the
+ * smallest squared distance to it, ties to the lowest f; cell[i] =
+ * facet_cell[f], bary[., i] the barycentric coordinates of the clamped foot
+ * point on that cell (the coordinate opposite the facet is exactly 0, all lie
+ * in [0, 1]), dist[i] the distance.  Other points keep cell and bary, dist[i]
+ * = 0.  facet_grid: the layout of flow_point_grid; its `cells` hold indices
+ * into facet_cell / facet_local (nfacets entries: the owning cell and the
+ * local facet index of every boundary facet), every facet listed in each
+ * bucket its padded bounding box overlaps.  A lane searches the rings of
+ * buckets around its own (clamped) bucket outward and stops when no point of
+ * a farther ring can be nearer than the best found: the grid narrows the
+ * candidates and never changes the answer of the search over all facets.
+ * xy: (2, n) SoA; bary: (3, n).  Not on strips.  n == 0: nothing launched. */
+int flow_nearest_cells(const flow_mesh* mesh, const flow_point_grid* facet_grid,
+                       int nfacets, const int* facet_cell, const int* facet_local,
+                       int n, const double* xy, int* cell, double* bary, double* dist,
+                       void* stream);
+
+/* out[a*n_to + i] = sum_l phi_l(bary[., i]) u[a*V_from->n + cell_dofs[l][cell[i]]],
+ * a < ncomp (1 | 2): the P1 / P2 field u of V_from (deg, n, cell_dofs and vptr
+ * read; the cell count is vptr[n] / nloc) at barycentric bary[., i] ((3, n_to)
+ * SoA) of its cell cell[i], one lane per target node, all components in one
+ * launch.  NaN where cell[i] is no cell.  No atomics: two calls give the same
+ * bits.  u and out must differ.  Not on strips.  n_to == 0: nothing launched. */
+int flow_transfer_apply(const flow_space* V_from, int ncomp, int n_to,
+                        const int* cell, const double* bary, const double* u,
+                        double* out, void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
