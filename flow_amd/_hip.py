@@ -447,6 +447,7 @@ SYMBOLS = {
     'flow_nearest_cells': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _I, _VP,
                            _VP, _VP, _VP, _VP],
     'flow_transfer_apply': [_P(SpaceS), _I, _I, _VP, _VP, _VP, _VP, _VP],
+    'flow_jump_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP, _VP],
     }
 
 _LIB = None

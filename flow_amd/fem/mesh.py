@@ -27,6 +27,7 @@ class Mesh(object):
       cell_edges   (Nc, 3)  edge id opposite local vertex i
       bfacets      (Nb,)    ids of edges with exactly one incident cell
       bfacet_cell  (Nb,), bfacet_local (Nb,)  the cell and its local facet index
+      cell_neighbors (Nc, 3)  the cell across local facet i, -1 on the boundary
     '''
     def __init__(self, points, cells=None, reorder=True):
         # (ids the vertices / cells had in the file / in the mesh this one was
@@ -57,6 +58,9 @@ class Mesh(object):
         # (cx, cy, radius) of the circle a body-fitted hole was pulled onto
         # (rectangle_with_fitted_hole), else None
         self.hole = None
+        # refine() (flow_amd/fem/adapt.py): the cell of the refined mesh each
+        # cell of this one is a child of, else None
+        self.parent_cell = None
         return
 
     # -- numbering -------------------------------------------------------------
@@ -160,12 +164,22 @@ class Mesh(object):
         order = numpy.argsort(inverse[flat_idx], kind='stable')
         flat_idx = flat_idx[order]
         assert numpy.array_equal(inverse[flat_idx], bfacets)
+        # the cell across each local facet: the two (cell, local facet) slots
+        # of an interior edge name each other's cell
+        assert counts.max() <= 2, 'an edge with more than two cells'
+        slots = numpy.argsort(inverse, kind='stable')
+        first = (numpy.cumsum(counts) - counts)[counts == 2]
+        one, two = slots[first], slots[first + 1]
+        neighbors = numpy.full(3 * len(c), -1, dtype=numpy.int32)
+        neighbors[one] = two // 3
+        neighbors[two] = one // 3
         self._topology = {
             'edges': edges,
             'cell_edges': cell_edges,
             'bfacets': bfacets,
             'bfacet_cell': (flat_idx // 3).astype(numpy.int32),
             'bfacet_local': (flat_idx % 3).astype(numpy.int32),
+            'cell_neighbors': neighbors.reshape(-1, 3),
             }
         return
 
@@ -193,6 +207,10 @@ class Mesh(object):
     @property
     def bfacet_local(self):
         return self._topo('bfacet_local')
+
+    @property
+    def cell_neighbors(self):
+        return self._topo('cell_neighbors')
 
     def num_edges(self):
         return len(self.edges)

@@ -1322,6 +1322,26 @@ int flow_transfer_apply(const flow_space* V_from, int ncomp, int n_to,
                         const int* cell, const double* bary, const double* u,
                         double* out, void* stream);
 
+/* ---- adaptive refinement (flow_amd/fem/adapt.py): fem.JumpIndicator ----------
+ * eta2[c] = sum over the interior edges E of cell c of
+ *     |E| / 24 * int_E sum_{a < ncomp} [grad u_a . n]^2 ds,
+ * [.] the jump across E, for the P1 / P2 field u of V (deg, n and cell_dofs
+ * read; ncomp 1 | 2, component-blocked); boundary edges contribute nothing.
+ * One lane per cell, one launch, no host synchronisation, no atomics: every
+ * interior edge is evaluated from both of its cells and two calls give the
+ * same bits.  Edge quadrature: the mid point for P1, 2-point Gauss for P2
+ * (both exact).  facet_table: 3 * nc ints, entry [i*nc + c] for local facet i
+ * (the edge opposite local vertex i) of cell c: -1 on the boundary, else
+ * (neighbour << 3) | (the neighbour's local facet << 1) | flip, flip = 0 when
+ * the first vertex of the neighbour's facet (facet j: vertices j == 0 ? 1 : 0
+ * and j == 2 ? 1 : 2) is the first vertex of this cell's facet, 1 when it is
+ * the second.  nc < 2^28.  eta2[c] = NaN where an entry names no cell or no
+ * facet, or a dof index lies outside [0, n).  u and eta2 must differ.  Not on
+ * strips. */
+int flow_jump_indicator(const flow_mesh* mesh, const flow_space* V, int ncomp,
+                        const int* facet_table, const double* u, double* eta2,
+                        void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
