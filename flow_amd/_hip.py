@@ -448,6 +448,9 @@ SYMBOLS = {
                            _VP, _VP, _VP, _VP],
     'flow_transfer_apply': [_P(SpaceS), _I, _I, _VP, _VP, _VP, _VP, _VP],
     'flow_jump_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP, _VP],
+    'flow_recover_gradient': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP],
+    'flow_zz_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _I, _VP, _VP,
+                          _VP],
     }
 
 _LIB = None

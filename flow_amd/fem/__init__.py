@@ -32,6 +32,9 @@ from .points import Probes                                      # noqa: F401
 from .tracers import Tracers                                    # noqa: F401
 from .transfer import Transfer                                  # noqa: F401
 from .adapt import JumpIndicator, jump_indicator, mark, refine  # noqa: F401
+from .recovery import (                                         # noqa: F401
+    GradientRecovery, recover_gradient, zz_indicator,
+    )
 from ..message import begin, end, info                          # noqa: F401
 
 DOLFIN_EPS = 3.0e-16

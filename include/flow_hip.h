@@ -1342,6 +1342,34 @@ int flow_jump_indicator(const flow_mesh* mesh, const flow_space* V, int ncomp,
                         const int* facet_table, const double* u, double* eta2,
                         void* stream);
 
+/* ---- recovered gradients (flow_amd/fem/recovery.py): fem.GradientRecovery -----
+ * out[(2*a + d)*n + i] = sum_c |T_c| d(u_a)/dx_d|_c(x_i) / sum_c |T_c|, a < ncomp
+ * (1 | 2), d = 0, 1, n = V->n: the area-weighted mean, over the cells c of the
+ * patch of node i, of the gradient of the P1 / P2 field u of V (component-
+ * blocked) in c AT the node (Zienkiewicz-Zhu).  One lane per node, all
+ * components in one launch.  The patch of node i is its row vptr[i] ..
+ * vptr[i+1] of vsrc; the entry l*nc + c names local node l of cell c (0-2 the
+ * vertices, 3-5 the mid points of the edges opposite them) and the terms are
+ * added in the order of the map: no atomics, two calls give the same bits, and
+ * the planes of one component do not depend on ncomp.  Boundary nodes get the
+ * mean over their one-sided patch, nothing else.  NaN at a node whose row is
+ * empty or leaves the map, or whose patch names a cell outside [0, nc) or a
+ * dof outside [0, n).  V: deg, n, cell_dofs, vptr and vsrc are read.  u and
+ * out (2 * ncomp * n doubles) must differ.  6 * nc < 2^31.  Not on strips. */
+int flow_recover_gradient(const flow_mesh* mesh, const flow_space* V, int ncomp,
+                          const double* u, double* out, void* stream);
+
+/* eta2[c] = sum_{a < ncomp} int_T |G_a - grad u_a|^2 dx, G_a the P_deg vector
+ * field with the nodal values G[(2*a + d)*n + i] (the layout
+ * flow_recover_gradient writes): the Zienkiewicz-Zhu indicator.  One lane per
+ * cell, one launch, no atomics.  rule: nq <= FLOW_FORM_MAX_POINTS rows (xi,
+ * eta, w) in device memory, weights summing to 1/2 (flow_form.rule's
+ * convention); the integrand has degree 2 * deg.  NaN where a dof index lies
+ * outside [0, n).  eta2 must differ from u and G.  Not on strips. */
+int flow_zz_indicator(const flow_mesh* mesh, const flow_space* V, int ncomp,
+                      const double* u, const double* G, int nq, const double* rule,
+                      double* eta2, void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
