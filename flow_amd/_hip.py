@@ -18,6 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libflow_hip.so')
 
 REDUCE_WORK = 4096
+MULTI_DOT_BLOCKS = 1024      # FLOW_MULTI_DOT_BLOCKS: work of flow_multi_dot per column
 GMRES_MAX_RESTART = 30
 GMRES_PARTIALS = (GMRES_MAX_RESTART + 2) * 1024
 GMRES_STATE = 1280
@@ -451,6 +452,9 @@ SYMBOLS = {
     'flow_recover_gradient': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP],
     'flow_zz_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _I, _VP, _VP,
                           _VP],
+    'flow_multi_dot': [_I, _I, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP],
+    'flow_combine': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, _VP, _VP,
+                     ctypes.c_size_t, _VP],
     }
 
 _LIB = None

@@ -1370,6 +1370,34 @@ int flow_zz_indicator(const flow_mesh* mesh, const flow_space* V, int ncomp,
                       const double* u, const double* G, int nq, const double* rule,
                       double* eta2, void* stream);
 
+/* ---- reductions of stored fields (flow_amd/fem/snapshots.py): fem.Snapshots ---
+ * X is a column-major store of fields: column j starts at X + j*ldx; ldx >= n
+ * and even, X (and y) 16-byte aligned, so every column is.
+ *
+ * out[j] = sum_i X[j*ldx + i] * y[i], j < m (any m >= 1; m == 0 or n == 0:
+ * nothing is launched).  out (m doubles) is DEVICE memory: no host
+ * synchronisation.  The columns are handled eight per lane around one load of
+ * y; the grid is a function of n alone (at most FLOW_MULTI_DOT_BLOCKS blocks),
+ * each lane adds its entries in ascending i, the block sum has a fixed shape
+ * and a finishing launch adds the block sums in ascending block order: out[j]
+ * depends on n, column j and y alone -- the same bits whatever m is and
+ * wherever the column sits among the others -- and two calls give the same
+ * bits.  No atomics.  work: m * FLOW_MULTI_DOT_BLOCKS doubles.  The caller
+ * refuses strips (a rank holds its own rows only): no operand here says so. */
+#define FLOW_MULTI_DOT_BLOCKS 1024
+int flow_multi_dot(int n, int m, const double* X, size_t ldx, const double* y,
+                   double* work, double* out, void* stream);
+
+/* out[k*ldo + i] = (base ? base[i] : 0) + sum_{j < m} C[k*m + j] * X[j*ldx + i],
+ * k < r, i < n, the terms added in ascending j (fma): deterministic by
+ * construction.  C: r*m doubles in DEVICE memory; base: n doubles or NULL.
+ * m >= 1; ldx >= n, ldo >= n (no alignment asked).  One lane per row, eight
+ * outputs per lane around one load of X[j][i].  out must not overlap X, base
+ * or C (refused).  r == 0 or n == 0: nothing is launched. */
+int flow_combine(int n, int m, const double* X, size_t ldx, int r,
+                 const double* C, const double* base, double* out, size_t ldo,
+                 void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
