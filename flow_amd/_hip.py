@@ -452,6 +452,7 @@ SYMBOLS = {
     'flow_recover_gradient': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP],
     'flow_zz_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _I, _VP, _VP,
                           _VP],
+    'flow_distance_sweeps': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP, _VP],
     'flow_multi_dot': [_I, _I, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP],
     'flow_combine': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, _VP, _VP,
                      ctypes.c_size_t, _VP],

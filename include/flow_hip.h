@@ -1370,6 +1370,29 @@ int flow_zz_indicator(const flow_mesh* mesh, const flow_space* V, int ncomp,
                       const double* u, const double* G, int nq, const double* rule,
                       double* eta2, void* stream);
 
+/* ---- wall distance (flow_amd/fem/distance.py): fem.Distance -------------------
+ * nsweeps >= 1 Jacobi sweeps of the monotone Eikonal solver on the P1
+ * triangulation of the dofs of V (P1: the cells; P2: every cell cut into its
+ * three corner triangles and the middle one, mid points of the straight edges):
+ *   new[i] = min(old[i], min over the triangles at i of the Hopf-Lax update of
+ *            i from the triangle's two other values),
+ * sweep k reading buf_a and writing buf_b for even k and the other way round
+ * for odd k (k = 0 .. nsweeps - 1): the result is in buf_b when nsweeps is odd,
+ * in buf_a when it is even.  buf_a holds the start: 0 at the sources, +inf
+ * elsewhere (or any earlier iterate); an infinite value is never used as an
+ * input, and a dof no path of cells connects to a finite value keeps +inf.  One
+ * lane per dof walks its row vptr[i] .. vptr[i+1] of vsrc (entry l*nc + c:
+ * local node l of cell c); no atomics: two calls give the same bits.  *flag
+ * (device memory, zeroed by the caller) is set to 1 by every lane whose value
+ * the LAST of the nsweeps sweeps lowered -- a sweep that lowers nothing has
+ * reached the fixed point whatever the sweeps before it did.  Nothing is
+ * synchronised.  NaN at a dof whose row leaves the map, or whose patch names a
+ * cell outside [0, nc) or a dof outside [0, n).  V: deg, n, cell_dofs, vptr and
+ * vsrc are read.  buf_a and buf_b (n doubles each) must differ.  6 * nc < 2^31.
+ * Not on strips. */
+int flow_distance_sweeps(const flow_mesh* mesh, const flow_space* V, int nsweeps,
+                         double* buf_a, double* buf_b, int* flag, void* stream);
+
 /* ---- reductions of stored fields (flow_amd/fem/snapshots.py): fem.Snapshots ---
  * X is a column-major store of fields: column j starts at X + j*ldx; ldx >= n
  * and even, X (and y) 16-byte aligned, so every column is.
