@@ -249,6 +249,20 @@ class PointGridS(ctypes.Structure):
         ]
 
 
+STATS_MAX_FREQ = 8           # FLOW_STATS_MAX_FREQ
+STATS_COVARIANCE = 1         # FLOW_STATS_COVARIANCE
+STATS_EXTREMA = 2            # FLOW_STATS_EXTREMA
+
+
+class StatsFreq(ctypes.Structure):
+    '''flow_stats_freq (include/flow_hip.h): w cos phi_k and -w sin phi_k'''
+    _fields_ = [
+        ('n', ctypes.c_int),
+        ('c', ctypes.c_double * STATS_MAX_FREQ),
+        ('s', ctypes.c_double * STATS_MAX_FREQ),
+        ]
+
+
 class NsParams(ctypes.Structure):
     _fields_ = [
         ('dt', ctypes.c_double), ('rho', ctypes.c_double),
@@ -456,6 +470,10 @@ SYMBOLS = {
     'flow_multi_dot': [_I, _I, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP],
     'flow_combine': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, _VP, _VP,
                      ctypes.c_size_t, _VP],
+    'flow_stats_update': [_I, _I, _I, _P(StatsFreq), _D, _D, _D, _VP, _VP,
+                          ctypes.c_size_t, _VP],
+    'flow_stats_merge': [_I, _I, _I, _I, _D, _D, _VP, _VP, ctypes.c_size_t,
+                         _VP],
     }
 
 _LIB = None

@@ -36,6 +36,7 @@ from .recovery import (                                         # noqa: F401
     GradientRecovery, recover_gradient, zz_indicator,
     )
 from .snapshots import Snapshots                                # noqa: F401
+from .statistics import Statistics                              # noqa: F401
 from .distance import Distance, wall_distance                   # noqa: F401
 from ..message import begin, end, info                          # noqa: F401
 

@@ -1421,6 +1421,49 @@ int flow_combine(int n, int m, const double* X, size_t ldx, int r,
                  const double* C, const double* base, double* out, size_t ldo,
                  void* stream);
 
+/* ---- running time statistics of a field (flow_amd/fem/statistics.py):
+ * fem.Statistics ---------------------------------------------------------------
+ * A store of planes of ld doubles each (ld >= n and even, the store 16-byte
+ * aligned), in this order: mean[dim]; M2[dim == 1 ? 1 : 3] (00; or 00, 01, 11)
+ * where flags & FLOW_STATS_COVARIANCE; per frequency k A_k[dim], B_k[dim];
+ * min[dim], max[dim], tmin[dim], tmax[dim] where flags & FLOW_STATS_EXTREMA.
+ * Entries at and past n of a plane (the padding) are never read or written.
+ *
+ * One sample x (dim * n doubles, component a at x + a*n; 8-byte aligned is
+ * enough) of weight w at time t, with the host scalars r = w / (W + w) and
+ * s = w * W / (W + w), W the weight so far, and freq->c[k] = w cos phi_k,
+ * freq->s[k] = -w sin phi_k, phi_k = 2 pi fmod(f_k t, 1) (freq: HOST memory,
+ * passed on by value; NULL: no frequencies):
+ *   delta_a = x_a - mean_a;  mean_a = fma(r, delta_a, mean_a)
+ *   M2_ab = fma(s * delta_a, delta_b, M2_ab)
+ *   A_k,a = fma(c[k], x_a, A_k,a);  B_k,a = fma(s[k], x_a, B_k,a)
+ *   if x_a < min_a: min_a = x_a, tmin_a = t   (strict; likewise max)
+ * ONE launch, one lane per pair of dofs, no LDS, no atomics, no reduction: two
+ * identical sequences of calls give the same bits.  Nothing is uploaded or
+ * synchronised.  n == 0: nothing is launched.  x must not overlap the planes
+ * (refused).  8 n dim + 16 n * planes bytes. */
+#define FLOW_STATS_MAX_FREQ 8
+#define FLOW_STATS_COVARIANCE 1
+#define FLOW_STATS_EXTREMA 2
+typedef struct flow_stats_freq {
+  int n;                              /* frequencies in use, 0..8 */
+  double c[FLOW_STATS_MAX_FREQ];      /*  w cos phi_k */
+  double s[FLOW_STATS_MAX_FREQ];      /* -w sin phi_k */
+} flow_stats_freq;
+int flow_stats_update(int n, int dim, int flags, const flow_stats_freq* freq,
+                      double r, double s, double t, const double* x,
+                      double* planes, size_t ld, void* stream);
+
+/* Chan's combination of two such stores (same n, dim, flags, nfreq, ld) into
+ * `planes`, with the host scalars q = Wb / W and g = Wa Wb / W, W = Wa + Wb:
+ *   d_a = mean_b - mean_a;  mean_a = fma(q, d_a, mean_a)
+ *   M2_ab = fma(g * d_a, d_b, M2a_ab + M2b_ab);  A, B add
+ *   if min_b < min_a: min_a = min_b, tmin_a = tmin_b  (ties keep `planes`')
+ * The same lanes as flow_stats_update; the stores must not overlap. */
+int flow_stats_merge(int n, int dim, int flags, int nfreq, double q, double g,
+                     double* planes, const double* other, size_t ld,
+                     void* stream);
+
 /* ---- K7: Dirichlet conditions (bcs= in solve, pressure_correction.py:226,
  * 327,452; bc.apply(A, b), heat.py:113-114).  dofs sorted, in operator
  * numbering (a*n + i). ------------------------------------------------------ */
