@@ -462,6 +462,8 @@ SYMBOLS = {
     'flow_nearest_cells': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _I, _VP,
                            _VP, _VP, _VP, _VP],
     'flow_transfer_apply': [_P(SpaceS), _I, _I, _VP, _VP, _VP, _VP, _VP],
+    'flow_project_load': [_P(MeshS), _P(SpaceS), _P(MeshS), _P(SpaceS), _I, _VP,
+                          _VP, _I, _VP, _I, _VP, _VP, _VP, _VP],
     'flow_jump_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP, _VP],
     'flow_recover_gradient': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP],
     'flow_zz_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _I, _VP, _VP,

@@ -1322,6 +1322,38 @@ int flow_transfer_apply(const flow_space* V_from, int ncomp, int n_to,
                         const int* cell, const double* bary, const double* u,
                         double* out, void* stream);
 
+/* ---- conservative transfer (flow_amd/fem/projection.py): fem.Projection -------
+ * b[a*V_to->n + i] = int phi_i^to u_a^from dx, a < ncomp (1 | 2): the load
+ * vector of the L2 (Galerkin) projection of the P1 / P2 field u of V_from on
+ * mesh_from into the P1 / P2 space V_to on mesh_to, integrated exactly over the
+ * intersections of the cells of the two meshes.  pptr (mesh_to->nc + 1) / psrc
+ * (npairs): per target cell the candidate source cells, ascending -- every
+ * source cell that meets the target cell in positive area must be listed,
+ * others may be (cells that do not overlap contribute nothing).  One target
+ * cell per lane: each listed source triangle is clipped to the target triangle
+ * (Sutherland-Hodgman, closed inside test), the polygon fanned from its first
+ * vertex and the 7-point degree-5 rule applied to each sub-triangle (exact: the
+ * integrand has degree <= 4), all in the order of the list; then
+ * scratch[(a*nloc_to + i)*nc_to + c] holds the cell's sums and the gather over
+ * V_to->vptr / vsrc adds them into b.  No atomics: two calls give the same
+ * bits.  coverage[c] (nc_to doubles, always written) = area of the target cell
+ * covered by listed source cells / its area.  scale = 1: the sums of cell c are
+ * divided by coverage[c] (the source's mean over the covered part stands for
+ * the rest; NaN where coverage is 0), scale = 0: left as they are.
+ * u == NULL: the geometry alone -- coverage is filled, V_from, V_to, scratch
+ * and b are not read (one launch).
+ * NaN in coverage[c] and in the sums of cell c where its row leaves the pair
+ * list, names a source cell outside [0, mesh_from->nc) or a dof outside [0,
+ * V_from->n); nothing outside the arrays is read.  scratch: ncomp * nloc_to *
+ * nc_to doubles.  No alignment beyond that of double is relied on.  u, b,
+ * scratch and coverage must differ.  6 * nc < 2^31 on both meshes.  Not on
+ * strips. */
+int flow_project_load(const flow_mesh* mesh_from, const flow_space* V_from,
+                      const flow_mesh* mesh_to, const flow_space* V_to, int ncomp,
+                      const int* pptr, const int* psrc, int npairs, const double* u,
+                      int scale, double* scratch, double* coverage, double* b,
+                      void* stream);
+
 /* ---- adaptive refinement (flow_amd/fem/adapt.py): fem.JumpIndicator ----------
  * eta2[c] = sum over the interior edges E of cell c of
  *     |E| / 24 * int_E sum_{a < ncomp} [grad u_a . n]^2 ds,
