@@ -213,6 +213,7 @@ FORM_MAX_EXPRESSIONS = 4
 FORM_MAX_POINTS = 256
 FORM_SLOTS = 9
 FORM_NEWTON_SLOTS = 12
+PROFILE_CURVES_PER_LAUNCH = 32   # FLOW_PROFILE_CURVES_PER_LAUNCH
 
 
 class FormS(ctypes.Structure):
@@ -455,6 +456,9 @@ SYMBOLS = {
                          _VP],
     'flow_form_facet_functional': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP,
                                    _P(_D), _VP],
+    'flow_form_facet_values': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP,
+                               _VP, _VP, _VP],
+    'flow_profile_cumsum': [_I, _P(_I), _I, _I, _VP, _VP, _VP],
     'flow_locate_points': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _VP, _VP],
     'flow_form_points': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP],
     'flow_advect_points': [_P(MeshS), _P(PointGridS), _P(SpaceS), _VP, _VP, _I,

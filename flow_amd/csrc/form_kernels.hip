@@ -503,6 +503,103 @@ __global__ __launch_bounds__(kBlock) void form_facet_kernel(
   scratch[k] = form_facet<NF, EXT>(F, nc, xy, c, lf);
 }
 
+// Wall distributions (flow_amd/fem/profile.py, flow_form_facet_values): one
+// lane per (facet, sample) -- a boundary holds O(sqrt(N)) facets, the samples
+// are the parallelism.  Lane (k, j) runs the program at row lf*m + j of the
+// rule and writes output o to values[o*npoints + dest[k]*m + j'], j' = m-1-j
+// where the curve runs against the facet's own direction (flip[k]): the
+// samples land in arclength order.  Lane j == 0 of a facet goes on over the
+// other rows and adds up the facet's integral with the arithmetic and the
+// order of form_facet, to integrals[o*nfacets + dest[k]].  A facet outside
+// the mesh gives NaN, a destination outside the list is not written.
+template <int NF, bool EXT>
+__global__ __launch_bounds__(kBlock) void form_facet_values_kernel(
+    int nc, int nfacets, const int* __restrict__ fcell,
+    const int* __restrict__ flocal, const int* __restrict__ fdest,
+    const int* __restrict__ fflip, const double* __restrict__ xy,
+    const flow_form F, double* __restrict__ values,
+    double* __restrict__ integrals) {
+  const int m = F.nq;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nfacets * m) return;
+  const int k = i / m, j = i - k * m;
+  const int d = fdest[k];
+  if (d < 0 || d >= nfacets) return;
+  const bool whole = integrals != nullptr && j == 0;
+  const size_t np = static_cast<size_t>(nfacets) * m;
+  double* const val = values + static_cast<size_t>(d) * m + (fflip[k] ? m - 1 - j : j);
+  const int c = fcell[k], lf = flocal[k];
+  if (c < 0 || c >= nc || lf < 0 || lf > 2) {
+    const double bad = __builtin_nan("");
+    val[0] = bad;
+    if (F.nout == 2) val[np] = bad;
+    if (whole) {
+      integrals[d] = bad;
+      if (F.nout == 2) integrals[static_cast<size_t>(nfacets) + d] = bad;
+    }
+    return;
+  }
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
+  const double gx = lf == 0 ? g.gl[0][0] : (lf == 1 ? g.gl[1][0] : g.gl[2][0]);
+  const double gy = lf == 0 ? g.gl[0][1] : (lf == 1 ? g.gl[1][1] : g.gl[2][1]);
+  const double gn = sqrt(gx * gx + gy * gy);
+  const double n0 = -gx / gn, n1 = -gy / gn;
+  const double len = g.adet * gn;
+  double total0 = 0.0, total1 = 0.0;
+  // (one loop for the sample and the integral: the interpreter is inlined once)
+  for (int q = j, qe = whole ? m : j + 1; q < qe; ++q) {
+    const int row = lf * m + q;
+    const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    double out0 = 0.0, out1 = 0.0;
+    form_point<NF, true, EXT>(F, U, X, Y, g, L, row, nc, c, n0, n1, out0, out1);
+    if (q == j) {
+      val[0] = out0;
+      if (F.nout == 2) val[np] = out1;
+    }
+    total0 += F.rule[3 * row + 2] * len * out0;
+    total1 += F.rule[3 * row + 2] * len * out1;
+  }
+  if (whole) {
+    integrals[d] = total0;
+    if (F.nout == 2) integrals[static_cast<size_t>(nfacets) + d] = total1;
+  }
+}
+
+// flow_profile_cumsum: one lane per (curve, row), the curve's facets added
+// strictly left to right.  Boundaries hold thousands of facets, not millions,
+// and the fixed order is the point: numpy.cumsum of the integrals gives the
+// same bits.  The offsets travel with the launch.
+struct ProfileCurves {
+  int off[FLOW_PROFILE_CURVES_PER_LAUNCH + 1];
+};
+
+__global__ __launch_bounds__(kBlock) void profile_cumsum_kernel(
+    int ncurves, const ProfileCurves C, int nrows, int nfacets,
+    const double* __restrict__ integrals, double* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ncurves * nrows) return;
+  const int c = i / nrows, r = i - c * nrows;
+  // (selects over the argument array: the offsets stay in scalar registers)
+  int b = 0, e = 0;
+#pragma unroll
+  for (int k = 0; k < FLOW_PROFILE_CURVES_PER_LAUNCH; ++k) {
+    b = k == c ? C.off[k] : b;
+    e = k == c ? C.off[k + 1] : e;
+  }
+  const double* src = integrals + static_cast<size_t>(r) * nfacets;
+  double* dst = out + static_cast<size_t>(r) * nfacets;
+  double s = 0.0;
+  for (int k = b; k < e; ++k) {
+    s += src[k];
+    dst[k] = s;
+  }
+}
+
 // The point of the mesh's cell c at barycentric (l0, l1, l2): the test of
 // flow_locate_points.  Contraction stays off, so that the host's numpy
 // evaluation of the same expressions (flow_amd/fem/points.py) gives the same
@@ -1096,6 +1193,38 @@ static int launch_facets(const flow_mesh* mesh, const flow_form* F, int nfacets,
   return FLOW_OK;
 }
 
+static int launch_facet_values(const flow_mesh* mesh, const flow_form* F, int nfacets,
+                               const int* fcell, const int* flocal, const int* fdest,
+                               const int* fflip, double* values, double* integrals,
+                               hipStream_t st) {
+  const dim3 grid((nfacets * F->nq + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
+  switch (F->nfield) {
+#define FLOW_FORM_VALUES_CASE(NF)                                                \
+    case NF:                                                                     \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_facet_values_kernel<NF, true>), grid,           \
+                           dim3(kBlock), 0, st, mesh->nc, nfacets, fcell, flocal,\
+                           fdest, fflip, mesh->xy, *F, values, integrals);       \
+      else                                                                       \
+        hipLaunchKernelGGL((form_facet_values_kernel<NF, false>), grid,          \
+                           dim3(kBlock), 0, st, mesh->nc, nfacets, fcell, flocal,\
+                           fdest, fflip, mesh->xy, *F, values, integrals);       \
+      break;
+    FLOW_FORM_VALUES_CASE(0)
+    FLOW_FORM_VALUES_CASE(1)
+    FLOW_FORM_VALUES_CASE(2)
+    FLOW_FORM_VALUES_CASE(3)
+    FLOW_FORM_VALUES_CASE(4)
+    FLOW_FORM_VALUES_CASE(5)
+    default:
+    FLOW_FORM_VALUES_CASE(6)
+#undef FLOW_FORM_VALUES_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
 static int launch_points(const flow_mesh* mesh, const flow_form* F, int n,
                          const int* cell, const double* bary, double* out,
                          hipStream_t st) {
@@ -1288,6 +1417,52 @@ extern "C" int flow_form_facet_functional(const flow_mesh* mesh, const flow_form
                      scratch, work);
   FLOW_CHECK_LAUNCH();
   return sum_partials_host(work, nparts, result_host, st);
+}
+
+extern "C" int flow_form_facet_values(const flow_mesh* mesh, const flow_form* form,
+                                      int nfacets, const int* facet_cell,
+                                      const int* facet_local, const int* facet_dest,
+                                      const int* facet_flip, double* values,
+                                      double* integrals, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "wall distributions on strips");
+  if ((rc = check_form(form, 3, true))) return rc;
+  FLOW_REQUIRE(nfacets >= 0, "facet count");
+  if (nfacets == 0) return FLOW_OK;
+  FLOW_REQUIRE(static_cast<long long>(nfacets) * form->nq < (1LL << 31) - kBlock,
+               "facet count (samples)");
+  FLOW_REQUIRE(facet_cell && facet_local && facet_dest && facet_flip, "facet lists");
+  FLOW_REQUIRE(values, "values pointer");
+  return launch_facet_values(mesh, form, nfacets, facet_cell, facet_local, facet_dest,
+                             facet_flip, values, integrals, as_stream(stream));
+}
+
+extern "C" int flow_profile_cumsum(int ncurves, const int* curve_facets, int nrows,
+                                   int nfacets, const double* integrals, double* out,
+                                   void* stream) {
+  FLOW_REQUIRE(ncurves >= 0 && nrows >= 0 && nfacets >= 0, "counts");
+  FLOW_REQUIRE(ncurves == 0 || nrows <= ((1 << 30) / FLOW_PROFILE_CURVES_PER_LAUNCH),
+               "row count");
+  FLOW_REQUIRE(curve_facets, "curve offsets");
+  FLOW_REQUIRE(curve_facets[0] == 0 && curve_facets[ncurves] == nfacets,
+               "curve offsets (first 0, last nfacets)");
+  for (int c = 0; c < ncurves; ++c)
+    FLOW_REQUIRE(curve_facets[c] <= curve_facets[c + 1], "curve offsets (sorted)");
+  if (ncurves == 0 || nrows == 0 || nfacets == 0) return FLOW_OK;
+  FLOW_REQUIRE(integrals && out, "pointers");
+  hipStream_t st = as_stream(stream);
+  for (int c0 = 0; c0 < ncurves; c0 += FLOW_PROFILE_CURVES_PER_LAUNCH) {
+    const int n = ncurves - c0 < FLOW_PROFILE_CURVES_PER_LAUNCH
+                      ? ncurves - c0 : FLOW_PROFILE_CURVES_PER_LAUNCH;
+    ProfileCurves C;
+    for (int k = 0; k <= FLOW_PROFILE_CURVES_PER_LAUNCH; ++k)
+      C.off[k] = curve_facets[c0 + (k < n ? k : n)];
+    hipLaunchKernelGGL(profile_cumsum_kernel, dim3((n * nrows + kBlock - 1) / kBlock),
+                       dim3(kBlock), 0, st, n, C, nrows, nfacets, integrals, out);
+    FLOW_CHECK_LAUNCH();
+  }
+  return FLOW_OK;
 }
 
 static int check_point_grid(const flow_point_grid* grid) {

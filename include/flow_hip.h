@@ -1196,6 +1196,51 @@ int flow_form_facet_functional(const flow_mesh* mesh, const flow_form* form,
                                const int* facet_local, double* scratch,
                                double* work, double* result_host, void* stream);
 
+/* Wall distributions (flow_amd/fem/profile.py, BoundaryProfile): the program
+ * at every sample of every listed exterior facet, not reduced.  The rule is
+ * that of flow_form_facet_functional (3*nq rows, m = nq samples per facet);
+ * one lane per (facet, sample), nfacets*m lanes: a boundary holds O(sqrt(N))
+ * facets, so the samples are the parallelism.  Lane (k, j) computes the
+ * facet's normal and length as the facet functional does, runs the program at
+ * row facet_local[k]*m + j and writes output o < nout (1 | 2) to
+ *     values[o*npoints + facet_dest[k]*m + j'],   npoints = nfacets*m,
+ * j' = m-1-j where facet_flip[k] != 0, else j: with facet_dest the facet's
+ * position along its boundary curve and facet_flip set where the curve runs
+ * against the facet's own direction (from vertex facet_v0 to facet_v1), the
+ * samples arrive in arclength order and no permutation pass follows.
+ * integrals != NULL: lane j == 0 also writes the facet's integral of output o
+ * to integrals[o*nfacets + facet_dest[k]], summed over the m rows with the
+ * arithmetic and the order of the facet functional's per-facet value (the same
+ * bits).  facet_cell, facet_local, facet_dest, facet_flip: device int32 arrays
+ * of nfacets entries; facet_dest must be a permutation of 0..nfacets-1, which
+ * the caller checks (a destination outside 0..nfacets-1 is skipped, a
+ * repeated one leaves entries unwritten).  A facet whose cell or local index
+ * is out of range gives NaN in its samples and its integral.  values:
+ * nout*npoints doubles; integrals: nout*nfacets doubles or NULL.  nfacets ==
+ * 0: nothing launched.  No atomics: two calls give the same bits.  Not on
+ * strips. */
+int flow_form_facet_values(const flow_mesh* mesh, const flow_form* form,
+                           int nfacets, const int* facet_cell,
+                           const int* facet_local, const int* facet_dest,
+                           const int* facet_flip, double* values,
+                           double* integrals, void* stream);
+
+/* Running integrals along boundary curves: for every curve c < ncurves and
+ * row r < nrows, out[r*nfacets + k] = integrals[r*nfacets + b] + ... +
+ * integrals[r*nfacets + k] for b = curve_facets[c] <= k < curve_facets[c+1],
+ * restarting at every curve.  One lane per (curve, row) adds strictly left to
+ * right: boundaries hold thousands of facets, not millions, and the fixed
+ * order is the point of this entry -- a sequential sum on the host
+ * (numpy.cumsum) gives the same bits, which no scan tree does.  curve_facets:
+ * HOST array of ncurves + 1 offsets, 0 first, nfacets last, non-decreasing
+ * (checked here; they travel with the launches by value,
+ * FLOW_PROFILE_CURVES_PER_LAUNCH curves each).  integrals, out: device,
+ * nrows*nfacets doubles, two different arrays. */
+#define FLOW_PROFILE_CURVES_PER_LAUNCH 32
+int flow_profile_cumsum(int ncurves, const int* curve_facets, int nrows,
+                        int nfacets, const double* integrals, double* out,
+                        void* stream);
+
 /* Load vector b_(o,i) = int out_o phi_i for o < form->nout (the right-hand
  * side of project(f, V)); V: test space (deg 1|2).  scratch: nout*nloc*nc. */
 int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
