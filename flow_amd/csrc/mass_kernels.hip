@@ -12,8 +12,8 @@
 // is fixed and its contraction is a bound, not an estimate.
 //
 // All kernels are HBM-bound CSR-stream products (csr_stream.h; the fp16 tile
-// is the one of pmg_kernels.hip with ONE half per nonzero instead of a half2:
-// the mass matrix is the same for both velocity components).
+// is the one of csr_stream16.h with ONE half per nonzero: the mass matrix is
+// the same for both velocity components).
 #include "common.h"
 #include "csr_stream.h"
 #include "csr_stream16.h"
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void mass_cheb_kernel(
     const double* __restrict__ xbase, int xs,
     double* __restrict__ zz_part, double* __restrict__ xx_part,
     const double* __restrict__ stop, int own_lo = 0, int own_hi = 0x7fffffff) {
-  __shared__ V prod[kMassTile];
+  __shared__ V prod[kTile16];
   if (stopped(stop)) return;
   // (PACKED: `vals` is the packed stream, `cols` the tiles' base columns)
   int r, r1;
@@ -199,12 +199,13 @@ __global__ __launch_bounds__(kBlock) void mass_cheb_kernel(
     if (MODE == 2) load_xrow(xr, x, xbase, xs, row, V());
   };
   V s = PACKED
-            ? mass_tile_row_sum_packed<V>(rowptr,
-                                          static_cast<const unsigned*>(vals), cols,
-                                          rowblocks, g, prod, r, r1, early)
-            : mass_tile_row_sum<V>(rowptr, cols,
-                                   static_cast<const __half*>(vals), rowblocks, g,
-                                   prod, r, r1, early);
+            ? fp16_tile_row_sum(
+                  rowptr, PackedStream{static_cast<const unsigned*>(vals), cols},
+                  rowblocks, g, prod, r, r1, early)
+            : fp16_tile_row_sum(
+                  rowptr,
+                  Cols32Stream<__half>{static_cast<const __half*>(vals), cols},
+                  rowblocks, g, prod, r, r1, early);
   double2 dots = make_double2(0.0, 0.0);
   if (r < r1) {
     apply_mask(mask, n, r, own, s);
@@ -330,20 +331,9 @@ __global__ __launch_bounds__(kBlock) void mass_pack16_kernel(
     const int* __restrict__ cols, const int* __restrict__ diag_idx,
     const double* __restrict__ vals, int* __restrict__ cbase,
     unsigned* __restrict__ packed, int* __restrict__ overflow) {
-  __shared__ int wmin[kBlock / 64];
   const int tile = blockIdx.x;
   const int r0 = rowblocks[tile], r1 = rowblocks[tile + 1];
-  const int k0 = rowptr[r0], k1 = rowptr[r1];
-  int m = 0x7fffffff;
-  for (int k = k0 + threadIdx.x; k < k1; k += kBlock) m = min(m, cols[k]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = min(m, __shfl_down(m, off, 64));
-  if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = m;
-  __syncthreads();
-  int base = wmin[0];
-#pragma unroll
-  for (int w = 1; w < kBlock / 64; ++w) base = min(base, wmin[w]);
-  if (k0 >= k1) base = 0;
+  const int base = tile_lowest_col(cols, rowptr[r0], rowptr[r1]);
   if (threadIdx.x == 0) cbase[tile] = base;
   const int r = r0 + threadIdx.x;
   if (r < r1) {
@@ -362,21 +352,6 @@ __global__ __launch_bounds__(kBlock) void mass_pack16_kernel(
 // host side
 // ---------------------------------------------------------------------------
 namespace {
-
-struct Cheb {
-  double theta, delta, sigma, rho;
-  Cheb(double lo, double hi)
-      : theta(0.5 * (hi + lo)), delta(0.5 * (hi - lo)), sigma(theta / delta),
-        rho(1.0 / sigma) {}
-  float first() const { return static_cast<float>(1.0 / theta); }
-  // coefficients of the next step: d' = c1 d + c2 rho'
-  void next(float* c1, float* c2) {
-    const double rn = 1.0 / (2.0 * sigma - rho);
-    *c1 = static_cast<float>(rn * rho);
-    *c2 = static_cast<float>(2.0 * rn / delta);
-    rho = rn;
-  }
-};
 
 // tiles of the products of one correction: by default every product runs over
 // M->rowblocks16; K15: product j over its own, shrinking row range

@@ -38,114 +38,7 @@
 
 namespace flow {
 
-constexpr int kPmgQuads = 2;                      // quads of nonzeros per lane
-constexpr int kPmgTile = kBlock * 4 * kPmgQuads;  // LDS products per workgroup
-static_assert(FLOW_PMG_NNZ_PER_BLOCK == kPmgTile - 4,
-              "tile minus alignment slack (base aligned down to a multiple of 4)");
-static_assert(kPmgTile == kMassTile, "one tile shape for both fp16 streams");
-
 __device__ __forceinline__ float2 f2(float a, float b) { return make_float2(a, b); }
-
-struct Half2x4 {           // four nonzeros: (block 0, block 1) each, 16 bytes
-  __half2 v[4];
-};
-static_assert(sizeof(Half2x4) == 16, "packed quad");
-
-// One tile of the packed stream -- rows [r0, r1) of workgroup blockIdx.x (at
-// most kBlock rows, kPmgTile - 4 nonzeros): every lane loads kPmgQuads 16-byte
-// quads of values and of column indices (the tile base is aligned down to a
-// multiple of four nonzeros), all of them and all gathers behind them in flight
-// before the first use -- the kernel is bound by the chain of dependent loads
-// of a tile (row blocks -> row pointers -> indices -> gathers), so a tile
-// carries as many bytes as the LDS products of a workgroup allow (16 KB: still
-// eight workgroups per CU) --, the products of both blocks with the gathered
-// vector g go through LDS, then lane i sums row r0 + i.  Window-safe like
-// stream_tile_row_sum (la_kernels.hip): g is only dereferenced for the tile's
-// own nonzeros (slack and idle lanes gather the tile's first column).
-// C16: the column indices are 16-bit offsets from the tile's lowest column
-// (cols16 / cbase of flow_pmg_level: 6 B per nonzero instead of 8).
-// early(r, has_row): called as soon as the lane knows its row -- the caller
-// issues the loads of its epilogue there, so that they travel with the tile's
-// own loads instead of forming one more link of the dependent chain behind
-// the row sum (a workgroup lives ~6 us, a link of the chain is ~1 us of it).
-template <bool C16, class Early>
-__device__ __forceinline__ float2 pmg_tile_row_sum(
-    const int* __restrict__ rowptr, const void* __restrict__ cols_any,
-    const int* __restrict__ cbase,
-    const __half2* __restrict__ vals, const int* __restrict__ rowblocks,
-    const float2* __restrict__ g, float2* __restrict__ prod, int& r, int& r1,
-    Early early) {
-  const int* __restrict__ cols = static_cast<const int*>(cols_any);
-  const unsigned short* __restrict__ cols16 =
-      static_cast<const unsigned short*>(cols_any);
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int r0 = rowblocks[tile];
-  r1 = rowblocks[tile + 1];
-  const int base = C16 ? cbase[tile] : 0;
-  const int k0 = rowptr[r0];
-  const int k1 = rowptr[r1];
-  const int ka = k0 & ~3;
-  r = r0 + threadIdx.x;
-  early(r, r < r1);
-  int a = 0, b = 0;
-  if (r < r1) {
-    a = rowptr[r] - ka;
-    b = rowptr[r + 1] - ka;
-  }
-  const int lo = k0 - ka, hi = k1 - ka;          // hi <= kPmgTile - 1
-  const Half2x4* __restrict__ vq = reinterpret_cast<const Half2x4*>(vals + ka);
-  const int4* __restrict__ cq = reinterpret_cast<const int4*>(cols + ka);
-  const ushort4* __restrict__ cq16 =
-      reinterpret_cast<const ushort4*>(cols16 + ka);
-  Half2x4 v[kPmgQuads];
-  int4 c[kPmgQuads];
-#pragma unroll
-  for (int q = 0; q < kPmgQuads; ++q) {
-    const int p = threadIdx.x + q * kBlock;
-    c[q] = make_int4(0, 0, 0, 0);
-    if (4 * p < hi) {
-      v[q] = vq[p];
-      if (C16) {
-        const ushort4 u = cq16[p];
-        c[q] = make_int4(base + u.x, base + u.y, base + u.z, base + u.w);
-      } else {
-        c[q] = cq[p];
-      }
-    }
-  }
-  if (k0 < k1) {                                   // (block-uniform)
-    const int safe = C16 ? base + cols16[k0] : cols[k0];
-    float2 gg[kPmgQuads][4];
-#pragma unroll
-    for (int q = 0; q < kPmgQuads; ++q) {          // all gathers in flight
-      const int e0 = 4 * (threadIdx.x + q * kBlock);
-      const int cc[4] = {c[q].x, c[q].y, c[q].z, c[q].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = e0 + j;
-        gg[q][j] = g[(e >= lo && e < hi) ? cc[j] : safe];
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < kPmgQuads; ++q) {
-      const int e0 = 4 * (threadIdx.x + q * kBlock);
-      if (e0 < hi) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float2 w = __half22float2(v[q].v[j]);
-          prod[e0 + j] = f2(w.x * gg[q][j].x, w.y * gg[q][j].y);
-        }
-      }
-    }
-  }
-  __syncthreads();
-  float2 s = f2(0.f, 0.f);
-  for (int k = a; k < b; ++k) {
-    s.x += prod[k].x;
-    s.y += prod[k].y;
-  }
-  return s;
-}
 
 // One product with the packed operator plus what the Chebyshev iteration does
 // with it, row by row:   rho' = rho_in - (D^-1 A) g
@@ -177,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void pmg_cheb_kernel(
     const float2* __restrict__ d_extra, double* __restrict__ z,
     const unsigned char* __restrict__ bc, const double* __restrict__ rin,
     const double* __restrict__ stop) {
-  __shared__ float2 prod[kPmgTile];
+  __shared__ float2 prod[kTile16];
   if (stopped(stop)) return;
   int r, r1;
   float2 s;
@@ -192,17 +85,25 @@ __global__ __launch_bounds__(kBlock) void pmg_cheb_kernel(
     if (MODE == 2 && d_extra) extra = d_extra[row];
   };
   if (FMT == 2) {
-    s = mass_tile_row_sum_packed<float2>(rowptr,
-                                         static_cast<const unsigned*>(vals),
-                                         cbase, rowblocks, g, prod, r, r1, early);
+    s = fp16_tile_row_sum(
+        rowptr, PackedStream{static_cast<const unsigned*>(vals), cbase},
+        rowblocks, g, prod, r, r1, early);
     if (r < r1 && idrows) {
       if (idrows[r]) s.x = g[r].x;
       if (idrows[static_cast<size_t>(n) + r]) s.y = g[r].y;
     }
+  } else if (FMT == 1) {
+    s = fp16_tile_row_sum(
+        rowptr,
+        Cols16Stream{static_cast<const __half2*>(vals),
+                     static_cast<const unsigned short*>(cols), cbase},
+        rowblocks, g, prod, r, r1, early);
   } else {
-    s = pmg_tile_row_sum<FMT == 1>(rowptr, cols, cbase,
-                                   static_cast<const __half2*>(vals), rowblocks,
-                                   g, prod, r, r1, early);
+    s = fp16_tile_row_sum(
+        rowptr,
+        Cols32Stream<__half2>{static_cast<const __half2*>(vals),
+                              static_cast<const int*>(cols)},
+        rowblocks, g, prod, r, r1, early);
   }
   if (r >= r1) return;
   rho.x -= s.x;
@@ -443,19 +344,9 @@ __global__ __launch_bounds__(kBlock) void pmg_cols16_kernel(
     const int* __restrict__ rowblocks, const int* __restrict__ rowptr,
     const int* __restrict__ cols, int* __restrict__ cbase,
     unsigned short* __restrict__ cols16, int* __restrict__ overflow) {
-  __shared__ int wmin[kBlock / 64];
   const int tile = blockIdx.x;
   const int k0 = rowptr[rowblocks[tile]], k1 = rowptr[rowblocks[tile + 1]];
-  int m = 0x7fffffff;
-  for (int k = k0 + threadIdx.x; k < k1; k += kBlock) m = min(m, cols[k]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = min(m, __shfl_down(m, off, 64));
-  if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = m;
-  __syncthreads();
-  int base = wmin[0];
-#pragma unroll
-  for (int w = 1; w < kBlock / 64; ++w) base = min(base, wmin[w]);
-  if (k0 >= k1) base = 0;
+  const int base = tile_lowest_col(cols, k0, k1);
   if (threadIdx.x == 0) cbase[tile] = base;
   for (int k = k0 + threadIdx.x; k < k1; k += kBlock) {
     const int off = cols[k] - base;
@@ -575,21 +466,6 @@ int pmg_check(const flow_pmg* M, int op_size) {
 }
 
 namespace {
-
-struct Cheb {
-  double theta, delta, sigma, rho;
-  Cheb(double lo, double hi)
-      : theta(0.5 * (hi + lo)), delta(0.5 * (hi - lo)), sigma(theta / delta),
-        rho(1.0 / sigma) {}
-  float first() const { return static_cast<float>(1.0 / theta); }
-  // coefficients of the next step: d' = c1 d + c2 rho'
-  void next(float* c1, float* c2) {
-    const double rn = 1.0 / (2.0 * sigma - rho);
-    *c1 = static_cast<float>(rn * rho);
-    *c2 = static_cast<float>(2.0 * rn / delta);
-    rho = rn;
-  }
-};
 
 template <int MODE>
 void launch_cheb(const flow_pmg_level* L, const float2* g, const float2* rho_in,

@@ -15,10 +15,11 @@ Variants (the kernel each one restates):
   'stream'       stream_tile_row_sum: spmv_stream_kernel, mg_level_kernel
   'block2'       spmv_stream_block2_kernel
   'pair'         spmv_stream_pair_kernel (both components use the same indices)
-  'quad'         pmg_tile_row_sum (pmg_kernels.hip) / mass_tile_row_sum
-                 (mass_kernels.hip): QUADS of nonzeros per lane from a base
-                 aligned down to a multiple of four, FLOW_PMG_NNZ_PER_BLOCK
-                 nonzeros per tile; arrays readable three entries past nnz
+  'quad'         fp16_tile_row_sum (csr_stream16.h), the one tile routine of
+                 mass_cheb_kernel and pmg_cheb_kernel in all four stream
+                 formats: QUADS of nonzeros per lane from a base aligned down
+                 to a multiple of four, FLOW_PMG_NNZ_PER_BLOCK nonzeros per
+                 tile; arrays readable three entries past nnz
   'stream_r2a'   stream_tile_row_sum as it was when the world-3 fault of round 2
                  happened (every lane gathers x[col] of whatever index pair it
                  loaded; idle lanes hold column 0) -- kept to show that the
@@ -99,7 +100,7 @@ def quad_tile_accesses(rowptr, cols, rowblocks):
     rowptr = numpy.asarray(rowptr, dtype=numpy.int64)
     cols = numpy.asarray(cols, dtype=numpy.int64)
     rb = numpy.asarray(rowblocks, dtype=numpy.int64)
-    quads = (_hip.PMG_NNZ_PER_BLOCK + 4) // (4 * BLOCK)      # kPmgQuads
+    quads = (_hip.PMG_NNZ_PER_BLOCK + 4) // (4 * BLOCK)      # kQuads16
     k0 = rowptr[rb[:-1]]
     k1 = rowptr[rb[1:]]
     ka = k0 & ~3
@@ -128,8 +129,9 @@ def quad_tile_accesses(rowptr, cols, rowblocks):
 
 
 def cols16_tables(rowptr, cols, rowblocks):
-    '''pmg_cols16_kernel (pmg_kernels.hip) in numpy: per row block its lowest
-    column (0 for an empty block) and per nonzero the offset from it --
+    '''pmg_cols16_kernel / mass_pack16_kernel in numpy: per row block its
+    lowest column (tile_lowest_col of csr_stream16.h: 0 for an empty block)
+    and per nonzero the offset from it --
     (cbase, offsets, fits): `fits` = every offset fits in 16 bits.  The kernels
     that read flow_pmg_level.cols16 or the packed streams (flow_mass.packed16,
     flow_pmg_level.packed) rebuild the column as cbase[tile] + offset: with

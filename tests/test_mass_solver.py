@@ -211,6 +211,43 @@ def test_pair_mass_solve_with_identity_rows(hip, packed):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('case', ['scalar-p1', 'scalar-p2', 'pair'])
+def test_packed_and_plain_streams_solve_bit_for_bit_alike(hip, case):
+    '''The packed stream (fp16 value | 16-bit column offset) encodes the same
+    columns and the same fp16 values as the plain one (half + int32 column),
+    and both go through the one tile routine (fp16_tile_row_sum): the same
+    products summed in the same order -- the same corrections, the same
+    count, the same bits.'''
+    import torch
+    from flow_amd.fem import ops
+    rng = numpy.random.RandomState(33)
+    mesh = fem.karman_channel(60, 14, fitted=True)
+    V = fem.FunctionSpace(mesh, 'CG', 1 if case == 'scalar-p1' else 2)
+    A = ops.assemble_mass(V)
+    n = V.N
+    if case == 'pair':
+        # (kind 4 with identity rows, as in the test above)
+        free = (rng.uniform(size=2 * n) > 0.07).astype(numpy.uint8)
+        A = ops.Matrix(V.layout, 4, A.vals, rowmask=_dev(free))
+        b = rng.standard_normal(2 * n)
+        x0 = rng.standard_normal(2 * n)
+        x0[free == 0] = b[free == 0]
+    else:
+        b = rng.standard_normal(n)
+        x0 = numpy.zeros(n)
+    got = []
+    for packed in (False, True):
+        solver = fmass.MassSolver(A, A.diag_inv(), packed=packed)
+        assert (solver.packed16 is not None) == packed
+        x = _dev(x0)
+        info = solver.solve(_dev(b), x, 1e-12)
+        got.append((info.iterations, x))
+    assert got[0][0] == got[1][0] and got[0][0] >= 2, got
+    assert torch.isfinite(got[0][1]).all()
+    assert torch.equal(got[0][1], got[1][1])
+
+
+@pytest.mark.gpu
 def test_contraction_watch_adapts_and_falls_back(hip):
     '''The run-time watch on the a-priori contraction (mass_scalar_kernel;
     ADVICE r5): (a) a bound that is too OPTIMISTIC does not fail the solve --

@@ -405,6 +405,43 @@ def test_one_plane_levels_match_the_numpy_cycle(newton_system, monkeypatch):
         assert 0.93 * want < lam <= 1.001 * want, (lam, want)
 
 
+@pytest.mark.gpu
+def test_int32_columns_match_the_numpy_cycle_and_the_16_bit_offsets(
+        newton_system, monkeypatch):
+    '''The fallback format of the two-plane levels (int32 columns: what a level
+    gets when a tile's columns span 65536 or more) against the numpy cycle,
+    and against the default format (16-bit offsets from the tile's lowest
+    column) bit for bit: the two encode the same columns and the same fp16
+    values and go through the one tile routine (fp16_tile_row_sum), so the
+    power iterations find the same intervals and the cycles the same z.'''
+    from flow_amd import device
+    from flow_amd.fem import pmg as fpmg
+    prob, infos, pre0, J, J1 = newton_system
+    lay = prob.W.layout
+    n, n1 = lay.N, pre0.lay1.N
+    bc0 = device.to_host(pre0._keep['bc_fine']).numpy().astype(bool)
+    bc1 = device.to_host(pre0._keep['bc_coarse']).numpy().astype(bool)
+
+    def fresh(cols16):
+        monkeypatch.setattr(fpmg, 'COLS16', cols16)
+        pre = fpmg.Pmg(prob.W)
+        for lvl in (pre.fine, pre.coarse):
+            assert bool(lvl.struct.cols16) == cols16 and not lvl.struct.packed
+        pre.set_bcs(numpy.nonzero(bc0)[0].astype(numpy.int32))
+        return pre.refactor(J, J1)
+    pre32, pre16 = fresh(False), fresh(True)
+    assert pre32.lam == pre16.lam
+    Js, J1s = J.to_scipy().tocsr(), J1.to_scipy().tocsr()
+    P = _prolongation(lay)[0]
+    A = [Js[a * n:(a + 1) * n, a * n:(a + 1) * n].tocsr() for a in (0, 1)]
+    A1 = [J1s[a * n1:(a + 1) * n1, a * n1:(a + 1) * n1].tocsr() for a in (0, 1)]
+    _compare_with_numpy_cycle(pre32, A, A1, P, bc0, bc1, n, n1)
+    r = device.to_device(numpy.random.RandomState(6).standard_normal(2 * n))
+    z32 = device.to_host(pre32.apply(r, device.zeros(2 * n))).numpy()
+    z16 = device.to_host(pre16.apply(r, device.zeros(2 * n))).numpy()
+    assert numpy.isfinite(z32).all() and numpy.array_equal(z32, z16)
+
+
 def _compare_with_numpy_cycle(pre, A, A1, P, bc0, bc1, n, n1):
     from flow_amd import device
     rng = numpy.random.RandomState(4)
