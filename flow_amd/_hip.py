@@ -468,6 +468,8 @@ SYMBOLS = {
     'flow_transfer_apply': [_P(SpaceS), _I, _I, _VP, _VP, _VP, _VP, _VP],
     'flow_project_load': [_P(MeshS), _P(SpaceS), _P(MeshS), _P(SpaceS), _I, _VP,
                           _VP, _I, _VP, _I, _VP, _VP, _VP, _VP],
+    'flow_supermesh_norms': [_P(MeshS), _P(SpaceS), _P(MeshS), _P(SpaceS), _I,
+                             _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _P(_D), _VP],
     'flow_jump_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP, _VP],
     'flow_recover_gradient': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP],
     'flow_zz_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _I, _VP, _VP,

@@ -47,6 +47,23 @@
 // Guards: a row that leaves the pair list, a source cell outside [0, nc_from)
 // or a dof outside its range gives NaN in that target cell's entries and in
 // coverage[c], never a read outside the arrays.
+//
+//   flow_supermesh_norms  error norms and inner products of two fields on
+//                      different meshes (flow_amd/fem/supermesh.py), over the
+//                      same pairs with the same clip, fan and rule: one TARGET
+//                      cell per lane (mesh_b; the source is mesh_a), at every
+//                      quadrature point u and grad u in the source cell, w and
+//                      grad w in the target cell, and per component
+//                        (u - w)^2 and |grad u - grad w|^2   (product = 0)
+//                        u w       and grad u . grad w       (product = 1)
+//                      into cell_values[c] and cell_values[nc_b + c].  The
+//                      integrands have degree <= 4 on every piece: exact.  The
+//                      two planes are summed, on request, as the functionals
+//                      are (form_kernels.hip): per-block partials of strided
+//                      per-lane sums, at most kRedBlocks of them, then one
+//                      finishing block per plane.  NaN in both values of a
+//                      target cell under the guards above (its own dofs
+//                      included).
 #include <climits>
 #include <cmath>
 
@@ -289,6 +306,142 @@ __global__ __launch_bounds__(kBlock) void project_load_kernel(
   coverage[c] = ok ? covered / cell : nan;
 }
 
+// the physical gradient of sum_j U[j] phi_j at the barycentric point L of the
+// cell t (its own vertex order; lambda_0 = 1 - lambda_1 - lambda_2)
+template <int DEG>
+__device__ __forceinline__ void grad_at(const Tri& t, const double U[Elem<DEG>::NL],
+                                        const double L[3], double g[2]) {
+  double r[3];
+  ref_gradient<DEG>(U, L, r);
+  const double a = (r[1] - r[0]) * t.inv, b = (r[2] - r[0]) * t.inv;
+  g[0] = a * t.j11 - b * t.j10;
+  g[1] = b * t.j00 - a * t.j01;
+}
+
+// the nodal values of cell c (NaN-free: a dof outside [0, n) reads dof 0 and
+// clears ok)
+template <int NL, int NCOMP>
+__device__ __forceinline__ void load_cell_values(const int* __restrict__ cd, int nc, int c,
+                                                 int n, const double* __restrict__ u,
+                                                 double U[NCOMP][NL], bool& ok) {
+#pragma unroll
+  for (int l = 0; l < NL; ++l) {
+    const int dl = cd[l * nc + c];
+    const bool in = dl >= 0 && dl < n;
+    ok = ok && in;
+    const int d = in ? dl : 0;
+#pragma unroll
+    for (int a = 0; a < NCOMP; ++a) U[a][l] = u[static_cast<size_t>(a) * n + d];
+  }
+}
+
+// u of (mesh_a, V_a) against w of (mesh_b, V_b) on the cells of mesh_b:
+// cell_values[c] the value plane, cell_values[nc_b + c] the gradient plane
+template <int DA, int DB, int NCOMP>
+__global__ __launch_bounds__(kBlock) void supermesh_norms_kernel(
+    int nc_a, const double* __restrict__ xy_a, const int* __restrict__ cd_a, int n_a,
+    int nc_b, const double* __restrict__ xy_b, const int* __restrict__ cd_b, int n_b,
+    const int* __restrict__ pptr, const int* __restrict__ psrc, int npairs,
+    const double* __restrict__ u, const double* __restrict__ w, int product,
+    double* __restrict__ cell_values) {
+  constexpr int NA = Elem<DA>::NL, NB = Elem<DB>::NL;
+  FLOW_POLY_LDS();
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc_b) return;
+  const Tri T = load_tri(xy_b, nc_b, c);
+  int p0, p1;
+  bool ok;
+  pair_row(pptr, npairs, c, p0, p1, ok);
+  double W[NCOMP][NB];
+  load_cell_values<NB, NCOMP>(cd_b, nc_b, c, n_b, w, W, ok);
+  double val = 0.0, grd = 0.0;
+#pragma unroll 1
+  for (int t = p0; t < p1; ++t) {
+    const int s = psrc[t];
+    if (s < 0 || s >= nc_a) {
+      ok = false;
+      continue;
+    }
+    const Tri S = load_tri(xy_a, nc_a, s);
+    const int n = clip_pair(T, S, ax, ay, bx, by);
+    if (n < 3) continue;
+    double U[NCOMP][NA];
+    load_cell_values<NA, NCOMP>(cd_a, nc_a, s, n_a, u, U, ok);
+    // corner 0 of every sub-triangle of the fan, in both cells
+    double Lt[3][3], Ls[3][3];
+    const double x0 = ax[0], y0 = ay[0];
+    bary_of(T, x0, y0, Lt[0]);
+    bary_of(S, x0, y0, Ls[0]);
+    double x1 = ax[kBlock], y1 = ay[kBlock];
+    bary_of(T, x1, y1, Lt[1]);
+    bary_of(S, x1, y1, Ls[1]);
+#pragma unroll 1
+    for (int k = 2; k < n; ++k) {
+      const double x2 = ax[k * kBlock], y2 = ay[k * kBlock];
+      bary_of(T, x2, y2, Lt[2]);
+      bary_of(S, x2, y2, Ls[2]);
+      const double area = 0.5 * ((x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0));
+      // (the points in a loop, not unrolled: nothing here folds to a literal,
+      // and unrolled the vector instances take all 256 VGPRs -- one wave per
+      // SIMD -- against 221 at most this way)
+#pragma unroll 1
+      for (int q = 0; q < 7; ++q) {
+        double lt[3], ls[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          lt[j] = kQ7L[q][0] * Lt[0][j] + kQ7L[q][1] * Lt[1][j] + kQ7L[q][2] * Lt[2][j];
+          ls[j] = kQ7L[q][0] * Ls[0][j] + kQ7L[q][1] * Ls[1][j] + kQ7L[q][2] * Ls[2][j];
+        }
+        const double wq = kQ7W[q] * area;
+#pragma unroll
+        for (int a = 0; a < NCOMP; ++a) {
+          const double uv = eval_at<DA>(U[a], ls), wv = eval_at<DB>(W[a], lt);
+          double gu[2], gw[2];
+          grad_at<DA>(S, U[a], ls, gu);
+          grad_at<DB>(T, W[a], lt, gw);
+          if (product) {
+            val += wq * (uv * wv);
+            grd += wq * (gu[0] * gw[0] + gu[1] * gw[1]);
+          } else {
+            const double d = uv - wv, d0 = gu[0] - gw[0], d1 = gu[1] - gw[1];
+            val += wq * (d * d);
+            grd += wq * (d0 * d0 + d1 * d1);
+          }
+        }
+      }
+      x1 = x2;
+      y1 = y2;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        Lt[1][j] = Lt[2][j];
+        Ls[1][j] = Ls[2][j];
+      }
+    }
+  }
+  const double nan = __builtin_nan("");
+  cell_values[c] = ok ? val : nan;
+  cell_values[static_cast<size_t>(nc_b) + c] = ok ? grd : nan;
+}
+
+// fixed-order sums of the planes blockIdx.y of `in` (n entries each): block
+// (x, y) leaves the sum of its lanes' strided sums in out[y * out_stride + x].
+// Stage 1 over the cells, stage 2 (one block per plane, FINISH) over stage 1's
+// partials
+template <bool FINISH>
+__global__ __launch_bounds__(kBlock) void supermesh_sum_kernel(
+    int n, const double* __restrict__ in, size_t in_stride, double* __restrict__ out,
+    int out_stride) {
+  const double* __restrict__ p = in + blockIdx.y * in_stride;
+  double s = 0.0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    s += FINISH ? load_scalar(p + i) : p[i];
+  s = block_sum_once(s);
+  if (threadIdx.x == 0) {
+    if (FINISH) store_scalar(out + blockIdx.y * out_stride + blockIdx.x, s);
+    else out[blockIdx.y * out_stride + blockIdx.x] = s;
+  }
+}
+
 int check_side(const flow_mesh* mesh, const flow_space* V, const char* what) {
   FLOW_REQUIRE(mesh && mesh->nc >= 1 && mesh->nc <= INT_MAX / 6 && mesh->xy, what);
   FLOW_REQUIRE(mesh->c1 == 0, "field projection on strips");
@@ -352,4 +505,59 @@ extern "C" int flow_project_load(const flow_mesh* mesh_from, const flow_space* V
   const int nl = V_to->deg == 1 ? 3 : 6;
   return gather(V_to->n, ncomp, V_to->vptr, V_to->vsrc, scratch,
                 static_cast<size_t>(nl) * nc, b, st);
+}
+
+extern "C" int flow_supermesh_norms(const flow_mesh* mesh_a, const flow_space* V_a,
+                                    const flow_mesh* mesh_b, const flow_space* V_b,
+                                    int ncomp, const int* pptr, const int* psrc,
+                                    int npairs, const double* u, const double* w,
+                                    int product, double* cell_values, double* work,
+                                    double* totals_host, void* stream) {
+  FLOW_REQUIRE(V_a && V_b, "spaces");
+  int rc = check_side(mesh_a, V_a, "source mesh / space");
+  if (rc) return rc;
+  if ((rc = check_side(mesh_b, V_b, "target mesh / space"))) return rc;
+  FLOW_REQUIRE(npairs >= 0 && pptr && (psrc || npairs == 0), "pair list");
+  FLOW_REQUIRE(ncomp == 1 || ncomp == 2, "components");
+  FLOW_REQUIRE(product == 0 || product == 1, "product");
+  FLOW_REQUIRE(u && w && cell_values, "pointers");
+  FLOW_REQUIRE(work || !totals_host, "totals without a work buffer");
+  // (u and w are only read: the same field twice is allowed)
+  FLOW_REQUIRE(u != cell_values && w != cell_values && u != work && w != work &&
+                   cell_values != work,
+               "operands that are the same buffer");
+  static_assert(3 * kRedBlocks + 2 <= FLOW_REDUCE_WORK, "work size");
+  hipStream_t st = as_stream(stream);
+  const int nc = mesh_b->nc;
+  const dim3 blocks((nc + kBlock - 1) / kBlock);
+#define FLOW_SUPERMESH(DA, DB, NCOMP)                                                      \
+  hipLaunchKernelGGL((supermesh_norms_kernel<DA, DB, NCOMP>), blocks, dim3(kBlock), 0, st, \
+                     mesh_a->nc, mesh_a->xy, V_a->cell_dofs, V_a->n, nc, mesh_b->xy,       \
+                     V_b->cell_dofs, V_b->n, pptr, psrc, npairs, u, w, product,            \
+                     cell_values)
+  const int key = (V_a->deg - 1) * 4 + (V_b->deg - 1) * 2 + (ncomp - 1);
+  switch (key) {
+    case 0: FLOW_SUPERMESH(1, 1, 1); break;
+    case 1: FLOW_SUPERMESH(1, 1, 2); break;
+    case 2: FLOW_SUPERMESH(1, 2, 1); break;
+    case 3: FLOW_SUPERMESH(1, 2, 2); break;
+    case 4: FLOW_SUPERMESH(2, 1, 1); break;
+    case 5: FLOW_SUPERMESH(2, 1, 2); break;
+    case 6: FLOW_SUPERMESH(2, 2, 1); break;
+    default: FLOW_SUPERMESH(2, 2, 2); break;
+  }
+#undef FLOW_SUPERMESH
+  FLOW_CHECK_LAUNCH();
+  if (!totals_host) return FLOW_OK;
+  // [0, nparts) and [kRedBlocks, + nparts): the partials of the two planes;
+  // the two totals behind them
+  const int nparts = grid_for(nc, kBlock, kRedBlocks);
+  double* totals = work + 3 * kRedBlocks;
+  hipLaunchKernelGGL(supermesh_sum_kernel<false>, dim3(nparts, 2), dim3(kBlock), 0, st, nc,
+                     cell_values, static_cast<size_t>(nc), work, kRedBlocks);
+  FLOW_CHECK_LAUNCH();
+  hipLaunchKernelGGL(supermesh_sum_kernel<true>, dim3(1, 2), dim3(kBlock), 0, st, nparts,
+                     work, static_cast<size_t>(kRedBlocks), totals, 1);
+  FLOW_CHECK_LAUNCH();
+  return flow_read_doubles(totals, 2, totals_host, stream);
 }

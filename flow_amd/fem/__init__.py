@@ -32,6 +32,7 @@ from .points import Probes                                      # noqa: F401
 from .tracers import Tracers                                    # noqa: F401
 from .transfer import Transfer                                  # noqa: F401
 from .projection import Projection, project_onto               # noqa: F401
+from .supermesh import Supermesh, mesh_errornorm                # noqa: F401
 from .adapt import JumpIndicator, jump_indicator, mark, refine  # noqa: F401
 from .recovery import (                                         # noqa: F401
     GradientRecovery, recover_gradient, zz_indicator,
