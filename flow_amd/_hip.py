@@ -264,6 +264,18 @@ class StatsFreq(ctypes.Structure):
         ]
 
 
+ISOLINE_LEVELS_PER_LAUNCH = 32   # FLOW_ISOLINE_LEVELS_PER_LAUNCH
+
+
+class IsolineLevels(ctypes.Structure):
+    '''flow_isoline_levels (include/flow_hip.h): the levels of one launch'''
+    _fields_ = [
+        ('n', ctypes.c_int),
+        ('base', ctypes.c_int),
+        ('c', ctypes.c_double * ISOLINE_LEVELS_PER_LAUNCH),
+        ]
+
+
 class NsParams(ctypes.Structure):
     _fields_ = [
         ('dt', ctypes.c_double), ('rho', ctypes.c_double),
@@ -475,6 +487,12 @@ SYMBOLS = {
     'flow_zz_indicator': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _I, _VP, _VP,
                           _VP],
     'flow_distance_sweeps': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP, _VP],
+    'flow_isoline_count': [_P(MeshS), _P(SpaceS), _VP, _P(IsolineLevels), _VP,
+                           _VP],
+    'flow_isoline_emit': [_P(MeshS), _P(SpaceS), _VP, _P(IsolineLevels), _VP,
+                          _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'flow_isoline_measure': [_P(MeshS), _P(SpaceS), _VP, _P(IsolineLevels),
+                             _VP, _VP, _VP],
     'flow_multi_dot': [_I, _I, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP],
     'flow_combine': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, _VP, _VP,
                      ctypes.c_size_t, _VP],

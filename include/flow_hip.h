@@ -1502,6 +1502,69 @@ int flow_zz_indicator(const flow_mesh* mesh, const flow_space* V, int ncomp,
 int flow_distance_sweeps(const flow_mesh* mesh, const flow_space* V, int nsweeps,
                          double* buf_a, double* buf_b, int* flag, void* stream);
 
+/* ---- contour lines and level-set measures (flow_amd/fem/isolines.py):
+ * fem.Isolines ---------------------------------------------------------------
+ * f_h is the continuous piecewise-linear interpolant of the nodal values f (n
+ * doubles) of V: the field itself on P1; on P2 every cell is cut into its
+ * three corner triangles and the middle one, as for the wall distance, in that
+ * order.  A node is above iff f >= c.  A sub-triangle with three finite values
+ * that are not all on one side holds one segment of {f_h == c}, between the
+ * crossings of two of its sub-edges -- except where the ONE node above lies
+ * exactly on c (both crossings are that node: nothing is emitted).  The
+ * crossing of the sub-edge with dofs a < b is x_a + t (x_b - x_a),
+ * t = (c - f_a) / (f_b - f_a), from the lower dof to the higher whichever cell
+ * computes it: the same bits from both cells at an edge.  A segment has the
+ * above side on its left.  A sub-triangle with a non-finite value holds no
+ * segment and adds nothing to a length or an area.
+ *
+ * The levels of a launch travel in the kernel arguments (levels: HOST memory,
+ * passed on by value; nothing is uploaded): at most
+ * FLOW_ISOLINE_LEVELS_PER_LAUNCH of them, level k of the launch being level
+ * base + k of the caller's list.  levels->n == 0: nothing is launched.  One
+ * lane per cell in all three; no atomics; nothing is synchronised.  V: deg, n
+ * and cell_dofs are read.  6 * nc < 2^31.  Not on strips. */
+#define FLOW_ISOLINE_LEVELS_PER_LAUNCH 32
+typedef struct flow_isoline_levels {
+  int n;                                      /* levels in use, 0..32 */
+  int base;                                   /* index of the first one */
+  double c[FLOW_ISOLINE_LEVELS_PER_LAUNCH];
+} flow_isoline_levels;
+
+/* count[cell] (nc ints) = the segments of the cell over the launch's levels.
+ * mesh->xy is not read.  A cell that names a dof outside [0, n) counts 1 (the
+ * record flow_isoline_emit fills with NaN and -1) and reads nothing outside
+ * the arrays. */
+int flow_isoline_count(const flow_mesh* mesh, const flow_space* V, const double* f,
+                       const flow_isoline_levels* levels, int* count, void* stream);
+
+/* The segments of the launch's levels: cell c writes its count[c] segments at
+ * offset[c], offset[c] + 1, ..., ordered by level, then by sub-triangle; count
+ * is what flow_isoline_count gave for the same f and levels, offset (nc ints)
+ * the caller's exclusive scan of it (plus whatever earlier launches put in
+ * front of the cell).  Per segment s: xy[4 s ..] = x0, y0, x1, y1; level[s] =
+ * base + k; cell[s]; keys[4 s ..] = a0, b0, a1, b1, the dofs a < b of the two
+ * crossed sub-edges; bary[6 s ..] = the barycentric coordinates of both end
+ * points in the parent cell.  A record at or past `capacity` is not written,
+ * nor one beyond count[c]; a negative offset writes nothing.  A cell that names
+ * a dof outside [0, n) writes NaN (xy, bary), -1 (level, keys) and its index
+ * (cell) into its one record.  capacity == 0: nothing is launched. */
+int flow_isoline_emit(const flow_mesh* mesh, const flow_space* V, const double* f,
+                      const flow_isoline_levels* levels, const int* count,
+                      const int* offset, int capacity, double* xy, int* level,
+                      int* cell, int* keys, double* bary, void* stream);
+
+/* out[2 k] = the length of {f_h == c_k}, out[2 k + 1] = the area of
+ * {f_h >= c_k}, k < levels->n, in DEVICE memory (2 * 32 doubles are enough).
+ * Every sub-triangle is clipped exactly.  Per level each block of 256 cells
+ * adds its lanes in a fixed shape and writes partials[(2 k + q) * nblocks +
+ * block], nblocks = (nc + 255) / 256; a second launch adds each row in a
+ * fixed order: the grid depends on nc alone and two calls give the same bits.
+ * partials: 2 * levels->n * nblocks doubles.  A cell that names a dof outside
+ * [0, n) adds nothing. */
+int flow_isoline_measure(const flow_mesh* mesh, const flow_space* V, const double* f,
+                         const flow_isoline_levels* levels, double* partials,
+                         double* out, void* stream);
+
 /* ---- reductions of stored fields (flow_amd/fem/snapshots.py): fem.Snapshots ---
  * X is a column-major store of fields: column j starts at X + j*ldx; ldx >= n
  * and even, X (and y) 16-byte aligned, so every column is.
