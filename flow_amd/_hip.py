@@ -493,6 +493,12 @@ SYMBOLS = {
                           _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_isoline_measure': [_P(MeshS), _P(SpaceS), _VP, _P(IsolineLevels),
                              _VP, _VP, _VP],
+    'flow_region_init': [_P(SpaceS), _VP, _D, _I, _VP, _VP],
+    'flow_region_sweeps': [_P(MeshS), _P(SpaceS), _I, _VP, _VP, _VP, _VP],
+    'flow_region_moments': [_P(MeshS), _P(SpaceS), _VP, _D, _VP, _P(SpaceS), _I,
+                            _VP, _VP, _VP, _VP],
+    'flow_region_segment_sum': [_I, _VP, _VP, _I, _I, _VP, _VP, _VP],
+    'flow_region_segment_minmax': [_I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP],
     'flow_multi_dot': [_I, _I, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP],
     'flow_combine': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, _VP, _VP,
                      ctypes.c_size_t, _VP],

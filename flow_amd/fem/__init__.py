@@ -41,6 +41,7 @@ from .snapshots import Snapshots                                # noqa: F401
 from .statistics import Statistics                              # noqa: F401
 from .distance import Distance, wall_distance                   # noqa: F401
 from .isolines import Isolines, isolines                        # noqa: F401
+from .regions import Regions, regions                           # noqa: F401
 from .profile import (                                          # noqa: F401
     BoundaryProfile, traction, wall_shear, pressure_coefficient, normal_flux,
     )

@@ -1565,6 +1565,73 @@ int flow_isoline_measure(const flow_mesh* mesh, const flow_space* V, const doubl
                          const flow_isoline_levels* levels, double* partials,
                          double* out, void* stream);
 
+/* ---- connected components of a level set (flow_amd/fem/regions.py):
+ * fem.Regions ----------------------------------------------------------------
+ * The graph is the P1 triangulation of the dofs of V, as for the wall distance
+ * and the contour lines: on P1 the cells, on P2 every cell cut into its three
+ * corner triangles and the middle one, in that order.  A dof is INSIDE iff its
+ * value is finite and f >= level (side 0) or f < level (side 1).  Two inside
+ * dofs joined by a sub-edge are in one component; its label is its smallest
+ * dof.  No atomics anywhere; nothing is synchronised.  6 * nc < 2^31 (rows of
+ * the map are entries l*nc + c, slots below are s*nc + c < 4 nc).  Not on
+ * strips.
+ *
+ * label[i] (n ints) = inside(i) ? i : -1.  V: n is read. */
+int flow_region_init(const flow_space* V, const double* f, double level, int side,
+                     int* label, void* stream);
+
+/* nsweeps >= 1 Jacobi sweeps between two label buffers, sweep k reading buf_a
+ * and writing buf_b for even k and the other way round for odd k, as
+ * flow_distance_sweeps: the result is in buf_b when nsweeps is odd.  One lane
+ * per dof walks its row vptr[i] .. vptr[i+1] of vsrc; for an inside dof
+ *   m = min(old[i], min over the inside sub-edge neighbours j of old[j]),
+ *   new[i] = old[m]   (one pointer jump),
+ * an outside dof (label < 0) stays -1.  A label is always the index of an
+ * inside dof of the same component and <= i, so old[m] is a legal read; the
+ * fixed point (labels constant on components, L[r] = r) is unique and depends
+ * on no ordering.  *flag (device memory, zeroed by the caller) is set to 1 by
+ * every lane whose label the LAST of the nsweeps sweeps lowered.  A dof whose
+ * row leaves the map, whose patch names a dof outside [0, n) or whose label is
+ * no such index is written as -1 and nothing outside the arrays is read.  V:
+ * deg, n, cell_dofs, vptr and vsrc are read; mesh->xy is not. */
+int flow_region_sweeps(const flow_mesh* mesh, const flow_space* V, int nsweeps,
+                       int* buf_a, int* buf_b, int* flag, void* stream);
+
+/* One lane per cell.  ids (n ints): the compact component id of every dof, < 0
+ * outside.  Per sub-triangle slot s*nc + cell (s = 0 on P1, 0..3 on P2; nslots
+ * = nc or 4 nc): key[slot] = the id of the sub-triangle's inside dofs (they
+ * share one) or -1 where it has none or a non-finite value, and
+ * vals[r*nslots + slot], r < 3 + ncomp, = the integrals of 1, x, y and g_a
+ * over the piece of the sub-triangle where f_h is inside: the whole of it with
+ * 3 inside dofs, the corner at the inside node with 1, and with 2 (A, B inside,
+ * C outside) the quadrilateral A, B, Q, P, P on A-C and Q on B-C, cut by the
+ * diagonal A-Q.  Crossings are those of the contour lines (from the lower dof
+ * of the sub-edge).  g (ncomp * G->n doubles, component a at g + a*G->n) is the
+ * P1 / P2 polynomial of the parent cell on the space G of the same mesh (deg,
+ * n, cell_dofs are read); every triangle is integrated with the edge-midpoint
+ * rule, exact for degree 2; areas are absolute values.  Every slot is written,
+ * with zeros where there is no piece.  ncomp 0..2; ncomp == 0: G and g are not
+ * read.  key == NULL: the keys are not written.  A cell that names a dof
+ * outside [0, n) (or of g outside [0, G->n)) writes -1 and zeros. */
+int flow_region_moments(const flow_mesh* mesh, const flow_space* V, const double* f,
+                        double level, const int* ids, const flow_space* G, int ncomp,
+                        const double* g, int* key, double* vals, void* stream);
+
+/* out[r*count + k] = sum over t in [offsets[k], offsets[k+1]) of
+ * vals[r*nslots + perm[t]], r < nrows, k < count: one block per (k, r), lanes
+ * stride over the segment in a fixed assignment and a block sum of fixed shape
+ * finishes -- the same inputs give the same bits.  offsets: count + 1 ints
+ * (clipped to [0, nslots]); perm: nslots ints (an entry outside [0, nslots)
+ * adds nothing).  count == 0 or nrows == 0: nothing is launched. */
+int flow_region_segment_sum(int count, const int* offsets, const int* perm, int nrows,
+                            int nslots, const double* vals, double* out, void* stream);
+
+/* The same with the minimum and the maximum: out_min[r*count + k], out_max[..]
+ * over vals[r*n + perm[t]]; +inf and -inf for an empty segment. */
+int flow_region_segment_minmax(int count, const int* offsets, const int* perm, int nrows,
+                               int n, const double* vals, double* out_min,
+                               double* out_max, void* stream);
+
 /* ---- reductions of stored fields (flow_amd/fem/snapshots.py): fem.Snapshots ---
  * X is a column-major store of fields: column j starts at X + j*ldx; ldx >= n
  * and even, X (and y) 16-byte aligned, so every column is.
