@@ -22,73 +22,123 @@ constexpr int kTile2 = 2 * kBlock * kPairs2;
 static_assert(FLOW_SPMV_ROWS_PER_BLOCK == kBlock, "one lane per row");
 static_assert(FLOW_SPMV_NNZ_PER_BLOCK == kTile2 - 2, "tile minus alignment slack");
 
-// The rows [r0, r1) of one workgroup (<= kBlock rows, <= kTile - 2 nonzeros): the
-// products go through LDS (prod, kTile doubles), then lane i sums row r0 + i.
-// Returns that row's sum (0 for a lane without a row).
+// The rows [r0, r1) of one workgroup (<= kBlock rows, <= kTile - 2 nonzeros), as
+// the lanes hold them between the tile's own loads and a product: load() fetches
+// the value pairs and column pairs once, row_sum(x, prod) gathers x, parks the
+// products in LDS (prod, kTile doubles) and sums row r0 + lane: gather(), park(),
+// a barrier, sum().  One load() may be followed by those steps for several x,
+// each with a prod of its own (the block product of eigen_kernels.hip): every
+// column then has the bits of a product on its own.
+struct StreamTile {
+  double2 v[kPairs];
+  int2 c[kPairs];
+  int a, b;          // the lane's row in prod: [a, b)
+  int k0, k1, ka;    // the tile's own nonzeros [k0, k1); ka: k0 aligned down
+
+  template <class Early = NoEarly>
+  __device__ __forceinline__ void load(int r0, int r1, const int* __restrict__ rowptr,
+                                       const int* __restrict__ cols,
+                                       const double* __restrict__ vals,
+                                       Early early = Early()) {
+    k0 = rowptr[r0];
+    k1 = rowptr[r1];
+    // 16-byte value loads / 8-byte index loads: every lane owns PAIRS pairs of
+    // consecutive nonzeros; the tile base is aligned down to an even index (value
+    // planes start 16-B aligned and the host caps a block at kTile-2 nonzeros).
+    ka = k0 & ~1;
+    const int r = r0 + threadIdx.x;
+    early(r, r < r1);
+    a = 0;
+    b = 0;
+    if (r < r1) {
+      a = rowptr[r] - ka;
+      b = rowptr[r + 1] - ka;
+    }
+    const double2* __restrict__ v2p = reinterpret_cast<const double2*>(vals + ka);
+    const int2* __restrict__ c2p = reinterpret_cast<const int2*>(cols + ka);
+    const int npair = (k1 - ka + 1) >> 1;   // a trailing odd element reads one
+                                            // entry of the next tile (unused)
+#pragma unroll
+    for (int j = 0; j < kPairs; ++j) {
+      const int p = threadIdx.x + j * kBlock;
+      const bool ok = p < npair;
+      v[j] = ok ? v2p[p] : make_double2(0.0, 0.0);
+      c[j] = ok ? c2p[p] : make_int2(0, 0);
+    }
+  }
+
+  // x at the lane's nonzeros (x0: the even, x1: the odd entry of each pair)
+  struct Gathered {
+    double x0[kPairs], x1[kPairs];
+  };
+  __device__ __forceinline__ Gathered gather(const int* __restrict__ cols,
+                                             const double* __restrict__ x) const {
+    Gathered g;
+    // x is only gathered for the tile's OWN nonzeros [k0, k1): the alignment
+    // slack before k0, the odd element behind k1 (a column of another row, or
+    // the padding 0 behind the last nonzero) and the idle lanes must not be
+    // dereferenced -- x may be a window of a larger vector (row-sharded solves
+    // pass x shifted to global row numbering: x[0] is then far outside it)
+    // Those entries gather the tile's first column instead (an index select,
+    // the loads themselves stay unconditional and all in flight).
+    const int lo = k0 - ka, hi = k1 - ka;
+    const int safe = cols[k0 < k1 ? k0 : (k0 > 0 ? k0 - 1 : 0)];
+    if (k0 < k1) {                       // (block-uniform)
+#pragma unroll
+      for (int j = 0; j < kPairs; ++j) {   // all gathers in flight before any use
+        const int e = 2 * (threadIdx.x + j * kBlock);
+        g.x0[j] = x[(e >= lo && e < hi) ? c[j].x : safe];
+        g.x1[j] = x[(e + 1 < hi) ? c[j].y : safe];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPairs; ++j) g.x0[j] = g.x1[j] = 0.0;
+    }
+    return g;
+  }
+
+  // the lane's products into LDS (prod: kTile doubles)
+  __device__ __forceinline__ void park(const Gathered& g,
+                                       double* __restrict__ prod) const {
+    const int npair = (k1 - ka + 1) >> 1;
+#pragma unroll
+    for (int j = 0; j < kPairs; ++j) {
+      const int p = threadIdx.x + j * kBlock;
+      if (p < npair) {
+        prod[2 * p] = v[j].x * g.x0[j];
+        prod[2 * p + 1] = v[j].y * g.x1[j];
+      }
+    }
+  }
+
+  // the lane's row out of the parked products (behind a barrier)
+  __device__ __forceinline__ double sum(const double* __restrict__ prod) const {
+    double s = 0.0;
+    for (int k = a; k < b; ++k) s += prod[k];
+    return s;
+  }
+
+  __device__ __forceinline__ double row_sum(const int* __restrict__ cols,
+                                            const double* __restrict__ x,
+                                            double* __restrict__ prod) const {
+    const Gathered g = gather(cols, x);
+    park(g, prod);
+    __syncthreads();
+    return sum(prod);
+  }
+};
+
+// The products of the rows [r0, r1) with x go through LDS (prod, kTile doubles),
+// then lane i sums row r0 + i.  Returns that row's sum (0 for a lane without a
+// row).
 template <class Early = NoEarly>
 __device__ __forceinline__ double stream_rows_sum(
     int r0, int r1, const int* __restrict__ rowptr, const int* __restrict__ cols,
     const double* __restrict__ vals, const double* __restrict__ x,
     double* __restrict__ prod, Early early = Early()) {
-  const int k0 = rowptr[r0];
-  const int k1 = rowptr[r1];
-  // 16-byte value loads / 8-byte index loads: every lane owns PAIRS pairs of
-  // consecutive nonzeros; the tile base is aligned down to an even index (value
-  // planes start 16-B aligned and the host caps a block at kTile-2 nonzeros).
-  const int ka = k0 & ~1;
-  const int r = r0 + threadIdx.x;
-  early(r, r < r1);
-  int a = 0, b = 0;
-  if (r < r1) {
-    a = rowptr[r] - ka;
-    b = rowptr[r + 1] - ka;
-  }
-  const double2* __restrict__ v2p = reinterpret_cast<const double2*>(vals + ka);
-  const int2* __restrict__ c2p = reinterpret_cast<const int2*>(cols + ka);
-  const int npair = (k1 - ka + 1) >> 1;   // a trailing odd element reads one
-                                          // entry of the next tile (unused)
-  double2 v[kPairs];
-  int2 c[kPairs];
-#pragma unroll
-  for (int j = 0; j < kPairs; ++j) {
-    const int p = threadIdx.x + j * kBlock;
-    const bool ok = p < npair;
-    v[j] = ok ? v2p[p] : make_double2(0.0, 0.0);
-    c[j] = ok ? c2p[p] : make_int2(0, 0);
-  }
-  // x is only gathered for the tile's OWN nonzeros [k0, k1): the alignment
-  // slack before k0, the odd element behind k1 (a column of another row, or
-  // the padding 0 behind the last nonzero) and the idle lanes must not be
-  // dereferenced -- x may be a window of a larger vector (row-sharded solves
-  // pass x shifted to global row numbering: x[0] is then far outside it)
-  // Those entries gather the tile's first column instead (an index select,
-  // the loads themselves stay unconditional and all in flight).
-  const int lo = k0 - ka, hi = k1 - ka;
-  const int safe = cols[k0 < k1 ? k0 : (k0 > 0 ? k0 - 1 : 0)];
-  double x0[kPairs], x1[kPairs];
-  if (k0 < k1) {                       // (block-uniform)
-#pragma unroll
-    for (int j = 0; j < kPairs; ++j) {   // all gathers in flight before any use
-      const int e = 2 * (threadIdx.x + j * kBlock);
-      x0[j] = x[(e >= lo && e < hi) ? c[j].x : safe];
-      x1[j] = x[(e + 1 < hi) ? c[j].y : safe];
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < kPairs; ++j) x0[j] = x1[j] = 0.0;
-  }
-#pragma unroll
-  for (int j = 0; j < kPairs; ++j) {
-    const int p = threadIdx.x + j * kBlock;
-    if (p < npair) {
-      prod[2 * p] = v[j].x * x0[j];
-      prod[2 * p + 1] = v[j].y * x1[j];
-    }
-  }
-  __syncthreads();
-  double s = 0.0;
-  for (int k = a; k < b; ++k) s += prod[k];
-  return s;
+  StreamTile t;
+  t.load(r0, r1, rowptr, cols, vals, early);
+  return t.row_sum(cols, x, prod);
 }
 
 // One tile of the CSR stream -- the rows [r0, r1) of workgroup blockIdx.x (XCD-

@@ -18,7 +18,8 @@
 //                   that order.  Nothing in the chain of one column involves
 //                   another column or m: out[j] has the same bits whatever m is
 //                   and wherever the column sits in its chunk, and two calls
-//                   agree bit for bit.  No atomics.
+//                   agree bit for bit.  No atomics.  (The chain itself:
+//                   multi_dot.h, shared with flow_block_gram.)
 //   flow_combine    out[k*ldo + i] = (base ? base[i] : 0) + sum_j C[k*m + j] *
 //                   X[j*ldx + i], k < r, the terms added in ascending j by fma.
 //                   One lane per row i; the outputs are taken in chunks of
@@ -36,77 +37,22 @@
 #include <cstdint>
 
 #include "common.h"
+#include "multi_dot.h"
 
 namespace flow {
 namespace {
 
-constexpr int kChunk = 8;        // columns (outputs) a lane keeps in registers
 constexpr int kCoefTile = 32;    // columns of C staged in LDS at a time
 constexpr int kMaxGridY = 65535;
-
-// grid.x of flow_multi_dot: a function of n alone
-inline int dot_grid(int n) {
-  const long long pairs = (static_cast<long long>(n) + 1) / 2;
-  return grid_for(pairs, kBlock, kRedBlocks);
-}
 
 // columns j0 + blockIdx.y*kChunk .. + MC of X against y
 template <int MC>
 __global__ __launch_bounds__(kBlock) void multi_dot_kernel(
     int n, int m, int j0, const double* __restrict__ X, size_t ldx,
     const double* __restrict__ y, double* __restrict__ work) {
-  __shared__ double wave_part[MC][4];
   const int jc = j0 + blockIdx.y * kChunk;
-  const double* __restrict__ col[MC];
-#pragma unroll
-  for (int c = 0; c < MC; ++c) col[c] = X + static_cast<size_t>(jc + c) * ldx;
-  double acc[MC];
-#pragma unroll
-  for (int c = 0; c < MC; ++c) acc[c] = 0.0;
-  const int full = n / 2;                        // whole pairs
-  const int stride = gridDim.x * kBlock;
-  int p = blockIdx.x * kBlock + threadIdx.x;
-  for (; p < full; p += stride) {
-    const double2 yy = reinterpret_cast<const double2*>(y)[p];
-    double2 xx[MC];
-#pragma unroll
-    for (int c = 0; c < MC; ++c) xx[c] = reinterpret_cast<const double2*>(col[c])[p];
-#pragma unroll
-    for (int c = 0; c < MC; ++c) {
-      acc[c] = fma(xx[c].x, yy.x, acc[c]);
-      acc[c] = fma(xx[c].y, yy.y, acc[c]);
-    }
-  }
-  // the last entry of an odd n: the lane whose turn pair `full` would be
-  if ((n & 1) && p == full) {
-    const double yl = y[n - 1];
-#pragma unroll
-    for (int c = 0; c < MC; ++c) acc[c] = fma(col[c][n - 1], yl, acc[c]);
-  }
-#pragma unroll
-  for (int c = 0; c < MC; ++c) {
-    double v = acc[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) wave_part[c][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < MC) {
-    const int c = threadIdx.x;
-    work[static_cast<size_t>(blockIdx.x) * m + jc + c] =
-        wave_part[c][0] + wave_part[c][1] + wave_part[c][2] + wave_part[c][3];
-  }
-}
-
-// one lane per column: the block partials in ascending block order
-__global__ __launch_bounds__(kBlock) void multi_dot_finish_kernel(
-    int m, int nparts, const double* __restrict__ work, double* __restrict__ out) {
-  const int j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= m) return;
-  double s = 0.0;
-#pragma unroll 8
-  for (int b = 0; b < nparts; ++b) s += work[static_cast<size_t>(b) * m + j];
-  out[j] = s;
+  dot_columns<MC>(n, X + static_cast<size_t>(jc) * ldx, ldx, y,
+                  work + static_cast<size_t>(blockIdx.x) * m + jc, 1);
 }
 
 // outputs k0 + blockIdx.y*kChunk .. + RC, one lane per row
@@ -148,16 +94,6 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(
 }
 
 static_assert(kCoefTile * kChunk <= kBlock, "one lane per staged coefficient");
-// wave_part[..][4] and w0 + w1 + w2 + w3 in multi_dot_kernel
-static_assert(kBlock == 4 * 64, "the block sum is written for four waves of 64");
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// do [a, a + na) and [b, b + nb) (in doubles) share an entry?
-inline bool overlap(const double* a, size_t na, const double* b, size_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + 8 * nb && b0 < a0 + 8 * na;
-}
 
 template <int MC>
 void launch_dot(int g, int chunks, int n, int m, int j0, const double* X, size_t ldx,

@@ -180,6 +180,28 @@ class Matrix(object):
             ))
         return y
 
+    def apply_block(self, X, ldx, m, Y, ldy, chunk=0):
+        '''Y[:, j] = A X[:, j] for the first m columns of the column stores X
+        and Y (tensors, column strides ldx and ldy: >= N and even, the stores
+        16-byte aligned, Y not overlapping X): one launch that reads the
+        matrix once; every column has the bits of apply() on that column
+        (flow_operator_apply_block; scalar matrices only).  chunk: columns a
+        workgroup takes at a time (2, 4, 8; 0: the library's choice).'''
+        lib = _hip.lib()
+        if self.kind != 0:
+            raise ValueError('apply_block: a scalar matrix (kind 0), not kind '
+                             '%d' % self.kind)
+        m = int(m)
+        if m == 0:
+            return Y
+        n = self.layout.N
+        _hip.check(lib.flow_operator_apply_block_chunk(
+            ctypes.byref(self.operator()), m,
+            _hip.f64(X, (m - 1) * ldx + n, 'X'), ldx,
+            _hip.f64(Y, (m - 1) * ldy + n, 'Y'), ldy, int(chunk),
+            _hip.stream()))
+        return Y
+
     def diag_inv(self):
         lib = _hip.lib()
         out = device.empty(self.size)

@@ -1660,6 +1660,36 @@ int flow_combine(int n, int m, const double* X, size_t ldx, int r,
                  const double* C, const double* base, double* out, size_t ldo,
                  void* stream);
 
+/* ---- block kernels of the eigensolver (flow_amd/fem/eigen.py): fem.Eigenmodes --
+ * X and Y are column-major stores with the conventions above: column j at
+ * X + j*ldx, ld >= n and even, the store 16-byte aligned, the padding (entries
+ * at and past n of a column) never read or written.
+ *
+ * Y[:, j] = A X[:, j], j < m, for a scalar operator (kind 0; other kinds are
+ * refused).  ONE launch: a workgroup loads its CSR-stream tile of A once and
+ * runs over the columns in chunks, so the 12 B per nonzero of A are read once
+ * instead of m times.  Column j has exactly the bits flow_operator_apply gives
+ * for that column (the same products, the same summation order per row).  Y
+ * must not overlap X (refused).  m == 0: nothing is launched. */
+int flow_operator_apply_block(const flow_operator* A, int m, const double* X,
+                              size_t ldx, double* Y, size_t ldy, void* stream);
+/* The same with the chunk width chosen by the caller (2, 4 or 8 columns; 0: the
+ * library's own): for tools/eigen_lab.py.  The bits do not depend on it. */
+int flow_operator_apply_block_chunk(const flow_operator* A, int m, const double* X,
+                                    size_t ldx, double* Y, size_t ldy, int mc,
+                                    void* stream);
+
+/* out[i*mb + j] = sum_r X[i*ldx + r] * Y[j*ldy + r], i < ma, j < mb: the Gram
+ * matrix of two blocks in DEVICE memory (no host synchronisation), one launch
+ * plus one finishing launch for all ma*mb entries.  Entry (i, j) has the bits
+ * flow_multi_dot(n, ma, X, ldx, Y + j*ldy, ...) leaves in out[i]: it depends on
+ * n and its two columns alone, and two calls give the same bits.  No atomics.
+ * work: ma * mb * FLOW_MULTI_DOT_BLOCKS doubles.  work and out must not overlap
+ * X, Y or each other (refused).  n, ma or mb == 0: nothing is launched. */
+int flow_block_gram(int n, int ma, const double* X, size_t ldx, int mb,
+                    const double* Y, size_t ldy, double* work, double* out,
+                    void* stream);
+
 /* ---- running time statistics of a field (flow_amd/fem/statistics.py):
  * fem.Statistics ---------------------------------------------------------------
  * A store of planes of ld doubles each (ld >= n and even, the store 16-byte
