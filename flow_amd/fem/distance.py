@@ -25,8 +25,7 @@ straight edge: cells are affine).  Source dofs get 0, every other dof starts
 at +inf.
 
 Scheme (flow_distance_sweeps, csrc/distance_kernels.hip).  The graph is the
-P1 triangulation of the dofs: the cells for P1; for P2 every cell cut into its
-three corner triangles and the middle one.  A node C is updated from a
+P1 triangulation of the dofs (csrc/subtri.h).  A node C is updated from a
 triangle (C, A, B) by the Hopf-Lax formula (Bornemann and Rasch): the minimum
 over the edge A-B of T(x) + |C - x|, T linear on the edge -- the two end points
 and, where there is one, the interior stationary point.  The end points keep
@@ -51,15 +50,13 @@ nodes per sweep.  Not on strips.
 '''
 import numpy
 
+from . import ops
+from ._levelset import field_on, scalar_p12_space, sweep_to_fixed_point
+
 # sweeps per batch, one read-back of the flag behind each: the fastest of 8, 32
 # and 128 on the bench mesh, P1 and P2 ("Wall distance",
 # has the table and what it does not show)
 CHECK_EVERY = 128
-
-
-def _no_strips():
-    from .ops import _no_strips as refuse
-    refuse('Wall distance')
 
 
 def _facet_dofs(V, facets):
@@ -117,21 +114,10 @@ class Distance(object):
     module's text.  The two buffers and the flag are allocated once.'''
 
     def __init__(self, V, sources='on_boundary'):
-        if not hasattr(V, 'layout'):
-            raise NotImplementedError(
-                'V: a mixed space; take the distance on one of its scalar '
-                'sub-spaces')
-        if getattr(V, 'component', None) is not None:
-            raise NotImplementedError(
-                'V: a component view (W.sub(i)); the distance is a scalar '
-                'field: use W.sub(i).collapse()')
-        if V.dim != 1:
-            raise NotImplementedError(
-                'V: %r components; the distance is a scalar field' % (V.dim,))
-        if V.degree not in (1, 2):
-            raise ValueError('V: P%r; the wall distance takes P1 or P2'
-                             % (V.degree,))
-        _no_strips()
+        scalar_p12_space(V, 'take the distance on',
+                         'the distance is a scalar field', 'the wall distance',
+                         ValueError)
+        ops._no_strips('Wall distance')
         self.V = V
         self.dofs = source_dofs(V, sources)
         self.sweeps = 0
@@ -157,38 +143,28 @@ class Distance(object):
         _hip.NotConverged after more than V.N + CHECK_EVERY sweeps (no dof
         changes more often than V.N times).'''
         import ctypes
-        from .. import _hip, device
+        from .. import _hip
         from .function import Function
-        from .ops import mesh_struct, space_struct
-        _no_strips()
+        ops._no_strips('Wall distance')
         V, N = self.V, self.V.N
-        if out is not None and (
-                not isinstance(out, Function)
-                or getattr(out.function_space(), 'component', None) is not None
-                or not out.function_space().same_as(V)):
-            raise ValueError('out: not a Function on the space this distance '
-                             'was built for')
+        if out is not None:
+            field_on(V, out, 'out', 'this distance was')
         lib = _hip.lib()
         start, a, b, flag = self._buffers()
-        mesh_s, space_s = mesh_struct(V.mesh()), space_struct(V.layout)
-        _hip.copy(a, start)
-        self.sweeps = 0
-        while True:
-            if self.sweeps > N:
-                raise _hip.NotConverged(
-                    'wall distance: no fixed point after %d sweeps on %d dofs'
-                    % (self.sweeps, N))
-            flag.zero_()
+        mesh_s = ops.mesh_struct(V.mesh())
+        space_s = ops.space_struct(V.layout)
+
+        def enqueue(a, b, nsweeps):
             _hip.check(lib.flow_distance_sweeps(
-                ctypes.byref(mesh_s), ctypes.byref(space_s), CHECK_EVERY,
+                ctypes.byref(mesh_s), ctypes.byref(space_s), nsweeps,
                 _hip.f64(a, N, 'distance buffer'),
                 _hip.f64(b, N, 'distance buffer'),
                 _hip.i32(flag, 1, 'flag'), _hip.stream()))
-            self.sweeps += CHECK_EVERY
-            if CHECK_EVERY % 2:
-                a, b = b, a
-            if int(device.to_host(flag)[0]) == 0:
-                break
+
+        _hip.copy(a, start)
+        self.sweeps = 0
+        a, b, self.sweeps = sweep_to_fixed_point(
+            enqueue, a, b, flag, CHECK_EVERY, N, 'wall distance')
         if out is None:
             out = Function(V)
         _hip.copy(out.data, a)

@@ -27,11 +27,10 @@ f == c, how long is that line, and how large is {f >= c}?
     isolines(f, levels)              # Isolines(f.function_space()).extract(...)
 
 What is contoured.  f_h, the continuous piecewise-LINEAR interpolant of the
-nodal values of f.  On P1 that is the field itself.  On P2 every cell is cut
-into its three corner triangles and the middle one (the sub-triangulation of
-the wall distance), and f_h is linear on each: the contour is that of f_h, NOT
-of the quadratic, so its position is second order in the mesh width -- what a
-plot of the nodal values shows, at the resolution of the dofs.
+nodal values of f: linear on every triangle of the P1 triangulation of the
+dofs (csrc/subtri.h).  On P1 that is the field itself.  On P2 the contour is
+that of f_h, NOT of the quadratic, so its position is second order in the mesh
+width -- what a plot of the nodal values shows, at the resolution of the dofs.
 
 Definitions (csrc/isoline_kernels.hip; tests/isolines_reference.py restates
 them in numpy).
@@ -44,10 +43,10 @@ them in numpy).
     the chain of keys is cut there although the coordinates still meet).  So
     a field equal to c everywhere emits nothing, and a node on the level
     yields neither a zero-length nor a duplicate segment.
-  * The crossing of the sub-edge (a, b), global dofs a < b, is
-    x_a + t (x_b - x_a), t = (c - f_a) / (f_b - f_a): always from the lower
-    dof towards the higher, so the two cells at an edge produce the same
-    bits, and `keys` carries (a, b): polylines are chained on integers.
+  * A crossing is computed from the lower dof of its sub-edge (a, b), a < b,
+    towards the higher (subtri.h's rule), so the two cells at an edge produce
+    the same bits, and `keys` carries (a, b): polylines are chained on
+    integers.
   * A segment has the above side on its left: chained lines have one
     orientation, a closed contour round a maximum is counter-clockwise.
   * A sub-triangle with a non-finite nodal value (Distance yields inf) emits
@@ -65,12 +64,10 @@ nothing more is launched.  Not on strips.
 '''
 import numpy
 
+from . import ops
+from ._levelset import field_on, scalar_p12_space
+
 INT32_MAX = 2**31 - 1
-
-
-def _no_strips():
-    from .ops import _no_strips as refuse
-    refuse('Isolines')
 
 
 def _levels(levels):
@@ -198,11 +195,10 @@ class Contours(object):
         import ctypes
         from .. import _hip, device
         from . import forms
-        from .ops import _form_struct, mesh_struct
         t = float(t)
         if not 0.0 <= t <= 1.0:
             raise ValueError('t: %r is outside [0, 1]' % (t,))
-        _no_strips()
+        ops._no_strips('Isolines')
         mesh = self.V.mesh()
         form = forms.as_form(expr)
         forms._join_mesh(form.mesh, mesh)
@@ -212,9 +208,9 @@ class Contours(object):
         if n:
             lam = (self.bary[:, 0, :] * (1.0 - t) + self.bary[:, 1, :] * t) \
                 .t().contiguous()
-            fs, keep = _form_struct(prog, mesh, 0)
+            fs, keep = ops._form_struct(prog, mesh, 0)
             _hip.check(_hip.lib().flow_form_points(
-                ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs), n,
+                ctypes.byref(ops.mesh_struct(mesh)), ctypes.byref(fs), n,
                 _hip.i32(self.cell, n, 'cells'),
                 _hip.f64(lam, 3 * n, 'barycentric coordinates'),
                 _hip.f64(out, nout * n, 'out'), _hip.stream()))
@@ -227,49 +223,26 @@ class Isolines(object):
     the scalar P1 / P2 space V; see the module's text.'''
 
     def __init__(self, V):
-        if not hasattr(V, 'layout'):
-            raise NotImplementedError(
-                'V: a mixed space; contour a Function on one of its scalar '
-                'sub-spaces')
-        if getattr(V, 'component', None) is not None:
-            raise NotImplementedError(
-                'V: a component view (W.sub(i)); contours are those of a '
-                'scalar field: use W.sub(i).collapse()')
-        if V.dim != 1:
-            raise NotImplementedError(
-                'V: %r components; contours are those of a scalar field'
-                % (V.dim,))
-        if V.degree not in (1, 2):
-            raise NotImplementedError(
-                'V: P%r; Isolines takes P1 or P2' % (V.degree,))
-        _no_strips()
+        scalar_p12_space(V, 'contour a Function on',
+                         'contours are those of a scalar field', 'Isolines')
+        ops._no_strips('Isolines')
         self.V = V
         self._work = None
 
-    def _field(self, f):
-        from .function import Function
-        if not isinstance(f, Function) \
-                or getattr(f.function_space(), 'component', None) is not None \
-                or not f.function_space().same_as(self.V):
-            raise ValueError('f: not a Function on the space these isolines '
-                             'were built for')
-        return f
-
     def _structs(self):
         import ctypes
-        from .ops import mesh_struct, space_struct
         V = self.V
-        return (ctypes.byref(mesh_struct(V.mesh())),
-                ctypes.byref(space_struct(V.layout)))
+        return (ctypes.byref(ops.mesh_struct(V.mesh())),
+                ctypes.byref(ops.space_struct(V.layout)))
 
     def extract(self, f, levels):
         '''The segments of {f_h == c} for every c in levels, as Contours.'''
         import ctypes
         import torch
         from .. import _hip, device
-        f = self._field(f)
+        f = field_on(self.V, f, 'f', 'these isolines were')
         levels = _levels(levels)
-        _no_strips()
+        ops._no_strips('Isolines')
         lib = _hip.lib()
         V = self.V
         nc = V.mesh().num_cells()
@@ -321,9 +294,9 @@ class Isolines(object):
         '''numpy (nlevels, 2): length and area per level; one read-back.'''
         import ctypes
         from .. import _hip, device
-        f = self._field(f)
+        f = field_on(self.V, f, 'f', 'these isolines were')
         levels = _levels(levels)
-        _no_strips()
+        ops._no_strips('Isolines')
         lib = _hip.lib()
         V = self.V
         nc = V.mesh().num_cells()

@@ -31,10 +31,9 @@ how many vortices are there, where is each one and how strong is it?
 Definitions (csrc/region_kernels.hip; tests/regions_reference.py restates them
 in numpy).
 
-  * The graph is Isolines' and Distance's P1 triangulation of the dofs: on P1
-    the cells; on P2 every cell cut into its three corner triangles and the
-    middle one.  The two vertices of a P2 edge are therefore no neighbours:
-    the mid point lies between them.
+  * The graph is the P1 triangulation of the dofs (csrc/subtri.h), Isolines'
+    and Distance's.  The two vertices of a P2 edge are therefore no
+    neighbours: the mid point lies between them.
   * A dof with a non-finite value is outside.  Two inside dofs joined by a
     sub-edge are in one component; since f_h is linear on a sub-triangle these
     are exactly the components of {f_h >= c}.  A component's label is its
@@ -44,8 +43,7 @@ in numpy).
     piece.  With 3 inside dofs the piece is the sub-triangle, with 1 the
     corner at that node, with 2 (A, B inside, C outside) the quadrilateral A,
     B, Q, P, P on A-C and Q on B-C, cut by the diagonal A-Q.  Crossings are
-    Isolines': from the lower dof of the sub-edge to the higher, so that
-    neighbouring cells compute the same bits.  All inside dofs of a
+    Isolines', by the one rule of subtri.h.  All inside dofs of a
     sub-triangle share a component, which owns the piece; the four
     sub-triangles of a P2 cell may belong to different components.
   * Per piece the integrals of 1, x, y and g_a, g the true P1 / P2 polynomial
@@ -71,17 +69,15 @@ one time step to the next; not on strips.
 '''
 import numpy
 
+from . import ops
+from ._levelset import field_on, scalar_p12_space, sweep_to_fixed_point
+
 # sweeps per batch, one read-back of the flag behind each: of 4, 8 and 32 on
 # the bench mesh the fastest on P2 and level with 4 on P1 (DESIGN.md, section
 # 3, "Regions", has the table)
 CHECK_EVERY = 8
 
 SIDES = {'above': 0, 'below': 1}
-
-
-def _no_strips():
-    from .ops import _no_strips as refuse
-    refuse('Regions')
 
 
 def segment_offsets(sorted_keys, count):
@@ -137,7 +133,7 @@ class Components(object):
         import torch
         from .. import device
         W = self._operand(g, 'integrate')
-        _no_strips()
+        ops._no_strips('Regions')
         out = torch.empty((W.dim, self.count), dtype=torch.float64,
                           device=device.get())
         if self.count:
@@ -156,7 +152,7 @@ class Components(object):
         if W.degree != self.V.degree:
             raise ValueError('g: extrema runs over the dofs of V: a Function '
                              'on V or on the vector space of its degree')
-        _no_strips()
+        ops._no_strips('Regions')
         dev = device.get()
         lo = torch.empty((W.dim, self.count), dtype=torch.float64, device=dev)
         hi = torch.empty((W.dim, self.count), dtype=torch.float64, device=dev)
@@ -192,34 +188,12 @@ class Regions(object):
     once.'''
 
     def __init__(self, V):
-        if not hasattr(V, 'layout'):
-            raise NotImplementedError(
-                'V: a mixed space; label a Function on one of its scalar '
-                'sub-spaces')
-        if getattr(V, 'component', None) is not None:
-            raise NotImplementedError(
-                'V: a component view (W.sub(i)); regions are those of a '
-                'scalar field: use W.sub(i).collapse()')
-        if V.dim != 1:
-            raise NotImplementedError(
-                'V: %r components; regions are those of a scalar field'
-                % (V.dim,))
-        if V.degree not in (1, 2):
-            raise NotImplementedError(
-                'V: P%r; Regions takes P1 or P2' % (V.degree,))
-        _no_strips()
+        scalar_p12_space(V, 'label a Function on',
+                         'regions are those of a scalar field', 'Regions')
+        ops._no_strips('Regions')
         self.V = V
         self.nslots = (1 if V.degree == 1 else 4) * V.mesh().num_cells()
         self._dev = None
-
-    def _field(self, f):
-        from .function import Function
-        if not isinstance(f, Function) \
-                or getattr(f.function_space(), 'component', None) is not None \
-                or not f.function_space().same_as(self.V):
-            raise ValueError('f: not a Function on the space these regions '
-                             'were built for')
-        return f
 
     def _buffers(self):
         '''(label buffer a, b, flag, keys, integrals of the pieces).'''
@@ -235,29 +209,13 @@ class Regions(object):
         return self._dev
 
     def _structs(self):
-        from .ops import mesh_struct, space_struct
-        return mesh_struct(self.V.mesh()), space_struct(self.V.layout)
-
-    def _batch(self, a, b, flag, nsweeps):
-        '''nsweeps sweeps from a; (result, other buffer, flag as an int).'''
-        import ctypes
-        from .. import _hip, device
-        mesh_s, space_s = self._structs()
-        N = self.V.N
-        flag.zero_()
-        _hip.check(_hip.lib().flow_region_sweeps(
-            ctypes.byref(mesh_s), ctypes.byref(space_s), nsweeps,
-            _hip.i32(a, N, 'label buffer'), _hip.i32(b, N, 'label buffer'),
-            _hip.i32(flag, 1, 'flag'), _hip.stream()))
-        if nsweeps % 2:
-            a, b = b, a
-        return a, b, int(device.to_host(flag)[0])
+        return (ops.mesh_struct(self.V.mesh()),
+                ops.space_struct(self.V.layout))
 
     def _moments(self, f, level, ids, g, keys):
         '''Launch flow_region_moments; the (3 + ncomp, nslots) integrals.'''
         import ctypes
         from .. import _hip
-        from .ops import space_struct
         mesh_s, space_s = self._structs()
         V = self.V
         vals = self._buffers()[4]
@@ -266,7 +224,7 @@ class Regions(object):
         else:
             W = g.function_space()
             ncomp = W.dim
-            G = ctypes.byref(space_struct(W.layout))
+            G = ctypes.byref(ops.space_struct(W.layout))
             gp = _hip.f64(g.data, ncomp * W.N, 'g')
         _hip.check(_hip.lib().flow_region_moments(
             ctypes.byref(mesh_s), ctypes.byref(space_s),
@@ -293,7 +251,7 @@ class Regions(object):
         import ctypes
         import torch
         from .. import _hip, device
-        f = self._field(f)
+        f = field_on(self.V, f, 'f', 'these regions were')
         try:
             level = float(level)
         except (TypeError, ValueError):
@@ -302,24 +260,23 @@ class Regions(object):
             raise ValueError('level: must be finite, got %r' % (level,))
         if side not in SIDES:
             raise ValueError("side: 'above' or 'below', got %r" % (side,))
-        _no_strips()
+        ops._no_strips('Regions')
         lib = _hip.lib()
         V, N = self.V, self.V.N
         a, b, flag, keys, _ = self._buffers()
-        _, space_s = self._structs()
+        mesh_s, space_s = self._structs()
         _hip.check(lib.flow_region_init(
             ctypes.byref(space_s), _hip.f64(f.data, N, 'f'), level,
             SIDES[side], _hip.i32(a, N, 'labels'), _hip.stream()))
-        sweeps = 0
-        while True:
-            if sweeps > N:
-                raise _hip.NotConverged(
-                    'regions: no fixed point after %d sweeps on %d dofs'
-                    % (sweeps, N))
-            a, b, lowered = self._batch(a, b, flag, CHECK_EVERY)
-            sweeps += CHECK_EVERY
-            if not lowered:
-                break
+
+        def enqueue(a, b, nsweeps):
+            _hip.check(lib.flow_region_sweeps(
+                ctypes.byref(mesh_s), ctypes.byref(space_s), nsweeps,
+                _hip.i32(a, N, 'label buffer'), _hip.i32(b, N, 'label buffer'),
+                _hip.i32(flag, 1, 'flag'), _hip.stream()))
+
+        a, b, sweeps = sweep_to_fixed_point(
+            enqueue, a, b, flag, CHECK_EVERY, N, 'regions')
         # compact ids: plumbing on ints
         dev = device.get()
         is_root = a == torch.arange(N, dtype=torch.int32, device=dev)

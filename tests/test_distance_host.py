@@ -157,7 +157,7 @@ def test_a_node_no_path_reaches_keeps_inf():
 
 # -- the kernel's sub-triangles ------------------------------------------------------
 def _kernel_triangles(deg, i):
-    '''sub_triangle<DEG>(i, k, la, lb) of csrc/distance_kernels.hip, restated.'''
+    '''sub_triangle<DEG>(i, k, la, lb) of csrc/subtri.h, restated.'''
     if deg == 1:
         return [((i + 1) % 3, (i + 2) % 3)]
     e = i % 3

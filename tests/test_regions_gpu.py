@@ -254,6 +254,70 @@ def test_areas_against_isolines_and_the_mesh(hip, name, deg):
     assert ((host(up.labels) >= 0) != (host(down.labels) >= 0)).all()
 
 
+def _triangle_area(a, b, c):
+    '''add_triangle's formula (csrc/region_kernels.hip), in fp64.'''
+    return 0.5 * abs((b[0] - a[0]) * (c[1] - a[1]) - (c[0] - a[0]) * (b[1] - a[1]))
+
+
+@pytest.mark.parametrize('deg', [1, 2])
+@pytest.mark.parametrize('name', ['one', 'crossed 5x4'])
+def test_pieces_end_on_the_crossings_of_isolines(hip, name, deg):
+    '''Regions cuts a sub-triangle at the crossings Isolines emits (one
+    `cross` in csrc/subtri.h): the area of every cut piece, rebuilt on the
+    host from the end points of that sub-triangle's segment in Contours.xy
+    and the positions of its inside nodes, is the slot's area of the moments
+    launch.  Both sides evaluate add_triangle's expression on the same bits;
+    the kernel may contract its two products into one fma and the host does
+    not, a difference of at most 2^-53 (|u_x v_y| + |v_x u_y|) per triangle:
+    1e-14 relative leaves a factor of 90 for the pieces' shape.'''
+    from isolines_reference import SUBS
+    V, level = _space(name, deg), 0.25
+    mesh, cell_dofs = V.mesh(), numpy.asarray(V.layout.cell_dofs)
+    nc = mesh.num_cells()
+    values = nodal(V, _wave)
+    f = function(V, values)
+    R = fem.Regions(V)
+    assert R.label(f, level).count >= 1
+    keys = host(R._buffers()[3]).reshape(-1, nc)
+    areas = host(R._buffers()[4][0]).reshape(-1, nc)
+    S = fem.Isolines(V).extract(f, level)
+    xy, cell, skeys = host(S.xy), host(S.cell), host(S.keys)
+    seen, worst = {1: 0, 2: 0}, 0.0
+    for k in range(S.nseg):
+        c, dofs = cell[k], cell_dofs[cell[k]]
+        v = mesh.points[mesh.cell_vertices[c]]
+        X = [v[0], v[1], v[2], 0.5 * (v[1] + v[2]), 0.5 * (v[0] + v[2]),
+             0.5 * (v[0] + v[1])]
+        (s,) = [s for s, sub in enumerate(SUBS[deg])
+                if set(dofs[list(sub)]) == set(skeys[k])]
+        sub = SUBS[deg][s]
+        assert keys[s, c] >= 0                 # Regions holds a piece of it
+        # P, alone on its side: the dof on both crossed sub-edges; Q and R
+        # behind it in the cell's cyclic order
+        (lone,) = set(skeys[k, :2]) & set(skeys[k, 2:])
+        p = [dofs[m] for m in sub].index(lone)
+        P, Q, Rn = sub[p], sub[(p + 1) % 3], sub[(p + 2) % 3]
+        ends = {frozenset(skeys[k, :2].tolist()): xy[k, :2],
+                frozenset(skeys[k, 2:].tolist()): xy[k, 2:]}
+        pq = ends[frozenset((dofs[P], dofs[Q]))]
+        pr = ends[frozenset((dofs[P], dofs[Rn]))]
+        nin = int((values[dofs[list(sub)]] >= level).sum())
+        if nin == 1:
+            assert values[lone] >= level
+            want = _triangle_area(X[P], pq, pr)
+        else:
+            assert nin == 2 and values[lone] < level
+            want = _triangle_area(X[Q], X[Rn], pr) + _triangle_area(X[Q], pr, pq)
+        seen[nin] += 1
+        assert want > 0.0
+        worst = max(worst, abs(areas[s, c] - want) / want)
+    print('%s P%d: %d pieces with one inside node, %d with two: areas differ by '
+          '%.2e relative at most' % (name, deg, seen[1], seen[2], worst))
+    # what the case claims: one node alone above in some sub-triangle, two in another
+    assert seen[1] >= 1 and seen[2] >= 1
+    assert worst <= 1e-14
+
+
 # -- 5. a P2 cell split between two components -----------------------------------------
 def test_two_components_in_one_p2_cell(hip):
     V = _space('one', 2)
