@@ -49,6 +49,16 @@ struct Vals4 {              // the values of four nonzeros: 8 B (half), 16 B (ha
 };
 static_assert(sizeof(Vals4<__half>) == 8 && sizeof(Vals4<__half2>) == 16,
               "packed quad");
+// half(x) of an fp64 value in ONE rounding to nearest even (the setup kernels:
+// the scaled entries v * (1 / d)).  Written through float -- half(float(x)) --
+// the value would be rounded twice, one fp16 ulp off wherever x lies within
+// half a float ulp of a tie of the fp16 grid (2^-13 of all entries), unless the
+// compiler folds the two conversions into this one: it does on gfx950, so this
+// is what the streams have always held (tests/test_fp16_streams_gpu.py compares
+// them bit for bit).
+__device__ __forceinline__ __half half_rn(double x) {
+  return __half(static_cast<_Float16>(x));
+}
 __device__ __forceinline__ float widen(__half h) { return __half2float(h); }
 __device__ __forceinline__ float2 widen(__half2 h) { return __half22float2(h); }
 template <class T4>

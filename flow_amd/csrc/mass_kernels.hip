@@ -318,7 +318,7 @@ __global__ void mass_pack_kernel(int n, const int* __restrict__ rowptr,
        i += gridDim.x * blockDim.x) {
     const double inv = 1.0 / vals[diag_idx[i]];
     for (int k = rowptr[i]; k < rowptr[i + 1]; ++k)
-      vals16[k] = __float2half_rn(static_cast<float>(vals[k] * inv));
+      vals16[k] = half_rn(vals[k] * inv);
   }
 }
 
@@ -341,8 +341,7 @@ __global__ __launch_bounds__(kBlock) void mass_pack16_kernel(
     for (int k = rowptr[r]; k < rowptr[r + 1]; ++k) {
       const int off = cols[k] - base;
       if (off > 0xffff) atomicOr(overflow, 1);
-      const unsigned short h =
-          __half_as_ushort(__float2half_rn(static_cast<float>(vals[k] * inv)));
+      const unsigned short h = __half_as_ushort(half_rn(vals[k] * inv));
       packed[k] = (static_cast<unsigned>(off & 0xffff) << 16) | h;
     }
   }

@@ -259,8 +259,7 @@ __global__ void pmg_pack_kernel(int n, const int* __restrict__ rowptr,
     dinv[i] = f2(static_cast<float>(i0), static_cast<float>(i1));
     for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
       const bool in = keep == nullptr || keep[k] != 0;
-      vals[k] = in ? __floats2half2_rn(static_cast<float>(a00[k] * i0),
-                                       static_cast<float>(a11[k] * i1))
+      vals[k] = in ? __halves2half2(half_rn(a00[k] * i0), half_rn(a11[k] * i1))
                    : __floats2half2_rn(0.f, 0.f);
     }
   }
@@ -332,8 +331,7 @@ __global__ __launch_bounds__(kBlock) void pmg_pack1_kernel(
       else if (u1)
         v = a11[k];
     }
-    const unsigned short h =
-        __half_as_ushort(__float2half_rn(static_cast<float>(v * inv)));
+    const unsigned short h = __half_as_ushort(half_rn(v * inv));
     packed[k] = (static_cast<unsigned>((j - base) & 0xffff) << 16) | h;
   }
 }
