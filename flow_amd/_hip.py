@@ -470,6 +470,10 @@ SYMBOLS = {
                                    _P(_D), _VP],
     'flow_form_facet_values': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP,
                                _VP, _VP, _VP],
+    'flow_form_facet_matrix': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _VP,
+                               _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'flow_form_facet_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _VP,
+                               _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_profile_cumsum': [_I, _P(_I), _I, _I, _VP, _VP, _VP],
     'flow_locate_points': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _VP, _VP],
     'flow_form_points': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP],

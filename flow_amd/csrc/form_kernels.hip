@@ -1024,6 +1024,128 @@ __global__ __launch_bounds__(kBlock) void form_newton_kernel(
     dst[static_cast<size_t>(NL * NL + i) * nc] = be[i];
 }
 
+// ---------------------------------------------------------------------------
+// Forms of arguments over exterior facets (Neumann, Robin and Nitsche terms:
+// g*v*ds, h*u*v*ds, dot(grad(u), n)*v*ds).  A boundary holds O(sqrt(N))
+// facets, so a facet is shared by NL lanes: lane (i, k) -- k the position in
+// the facet list, fastest -- holds row i of the element matrix of facet k's
+// owning cell (RANK 2: NL doubles) or entry i of its element vector (RANK 1:
+// one).  ALL NL basis functions of the cell take part: the gradient of the
+// off-edge one does not vanish on the edge.  Geometry, normal, edge length
+// and the rows of the rule are those of form_facet; per point the arithmetic
+// is that of form_matrix_kernel / form_vector_kernel with w = rule weight x
+// edge length: t_j = sum_a w c_ba D_a phi_j, then Ke[i][j] += D_b phi_i t_j.
+// Entries go to scratch[(i*NL + j)*nfacets + k] (RANK 2) or
+// scratch[i*nfacets + k] (RANK 1); facet_gather_kernel sums them.  A facet
+// outside the mesh gives NaN, not a stray read.
+// ---------------------------------------------------------------------------
+template <int NF, int DEG, bool EXT, int RANK>
+__global__ __launch_bounds__(kBlock) void form_facet_arguments_kernel(
+    int nc, int nfacets, const int* __restrict__ fcell,
+    const int* __restrict__ flocal, const double* __restrict__ xy,
+    const flow_form F, int live, double* __restrict__ scratch) {
+  constexpr int NL = Elem<DEG>::NL;
+  constexpr int NR = RANK == 2 ? NL : 1;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= nfacets * NL) return;
+  const int i = idx / nfacets, k = idx - i * nfacets;
+  double* const dst = scratch + static_cast<size_t>(i) * NR * nfacets + k;
+  const int c = fcell[k], lf = flocal[k];
+  if (c < 0 || c >= nc || lf < 0 || lf > 2) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j)
+      dst[static_cast<size_t>(j) * nfacets] = __builtin_nan("");
+    return;
+  }
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
+  // (selects, not g.gl[lf]: a run-time index would put g in scratch memory)
+  const double gx = lf == 0 ? g.gl[0][0] : (lf == 1 ? g.gl[1][0] : g.gl[2][0]);
+  const double gy = lf == 0 ? g.gl[0][1] : (lf == 1 ? g.gl[1][1] : g.gl[2][1]);
+  const double gn = sqrt(gx * gx + gy * gy);
+  const double n0 = -gx / gn, n1 = -gy / gn;
+  const double len = g.adet * gn;
+  double acc[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) acc[j] = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const int row = lf * F.nq + q;
+    const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
+    const double w = F.rule[3 * row + 2] * len;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlots<RANK == 2 ? FLOW_FORM_SLOTS : 3> out;
+#pragma unroll
+    for (int s = 0; s < (RANK == 2 ? FLOW_FORM_SLOTS : 3); ++s) out.v[s] = 0.0;
+    form_point_n<NF, true, EXT>(F, U, X, Y, g, L, row, nc, c, n0, n1, out);
+    double phi[NL], dphi[NL][3], gphi[NL][2];
+    basis<DEG>(L, phi, dphi);
+    phys_grad<NL>(g, dphi, gphi);
+    // (the mask through an empty asm, as in form_matrix_kernel)
+    int m = live;
+    asm volatile("" : "+s"(m));
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if constexpr (RANK == 2) {
+        if (((m >> (3 * b)) & 7) == 0) continue;
+      } else {
+        if (((m >> b) & 1) == 0) continue;
+      }
+      // D_b phi_i of the lane's own test function (selects: a run-time index
+      // would put the tables in scratch memory)
+      double di = 0.0;
+#pragma unroll
+      for (int t = 0; t < NL; ++t) di = t == i ? arg_basis<NL>(b, phi, gphi, t) : di;
+      if constexpr (RANK == 2) {
+        double t[NL];
+#pragma unroll
+        for (int j = 0; j < NL; ++j) t[j] = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          if (((m >> (3 * b + a)) & 1) == 0) continue;
+          const double s = w * out.v[3 * b + a];
+#pragma unroll
+          for (int j = 0; j < NL; ++j) t[j] += s * arg_basis<NL>(a, phi, gphi, j);
+        }
+#pragma unroll
+        for (int j = 0; j < NL; ++j) acc[j] += di * t[j];
+      } else {
+        acc[0] += (w * out.v[b]) * di;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NR; ++j) dst[static_cast<size_t>(j) * nfacets] = acc[j];
+}
+
+// The gather over the facet contribution map (ops.facet_map): one lane per
+// target adds scratch[src[e]], e in [ptr[t], ptr[t+1]), in that order and
+// writes out[targets[t]]; the rest of `out` is not touched.  No atomics: two
+// calls give the same bits.  A target outside `out` is skipped; a row of ptr or
+// an entry of src outside the scratch gives NaN, not a stray read.
+__global__ __launch_bounds__(kBlock) void facet_gather_kernel(
+    int ntargets, const int* __restrict__ targets, const int* __restrict__ ptr,
+    const int* __restrict__ src, int nsrc, const double* __restrict__ scratch,
+    int nout, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ntargets) return;
+  const int tg = targets[t];
+  if (tg < 0 || tg >= nout) return;
+  const int b = ptr[t], e = ptr[t + 1];
+  double s = 0.0;
+  if (b < 0 || e > nsrc || b > e) {
+    s = __builtin_nan("");
+  } else {
+    for (int q = b; q < e; ++q) {
+      const int x = src[q];
+      s += (x >= 0 && x < nsrc) ? scratch[x] : __builtin_nan("");
+    }
+  }
+  out[tg] = s;
+}
+
 // rows: the rule holds rows * nq points (1: cells; 3: the three local
 // facets); facet: NORMAL is legal; points: the program runs at located
 // points -- no rule, no Expression lattices (they are tabulated at the
@@ -1347,6 +1469,79 @@ static int launch_newton(const flow_mesh* mesh, const flow_form* F, int live,
   return FLOW_OK;
 }
 
+template <int DEG, int RANK>
+static int launch_facet_arguments(const flow_mesh* mesh, const flow_form* F, int live,
+                                  int nfacets, const int* fcell, const int* flocal,
+                                  double* scratch, hipStream_t st) {
+  const dim3 grid((nfacets * (DEG == 1 ? 3 : 6) + kBlock - 1) / kBlock);
+  const bool ext = form_is_extended(F);
+  switch (F->nfield) {
+#define FLOW_FORM_FACET_ARGS_CASE(NF)                                            \
+    case NF:                                                                     \
+      if (ext)                                                                   \
+        hipLaunchKernelGGL((form_facet_arguments_kernel<NF, DEG, true, RANK>),   \
+                           grid, dim3(kBlock), 0, st, mesh->nc, nfacets, fcell,  \
+                           flocal, mesh->xy, *F, live, scratch);                 \
+      else                                                                       \
+        hipLaunchKernelGGL((form_facet_arguments_kernel<NF, DEG, false, RANK>),  \
+                           grid, dim3(kBlock), 0, st, mesh->nc, nfacets, fcell,  \
+                           flocal, mesh->xy, *F, live, scratch);                 \
+      break;
+    FLOW_FORM_FACET_ARGS_CASE(0)
+    FLOW_FORM_FACET_ARGS_CASE(1)
+    FLOW_FORM_FACET_ARGS_CASE(2)
+    FLOW_FORM_FACET_ARGS_CASE(3)
+    FLOW_FORM_FACET_ARGS_CASE(4)
+    FLOW_FORM_FACET_ARGS_CASE(5)
+    default:
+    FLOW_FORM_FACET_ARGS_CASE(6)
+#undef FLOW_FORM_FACET_ARGS_CASE
+  }
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+// flow_form_facet_matrix (RANK 2) / flow_form_facet_vector (RANK 1)
+template <int RANK>
+static int facet_arguments(const flow_mesh* mesh, const flow_space* V,
+                           const flow_form* form, int nfacets, const int* facet_cell,
+                           const int* facet_local, int ntargets, const int* map_targets,
+                           const int* map_ptr, const int* map_src, double* scratch,
+                           double* out, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  int live = 0;
+  if ((rc = check_form(form, 3, true, false, RANK == 2 ? FLOW_FORM_SLOTS : 3, &live)))
+    return rc;
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 &&
+                   (RANK == 1 || V->nnz > 0) && V->cell_dofs,
+               "space");
+  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(nfacets >= 0 && ntargets >= 0, "facet / target count");
+  if (nfacets == 0 || ntargets == 0) return FLOW_OK;
+  const int nl = V->deg == 1 ? 3 : 6;
+  const long long nsrc = static_cast<long long>(nfacets) * nl * (RANK == 2 ? nl : 1);
+  FLOW_REQUIRE(nsrc < (1LL << 31) - kBlock, "facet count (scratch entries)");
+  FLOW_REQUIRE(ntargets <= (RANK == 2 ? V->nnz : V->n) && ntargets <= nsrc,
+               "target count");
+  FLOW_REQUIRE(facet_cell && facet_local, "facet lists");
+  FLOW_REQUIRE(map_targets && map_ptr && map_src, "facet contribution map");
+  FLOW_REQUIRE(scratch && out, "pointers");
+  hipStream_t st = as_stream(stream);
+  rc = V->deg == 1
+           ? launch_facet_arguments<1, RANK>(mesh, form, live, nfacets, facet_cell,
+                                             facet_local, scratch, st)
+           : launch_facet_arguments<2, RANK>(mesh, form, live, nfacets, facet_cell,
+                                             facet_local, scratch, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(facet_gather_kernel, dim3((ntargets + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, st, ntargets, map_targets, map_ptr, map_src,
+                     static_cast<int>(nsrc), scratch, RANK == 2 ? V->nnz : V->n, out);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
 }  // namespace flow
 
 using namespace flow;
@@ -1620,4 +1815,24 @@ extern "C" int flow_form_newton(const flow_mesh* mesh, const flow_space* V,
   return gather(V->n, 1, V->vptr, V->vsrc,
                 scratch + static_cast<size_t>(nl) * nl * mesh->nc,
                 static_cast<size_t>(nl) * mesh->nc, b, st);
+}
+
+extern "C" int flow_form_facet_matrix(const flow_mesh* mesh, const flow_space* V,
+                                      const flow_form* form, int nfacets,
+                                      const int* facet_cell, const int* facet_local,
+                                      int ntargets, const int* map_targets,
+                                      const int* map_ptr, const int* map_src,
+                                      double* scratch, double* vals, void* stream) {
+  return facet_arguments<2>(mesh, V, form, nfacets, facet_cell, facet_local, ntargets,
+                            map_targets, map_ptr, map_src, scratch, vals, stream);
+}
+
+extern "C" int flow_form_facet_vector(const flow_mesh* mesh, const flow_space* V,
+                                      const flow_form* form, int nfacets,
+                                      const int* facet_cell, const int* facet_local,
+                                      int ntargets, const int* map_targets,
+                                      const int* map_ptr, const int* map_src,
+                                      double* scratch, double* b, void* stream) {
+  return facet_arguments<1>(mesh, V, form, nfacets, facet_cell, facet_local, ntargets,
+                            map_targets, map_ptr, map_src, scratch, b, stream);
 }

@@ -26,7 +26,7 @@ from .forms import (                                            # noqa: F401
     ln, sin, cos, dot, inner, grad, div, curl, TestFunction, TrialFunction,
     lhs, rhs, system, dS, derivative, action, adjoint,
     conditional, lt, le, gt, ge, eq, ne, And, Or, Not, max_value, min_value,
-    sign, tanh, CellVolume, Circumradius, CellDiameter,
+    sign, tanh, CellVolume, Circumradius, CellDiameter, facet_arguments,
     )
 from .points import Probes                                      # noqa: F401
 from .tracers import Tracers                                    # noqa: F401

@@ -406,8 +406,6 @@ def _check_forms(a, m, symmetric):
         elif not W.same_as(V):
             raise ValueError('a and m: forms on different spaces')
         for _, part in f.terms():
-            if part.integral_type != 'cell':
-                raise NotImplementedError('test and trial functions under ds')
             if not symmetric and \
                     not forms.is_symmetric_table(part.argument_table()[1]):
                 raise ValueError(

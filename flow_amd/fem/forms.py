@@ -58,10 +58,24 @@ argument is a ValueError.  The coefficients c are argument-free scalar trees;
 they compile to one Program with one output slot per term (3 b + a, or b).
 `form_compiler_parameters={'quadrature_rule': 'vertex'}` integrates with the
 cell vertices and weights |T|/3 (the lumped mass matrix of u*v*dx).
+Arguments under ds (Neumann, Robin and Nitsche terms) are OFF by default, as
+they always were (NotImplementedError); `facet_arguments(True)` switches them
+on for the process (it returns the previous setting; `with
+facet_arguments(True): ...` restores it on exit).  Then `g*v*ds(2)`,
+`h*u*v*ds(1)`, `-dot(grad(u), n)*v*ds` are forms of integral_type
+'exterior_facet' and rank 1 or 2; FacetNormal stays legal there, all the dofs
+of the owning cell take part (grad(u) of the off-edge basis function is not
+zero on the edge), and rank, arguments(), argument_table(), lhs / rhs / system
+and is_symmetric_table work on them as on dx parts -- h*(u - u_inf)*v*ds
+splits into its Robin pair.  They are assembled by one lane per (facet, local
+test dof) and a gather over the facet contribution map (ops.facet_map).
+Refused there: 'quadrature_rule': 'vertex' (ValueError: the vertex rule is a
+rule of cells) and strips (NotImplementedError).  The limit on field
+components is that of every program (MAX_FIELDS): the kernel's instance for
+six fields still runs without scratch memory or spills.
 Not supported (NotImplementedError): arguments on vector or mixed spaces, test
-and trial functions of different spaces, arguments under ds (Neumann / Robin
-terms: the facet gather needs a contribution map that does not exist yet),
-dS, action / adjoint.  lhs / rhs also split ONE integrand that holds terms of
+and trial functions of different spaces, dS, action / adjoint.  lhs / rhs
+also split ONE integrand that holds terms of
 both ranks, (source - dot(conv, grad(u))) * tau * dot(conv, grad(v)) * dx, by
 linearity, as UFL does; assembling such an integrand unsplit stays a
 ValueError.
@@ -81,10 +95,13 @@ bilinear form.  A derived part keeps the quadrature degree of the part it
 came from (unless metadata fixes one): for integrands polynomial in u that IS
 UFL's estimate -- replacing a factor u by du of the same space leaves the sum
 of degrees unchanged --, for the others it differs from dolfin's by
-quadrature error, like the estimates above.  Refused: a rank-2 form (the
-result would be a rank-3 form), u on a vector, component or mixed space,
-rank-0 ds parts (the argument would land under ds), a form that does not
-depend on u, u of another space than the form's arguments.  `F == 0` is the
+quadrature error, like the estimates above.  ds parts are derived like dx
+parts (a rank-0 ds functional gives a rank-1 ds form, a rank-1 ds residual
+part a rank-2 ds part) and keep their subdomain id and subdomain data too
+-- with facet_arguments(True); without it a ds part that holds u is refused.
+Refused: a rank-2 form (the result would be a rank-3 form), u on a vector,
+component or mixed space, a form that does not depend on u, u of another
+space than the form's arguments.  `F == 0` is the
 Equation of the nonlinear solve(F == 0, u, bcs, J=...) (ops.solve: Newton);
 a form of any rank compared with the number 0 gives one (solve refuses what
 is not a residual), any other number is a ValueError.
@@ -1085,6 +1102,33 @@ def _is_mesh(obj):
     return hasattr(obj, 'num_cells') and hasattr(obj, 'bfacets')
 
 
+class facet_arguments(object):
+    '''The switch of test and trial functions under ds (Neumann, Robin and
+    Nitsche terms).  Off by default: `v*ds` and derivative() of a ds part stay
+    the NotImplementedError they were.  `facet_arguments(True)` switches them
+    on at once, for the process; `.previous` is the setting it replaced, and
+    as a context manager it restores that on exit.  `facet_arguments.enabled`
+    is the current setting.'''
+    enabled = False
+
+    def __init__(self, on=True):
+        self.previous = facet_arguments.enabled
+        facet_arguments.enabled = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        facet_arguments.enabled = self.previous
+        return False
+
+
+_FACET_ARGUMENTS_OFF = (
+    'test and trial functions under ds (Neumann and Robin terms): '
+    'the facet gather needs a contribution map that is built only after '
+    'facet_arguments(True); they are off by default')
+
+
 class Measure(object):
     '''`dx` over the cells, `ds` over the exterior facets (UFL's
     Measure(integral_type, domain, subdomain_id, metadata, subdomain_data)).
@@ -1130,11 +1174,13 @@ class Measure(object):
         if self.integral_type == 'cell':
             check_no_normal(f, 'a dx integral')
             return Form(f, _join_mesh(f.mesh, self.mesh), self.metadata)
-        if has_leaf(f.comps, 'arg'):
-            raise NotImplementedError(
-                'test and trial functions under ds (Neumann and Robin terms): '
-                'the facet gather needs a contribution map that does not '
-                'exist yet')
+        if has_leaf(f.comps, 'arg') and not facet_arguments.enabled:
+            raise NotImplementedError(_FACET_ARGUMENTS_OFF)
+        if has_leaf(f.comps, 'arg') and quadrature_scheme(
+                self.metadata) == 'vertex':
+            raise ValueError(
+                "quadrature_rule 'vertex' on a ds part with test or trial "
+                "functions: the vertex rule is a rule of cells")
         mesh = _join_mesh(f.mesh, self.mesh)
         if self.subdomain_data is not None:
             mesh = _join_mesh(mesh, self.subdomain_data.mesh)
@@ -1404,16 +1450,15 @@ def derivative(F, u, du=None):
         tree = s_gateaux(part.integrand.comps, u, k, V)
         if _is_num(tree, 0.0):
             continue
-        if part.integral_type != 'cell':
-            raise NotImplementedError(
-                'derivative of a ds part: test and trial functions under ds '
-                '(Neumann and Robin terms): the facet gather needs a '
-                'contribution map that does not exist yet')
+        if part.integral_type != 'cell' and not facet_arguments.enabled:
+            raise NotImplementedError('derivative of a ds part: '
+                                      + _FACET_ARGUMENTS_OFF)
         mesh = _join_mesh(_join_mesh(part.integrand.mesh, part.mesh),
                           V.mesh())
         # (the degree of the part it came from: see the module docstring)
         derived = Form(FormExpr(tree, (), part.integrand.deg, mesh), mesh,
-                       part.metadata)
+                       part.metadata, part.integral_type, part.subdomain_id,
+                       part.subdomain_data)
         derived.derived_from = part
         parts.append((sign, derived))
     if not parts:
@@ -1631,16 +1676,17 @@ class Program(object):
         return out
 
 
-def argument_program(table, rank):
+def argument_program(table, rank, facet=False):
     '''The Program of a coefficient table (argument_table): rank 2, slot
-    3 b + a of 9; rank 1, slot b of 3; absent terms have no instruction.'''
+    3 b + a of 9; rank 1, slot b of 3; absent terms have no instruction.
+    facet: the table of a ds part (the normal exists).'''
     if rank == 2:
         items = [(3 * b + a, table[b][a]) for b in range(3) for a in range(3)]
     else:
         items = list(enumerate(table))
     items = [(k, t) for k, t in items if t is not None]
     return Program([t for _, t in items], slots=[k for k, _ in items],
-                   nout=9 if rank == 2 else 3)
+                   nout=9 if rank == 2 else 3, facet=facet)
 
 
 def _select_order(n):
@@ -1784,15 +1830,16 @@ def newton_program(tableJ, tableF, share=True):
                    shared=shared)
 
 
-def argument_programs(table, rank):
+def argument_programs(table, rank, facet=False):
     '''The coefficient table as a list of Programs whose cell tensors add up
     to the form's: [argument_program(table, rank)] where that fits the
     limits of flow_form; else the slots are dealt, in order, to as few
     programs as fit (each with its common subtrees computed once, as
     newton_program's), and the caller sums what they assemble.  ValueError
-    where one coefficient alone exceeds a limit.'''
+    where one coefficient alone exceeds a limit.  facet: the table of a ds
+    part, whose coefficients may read the normal.'''
     try:
-        return [argument_program(table, rank)]
+        return [argument_program(table, rank, facet)]
     except ValueError:
         pass
     if rank == 2:
@@ -1806,11 +1853,12 @@ def argument_programs(table, rank):
         try:
             shared, trees = share_subtrees([t for _, t in chunk])
             return Program(trees, slots=[k for k, _ in chunk], nout=nout,
-                           shared=shared)
+                           shared=shared, facet=facet)
         except ProgramLimit:
             # (subtrees that repeat inside one coefficient, too)
             return compile_trees([t for _, t in chunk],
-                                 slots=[k for k, _ in chunk], nout=nout)
+                                 slots=[k for k, _ in chunk], nout=nout,
+                                 facet=facet)
 
     progs, chunk = [], []
     for item in items:

@@ -961,8 +961,11 @@ def assemble(form, form_compiler_parameters=None):
     '''By the rank of the form.  0: assemble(f*dx), assemble(f*ds(k)) and
     signed sums of such forms -- the integral of a scalar integrand over the
     cells or the exterior facets of the mesh, a float.  1: forms of a
-    TestFunction, a Vector.  2: forms of a TrialFunction and a TestFunction
-    (over dx), a Matrix of kind 0 on the space's pattern.  The parts of a sum
+    TestFunction, a Vector.  2: forms of a TrialFunction and a TestFunction,
+    a Matrix of kind 0 on the space's pattern.  Parts of rank 1 and 2 over ds
+    (Neumann, Robin, Nitsche terms: forms.facet_arguments(True) allows them)
+    go through flow_form_facet_vector / flow_form_facet_matrix and the facet contribution map (facet_map); an
+    empty selection, ds(99), contributes zero.  The parts of a sum
     are assembled one by one, each at its own degree, and added in the order
     written; fixed-order reductions and gathers on the device: the same bits
     on every call.  form_compiler_parameters: 'quadrature_degree' replaces
@@ -1014,8 +1017,9 @@ def assemble(form, form_compiler_parameters=None):
 
 def _assemble_arguments(form, rank, form_compiler_parameters=None):
     '''assemble() of a form, or of a signed sum of forms, of rank 1 (a
-    Vector) or 2 (a Matrix): flow_form_vector / flow_form_matrix per part
-    (per program of a part whose table needs several).'''
+    Vector) or 2 (a Matrix): flow_form_vector / flow_form_matrix per dx
+    part, flow_form_facet_vector / flow_form_facet_matrix per ds part (per
+    program of a part whose table needs several).'''
     from . import forms
     from .function import Vector
     lib = _hip.lib()
@@ -1025,23 +1029,22 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
     nc = mesh.num_cells()
     total = None
     for sign, part in form.terms():
-        if part.integral_type != 'cell':
-            raise NotImplementedError('test and trial functions under ds')
+        facet = part.integral_type == 'exterior_facet'
         if forms.form_mesh(part.integrand, part.mesh) is not mesh:
             raise ValueError('the form is integrated over another mesh than '
                              'the one of its arguments')
         _, table = part.argument_table()
-        q = forms._quadrature_degree(part.metadata)
-        if q is None:
-            q = forms._quadrature_degree(form_compiler_parameters)
-        q = forms.check_degree(part.degree() if q is None else q)
-        scheme = forms.quadrature_scheme(form_compiler_parameters,
-                                         part.metadata)
+        q, scheme = _part_rule(part, form_compiler_parameters)
         # (one program, or several whose results add up where the table
         # exceeds the limits of flow_form: forms.argument_programs)
-        for prog in forms.argument_programs(table, rank):
-            fs, keep = _form_struct(prog, mesh, q, scheme=scheme)
-            if rank == 2:
+        for prog in forms.argument_programs(table, rank, facet):
+            fs, keep = _form_struct(prog, mesh, q, facet, scheme)
+            if facet:
+                # (the gather writes its targets only: the rest stays zero)
+                out = value_plane(lay) if rank == 2 else device.zeros(lay.N)
+                _facet_arguments(mesh, lay, rank, fs, part.subdomain_data,
+                                 part.subdomain_id, out)
+            elif rank == 2:
                 out = value_plane(lay)
                 buf = scratch(mesh, lay.nloc**2 * nc)
                 _hip.check(lib.flow_form_matrix(
@@ -1269,8 +1272,10 @@ class NewtonInfo(object):
     '''What solve(F == 0, ...) returns: `iterations` (linear solves done),
     `converged`, `residuals` (|F|_2 before the first and after every
     iteration), `linear_iterations` (of every linear solve), `fused` (every
-    part of the Jacobian was assembled together with a part of the residual
-    by flow_form_newton), `method` (of the linear solves).'''
+    dx part of the Jacobian was assembled together with a part of the
+    residual by flow_form_newton; ds parts are never fused and do not count:
+    they go through flow_form_facet_matrix / flow_form_facet_vector one by
+    one), `method` (of the linear solves).'''
 
     def __init__(self, fused, method):
         self.iterations = 0
@@ -1294,7 +1299,11 @@ def _part_rule(part, form_compiler_parameters):
     if q is None:
         q = forms._quadrature_degree(form_compiler_parameters)
     q = forms.check_degree(part.degree() if q is None else q)
-    return q, forms.quadrature_scheme(form_compiler_parameters, part.metadata)
+    scheme = forms.quadrature_scheme(form_compiler_parameters, part.metadata)
+    if scheme == 'vertex' and part.integral_type == 'exterior_facet':
+        raise ValueError("quadrature_rule 'vertex' on a ds part with test or "
+                         "trial functions: the vertex rule is a rule of cells")
+    return q, scheme
 
 
 def _fusable(tj, fparts, rules, used, rule, origin):
@@ -1305,7 +1314,8 @@ def _fusable(tj, fparts, rules, used, rule, origin):
     from . import forms
     for i in sorted(range(len(fparts)),
                     key=lambda i: fparts[i][1] is not origin):
-        if used[i] or rules[i] != rule:
+        if used[i] or rules[i] != rule \
+                or fparts[i][1].integral_type != 'cell':
             continue
         try:
             return i, forms.newton_program(
@@ -1318,9 +1328,11 @@ def _fusable(tj, fparts, rules, used, rule, origin):
 def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
     '''The launches that assemble (J, F) at one state, as a list of
     (kind, sign of the matrix part, sign of the vector part, Program,
-    degree, scheme), kind 'newton' | 'matrix' | 'vector'.  A part of J is
-    fused with a part of F of the same degree and rule (the one it was
-    derived from first) where forms.newton_program fits the limits of
+    degree, scheme), kind 'newton' | 'matrix' | 'vector' | 'facet_matrix' |
+    'facet_vector'; a facet job carries its part as a seventh entry (the
+    facet selection is the part's subdomain data and id).  ds parts are never
+    fused.  A dx part of J is fused with a part of F of the same degree and
+    rule (the one it was derived from first) where forms.newton_program fits the limits of
     flow_form; what is left goes through flow_form_matrix / flow_form_vector
     part by part (program by program where a table needs several:
     forms.argument_programs).  Host only.'''
@@ -1332,6 +1344,10 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
     for sj, pj in J.terms():
         rule = _part_rule(pj, form_compiler_parameters)
         tj = pj.argument_table()[1]
+        if pj.integral_type == 'exterior_facet':
+            jobs.extend(('facet_matrix', sj, 0.0, prog) + rule + (pj,)
+                        for prog in forms.argument_programs(tj, 2, True))
+            continue
         i, prog = _fusable(tj, fparts, rules, used, rule,
                            getattr(pj, 'derived_from', None)) \
             if fuse else (None, None)
@@ -1342,7 +1358,11 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
             jobs.extend(('matrix', sj, 0.0, prog) + rule
                         for prog in forms.argument_programs(tj, 2))
     for i, (sf, pf) in enumerate(fparts):
-        if not used[i]:
+        if pf.integral_type == 'exterior_facet':
+            jobs.extend(('facet_vector', 0.0, sf, prog) + rules[i] + (pf,)
+                        for prog in forms.argument_programs(
+                            pf.argument_table()[1], 1, True))
+        elif not used[i]:
             jobs.extend(('vector', 0.0, sf, prog) + rules[i]
                         for prog in forms.argument_programs(
                             pf.argument_table()[1], 1))
@@ -1353,15 +1373,15 @@ class NewtonAssembler(object):
     '''(J, F) at the current values of the fields, into buffers that live as
     long as the object: the value plane `A.vals`, the vector `b`, one more of
     each where a sum of parts needs it, and the mesh's scratch.  `fused`:
-    every part of J goes through flow_form_newton.'''
+    every dx part of J goes through flow_form_newton.  A ds job owns a zeroed
+    buffer that its gather writes the same entries of at every call (zeroed
+    again where the facet markers were changed).'''
 
     def __init__(self, J, F, V, form_compiler_parameters=None, fuse=True):
         from . import forms
         self.V = V
         self.mesh = V.mesh()
         for _, part in J.terms() + F.terms():
-            if part.integral_type != 'cell':
-                raise NotImplementedError('test and trial functions under ds')
             if forms.form_mesh(part.integrand, part.mesh) is not self.mesh:
                 raise ValueError('the form is integrated over another mesh '
                                  'than the one of its arguments')
@@ -1373,8 +1393,11 @@ class NewtonAssembler(object):
         self._plane = self._vector = None
         # (the structs hold pointers to the fields' data, which Newton updates
         # in place; the constants' values are refreshed by every assemble())
-        self.structs = [_form_struct(j[3], self.mesh, j[4], scheme=j[5])
+        self.structs = [_form_struct(j[3], self.mesh, j[4],
+                                     j[0].startswith('facet'), j[5])
                         for j in self.jobs]
+        # per ds job: [buffer, the map it was last gathered over]
+        self._facet = {}
 
     def assemble(self):
         lib = _hip.lib()
@@ -1384,16 +1407,27 @@ class NewtonAssembler(object):
         ms, ss = ctypes.byref(mesh_struct(mesh)), ctypes.byref(
             space_struct(lay))
         first_m = first_v = True
-        for (kind, sm, sv, prog, _, _), (fs, _) in zip(self.jobs,
-                                                       self.structs):
+        for jn, (job, (fs, _)) in enumerate(zip(self.jobs, self.structs)):
+            kind, sm, sv, prog = job[:4]
             for i, value in enumerate(prog.constant_values()):
                 fs.consts[i] = value
             vals = vec = None
-            if kind != 'vector':
+            if kind.startswith('facet'):
+                rank = 2 if kind == 'facet_matrix' else 1
+                out = self._facet_out(jn, rank, job[6])
+                _facet_arguments(mesh, lay, rank, fs, job[6].subdomain_data,
+                                 job[6].subdomain_id, out)
+                if rank == 2:
+                    vals = out
+                else:
+                    vec = out
+            elif kind != 'vector':
                 vals = self.A.vals if first_m and sm == 1.0 else self._tmp(0)
-            if kind != 'matrix':
+            if kind in ('newton', 'vector'):
                 vec = self.b if first_v and sv == 1.0 else self._tmp(1)
-            if kind == 'newton':
+            if kind.startswith('facet'):
+                pass
+            elif kind == 'newton':
                 n = (nl * nl + nl) * nc
                 _hip.check(lib.flow_form_newton(
                     ms, ss, ctypes.byref(fs),
@@ -1421,6 +1455,19 @@ class NewtonAssembler(object):
         if first_m or first_v:
             raise ValueError('an empty sum of forms has no rank')
         return self.A, self.b
+
+    def _facet_out(self, jn, rank, part):
+        lay = self.V.layout
+        fmap = facet_map(self.mesh, lay, rank, part.subdomain_data,
+                         part.subdomain_id)
+        held = self._facet.get(jn)
+        if held is None:
+            held = self._facet[jn] = [
+                value_plane(lay) if rank == 2 else device.zeros(lay.N), fmap]
+        elif held[1] is not fmap:       # re-marked: other targets
+            _hip.fill(held[0], 0.0)
+            held[1] = fmap
+        return held[0]
 
     def _tmp(self, which):
         if which == 0:
@@ -1537,6 +1584,13 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
     return out
 
 
+def _facet_selection(mesh, markers, subdomain_id):
+    '''Positions in mesh.bfacets of the facets ds(subdomain_id) selects.'''
+    if subdomain_id in (None, 'everywhere'):
+        return numpy.arange(len(mesh.bfacets))
+    return numpy.nonzero(markers.array()[mesh.bfacets] == subdomain_id)[0]
+
+
 def facet_lists(mesh, markers=None, subdomain_id='everywhere'):
     '''The exterior facets a ds integral runs over, as device int32 arrays
     (owning cell, local facet index) and their count: every boundary facet
@@ -1557,10 +1611,7 @@ def facet_lists(mesh, markers=None, subdomain_id='everywhere'):
     if held is not None and held[0] is (None if everywhere else markers) \
             and held[1] == version:
         return held[2:]
-    if everywhere:
-        sel = numpy.arange(len(mesh.bfacets))
-    else:
-        sel = numpy.nonzero(markers.array()[mesh.bfacets] == subdomain_id)[0]
+    sel = _facet_selection(mesh, markers, subdomain_id)
     cells = mesh.bfacet_cell[sel].astype(numpy.int32)
     local = mesh.bfacet_local[sel].astype(numpy.int32)
     nf = len(sel)
@@ -1574,6 +1625,100 @@ def facet_lists(mesh, markers=None, subdomain_id='everywhere'):
     held = (None if everywhere else markers, version, cells, local, nf)
     cache[key] = held
     return held[2:]
+
+
+def facet_map_host(mesh, layout, rank, markers=None,
+                   subdomain_id='everywhere'):
+    '''The facet contribution map of one (facet selection, space layout) pair
+    as numpy int32 arrays (targets, ptr, src).  The lanes of
+    flow_form_facet_matrix / flow_form_facet_vector write the element entries
+    of facet k of the selection (facet_lists' order) to scratch[(i*NL + j)*nf
+    + k] (rank 2) or scratch[i*nf + k] (rank 1), NL = layout.nloc -- ALL the
+    dofs of the owning cell, not only those on the edge.  targets: the sorted
+    unique indices of the nonzeros of the layout's CSR pattern (rank 2) or of
+    the dofs (rank 1) that any listed facet's cell touches; target t sums
+    scratch[src[e]], e in [ptr[t], ptr[t+1]), ascending by facet position,
+    then by ij (i).  Every scratch entry appears exactly once.'''
+    sel = _facet_selection(mesh, markers, subdomain_id)
+    nf, nl = len(sel), layout.nloc
+    if nf == 0:
+        return (numpy.zeros(0, numpy.int32), numpy.zeros(1, numpy.int32),
+                numpy.zeros(0, numpy.int32))
+    cd = layout.cell_dofs[mesh.bfacet_cell[sel]].astype(numpy.int64)  # (nf, nl)
+    if rank == 1:
+        tgt = cd.T.reshape(-1)                          # [i][k]
+    else:
+        N = layout.N
+        key = (cd[:, :, None] * N + cd[:, None, :]).transpose(1, 2, 0)
+        key = key.reshape(-1)                           # [i*nl + j][k]
+        rowptr = layout.pattern('rowptr').astype(numpy.int64)
+        ukey = numpy.repeat(numpy.arange(N, dtype=numpy.int64),
+                            numpy.diff(rowptr)) * N + layout.pattern('cols')
+        tgt = numpy.searchsorted(ukey, key)
+        assert (ukey[tgt] == key).all()
+    assert len(tgt) < 2**31
+    scr = numpy.arange(len(tgt), dtype=numpy.int64)
+    order = numpy.lexsort((scr // nf, scr % nf, tgt))   # (target, k, ij)
+    st = tgt[order]
+    first = numpy.nonzero(numpy.concatenate([[True], st[1:] != st[:-1]]))[0]
+    return (st[first].astype(numpy.int32),
+            numpy.concatenate([first, [len(st)]]).astype(numpy.int32),
+            order.astype(numpy.int32))
+
+
+def facet_map(mesh, layout, rank, markers=None, subdomain_id='everywhere'):
+    '''facet_map_host on the device: (targets, ptr, src, number of targets),
+    None arrays for an empty selection.  Cached on the mesh next to the
+    facet_lists entry and against the markers' version in the same way: a time
+    loop uploads nothing, re-marking rebuilds.  The SAME tuple is returned
+    while the entry holds.'''
+    everywhere = subdomain_id in (None, 'everywhere')
+    if markers is None and not everywhere:
+        raise ValueError('ds(%r) needs markers: Measure(\'ds\', domain=mesh, '
+                         'subdomain_data=markers)' % (subdomain_id,))
+    if markers is not None and markers.mesh is not mesh:
+        raise ValueError('the facet markers belong to another mesh')
+    cache = mesh._cache.setdefault('facet_maps', {})
+    key = (None if everywhere else id(markers),
+           None if everywhere else subdomain_id, id(layout), rank,
+           str(device.get()))
+    version = None if everywhere else markers.version
+    held = cache.get(key)
+    if held is not None and held[0] is (None if everywhere else markers) \
+            and held[1] == version and held[2] is layout:
+        return held[3]
+    targets, ptr, src = facet_map_host(mesh, layout, rank, markers,
+                                       subdomain_id)
+    nt = len(targets)
+    if nt:
+        fmap = (device.to_device(targets), device.to_device(ptr),
+                device.to_device(src), nt)
+    else:
+        fmap = (None, None, None, 0)
+    if len(cache) >= 32:
+        cache.clear()
+    # (markers and layout are kept alive with the entry: their ids stay unique)
+    cache[key] = (None if everywhere else markers, version, layout, fmap)
+    return fmap
+
+
+def _facet_arguments(mesh, lay, rank, fs, markers, subdomain_id, out):
+    '''One ds part of rank 1 | 2 into `out` (N | nnz doubles, zero outside
+    the map's targets): the element launch and the gather launch.'''
+    cells, local, nf = facet_lists(mesh, markers, subdomain_id)
+    if nf == 0:
+        return
+    targets, ptr, src, nt = facet_map(mesh, lay, rank, markers, subdomain_id)
+    n = lay.nloc**rank * nf
+    lib = _hip.lib()
+    fn = lib.flow_form_facet_matrix if rank == 2 else lib.flow_form_facet_vector
+    _hip.check(fn(
+        ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay)),
+        ctypes.byref(fs), nf, _hip.i32(cells, nf, 'facet cells'),
+        _hip.i32(local, nf, 'facet local indices'), nt,
+        _hip.i32(targets, nt, 'map targets'), _hip.i32(ptr, nt + 1, 'map ptr'),
+        _hip.i32(src, n, 'map src'), _hip.f64(scratch(mesh, n), n, 'scratch'),
+        _hip.f64(out, lay.nnz if rank == 2 else lay.N, 'out'), _hip.stream()))
 
 
 def form_load_vector(expr, V, form_compiler_parameters=None):

@@ -1282,6 +1282,43 @@ int flow_form_newton(const flow_mesh* mesh, const flow_space* V,
                      const flow_form* form, double* scratch, double* vals,
                      double* b, void* stream);
 
+/* Forms of arguments over exterior facets (Neumann, Robin and Nitsche terms:
+ * g*v*ds, h*u*v*ds, dot(grad(u), n)*v*ds).  The program is a coefficient
+ * table as for flow_form_matrix (nout = FLOW_FORM_SLOTS) / flow_form_vector
+ * (nout = 3) in which NORMAL is legal; the rule, the Expression tables and the
+ * facet lists are those of flow_form_facet_functional (3*nq rows).
+ *   Element kernel: one lane per (local test dof i < nloc, facet k), k
+ * fastest, nloc*nfacets lanes.  All nloc basis functions of the owning cell
+ * take part.  Lane (i, k) writes row i of the facet's element matrix to
+ *     scratch[(i*nloc + j)*nfacets + k]   (matrix; scratch: nloc^2 * nfacets)
+ * or entry i of its element vector to
+ *     scratch[i*nfacets + k]              (vector; scratch: nloc * nfacets),
+ * accumulated per point as flow_form_matrix / flow_form_vector do, with w =
+ * rule weight x facet length.  A facet whose cell or local index is out of
+ * range gives NaN.
+ *   Gather: one lane per target t < ntargets adds scratch[map_src[e]] for e in
+ * [map_ptr[t], map_ptr[t+1]) in that order and writes out[map_targets[t]]
+ * (targets: indices of nonzeros of V's CSR pattern | dofs); EVERY OTHER ENTRY
+ * OF THE OUTPUT IS LEFT AS IT IS, so the caller passes a zeroed buffer once
+ * and may reuse it while the map stays the same.  A target outside the output
+ * is skipped, a map row or source outside the scratch gives NaN.  map_targets
+ * (ntargets), map_ptr (ntargets + 1), map_src (all scratch entries): device
+ * int32 arrays the host builds once per (facet selection, space).  nfacets ==
+ * 0 or ntargets == 0: nothing launched.  No atomics: two calls give the same
+ * bits.  Not on strips. */
+int flow_form_facet_matrix(const flow_mesh* mesh, const flow_space* V,
+                           const flow_form* form, int nfacets,
+                           const int* facet_cell, const int* facet_local,
+                           int ntargets, const int* map_targets,
+                           const int* map_ptr, const int* map_src,
+                           double* scratch, double* vals, void* stream);
+int flow_form_facet_vector(const flow_mesh* mesh, const flow_space* V,
+                           const flow_form* form, int nfacets,
+                           const int* facet_cell, const int* facet_local,
+                           int ntargets, const int* map_targets,
+                           const int* map_ptr, const int* map_src,
+                           double* scratch, double* b, void* stream);
+
 /* ---- point evaluation (flow_amd/fem/points.py): u(x), Probes ---------------
  * A uniform bucket grid over the mesh's bounding box, built on the host once
  * per mesh: bucket (ix, iy) = (floor((x - x0) * hx_inv), floor((y - y0) *
