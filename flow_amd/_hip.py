@@ -474,6 +474,12 @@ SYMBOLS = {
                                _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_form_facet_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _VP,
                                _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'flow_form_block_matrix': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),
+                               _VP, _VP, ctypes.c_size_t, _VP],
+    'flow_form_block_vector': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),
+                               _VP, _VP, _VP],
+    'flow_bc_symmetric_blocks': [_I, _I, _VP, _VP, _VP, ctypes.c_size_t, _VP,
+                                 _VP, ctypes.c_size_t, _VP],
     'flow_profile_cumsum': [_I, _P(_I), _I, _I, _VP, _VP, _VP],
     'flow_locate_points': [_P(MeshS), _P(PointGridS), _I, _VP, _VP, _VP, _VP],
     'flow_form_points': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP],

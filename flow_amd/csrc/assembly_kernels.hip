@@ -37,6 +37,8 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(
   // idrow != nullptr: identity rows -- where idrow[p * id_stride + k] is set,
   // out = v[p * v_stride + k] instead of the sum (the Dirichlet rows of the
   // matrix-free Jacobian: one launch less than copying them afterwards)
+  // (block_gather_kernel in form_kernels.hip adds in this order and grouping
+  // with one scratch offset per plane: the two must stay in step, bit for bit)
   if (stopped(stop)) return;
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nout;
        k += gridDim.x * blockDim.x) {
@@ -889,6 +891,30 @@ __global__ void bc_symmetric_kernel(int n, const int* __restrict__ rowptr,
   }
 }
 
+// the symmetric elimination of a 2x2-block operator (kind 2), all four planes:
+// entry (i, j) of plane (r, s) belongs to row r*n + i and column s*n + j
+__global__ void bc_symmetric_blocks_kernel(int n, const int* __restrict__ rowptr,
+                                           const int* __restrict__ cols,
+                                           const double* __restrict__ vin,
+                                           size_t in_stride,
+                                           const unsigned char* __restrict__ isbc,
+                                           double* __restrict__ vout,
+                                           size_t out_stride) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += gridDim.x * blockDim.x) {
+    const bool r0 = isbc[i] != 0, r1 = isbc[n + i] != 0;
+    for (int k = rowptr[i]; k < rowptr[i + 1]; ++k) {
+      const int j = cols[k];
+      const bool c0 = isbc[j] != 0, c1 = isbc[n + j] != 0;
+      const double d = i == j ? 1.0 : 0.0;
+      vout[k] = (r0 || c0) ? d : vin[k];
+      vout[out_stride + k] = (r0 || c1) ? 0.0 : vin[in_stride + k];
+      vout[2 * out_stride + k] = (r1 || c0) ? 0.0 : vin[2 * in_stride + k];
+      vout[3 * out_stride + k] = (r1 || c1) ? d : vin[3 * in_stride + k];
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // K13 / K14: heat operator and SUPG tau
 // ---------------------------------------------------------------------------
@@ -1520,6 +1546,25 @@ extern "C" int flow_bc_symmetric_matrix(int n, const int* rowptr,
   FLOW_REQUIRE(n > 0 && rowptr && cols && vals_in && isbc && vals_out, "pointers");
   hipLaunchKernelGGL(bc_symmetric_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
                      as_stream(stream), n, rowptr, cols, vals_in, isbc, vals_out);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+extern "C" int flow_bc_symmetric_blocks(int n, int nnz, const int* rowptr,
+                                        const int* cols, const double* vals_in,
+                                        size_t in_stride, const unsigned char* isbc,
+                                        double* vals_out, size_t out_stride,
+                                        void* stream) {
+  FLOW_REQUIRE(n > 0 && nnz > 0 && rowptr && cols && vals_in && isbc && vals_out,
+               "pointers");
+  FLOW_REQUIRE(in_stride >= static_cast<size_t>(nnz) &&
+                   out_stride >= static_cast<size_t>(nnz),
+               "plane stride");
+  FLOW_REQUIRE(vals_in + 4 * in_stride <= vals_out || vals_out + 4 * out_stride <= vals_in,
+               "vals_in and vals_out must be distinct buffers");
+  hipLaunchKernelGGL(bc_symmetric_blocks_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
+                     as_stream(stream), n, rowptr, cols, vals_in, in_stride, isbc,
+                     vals_out, out_stride);
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
 }

@@ -1542,6 +1542,126 @@ static int facet_arguments(const flow_mesh* mesh, const flow_space* V,
   return FLOW_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Forms of arguments on a vector space (forms.py, vector_arguments): the table
+// of such a form is one scalar table per block (r, s) = (test, trial
+// component), compiled to the programs of a scalar form.  Every program runs
+// on the instances of form_matrix_kernel / form_vector_kernel that a scalar
+// form launches, into the scratch plane of its block; ONE gather then sums
+// the planes of all blocks into the value planes of a kind-2 operator (rank
+// 2) or into the two components of the vector (rank 1).
+// ---------------------------------------------------------------------------
+// offset of the scratch plane of block p in doubles; < 0: the block is absent
+struct BlockPlanes {
+  long long off[4];
+};
+
+// out[p*out_stride + k] = sum of scratch[off[p] + src[e]], e in [ptr[k],
+// ptr[k+1]), added in that order from 0.0 as gather_kernel adds them (the
+// same bits); 0.0 for an absent block
+template <int NP>
+__global__ __launch_bounds__(kBlock) void block_gather_kernel(
+    int nout, const int* __restrict__ ptr, const int* __restrict__ src,
+    const double* __restrict__ scratch, const BlockPlanes P, size_t out_stride,
+    double* __restrict__ out) {
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nout;
+       k += gridDim.x * blockDim.x) {
+    const int a = ptr[k];
+    const int b = ptr[k + 1];
+    double s[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) s[p] = 0.0;
+    for (int t = a; t < b; t += 4) {
+      int idx[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) idx[j] = t + j < b ? src[t + j] : -1;
+      double w[NP][4];
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          w[p][j] = (P.off[p] >= 0 && idx[j] >= 0) ? scratch[P.off[p] + idx[j]] : 0.0;
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[p] += w[p][j];
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) out[static_cast<size_t>(p) * out_stride + k] = s[p];
+  }
+}
+
+// dst += src, entry by entry: a further program of a block that has one
+__global__ __launch_bounds__(kBlock) void plane_add_kernel(
+    size_t n, const double* __restrict__ src, double* __restrict__ dst) {
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
+       i += static_cast<size_t>(gridDim.x) * blockDim.x)
+    dst[i] += src[i];
+}
+
+// flow_form_block_matrix (RANK 2) / flow_form_block_vector (RANK 1)
+template <int RANK>
+static int block_arguments(const flow_mesh* mesh, const flow_space* V, int nprog,
+                           const flow_form* forms, const int* blocks, double* scratch,
+                           double* out, size_t out_stride, void* stream) {
+  constexpr int NB = RANK == 2 ? 4 : 2;
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(nprog >= 1 && nprog <= 64 && forms && blocks, "block programs");
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 &&
+                   (RANK == 2 ? (V->nnz > 0 && V->cptr && V->csrc) : (V->vptr && V->vsrc)),
+               "space");
+  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(scratch && out, "pointers");
+  FLOW_REQUIRE(out_stride >= static_cast<size_t>(RANK == 2 ? V->nnz : V->n),
+               "plane stride");
+  int live[64];
+  int count[NB] = {};
+  for (int k = 0; k < nprog; ++k) {
+    FLOW_REQUIRE(blocks[k] >= 0 && blocks[k] < NB, "block tag");
+    if ((rc = check_form(forms + k, 1, false, false, RANK == 2 ? FLOW_FORM_SLOTS : 3,
+                         live + k)))
+      return rc;
+    ++count[blocks[k]];
+  }
+  // the scratch planes: one per present block, in the order of p, and one
+  // more behind them where a block has several programs
+  const int nl = V->deg == 1 ? 3 : 6;
+  const size_t plane = static_cast<size_t>(RANK == 2 ? nl * nl : nl) * mesh->nc;
+  BlockPlanes P;
+  int npresent = 0;
+  for (int p = 0; p < 4; ++p)
+    P.off[p] = (p < NB && count[p] > 0) ? static_cast<long long>(plane * npresent++) : -1;
+  double* const spare = scratch + plane * npresent;
+  hipStream_t st = as_stream(stream);
+  int seen[NB] = {};
+  for (int k = 0; k < nprog; ++k) {
+    const int p = blocks[k];
+    double* const own = scratch + P.off[p];
+    double* const dst = seen[p]++ ? spare : own;
+    if (RANK == 2)
+      rc = V->deg == 1 ? launch_matrix<1>(mesh, forms + k, live[k], dst, st)
+                       : launch_matrix<2>(mesh, forms + k, live[k], dst, st);
+    else
+      rc = V->deg == 1 ? launch_vector<1>(mesh, forms + k, live[k], dst, st)
+                       : launch_vector<2>(mesh, forms + k, live[k], dst, st);
+    if (rc) return rc;
+    if (dst == spare) {
+      hipLaunchKernelGGL(plane_add_kernel, dim3(grid_for(plane, kBlock, 1 << 20)),
+                         dim3(kBlock), 0, st, plane, spare, own);
+      FLOW_CHECK_LAUNCH();
+    }
+  }
+  const int nout = RANK == 2 ? V->nnz : V->n;
+  const int* ptr = RANK == 2 ? V->cptr : V->vptr;
+  const int* src = RANK == 2 ? V->csrc : V->vsrc;
+  hipLaunchKernelGGL(block_gather_kernel<NB>, dim3(grid_for(nout, kBlock, 1 << 20)),
+                     dim3(kBlock), 0, st, nout, ptr, src, scratch, P, out_stride, out);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
 }  // namespace flow
 
 using namespace flow;
@@ -1835,4 +1955,20 @@ extern "C" int flow_form_facet_vector(const flow_mesh* mesh, const flow_space* V
                                       double* scratch, double* b, void* stream) {
   return facet_arguments<1>(mesh, V, form, nfacets, facet_cell, facet_local, ntargets,
                             map_targets, map_ptr, map_src, scratch, b, stream);
+}
+
+extern "C" int flow_form_block_matrix(const flow_mesh* mesh, const flow_space* V,
+                                      int nprog, const flow_form* forms,
+                                      const int* blocks, double* scratch, double* vals,
+                                      size_t plane_stride, void* stream) {
+  return block_arguments<2>(mesh, V, nprog, forms, blocks, scratch, vals, plane_stride,
+                            stream);
+}
+
+extern "C" int flow_form_block_vector(const flow_mesh* mesh, const flow_space* V,
+                                      int nprog, const flow_form* forms,
+                                      const int* blocks, double* scratch, double* b,
+                                      void* stream) {
+  return block_arguments<1>(mesh, V, nprog, forms, blocks, scratch, b,
+                            V ? static_cast<size_t>(V->n) : 0, stream);
 }

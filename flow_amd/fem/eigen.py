@@ -413,6 +413,10 @@ def _check_forms(a, m, symmetric):
                     'written; LOBPCG takes symmetric problems only (pass '
                     'symmetric=True for a form that is symmetric all the '
                     'same)' % name)
+    if getattr(V, 'component', None) is None and V.dim == 2:
+        raise NotImplementedError(
+            'Eigenmodes of forms on a vector space (2x2-block operators) is '
+            'not implemented: LOBPCG runs on scalar matrices only')
     if getattr(V, 'component', None) is not None or V.dim != 1 \
             or V.degree not in (1, 2):
         raise ValueError('a, m: forms on one scalar P1 or P2 space')

@@ -73,8 +73,31 @@ Refused there: 'quadrature_rule': 'vertex' (ValueError: the vertex rule is a
 rule of cells) and strips (NotImplementedError).  The limit on field
 components is that of every program (MAX_FIELDS): the kernel's instance for
 six fields still runs without scratch memory or spills.
-Not supported (NotImplementedError): arguments on vector or mixed spaces, test
-and trial functions of different spaces, dS, action / adjoint.  lhs / rhs
+Arguments on a vector space (2x2-block forms: elasticity inner(sigma(u),
+eps(v))*dx, grad-div, the vector Laplacian, a Brinkman operator) are OFF by
+default too, as they always were (NotImplementedError);
+`vector_arguments(True)` switches them on like facet_arguments.  Then
+TestFunction(W) / TrialFunction(W) of a P1 / P2 VectorFunctionSpace is a
+2-vector whose components are leaves ('arg', number, d, W, comp) -- scalar
+arguments keep their 4-tuple --, so u[i], grad(u) (2x2), div, curl, dot,
+inner, as_vector, conditional and the tensor helpers sym(A), tr(A),
+transpose(A) / A.T, Identity(2), outer(a, b) (rank-2 FormExprs, with or without
+arguments; degrees by UFL's rules: sym tr transpose unchanged, Identity 0, outer
+the sum) work through the tensor machinery above.  extract_arguments keys
+become ((b, r), (a, s)), r the test and s the trial component; argument_table
+gives table[r][s] (rank 2) or table[r] (rank 1), each the table of a SCALAR
+form or None for a block without a term (callers tell by the space's dim);
+is_symmetric_table asks c[r][s][b][a] == c[s][r][a][b]; every present block
+compiles with argument_programs to the programs of a scalar form
+(block_items).  assemble gives a Matrix of kind 2 (four value planes over the
+scalar pattern, plane 2 r + s) or a Vector of 2N, component-major
+(flow_form_block_matrix / flow_form_block_vector); ds parts need both
+switches.  Refused there (NotImplementedError): W.sub(i) as an argument
+space, derivative() with respect to a vector Function, solve(F == 0),
+Eigenmodes, strips.
+Not supported (NotImplementedError): arguments on mixed spaces, test
+and trial functions of different spaces (a vector test function with a scalar
+trial function included), dS, action / adjoint.  lhs / rhs
 also split ONE integrand that holds terms of
 both ranks, (source - dot(conv, grad(u))) * tau * dot(conv, grad(v)) * dx, by
 linearity, as UFL does; assembling such an integrand unsplit stays a
@@ -179,7 +202,8 @@ CELL_QUANTITIES = ('volume', 'circumradius', 'diameter')
 # ('num', v) ('const', Constant, i) ('x', d) ('field', Function, i, d)
 # (d = 0 value, 1 d/dx, 2 d/dy) ('expr', Expression, i) ('n', d) (component
 # d of the outward unit normal, ds only) ('arg', number, d, V) (number 0 the
-# test, 1 the trial function of the space V; d as for fields) ('powi', a, n)
+# test, 1 the trial function of the space V; d as for fields; of a vector
+# space: ('arg', number, d, V, comp), component comp) ('powi', a, n)
 # and (op, a[, b]) for the UNARY / BINARY ops; ('reg', r) (register r of the
 # program, holding a subtree computed up front: newton_program only);
 # ('cell', mesh, k) (k = 0 |T|, 1 the circumradius, 2 the diameter of the cell);
@@ -281,7 +305,8 @@ def s_diff(n, d):
         if n[2] != 0:
             raise NotImplementedError('second derivatives of a test or trial '
                                       'function')
-        return ('arg', n[1], d + 1, n[3])
+        # (a component of a vector argument keeps its fifth entry)
+        return n[:2] + (d + 1,) + n[3:]
     if k == 'add':
         return s_add(s_diff(n[1], d), s_diff(n[2], d))
     if k == 'sub':
@@ -503,6 +528,10 @@ class FormExpr(object):
                 raise IndexError(i)
             c = c[i]
         return FormExpr(c, self.shape[len(idx):], self.deg, self.mesh)
+
+    @property
+    def T(self):
+        return transpose(self)
 
     def dx(self, i):
         if i not in (0, 1):
@@ -892,6 +921,54 @@ def as_vector(items):
                     _join_mesh(parts[0].mesh, parts[1].mesh))
 
 
+def _matrix(A, what):
+    A = as_form(A)
+    if A.shape != (2, 2):
+        raise ValueError('%s of a tensor of shape %r: a 2 x 2 tensor is '
+                         'expected' % (what, A.shape))
+    return A
+
+
+def transpose(A):
+    '''A^T of a rank-2 tensor (also A.T).'''
+    A = _matrix(A, 'transpose')
+    return FormExpr([[A.comps[j][i] for j in range(2)] for i in range(2)],
+                    (2, 2), A.deg, A.mesh)
+
+
+def sym(A):
+    '''(A + A^T) / 2.'''
+    A = _matrix(A, 'sym')
+    half = ('num', 0.5)
+    return FormExpr([[A.comps[i][j] if i == j else
+                      s_mul(half, s_add(A.comps[i][j], A.comps[j][i]))
+                      for j in range(2)] for i in range(2)], (2, 2), A.deg,
+                    A.mesh)
+
+
+def tr(A):
+    '''The trace A[0, 0] + A[1, 1].'''
+    A = _matrix(A, 'tr')
+    return FormExpr(s_add(A.comps[0][0], A.comps[1][1]), (), A.deg, A.mesh)
+
+
+def Identity(dim):
+    '''The dim x dim unit tensor (dim = 2: the meshes are 2-D).'''
+    if dim != 2:
+        raise ValueError('Identity(%r): the mesh is 2-D' % (dim,))
+    return FormExpr([[ONE, ZERO], [ZERO, ONE]], (2, 2), 0)
+
+
+def outer(a, b):
+    '''The rank-2 tensor a_i b_j of two vectors.'''
+    a, b = as_form(a), as_form(b)
+    if a.shape != (2,) or b.shape != (2,):
+        raise ValueError('outer of shapes %r and %r: two vectors are expected'
+                         % (a.shape, b.shape))
+    return FormExpr([[s_mul(a.comps[i], b.comps[j]) for j in range(2)]
+                     for i in range(2)], (2, 2), a.deg + b.deg, _join(a, b))
+
+
 def SpatialCoordinate(mesh):
     return FormExpr([('x', 0), ('x', 1)], (2,), 1, mesh)
 
@@ -908,22 +985,49 @@ def _argument(V, number):
         raise NotImplementedError(
             '%s on a mixed space: only scalar P1 / P2 spaces carry arguments'
             % name)
-    if V.dim != 1 or V.component is not None:
+    vector = vector_arguments.enabled and V.dim == 2 and V.component is None
+    if (V.dim != 1 or V.component is not None) and not vector:
         raise NotImplementedError(
             '%s on a vector space or a component view: only scalar P1 / P2 '
             'spaces carry arguments' % name)
     if V.degree not in (1, 2):
         raise ValueError('%s: spaces of degree 1 or 2 only' % name)
+    if vector:
+        return FormExpr([('arg', number, 0, V, c) for c in range(2)], (2,),
+                        V.degree, V.mesh())
     return FormExpr(('arg', number, 0, V), (), V.degree, V.mesh())
 
 
+class vector_arguments(object):
+    '''The switch of test and trial functions on vector spaces (2x2-block
+    forms: elasticity, grad-div, the vector Laplacian).  Off by default:
+    TestFunction(W) on a VectorFunctionSpace stays the NotImplementedError it
+    was.  `vector_arguments(True)` switches them on at once, for the process;
+    `.previous` is the setting it replaced, and as a context manager it
+    restores that on exit.  `vector_arguments.enabled` is the current
+    setting.'''
+    enabled = False
+
+    def __init__(self, on=True):
+        self.previous = vector_arguments.enabled
+        vector_arguments.enabled = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        vector_arguments.enabled = self.previous
+        return False
+
+
 def TestFunction(V):
-    '''The test function of the scalar space V (argument number 0).'''
+    '''The test function of the space V (argument number 0): a scalar, or
+    with vector_arguments(True) the 2-vector of a vector space.'''
     return _argument(V, 0)
 
 
 def TrialFunction(V):
-    '''The trial function of the scalar space V (argument number 1).'''
+    '''The trial function of the space V (argument number 1).'''
     return _argument(V, 1)
 
 
@@ -954,11 +1058,15 @@ def extract_arguments(n):
     '''The integrand tree n, linear in its arguments, as a table
     {(b, a): c}: n = sum c D_a u D_b v with argument-free trees c; b (test)
     and a (trial) are 0 value, 1 d/dx, 2 d/dy, or None where that argument is
-    absent.  Entries whose coefficient folds to zero are dropped.  ValueError,
-    naming the operation, where n is not linear in an argument.'''
+    absent.  Arguments of a vector space: the keys are ((b, r), (a, s)), n =
+    sum c D_a u_s D_b v_r with r the test and s the trial component.  Entries
+    whose coefficient folds to zero are dropped.  ValueError, naming the
+    operation, where n is not linear in an argument.'''
     k = n[0]
     if k == 'arg':
-        return {((n[2], None) if n[1] == 0 else (None, n[2])): ONE}
+        # (a component of a vector argument: (derivative, component))
+        d = n[2] if len(n) == 4 else (n[2], n[4])
+        return {((d, None) if n[1] == 0 else (None, d)): ONE}
     if not has_leaf(n, 'arg'):
         return {} if _is_num(n, 0.0) else {(None, None): n}
     if k in ('add', 'sub'):
@@ -1012,7 +1120,10 @@ def extract_arguments(n):
 
 def argument_table(integrand):
     '''(rank, table) of a scalar integrand: table[b][a] (rank 2) or table[b]
-    (rank 1) of coefficient trees, None where the term is absent.'''
+    (rank 1) of coefficient trees, None where the term is absent.  With
+    arguments of a vector space (callers tell by the space's dim) one such
+    table per block: table[r][s][b][a] or table[r][b], None for an absent
+    block.'''
     tab = {key: c for key, c in extract_arguments(integrand).items()
            if not _is_num(c, 0.0)}
     kinds = set((b is not None, a is not None) for b, a in tab)
@@ -1027,14 +1138,59 @@ def argument_table(integrand):
             'with lhs() / rhs()')
     if not kinds or kinds == {(False, False)}:
         return 0, None
+    if any(isinstance(b, tuple) for b, a in tab):
+        return _block_table(tab, 1 if kinds == {(True, False)} else 2)
     if kinds == {(True, False)}:
         return 1, [tab.get((b, None)) for b in range(3)]
     return 2, [[tab.get((b, a)) for a in range(3)] for b in range(3)]
 
 
+class BlockTable(list):
+    '''The table of a form of vector arguments: table[r][s] (rank 2) or
+    table[r] (rank 1).  A list; the type is what tells it from the table of
+    a scalar form (is_symmetric_table).'''
+
+
+def _block_table(tab, rank):
+    '''argument_table of vector arguments: table[r] (rank 1) or table[r][s]
+    (rank 2), r the test and s the trial component, each the table of a
+    scalar form or None where the block has no term.'''
+    if any(d is not None and not isinstance(d, tuple)
+           for key in tab for d in key):
+        raise NotImplementedError(
+            'test and trial functions of different spaces (a vector and a '
+            'scalar argument in one form)')
+    if rank == 1:
+        blocks = [[tab.get(((b, r), None)) for b in range(3)]
+                  for r in range(2)]
+        return 1, BlockTable(t if any(c is not None for c in t) else None
+                             for t in blocks)
+    blocks = [[[[tab.get(((b, r), (a, s))) for a in range(3)]
+                for b in range(3)] for s in range(2)] for r in range(2)]
+    return 2, BlockTable(
+        [t if any(c is not None for row in t for c in row) else None
+         for t in row] for row in blocks)
+
+
+def block_items(table, rank):
+    '''[(p, block table)] of the present blocks of a vector form's table: p =
+    2 r + s (rank 2) or r (rank 1).'''
+    if rank == 1:
+        return [(r, table[r]) for r in range(2) if table[r] is not None]
+    return [(2 * r + s, table[r][s]) for r in range(2) for s in range(2)
+            if table[r][s] is not None]
+
+
 def is_symmetric_table(table):
     '''Structural symmetry of a rank-2 table: c[b][a] and c[a][b] are the same
-    tree for every (a, b).'''
+    tree for every (a, b).  A BlockTable (2 x 2 blocks, vector arguments):
+    c[r][s][b][a] and c[s][r][a][b] are.'''
+    if isinstance(table, BlockTable):
+        def entry(r, s, b, a):
+            return None if table[r][s] is None else table[r][s][b][a]
+        return all(entry(r, s, b, a) == entry(s, r, a, b)
+                   for r in range(2) for s in range(2)
+                   for b in range(3) for a in range(3))
     return all(table[b][a] == table[a][b] for b in range(3) for a in range(b))
 
 
@@ -1379,9 +1535,9 @@ def _parts_of_rank(form, rank, sign):
         for (b, a), c in tab.items():
             if (a is not None) + 1 != rank:
                 continue
-            term = s_mul(c, ('arg', 0, b, found[0]))
+            term = s_mul(c, _arg_leaf(0, b, found[0]))
             if a is not None:
-                term = s_mul(term, ('arg', 1, a, found[1]))
+                term = s_mul(term, _arg_leaf(1, a, found[1]))
             tree = s_add(tree, term)
         if _is_num(tree, 0.0):
             continue
@@ -1390,6 +1546,13 @@ def _parts_of_rank(form, rank, sign):
                      f.subdomain_data)
         parts.append((sign * s, split))
     return FormSum(parts)
+
+
+def _arg_leaf(number, d, V):
+    '''The argument leaf of a key of extract_arguments: d, or (d, comp).'''
+    if isinstance(d, tuple):
+        return ('arg', number, d[0], V, d[1])
+    return ('arg', number, d, V)
 
 
 def lhs(F):

@@ -392,6 +392,23 @@ def symmetric_bc_matrix(A, isbc, out=None):
     return out
 
 
+def symmetric_bc_blocks(A, isbc, out=None):
+    '''symmetric_bc_matrix for the four planes of a kind-2 Matrix in one
+    launch; isbc: 2N bytes in operator numbering.'''
+    lib = _hip.lib()
+    lay = A.layout
+    assert A.kind == 2
+    if out is None:
+        out = Matrix(lay, 2)
+    _hip.check(lib.flow_bc_symmetric_blocks(
+        lay.N, lay.nnz, _hip.i32(lay.dev('rowptr')), _hip.i32(lay.dev('cols')),
+        _hip.f64(A.vals, 4 * A.stride), A.stride,
+        _hip.u8(isbc, 2 * lay.N, 'isbc'), _hip.f64(out.vals, 4 * out.stride),
+        out.stride, _hip.stream()
+        ))
+    return out
+
+
 class CoarseSpace(object):
     '''Piecewise-constant aggregate coarse space of a scalar SPD operator for
     the two-level additive preconditioner of flow_cg_solve (include/flow_hip.h,
@@ -962,7 +979,9 @@ def assemble(form, form_compiler_parameters=None):
     signed sums of such forms -- the integral of a scalar integrand over the
     cells or the exterior facets of the mesh, a float.  1: forms of a
     TestFunction, a Vector.  2: forms of a TrialFunction and a TestFunction,
-    a Matrix of kind 0 on the space's pattern.  Parts of rank 1 and 2 over ds
+    a Matrix of kind 0 on the space's pattern.  Arguments of a vector space
+    (forms.vector_arguments(True) allows them): a Vector of 2N, a Matrix of
+    kind 2 (_assemble_blocks).  Parts of rank 1 and 2 over ds
     (Neumann, Robin, Nitsche terms: forms.facet_arguments(True) allows them)
     go through flow_form_facet_vector / flow_form_facet_matrix and the facet contribution map (facet_map); an
     empty selection, ds(99), contributes zero.  The parts of a sum
@@ -1024,6 +1043,8 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
     from .function import Vector
     lib = _hip.lib()
     V = form.arguments()[0]
+    if V.dim == 2:
+        return _assemble_blocks(form, rank, form_compiler_parameters)
     lay = V.layout
     mesh = V.mesh()
     nc = mesh.num_cells()
@@ -1074,9 +1095,93 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
     return Matrix(lay, 0, total) if rank == 2 else Vector(total)
 
 
+def _assemble_blocks(form, rank, form_compiler_parameters=None):
+    '''assemble() of a form, or of a signed sum of forms, of arguments on a
+    vector space W: a Matrix of kind 2 (rank 2; plane 2 r + s the block of
+    test component r and trial component s) or a Vector of 2N (rank 1).  A dx
+    part is ONE call of flow_form_block_matrix / flow_form_block_vector with
+    the programs of all its blocks; a ds part goes block by block (program
+    by program) through flow_form_facet_matrix / flow_form_facet_vector with
+    the scalar layout's facet_map, into the block's plane or component.'''
+    from . import forms
+    from .function import Vector
+    lib = _hip.lib()
+    W = form.arguments()[0]
+    lay = W.layout
+    mesh = W.mesh()
+    nc = mesh.num_cells()
+    stride = plane_stride(lay) if rank == 2 else lay.N
+    nblocks = 4 if rank == 2 else 2
+    width = lay.nnz if rank == 2 else lay.N       # entries of a block
+    total = None
+    for sign, part in form.terms():
+        facet = part.integral_type == 'exterior_facet'
+        if forms.form_mesh(part.integrand, part.mesh) is not mesh:
+            raise ValueError('the form is integrated over another mesh than '
+                             'the one of its arguments')
+        _, table = part.argument_table()
+        q, scheme = _part_rule(part, form_compiler_parameters)
+        progs = [(p, prog) for p, block in forms.block_items(table, rank)
+                 for prog in forms.argument_programs(block, rank, facet)]
+        if facet:
+            # (the facet gather writes its targets only: the rest stays zero)
+            out = device.zeros(nblocks * stride)
+            seen = set()
+            for p, prog in progs:
+                fs, keep = _form_struct(prog, mesh, q, True, scheme)
+                dst = out[p * stride:p * stride + width]
+                tmp = device.zeros(width) if p in seen else dst
+                _facet_arguments(mesh, lay, rank, fs, part.subdomain_data,
+                                 part.subdomain_id, tmp)
+                if p in seen:
+                    axpby(1.0, tmp, 1.0, dst)
+                seen.add(p)
+                del keep
+        else:
+            structs = (_hip.FormS * len(progs))()
+            keeps = []
+            for k, (p, prog) in enumerate(progs):
+                fs, keep = _form_struct(prog, mesh, q, False, scheme)
+                structs[k] = fs
+                keeps.append(keep)
+            tags = (ctypes.c_int * len(progs))(*[p for p, _ in progs])
+            present = len(set(p for p, _ in progs))
+            several = len(progs) > present
+            ns = (present + several) * lay.nloc**rank * nc
+            buf = scratch(mesh, ns)
+            out = device.empty(nblocks * stride)
+            if rank == 2:
+                if stride != lay.nnz:       # (the entry behind every plane)
+                    _hip.fill(out, 0.0)
+                _hip.check(lib.flow_form_block_matrix(
+                    ctypes.byref(mesh_struct(mesh)),
+                    ctypes.byref(space_struct(lay)), len(progs), structs, tags,
+                    _hip.f64(buf, ns, 'scratch'),
+                    _hip.f64(out, 4 * stride, 'vals'), stride, _hip.stream()))
+            else:
+                _hip.check(lib.flow_form_block_vector(
+                    ctypes.byref(mesh_struct(mesh)),
+                    ctypes.byref(space_struct(lay)), len(progs), structs, tags,
+                    _hip.f64(buf, ns, 'scratch'), _hip.f64(out, 2 * lay.N, 'b'),
+                    _hip.stream()))
+            del keeps
+        if total is None and sign == 1.0:
+            total = out
+        else:
+            if total is None:
+                total = _hip.fill(device.empty(out.numel()), 0.0)
+            axpby(sign, out, 1.0, total)
+    if total is None:
+        raise ValueError('an empty sum of forms has no rank')
+    return Matrix(lay, 2, total) if rank == 2 else Vector(total)
+
+
 def _scalar_bcs(bcs, V):
     '''(dofs, values) on the device and the byte mask of the Dirichlet dofs
-    of conditions on the scalar space V (None, None, None without any).'''
+    of conditions on the space V (None, None, None without any).  V scalar:
+    conditions on V, a mask of N bytes.  V a vector space: conditions on V
+    and on V.sub(i), dofs in operator numbering (a*N + i), a mask of 2N
+    bytes.'''
     from .bcs import collect
     if bcs is None:
         bcs = []
@@ -1084,13 +1189,17 @@ def _scalar_bcs(bcs, V):
         bcs = [bcs]
     for bc in bcs:
         W = bc.function_space()
-        if W.component is not None or not W.same_as(V):
+        if V.dim == 2 and W.component is not None:
+            W = W.parent
+        elif W.component is not None:
+            W = None
+        if W is None or not W.same_as(V):
             raise ValueError('a Dirichlet condition lives on another space '
                              'than the form')
     dofs, vals = collect(list(bcs), V.size())
     if len(dofs) == 0:
         return None, None, None
-    mask = numpy.zeros(V.N, dtype=numpy.uint8)
+    mask = numpy.zeros(V.size(), dtype=numpy.uint8)
     mask[dofs] = 1
     return (device.to_device(dofs), device.to_device(vals),
             device.to_device(mask))
@@ -1113,14 +1222,16 @@ def assemble_system(a, L, bcs=None, form_compiler_parameters=None):
     '''(A, b) of the bilinear form a and the linear form L (None or an empty
     sum: zero) with dolfin's symmetric elimination of the Dirichlet
     conditions: rows and columns of their dofs are zeroed, the diagonal is 1,
-    b is lifted by the eliminated columns and b[dof] = g.'''
+    b is lifted by the eliminated columns and b[dof] = g.  Forms on a vector
+    space W: A of kind 2, b of 2N, conditions on W and on W.sub(i)
+    (flow_bc_symmetric_blocks).'''
     from . import forms
     from .function import Vector
     _no_strips('assemble_system')
     V = _form_space(a)
     A0 = assemble(a, form_compiler_parameters)
     if L is None or (isinstance(L, forms.FormSum) and not L.terms()):
-        b = Vector(device.zeros(V.N))
+        b = Vector(device.zeros(V.size()))
     else:
         if L.rank != 1:
             raise ValueError('the right-hand side must be a linear form '
@@ -1132,11 +1243,13 @@ def assemble_system(a, L, bcs=None, form_compiler_parameters=None):
     dofs, vals, mask = _scalar_bcs(bcs, V)
     if dofs is None:
         return A0, b
-    g = device.zeros(V.N)
+    g = device.zeros(V.size())
     _set_values(dofs, vals, g)
-    lift = A0.apply(g, device.empty(V.N))
+    lift = A0.apply(g, device.empty(V.size()))
     axpby(-1.0, lift, 1.0, b.data)
     _set_values(dofs, vals, b.data)
+    if A0.kind == 2:
+        return symmetric_bc_blocks(A0, mask), b
     return symmetric_bc_matrix(A0, mask), b
 
 
@@ -1146,11 +1259,17 @@ def apply_identity_rows(bc, A=None, b=None):
     Not on strips (the steppers apply their conditions themselves there).'''
     _no_strips('DirichletBC.apply')
     V = bc.function_space()
+    if V.component is not None or V.dim == 2:
+        # a condition on W or W.sub(i): a kind-2 matrix, vectors of 2N
+        V = V.parent if V.component is not None else V
+        kind = 2
+    else:
+        kind = 0
     dofs, vals, _ = _scalar_bcs([bc], V)
     if dofs is None:
         return
     if A is not None:
-        if A.kind != 0 or A.layout is not V.layout:
+        if A.kind != kind or A.layout is not V.layout:
             raise ValueError('the matrix does not belong to the space of the '
                              'condition')
         _hip.check(_hip.lib().flow_bc_identity_rows(
@@ -1159,7 +1278,7 @@ def apply_identity_rows(bc, A=None, b=None):
             _hip.stream()))
     if b is not None:
         data = b.data if hasattr(b, 'data') else b
-        if data.numel() != V.N:
+        if data.numel() != V.size():
             raise ValueError('the vector does not belong to the space of the '
                              'condition')
         _set_values(dofs, vals, data)
@@ -1513,6 +1632,10 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
         raise ValueError('solve(F == 0, u): F must be a form of rank 1, '
                          'linear in a test function')
     V = F.arguments()[0]
+    if V.dim != 1:
+        raise NotImplementedError(
+            'solve(F == 0) on a vector space: derivative() with respect to a '
+            'vector Function and the Newton assembler are scalar only')
     if not isinstance(u, Function) or not u.function_space().same_as(V):
         raise ValueError('solve writes into a Function of the space of the '
                          'test function')

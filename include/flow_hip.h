@@ -1319,6 +1319,35 @@ int flow_form_facet_vector(const flow_mesh* mesh, const flow_space* V,
                            const int* map_ptr, const int* map_src,
                            double* scratch, double* b, void* stream);
 
+/* Forms of a test function v and a trial function u of the VECTOR space on V's
+ * scalar pattern (forms.py, vector_arguments): the host rewrites the integrand
+ * as  sum_(r,s) sum_(b,a) c^rs_ba D_a u_s D_b v_r  (rank 2) or  sum_r sum_b
+ * c^r_b D_b v_r  (rank 1) and compiles the table of every block that has a
+ * term into the program(s) of a scalar form, as for flow_form_matrix /
+ * flow_form_vector.  forms: nprog (1..64) structs behind one another;
+ * blocks[k]: the block of program k, p = 2 r + s in 0..3 (matrix) or r in 0..1
+ * (vector), r the test and s the trial component -- host arrays.
+ *   Every program runs on the element kernel of flow_form_matrix /
+ * flow_form_vector, with its arithmetic, into the scratch plane of its block;
+ * a further program of a block is added to the plane entry by entry.  ONE
+ * gather over cptr / csrc (vptr / vsrc) then sums the planes of all blocks:
+ *   flow_form_block_matrix: vals + p*plane_stride, p = 0..3, the four value
+ *     planes of a kind-2 operator (plane_stride >= nnz doubles apart);
+ *   flow_form_block_vector: b[r*n + i], 2n doubles, component-major.
+ * The plane or component of a block without a program is set to zero.  A
+ * block whose only program is that of a scalar form gets the bits
+ * flow_form_matrix / flow_form_vector give that form.  No floating-point
+ * atomics: two calls give the same bits.  Not on strips.
+ * scratch: (blocks with a program, + 1 where one has several) * nloc^2 * nc
+ * doubles (matrix; vector: * nloc * nc). */
+int flow_form_block_matrix(const flow_mesh* mesh, const flow_space* V, int nprog,
+                           const flow_form* forms, const int* blocks,
+                           double* scratch, double* vals, size_t plane_stride,
+                           void* stream);
+int flow_form_block_vector(const flow_mesh* mesh, const flow_space* V, int nprog,
+                           const flow_form* forms, const int* blocks,
+                           double* scratch, double* b, void* stream);
+
 /* ---- point evaluation (flow_amd/fem/points.py): u(x), Probes ---------------
  * A uniform bucket grid over the mesh's bounding box, built on the host once
  * per mesh: bucket (ix, iy) = (floor((x - x0) * hx_inv), floor((y - y0) *
@@ -1787,6 +1816,15 @@ int flow_bc_set_values(int nbc, const int* dofs, const double* g, double* x,
 int flow_bc_symmetric_matrix(int n, const int* rowptr, const int* cols,
                              const double* vals_in, const unsigned char* isbc,
                              double* vals_out, void* stream);
+/* The same elimination for the four planes of a kind-2 operator (2x2 blocks
+ * over one scalar pattern; plane p = 2 r + s at vals + p*stride, stride >= nnz)
+ * in one launch: entry (i, j) of plane (r, s) becomes (r == s && i == j) ? 1 : 0
+ * where isbc[r*n + i] || isbc[s*n + j], and is copied otherwise.  isbc: 2n
+ * bytes in operator numbering.  vals_in and vals_out are distinct buffers. */
+int flow_bc_symmetric_blocks(int n, int nnz, const int* rowptr, const int* cols,
+                             const double* vals_in, size_t in_stride,
+                             const unsigned char* isbc, double* vals_out,
+                             size_t out_stride, void* stream);
 
 /* ---- K13/K14: heat operator (heat.py:20-89) and SUPG tau
  * (stabilization.py:50-143) -------------------------------------------------
