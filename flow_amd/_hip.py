@@ -478,6 +478,9 @@ SYMBOLS = {
                                _VP, _VP, ctypes.c_size_t, _VP],
     'flow_form_block_vector': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),
                                _VP, _VP, _VP],
+    'flow_form_block_newton': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),
+                               _P(_I), _VP, ctypes.c_size_t, _VP,
+                               ctypes.c_size_t, _VP, _VP],
     'flow_bc_symmetric_blocks': [_I, _I, _VP, _VP, _VP, ctypes.c_size_t, _VP,
                                  _VP, ctypes.c_size_t, _VP],
     'flow_profile_cumsum': [_I, _P(_I), _I, _I, _VP, _VP, _VP],

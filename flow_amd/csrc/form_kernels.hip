@@ -1662,6 +1662,183 @@ static int block_arguments(const flow_mesh* mesh, const flow_space* V, int nprog
   return FLOW_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Block Newton (flow_form_block_newton): the Jacobian of a residual on a vector
+// space is a 2x2-block form, the residual a 2-component one.  A job
+// newton(p) runs the form_newton_kernel instance of a scalar Newton pass for
+// block p = 2 r + s TOGETHER with residual component r -- they share the test
+// basis and the subtrees in u and grad u --, a job matrix(p) / vector(r) the
+// form_matrix_kernel / form_vector_kernel instance a block form launches.  ONE
+// gather then sums all of it: lanes [0, nnz) the four value planes over cptr /
+// csrc, lanes [nnz, nnz + n) the two vector components over vptr / vsrc.
+// ---------------------------------------------------------------------------
+// offsets of the scratch planes in doubles, < 0: absent.  mat[p]: Ke of block
+// p; vec[r]: be of component r (behind Ke of its block where a newton job
+// wrote it: form_newton_kernel puts be there)
+struct NewtonPlanes {
+  long long mat[4];
+  long long vec[2];
+};
+
+// the sum of block_gather_kernel for one output entry: NP planes over one
+// index list, added in its order from 0.0 (the same bits)
+template <int NP>
+__device__ __forceinline__ void block_sum(const int* __restrict__ src, int a, int b,
+                                          const double* __restrict__ scratch,
+                                          const long long (&off)[NP], double (&s)[NP]) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) s[p] = 0.0;
+  for (int t = a; t < b; t += 4) {
+    int idx[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) idx[j] = t + j < b ? src[t + j] : -1;
+    double w[NP][4];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w[p][j] = (off[p] >= 0 && idx[j] >= 0) ? scratch[off[p] + idx[j]] : 0.0;
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[p] += w[p][j];
+  }
+}
+
+// vals[p*vals_stride + k], k < nnz, and b[r*n + i], i < n, in one launch;
+// consecutive lanes take consecutive k (i): the stores coalesce, the index
+// loads run over neighbouring rows of cptr / csrc (vptr / vsrc)
+__global__ __launch_bounds__(kBlock) void block_newton_gather_kernel(
+    int nnz, int n, const int* __restrict__ cptr, const int* __restrict__ csrc,
+    const int* __restrict__ vptr, const int* __restrict__ vsrc,
+    const double* __restrict__ scratch, const NewtonPlanes P, size_t vals_stride,
+    double* __restrict__ vals, double* __restrict__ b) {
+  const long long total = static_cast<long long>(nnz) + n;
+  for (long long k = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+       k < total; k += static_cast<long long>(gridDim.x) * blockDim.x) {
+    if (k < nnz) {
+      double s[4];
+      block_sum<4>(csrc, cptr[k], cptr[k + 1], scratch, P.mat, s);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) vals[static_cast<size_t>(p) * vals_stride + k] = s[p];
+    } else {
+      const int i = static_cast<int>(k - nnz);
+      double s[2];
+      block_sum<2>(vsrc, vptr[i], vptr[i + 1], scratch, P.vec, s);
+#pragma unroll
+      for (int r = 0; r < 2; ++r) b[static_cast<size_t>(r) * n + i] = s[r];
+    }
+  }
+}
+
+static int block_newton(const flow_mesh* mesh, const flow_space* V, int nprog,
+                        const flow_form* forms, const int* kinds, const int* tags,
+                        double* scratch, size_t nscratch, double* vals,
+                        size_t plane_stride, double* b, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(nprog >= 1 && nprog <= 64 && forms && kinds && tags, "block programs");
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->nnz > 0 && V->cptr &&
+                   V->csrc && V->vptr && V->vsrc,
+               "space");
+  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(scratch && vals && b, "pointers");
+  FLOW_REQUIRE(plane_stride >= static_cast<size_t>(V->nnz), "plane stride");
+  int live[64];
+  int nmat[4] = {}, nvec[2] = {};
+  bool newton_mat[4] = {}, newton_vec[2] = {};
+  for (int k = 0; k < nprog; ++k) {
+    const int kind = kinds[k], tag = tags[k];
+    FLOW_REQUIRE(kind >= FLOW_BLOCK_NEWTON && kind <= FLOW_BLOCK_VECTOR, "block job kind");
+    FLOW_REQUIRE(tag >= 0 && tag < (kind == FLOW_BLOCK_VECTOR ? 2 : 4), "block tag");
+    if ((rc = check_form(forms + k, 1, false, false,
+                         kind == FLOW_BLOCK_NEWTON   ? FLOW_FORM_NEWTON_SLOTS
+                         : kind == FLOW_BLOCK_MATRIX ? FLOW_FORM_SLOTS
+                                                     : 3,
+                         live + k)))
+      return rc;
+    if (kind == FLOW_BLOCK_NEWTON) {
+      // (Ke and be of a newton job go straight to the planes of the block
+      // and the component: it is the first program of both)
+      FLOW_REQUIRE(nmat[tag] == 0 && nvec[tag >> 1] == 0,
+                   "a newton job is the first program of its block and component");
+      newton_mat[tag] = newton_vec[tag >> 1] = true;
+    }
+    if (kind != FLOW_BLOCK_VECTOR) ++nmat[tag];
+    if (kind != FLOW_BLOCK_MATRIX) ++nvec[kind == FLOW_BLOCK_VECTOR ? tag : tag >> 1];
+  }
+  // the scratch planes: per block with a program nl*nl*nc doubles, in the
+  // order of p, a newton job's nl*nc of be directly behind its Ke; then the
+  // components no newton job writes; then one spare plane where a block or a
+  // component has several programs
+  const int nl = V->deg == 1 ? 3 : 6;
+  const size_t mplane = static_cast<size_t>(nl) * nl * mesh->nc;
+  const size_t vplane = static_cast<size_t>(nl) * mesh->nc;
+  NewtonPlanes P;
+  size_t cur = 0;
+  for (int r = 0; r < 2; ++r) P.vec[r] = -1;
+  for (int p = 0; p < 4; ++p) {
+    P.mat[p] = -1;
+    if (nmat[p] == 0) continue;
+    P.mat[p] = static_cast<long long>(cur);
+    cur += mplane;
+    if (newton_mat[p]) {
+      P.vec[p >> 1] = static_cast<long long>(cur);
+      cur += vplane;
+    }
+  }
+  for (int r = 0; r < 2; ++r)
+    if (nvec[r] > 0 && !newton_vec[r]) {
+      P.vec[r] = static_cast<long long>(cur);
+      cur += vplane;
+    }
+  double* const spare = scratch + cur;
+  bool mspare = false, vspare = false;
+  for (int p = 0; p < 4; ++p) mspare = mspare || nmat[p] > 1;
+  for (int r = 0; r < 2; ++r) vspare = vspare || nvec[r] > 1;
+  cur += mspare ? mplane : vspare ? vplane : 0;
+  FLOW_REQUIRE(cur <= nscratch, "scratch size");
+  hipStream_t st = as_stream(stream);
+  int mseen[4] = {}, vseen[2] = {};
+  for (int k = 0; k < nprog; ++k) {
+    const int kind = kinds[k], tag = tags[k];
+    const flow_form* F = forms + k;
+    if (kind == FLOW_BLOCK_NEWTON) {
+      ++mseen[tag];
+      ++vseen[tag >> 1];
+      double* const dst = scratch + P.mat[tag];
+      rc = V->deg == 1 ? launch_newton<1>(mesh, F, live[k], dst, st)
+                       : launch_newton<2>(mesh, F, live[k], dst, st);
+      if (rc) return rc;
+      continue;
+    }
+    const bool mat = kind == FLOW_BLOCK_MATRIX;
+    double* const own = scratch + (mat ? P.mat[tag] : P.vec[tag]);
+    double* const dst = (mat ? mseen[tag]++ : vseen[tag]++) ? spare : own;
+    if (mat)
+      rc = V->deg == 1 ? launch_matrix<1>(mesh, F, live[k], dst, st)
+                       : launch_matrix<2>(mesh, F, live[k], dst, st);
+    else
+      rc = V->deg == 1 ? launch_vector<1>(mesh, F, live[k], dst, st)
+                       : launch_vector<2>(mesh, F, live[k], dst, st);
+    if (rc) return rc;
+    if (dst == spare) {
+      const size_t plane = mat ? mplane : vplane;
+      hipLaunchKernelGGL(plane_add_kernel, dim3(grid_for(plane, kBlock, 1 << 20)),
+                         dim3(kBlock), 0, st, plane, spare, own);
+      FLOW_CHECK_LAUNCH();
+    }
+  }
+  hipLaunchKernelGGL(
+      block_newton_gather_kernel,
+      dim3(grid_for(static_cast<long long>(V->nnz) + V->n, kBlock, 1 << 20)), dim3(kBlock),
+      0, st, V->nnz, V->n, V->cptr, V->csrc, V->vptr, V->vsrc, scratch, P, plane_stride,
+      vals, b);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
 }  // namespace flow
 
 using namespace flow;
@@ -1971,4 +2148,13 @@ extern "C" int flow_form_block_vector(const flow_mesh* mesh, const flow_space* V
                                       void* stream) {
   return block_arguments<1>(mesh, V, nprog, forms, blocks, scratch, b,
                             V ? static_cast<size_t>(V->n) : 0, stream);
+}
+
+extern "C" int flow_form_block_newton(const flow_mesh* mesh, const flow_space* V,
+                                      int nprog, const flow_form* forms, const int* kinds,
+                                      const int* tags, double* scratch, size_t nscratch,
+                                      double* vals, size_t plane_stride, double* b,
+                                      void* stream) {
+  return block_newton(mesh, V, nprog, forms, kinds, tags, scratch, nscratch, vals,
+                      plane_stride, b, stream);
 }

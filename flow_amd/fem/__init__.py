@@ -27,7 +27,7 @@ from .forms import (                                            # noqa: F401
     lhs, rhs, system, dS, derivative, action, adjoint,
     conditional, lt, le, gt, ge, eq, ne, And, Or, Not, max_value, min_value,
     sign, tanh, CellVolume, Circumradius, CellDiameter, facet_arguments,
-    vector_arguments, sym, tr, transpose, Identity, outer,
+    vector_arguments, vector_derivatives, sym, tr, transpose, Identity, outer,
     )
 from .points import Probes                                      # noqa: F401
 from .tracers import Tracers                                    # noqa: F401

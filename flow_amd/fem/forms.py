@@ -93,8 +93,9 @@ compiles with argument_programs to the programs of a scalar form
 scalar pattern, plane 2 r + s) or a Vector of 2N, component-major
 (flow_form_block_matrix / flow_form_block_vector); ds parts need both
 switches.  Refused there (NotImplementedError): W.sub(i) as an argument
-space, derivative() with respect to a vector Function, solve(F == 0),
-Eigenmodes, strips.
+space, Eigenmodes, strips, and -- OFF by default like the arguments
+themselves -- derivative() with respect to a vector Function and solve(F ==
+0): `vector_derivatives(True)` switches those on (below).
 Not supported (NotImplementedError): arguments on mixed spaces, test
 and trial functions of different spaces (a vector test function with a scalar
 trial function included), dS, action / adjoint.  lhs / rhs
@@ -124,7 +125,18 @@ part a rank-2 ds part) and keep their subdomain id and subdomain data too
 -- with facet_arguments(True); without it a ds part that holds u is refused.
 Refused: a rank-2 form (the result would be a rank-3 form), u on a vector,
 component or mixed space, a form that does not depend on u, u of another
-space than the form's arguments.  `F == 0` is the
+space than the form's arguments.  With `vector_derivatives(True)` (a process
+switch like vector_arguments, which it needs as well: alone it refuses with a
+message that names that switch) u may live on a P1 / P2 VectorFunctionSpace
+W: the leaf ('field', u, i, d) becomes ('arg', k, d, W, i), every other rule,
+the parts, signs, metadata, subdomain data, derived_from and the degree rule
+are the scalar ones; du, if given, is the TestFunction(W) / TrialFunction(W)
+of the right number; a functional gives a rank-1 form on W, a residual its
+2x2-block Jacobian, an energy twice the bilinear form.  Still refused: u on
+W.sub(i) or a mixed space, a rank-2 F, arguments of another space than u's (a
+scalar Function in a form on W included), a form that does not depend on u.
+solve(F == 0) on W is then the block Newton of ops.newton_solve
+(flow_form_block_newton).  `F == 0` is the
 Equation of the nonlinear solve(F == 0, u, bcs, J=...) (ops.solve: Newton);
 a form of any rank compared with the number 0 gives one (solve refuses what
 is not a residual), any other number is a ValueError.
@@ -343,9 +355,13 @@ def s_diff(n, d):
 
 def s_gateaux(n, u, k, V):
     '''d n / d u in the direction of argument number k of V = the space of the
-    scalar Function u: s_diff's chain rule with another leaf rule.'''
+    Function u: s_diff's chain rule with another leaf rule.  u scalar:
+    ('field', u, 0, d) becomes ('arg', k, d, V); u on a vector space: ('field',
+    u, i, d) becomes ('arg', k, d, V, i), component i of the vector argument.'''
     op = n[0]
     if op == 'field':
+        if n[1] is u and V.dim == 2:
+            return ('arg', k, n[3], V, n[2])
         if n[1] is u and n[2] == 0:
             return ('arg', k, n[3], V)
         return ZERO
@@ -1020,6 +1036,36 @@ class vector_arguments(object):
         return False
 
 
+class vector_derivatives(object):
+    '''The switch of derivative() with respect to a Function of a P1 / P2
+    VectorFunctionSpace and of solve(F == 0) there (block Newton).  Off by
+    default: both stay the NotImplementedError they were.
+    `vector_derivatives(True)` switches them on at once, for the process;
+    `.previous` is the setting it replaced, and as a context manager it
+    restores that on exit.  `vector_derivatives.enabled` is the current
+    setting.  The derivative is a form of vector arguments, so
+    vector_arguments(True) is needed as well.'''
+    enabled = False
+
+    def __init__(self, on=True):
+        self.previous = vector_derivatives.enabled
+        vector_derivatives.enabled = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        vector_derivatives.enabled = self.previous
+        return False
+
+
+_VECTOR_ARGUMENTS_OFF = (
+    'vector_derivatives(True) is on, but vector_arguments(True) is not: the '
+    'derivative with respect to a Function of a vector space is a form of '
+    'test and trial functions on that space, which vector_arguments switches '
+    'on')
+
+
 def TestFunction(V):
     '''The test function of the space V (argument number 0): a scalar, or
     with vector_arguments(True) the 2-vector of a vector space.'''
@@ -1571,7 +1617,8 @@ def system(F):
 
 def derivative(F, u, du=None):
     '''The Gateaux derivative of the form (or signed sum) F of rank 0 or 1
-    with respect to the scalar P1 / P2 Function u, part by part: a form of
+    with respect to the scalar P1 / P2 Function u (with
+    vector_derivatives(True): or one of a vector space), part by part: a form of
     rank + 1 whose new argument has the number of arguments F already has (0:
     the test, 1: the trial function of u's space).  du: that argument, given
     explicitly.  See the module docstring for the rules and the refusals.'''
@@ -1584,11 +1631,15 @@ def derivative(F, u, du=None):
         raise TypeError('derivative with respect to a Function (got %r)'
                         % (type(u),))
     V = u.function_space()
-    if not hasattr(V, 'layout') or not hasattr(V, 'dim') or V.dim != 1 \
-            or V.component is not None:
+    plain = hasattr(V, 'layout') and hasattr(V, 'dim') \
+        and V.component is None
+    vector = plain and V.dim == 2 and vector_derivatives.enabled
+    if not (plain and V.dim == 1) and not vector:
         raise NotImplementedError(
             'derivative with respect to a Function of a vector, component or '
             'mixed space: only scalar P1 / P2 spaces carry arguments')
+    if vector and not vector_arguments.enabled:
+        raise NotImplementedError(_VECTOR_ARGUMENTS_OFF)
     if V.degree not in (1, 2):
         raise ValueError('derivative: spaces of degree 1 or 2 only')
     found = F.arguments()
@@ -1603,8 +1654,16 @@ def derivative(F, u, du=None):
                 'different spaces or meshes')
     if du is not None:
         t = du.comps if isinstance(du, FormExpr) else None
-        if not (isinstance(t, tuple) and t[0] == 'arg' and t[1] == k
-                and t[2] == 0 and t[3].same_as(V)):
+        if vector:
+            # (the 2-vector of leaves TestFunction(W) / TrialFunction(W) is)
+            ok = du.shape == (2,) and all(
+                c[:3] == ('arg', k, 0) and len(c) == 5 and c[3].same_as(V)
+                and c[4] == i for i, c in enumerate(t)) \
+                if t is not None else False
+        else:
+            ok = isinstance(t, tuple) and t[0] == 'arg' and t[1] == k \
+                and t[2] == 0 and len(t) == 4 and t[3].same_as(V)
+        if not ok:
             raise ValueError(
                 'derivative: du must be the %s(V) of the space of u'
                 % ('TestFunction', 'TrialFunction')[k])

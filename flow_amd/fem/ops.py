@@ -7,7 +7,8 @@ tests/test_karman_vortex_street.py:262-268; tests/test_boussinesq.py:85),
 `assemble` / `assemble_system` / `solve` of forms (flow_amd/fem/forms.py):
 `solve(a == L, u, bcs)` a Krylov solve, `solve(F == 0, u, bcs, J)` Newton's
 method with the Jacobian and the residual assembled in one pass
-(newton_solve, NewtonAssembler, flow_form_newton).
+(newton_solve, NewtonAssembler, flow_form_newton; on vector spaces
+flow_form_block_newton).
 
 Everything numerical is a call into libflow_hip.so (flow_amd/_hip.py); torch
 only owns the HBM buffers.
@@ -1394,7 +1395,9 @@ class NewtonInfo(object):
     dx part of the Jacobian was assembled together with a part of the
     residual by flow_form_newton; ds parts are never fused and do not count:
     they go through flow_form_facet_matrix / flow_form_facet_vector one by
-    one), `method` (of the linear solves).'''
+    one; on a vector space: there is a 'newton' job, no dx component of the
+    residual needed a 'vector' job and no block of a fused row was split into
+    several programs -- block_jobs_fused), `method` (of the linear solves).'''
 
     def __init__(self, fused, method):
         self.iterations = 0
@@ -1454,8 +1457,11 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
     rule (the one it was derived from first) where forms.newton_program fits the limits of
     flow_form; what is left goes through flow_form_matrix / flow_form_vector
     part by part (program by program where a table needs several:
-    forms.argument_programs).  Host only.'''
+    forms.argument_programs).  Forms on a vector space: the jobs of
+    _block_newton_jobs.  Host only.'''
     from . import forms
+    if F.arguments()[0].dim == 2:
+        return _block_newton_jobs(J, F, form_compiler_parameters, fuse)
     fparts = F.terms()
     rules = [_part_rule(p, form_compiler_parameters) for _, p in fparts]
     used = [False] * len(fparts)
@@ -1488,13 +1494,284 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
     return jobs
 
 
+def _block_rows(tj, tf):
+    '''The dx jobs [(kind, Program, tag)] of one part of J (block table tj)
+    taken together with one part of F (block table tf), row by row (r = the
+    test component): block (r, s) and component r fuse into a 'newton' job
+    (tag p = 2 r + s) where forms.newton_program fits the limits of flow_form,
+    s = r first, else the other block of the row; the other blocks of the row
+    are 'matrix' jobs (tag p), a component that did not fuse 'vector' jobs
+    (tag r), program by program (forms.argument_programs).'''
+    from . import forms
+    rows = []
+    for r in range(2):
+        fused = None
+        if tf[r] is not None:
+            for s in (r, 1 - r):
+                if tj[r][s] is None:
+                    continue
+                try:
+                    fused = (s, forms.newton_program(tj[r][s], tf[r]))
+                    break
+                except ValueError:      # over a limit of flow_form
+                    continue
+        if fused is not None:
+            rows.append(('newton', fused[1], 2 * r + fused[0]))
+        for s in range(2):
+            if tj[r][s] is not None and (fused is None or s != fused[0]):
+                rows.extend(('matrix', prog, 2 * r + s)
+                            for prog in forms.argument_programs(tj[r][s], 2))
+        if tf[r] is not None and fused is None:
+            rows.extend(('vector', prog, r)
+                        for prog in forms.argument_programs(tf[r], 1))
+    return rows
+
+
+def _block_newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
+    '''newton_jobs for forms on a vector space W: (kind, sign of the matrix
+    part, sign of the vector part, Program, degree, scheme, part, tag, call).
+    kind as in newton_jobs; part: the ds part of a facet job, else None; tag:
+    the block plane p = 2 r + s ('newton', 'matrix', 'facet_matrix') or the
+    component r ('vector', 'facet_vector') -- a 'newton' job assembles block
+    p and component p // 2; call = (index of the part of J or None, index of
+    the part of F or None): the dx jobs of one call are ONE launch of
+    flow_form_block_newton (both indices), flow_form_block_matrix or
+    flow_form_block_vector.  A dx part of J is taken together with the first
+    unused dx part of F of the same degree and rule (the one it was derived
+    from first) with which at least one row fuses (_block_rows); without one,
+    and with fuse=False, its blocks are 'matrix' jobs and the parts of F
+    'vector' jobs: the pair assemble(J), assemble(F).'''
+    from . import forms
+    fparts = F.terms()
+    rules = [_part_rule(p, form_compiler_parameters) for _, p in fparts]
+    used = [False] * len(fparts)
+    jobs = []
+    for ji, (sj, pj) in enumerate(J.terms()):
+        rule = _part_rule(pj, form_compiler_parameters)
+        tj = pj.argument_table()[1]
+        if pj.integral_type == 'exterior_facet':
+            jobs.extend(('facet_matrix', sj, 0.0, prog) + rule
+                        + (pj, p, (ji, None))
+                        for p, block in forms.block_items(tj, 2)
+                        for prog in forms.argument_programs(block, 2, True))
+            continue
+        fi, rows = None, None
+        origin = getattr(pj, 'derived_from', None)
+        for i in sorted(range(len(fparts)),
+                        key=lambda i: fparts[i][1] is not origin):
+            if not fuse or used[i] or rules[i] != rule \
+                    or fparts[i][1].integral_type != 'cell':
+                continue
+            found = _block_rows(tj, fparts[i][1].argument_table()[1])
+            if any(kind == 'newton' for kind, _, _ in found):
+                fi, rows = i, found
+                break
+        if fi is None:
+            rows = [('matrix', prog, p)
+                    for p, block in forms.block_items(tj, 2)
+                    for prog in forms.argument_programs(block, 2)]
+        else:
+            used[fi] = True
+        sf = 0.0 if fi is None else fparts[fi][0]
+        jobs.extend((kind, 0.0 if kind == 'vector' else sj,
+                     0.0 if kind == 'matrix' else sf, prog) + rule
+                    + (None, tag, (ji, fi)) for kind, prog, tag in rows)
+    for i, (sf, pf) in enumerate(fparts):
+        facet = pf.integral_type == 'exterior_facet'
+        if used[i]:
+            continue
+        jobs.extend(('facet_vector' if facet else 'vector', 0.0, sf, prog)
+                    + rules[i] + (pf if facet else None, r, (None, i))
+                    for r, block in forms.block_items(
+                        pf.argument_table()[1], 1)
+                    for prog in forms.argument_programs(block, 1, facet))
+    return jobs
+
+
+def block_jobs_fused(jobs):
+    '''NewtonInfo.fused of the jobs of _block_newton_jobs: there is a 'newton'
+    job, no dx residual component needed a 'vector' job, and every block of a
+    row that has a 'newton' job in its call is ONE program (no table of such a
+    row was split).  ds jobs do not count.'''
+    if not any(j[0] == 'newton' for j in jobs) \
+            or any(j[0] == 'vector' for j in jobs):
+        return False
+    for j in jobs:
+        if j[0] != 'newton':
+            continue
+        row = [k[7] for k in jobs if k[8] == j[8]
+               and k[0] in ('newton', 'matrix') and k[7] // 2 == j[7] // 2]
+        if len(row) != len(set(row)):
+            return False
+    return True
+
+
+_BLOCK_KINDS = {'newton': 0, 'matrix': 1, 'vector': 2}     # include/flow_hip.h
+
+
+def _block_newton_scratch(kinds, tags, nl, nc):
+    '''Doubles of scratch flow_form_block_newton needs for these jobs
+    (include/flow_hip.h).'''
+    blocks = [t for k, t in zip(kinds, tags) if k != 'vector']
+    comps = [t if k == 'vector' else t // 2
+             for k, t in zip(kinds, tags) if k != 'matrix']
+    n = len(set(blocks)) * nl * nl * nc + len(set(comps)) * nl * nc
+    if len(blocks) > len(set(blocks)):
+        n += nl * nl * nc
+    elif len(comps) > len(set(comps)):
+        n += nl * nc
+    return n
+
+
+class _BlockNewton(object):
+    '''NewtonAssembler for forms on a vector space W: a kind-2 Matrix and a
+    vector of 2N.  Every part of J owns four value planes and every part of F
+    a vector of 2N, held as long as the object; a call (the dx jobs of a part
+    of J and the part of F it is taken with) is one launch of
+    flow_form_block_newton, a part on its own one of flow_form_block_matrix /
+    flow_form_block_vector; ds parts go block by block, program by program,
+    through the facet kernels into their part's zeroed buffer (a further
+    program of a block into a zeroed buffer of its own, then added).  The
+    parts are then added in the order written, as assemble() adds them: A and
+    b have the bits of assemble(J) and assemble(F).'''
+
+    def __init__(self, owner, J, F, form_compiler_parameters, fuse):
+        self.V = V = owner.V
+        self.mesh = owner.mesh
+        lay = V.layout
+        self.jobs = _block_newton_jobs(J, F, form_compiler_parameters, fuse)
+        self.fused = block_jobs_fused(self.jobs)
+        self.stride = plane_stride(lay)
+        self.jparts, self.fparts = J.terms(), F.terms()
+        if not self.jparts or not self.fparts:
+            raise ValueError('an empty sum of forms has no rank')
+        # (zeroed once: the launches write the nnz entries of a plane, not
+        # the one behind them)
+        self.jbuf = [device.zeros(4 * self.stride) for _ in self.jparts]
+        self.fbuf = [device.zeros(2 * lay.N) for _ in self.fparts]
+        self.A = Matrix(lay, 2, self._total(self.jparts, self.jbuf, 4 * self.stride))
+        self.b = self._total(self.fparts, self.fbuf, 2 * lay.N)
+        # the calls, in the order of the jobs: [call, kind of launch, job
+        # numbers, struct array, keepalives]
+        self.calls = []
+        for jn, job in enumerate(self.jobs):
+            facet = job[0].startswith('facet')
+            if self.calls and self.calls[-1][0] == job[8] and not facet \
+                    and self.calls[-1][1] != 'facet':
+                self.calls[-1][2].append(jn)
+            else:
+                self.calls.append([job[8], 'facet' if facet else None, [jn]])
+        for call in self.calls:
+            js = [self.jobs[jn] for jn in call[2]]
+            if call[1] is None:
+                call[1] = 'newton' if None not in call[0] else \
+                    'matrix' if call[0][1] is None else 'vector'
+            structs = (_hip.FormS * len(js))()
+            keeps = []
+            for k, j in enumerate(js):
+                fs, keep = _form_struct(j[3], self.mesh, j[4],
+                                        call[1] == 'facet', j[5])
+                structs[k] = fs
+                keeps.append(keep)
+            call.extend([structs, keeps])
+        # per further ds program of a block: [buffer]; per ds job: the map it
+        # was last gathered over
+        self._facet_tmp = {}
+        self._facet_map = {}
+
+    def _total(self, parts, bufs, n):
+        '''Where the parts are summed: the first part's own buffer where
+        nothing has to be added to it (one dx part of sign 1), else a buffer
+        of its own.'''
+        if len(parts) == 1 and parts[0][0] == 1.0 \
+                and parts[0][1].integral_type == 'cell':
+            return bufs[0]
+        return device.zeros(n)
+
+    def assemble(self):
+        lib = _hip.lib()
+        lay, mesh = self.V.layout, self.mesh
+        nc, nl, N, stride = mesh.num_cells(), lay.nloc, lay.N, self.stride
+        ms, ss = ctypes.byref(mesh_struct(mesh)), ctypes.byref(
+            space_struct(lay))
+        for (ji, fi), launch, jns, structs, _ in self.calls:
+            js = [self.jobs[jn] for jn in jns]
+            for k, j in enumerate(js):
+                for i, value in enumerate(j[3].constant_values()):
+                    structs[k].consts[i] = value
+            if launch == 'facet':
+                self._facet(jns[0], js[0], structs[0])
+                continue
+            kinds = [j[0] for j in js]
+            tags = [j[7] for j in js]
+            ctags = (ctypes.c_int * len(js))(*tags)
+            ns = _block_newton_scratch(kinds, tags, nl, nc)
+            buf = _hip.f64(scratch(mesh, ns), ns, 'scratch')
+            if launch == 'newton':
+                ckinds = (ctypes.c_int * len(js))(
+                    *[_BLOCK_KINDS[k] for k in kinds])
+                _hip.check(lib.flow_form_block_newton(
+                    ms, ss, len(js), structs, ckinds, ctags, buf, ns,
+                    _hip.f64(self.jbuf[ji], 4 * stride, 'vals'), stride,
+                    _hip.f64(self.fbuf[fi], 2 * N, 'b'), _hip.stream()))
+            elif launch == 'matrix':
+                _hip.check(lib.flow_form_block_matrix(
+                    ms, ss, len(js), structs, ctags, buf,
+                    _hip.f64(self.jbuf[ji], 4 * stride, 'vals'), stride,
+                    _hip.stream()))
+            else:
+                _hip.check(lib.flow_form_block_vector(
+                    ms, ss, len(js), structs, ctags, buf,
+                    _hip.f64(self.fbuf[fi], 2 * N, 'b'), _hip.stream()))
+        self._sum(self.jparts, self.jbuf, self.A.vals)
+        self._sum(self.fparts, self.fbuf, self.b)
+        return self.A, self.b
+
+    @staticmethod
+    def _sum(parts, bufs, total):
+        if total is bufs[0]:
+            return
+        _hip.fill(total, 0.0)
+        for (sign, _), buf in zip(parts, bufs):
+            axpby(sign, buf, 1.0, total)
+
+    def _facet(self, jn, job, fs):
+        '''One ds program into the plane or component of its block in its
+        part's buffer.'''
+        lay = self.V.layout
+        kind, part, tag, (ji, fi) = job[0], job[6], job[7], job[8]
+        rank = 2 if kind == 'facet_matrix' else 1
+        width = lay.nnz if rank == 2 else lay.N
+        step = self.stride if rank == 2 else lay.N
+        buf = self.jbuf[ji] if rank == 2 else self.fbuf[fi]
+        dst = buf[tag * step:tag * step + width]
+        first = not any(k[0] == kind and k[7] == tag and k[8] == job[8]
+                        for k in self.jobs[:jn])
+        out = dst
+        if not first:
+            if jn not in self._facet_tmp:
+                self._facet_tmp[jn] = device.zeros(width)
+            out = self._facet_tmp[jn]
+        fmap = facet_map(self.mesh, lay, rank, part.subdomain_data,
+                         part.subdomain_id)
+        if self._facet_map.setdefault(jn, fmap) is not fmap:
+            # re-marked: other targets
+            _hip.fill(out, 0.0)
+            self._facet_map[jn] = fmap
+        _facet_arguments(self.mesh, lay, rank, fs, part.subdomain_data,
+                         part.subdomain_id, out)
+        if not first:
+            axpby(1.0, out, 1.0, dst)
+
+
 class NewtonAssembler(object):
     '''(J, F) at the current values of the fields, into buffers that live as
     long as the object: the value plane `A.vals`, the vector `b`, one more of
     each where a sum of parts needs it, and the mesh's scratch.  `fused`:
     every dx part of J goes through flow_form_newton.  A ds job owns a zeroed
     buffer that its gather writes the same entries of at every call (zeroed
-    again where the facet markers were changed).'''
+    again where the facet markers were changed).  V a vector space: `A` of
+    kind 2, `b` of 2N, `fused` by block_jobs_fused (_BlockNewton).'''
 
     def __init__(self, J, F, V, form_compiler_parameters=None, fuse=True):
         from . import forms
@@ -1504,6 +1781,14 @@ class NewtonAssembler(object):
             if forms.form_mesh(part.integrand, part.mesh) is not self.mesh:
                 raise ValueError('the form is integrated over another mesh '
                                  'than the one of its arguments')
+        self._blocks = None
+        if V.dim == 2:
+            # forms on a vector space: a kind-2 Matrix, a vector of 2N
+            self._blocks = _BlockNewton(self, J, F, form_compiler_parameters,
+                                        fuse)
+            self.jobs, self.fused = self._blocks.jobs, self._blocks.fused
+            self.A, self.b = self._blocks.A, self._blocks.b
+            return
         self.jobs = newton_jobs(J, F, form_compiler_parameters, fuse)
         self.fused = all(j[0] != 'matrix' for j in self.jobs)
         lay = V.layout
@@ -1519,6 +1804,8 @@ class NewtonAssembler(object):
         self._facet = {}
 
     def assemble(self):
+        if self._blocks is not None:
+            return self._blocks.assemble()
         lib = _hip.lib()
         lay, mesh = self.V.layout, self.mesh
         nc = mesh.num_cells()
@@ -1624,7 +1911,11 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
     dolfin's keys and defaults (NEWTON_DEFAULTS; 'linear_solver' and
     'krylov_solver' as for the linear solve; 'report' prints a line per
     iteration through message.info).  Raises _hip.NotConverged unless
-    'error_on_nonconvergence' is False.  Not on strips.'''
+    'error_on_nonconvergence' is False.  Not on strips.  F on a vector space
+    W (forms.vector_derivatives(True)): the same loop with a kind-2 matrix and
+    vectors of 2N -- (J, F) by flow_form_block_newton where rows fuse
+    (_block_newton_jobs), conditions on W and W.sub(i), the elimination of
+    flow_bc_symmetric_blocks.'''
     from . import forms
     from ..message import info as say
     ns, symmetric = newton_parameters(solver_parameters)
@@ -1632,7 +1923,7 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
         raise ValueError('solve(F == 0, u): F must be a form of rank 1, '
                          'linear in a test function')
     V = F.arguments()[0]
-    if V.dim != 1:
+    if V.dim != 1 and not forms.vector_derivatives.enabled:
         raise NotImplementedError(
             'solve(F == 0) on a vector space: derivative() with respect to a '
             'vector Function and the Newton assembler are scalar only')
@@ -1659,8 +1950,8 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
     if dofs is not None:
         _set_values(dofs, vals, u.data)
         zero = device.zeros(dofs.numel())
-        Abc = Matrix(V.layout, 0)
-    delta = device.empty(V.N)
+        Abc = Matrix(V.layout, 2 if V.dim == 2 else 0)
+    delta = device.empty(V.size())
     ilu = None
     out = NewtonInfo(asm.fused, method)
     rtol, atol = ns['relative_tolerance'], ns['absolute_tolerance']
@@ -1669,7 +1960,8 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
     while True:
         A, b = asm.assemble()
         if dofs is not None:
-            A = symmetric_bc_matrix(A, mask, Abc)
+            A = symmetric_bc_blocks(A, mask, Abc) if V.dim == 2 else \
+                symmetric_bc_matrix(A, mask, Abc)
             _set_values(dofs, zero, b)
         r = vector_norm(b)
         r0 = r if r0 is None else r0

@@ -1348,6 +1348,37 @@ int flow_form_block_vector(const flow_mesh* mesh, const flow_space* V, int nprog
                            const flow_form* forms, const int* blocks,
                            double* scratch, double* b, void* stream);
 
+/* The Jacobian (a 2x2-block form) and the residual (2 components) of a Newton
+ * iteration on the VECTOR space on V's scalar pattern, at one state, in one
+ * call (forms.py, vector_derivatives; ops.py, NewtonAssembler).  forms: nprog
+ * (1..64) structs behind one another; kinds[k], tags[k] (host arrays):
+ *   FLOW_BLOCK_NEWTON, p: the program of flow_form_newton (nout =
+ *     FLOW_FORM_NEWTON_SLOTS) for block p = 2 r + s together with residual
+ *     component r = p / 2, on its element kernel: Ke to the block's scratch
+ *     plane, be directly behind it.  It must be the first program of its block
+ *     and of its component;
+ *   FLOW_BLOCK_MATRIX, p: a program of flow_form_block_matrix for block p;
+ *   FLOW_BLOCK_VECTOR, r: a program of flow_form_block_vector for component r.
+ * A further program of a block or component is added to its plane entry by
+ * entry, in the order of the list.  ONE gather launch then sums everything:
+ * lanes [0, nnz) write vals + p*plane_stride, p = 0..3, over cptr / csrc,
+ * lanes [nnz, nnz + n) write b[r*n + i] over vptr / vsrc, each sum in the
+ * order and arithmetic of the gather of flow_form_block_matrix /
+ * flow_form_block_vector: the bits those give for the same programs.  A
+ * block or component without a program is set to zero.  No atomics: two calls
+ * give the same bits.  Not on strips.
+ * scratch (nscratch doubles, checked): nloc^2 * nc per block with a program,
+ * + nloc * nc per component with one, + one more plane (nloc^2 * nc, or nloc *
+ * nc where only a component does) where a block or component has several. */
+#define FLOW_BLOCK_NEWTON 0
+#define FLOW_BLOCK_MATRIX 1
+#define FLOW_BLOCK_VECTOR 2
+int flow_form_block_newton(const flow_mesh* mesh, const flow_space* V, int nprog,
+                           const flow_form* forms, const int* kinds,
+                           const int* tags, double* scratch, size_t nscratch,
+                           double* vals, size_t plane_stride, double* b,
+                           void* stream);
+
 /* ---- point evaluation (flow_amd/fem/points.py): u(x), Probes ---------------
  * A uniform bucket grid over the mesh's bounding box, built on the host once
  * per mesh: bucket (ix, iy) = (floor((x - x0) * hx_inv), floor((y - y0) *
