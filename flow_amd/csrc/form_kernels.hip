@@ -23,6 +23,7 @@
 // unrolled compile-time loops -- a register file indexed at run time would
 // live in scratch memory.  Scratch stays at 0 bytes per lane.
 #include <cmath>
+#include <type_traits>
 
 #include "fem_device.h"
 
@@ -136,7 +137,8 @@ __device__ __forceinline__ double field_at(const flow_form& F,
 //
 // OUT receives the `out` instructions: FormOut2 for the functionals, load
 // vectors and points, FormSlots<9> / <3> for the coefficient tables of rank-2
-// / rank-1 forms.  Like the registers, the outputs are named values.
+// / rank-1 forms, <12> for both tables of a Newton pass.  Like the registers,
+// the outputs are named values.
 struct FormOut2 {
   double& out0;
   double& out1;
@@ -161,30 +163,14 @@ struct FormSlots {
       case 5: v[5 < N ? 5 : 0] = r; break;
       case 6: v[6 < N ? 6 : 0] = r; break;
       case 7: v[7 < N ? 7 : 0] = r; break;
+      // (N = 12, the set of form_newton_kernel: 3 b + a of the Jacobian's
+      // table, then 9 + b of the residual's.  In a smaller set these cases
+      // store where the default does, and fold into it: the switch of
+      // FormSlots<9> / <3> is the one it was before N = 12 existed)
+      case 8: v[8 < N ? 8 : N - 1] = r; break;
+      case 9: v[9 < N ? 9 : N - 1] = r; break;
+      case 10: v[10 < N ? 10 : N - 1] = r; break;
       default: v[N - 1] = r; break;
-    }
-  }
-};
-
-// the 12 slots of form_newton_kernel: 3 b + a of the Jacobian's table, then
-// 9 + b of the residual's (a set of its own: FormSlots<9> / <3> and the code
-// of the kernels that use them stay as they are)
-struct FormSlotsNewton {
-  double v[FLOW_FORM_NEWTON_SLOTS];
-  __device__ __forceinline__ void set(int b, double r) {
-    switch (b) {
-      case 0: v[0] = r; break;
-      case 1: v[1] = r; break;
-      case 2: v[2] = r; break;
-      case 3: v[3] = r; break;
-      case 4: v[4] = r; break;
-      case 5: v[5] = r; break;
-      case 6: v[6] = r; break;
-      case 7: v[7] = r; break;
-      case 8: v[8] = r; break;
-      case 9: v[9] = r; break;
-      case 10: v[10] = r; break;
-      default: v[11] = r; break;
     }
   }
 };
@@ -372,24 +358,65 @@ __device__ __forceinline__ void load_form_fields(const flow_form& F, int nc, int
   }
 }
 
+// What a lane holds of its cell while the program runs: the geometry, the
+// vertex coordinates and the local values of the form's fields.  Every form
+// kernel starts with load_form_cell.
+template <int NF>
+struct FormCell {
+  Geom g;
+  double X[3], Y[3];
+  double U[NF > 0 ? NF : 1][6];
+};
+
+template <int NF>
+__device__ __forceinline__ void load_form_cell(const flow_form& F, int nc,
+                                               const double* xy, int c,
+                                               FormCell<NF>& C) {
+  C.g = load_geom(xy, nc, c);
+#pragma unroll
+  for (int v = 0; v < 3; ++v) C.X[v] = xy[v * nc + c];
+#pragma unroll
+  for (int v = 0; v < 3; ++v) C.Y[v] = xy[(3 + v) * nc + c];
+  load_form_fields<NF>(F, nc, c, C.U);
+}
+
+// Outward unit normal (n0, n1) and length of local facet lf of a cell:
+// -grad(lambda_lf) / |grad lambda_lf| and |det J| |grad lambda_lf|.
+struct FacetFrame {
+  double n0, n1, len;
+};
+
+__device__ __forceinline__ FacetFrame facet_frame(const Geom& g, int lf) {
+  // (selects, not g.gl[lf]: a run-time index would put g in scratch memory.
+  // Selects of VALUES loaded beforehand: g is a reference here, and loads
+  // under the branches of a conditional are merged into one load from a
+  // selected address, which is a run-time index again.  The unary + makes
+  // each operand a value: a conditional between two named doubles is itself
+  // an lvalue, that is, a selected address once more)
+  const double x0 = g.gl[0][0], x1 = g.gl[1][0], x2 = g.gl[2][0];
+  const double y0 = g.gl[0][1], y1 = g.gl[1][1], y2 = g.gl[2][1];
+  const double gx = lf == 0 ? +x0 : (lf == 1 ? +x1 : +x2);
+  const double gy = lf == 0 ? +y0 : (lf == 1 ? +y1 : +y2);
+  const double gn = sqrt(gx * gx + gy * gy);
+  return {-gx / gn, -gy / gn, g.adet * gn};
+}
+
 // Runs the program at every point of the rule on cell c.  TD = 0: returns
 // sum_q w_q |det J| out_0(x_q); TD = 1, 2: acc[o][i] += w_q |det J| out_o phi_i.
 template <int NF, int TD, bool EXT>
 __device__ __forceinline__ double form_cell(const flow_form& F, int nc,
                                             const double* __restrict__ xy, int c,
                                             double (&acc)[2][6]) {
-  const Geom g = load_geom(xy, nc, c);
-  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
-  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
-  double U[NF > 0 ? NF : 1][6];
-  load_form_fields<NF>(F, nc, c, U);
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
+  const Geom& g = C.g;
   double total = 0.0;
   for (int q = 0; q < F.nq; ++q) {
     const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
     const double w = F.rule[3 * q + 2] * g.adet;
     const double L[3] = {1.0 - xi - eta, xi, eta};
     double out0 = 0.0, out1 = 0.0;
-    form_point<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out0, out1);
+    form_point<NF, false, EXT>(F, C.U, C.X, C.Y, g, L, q, nc, c, 0.0, 0.0, out0, out1);
     if constexpr (TD == 0) {
       total += w * out0;
     } else {
@@ -422,25 +449,18 @@ template <int NF, bool EXT>
 __device__ __forceinline__ double form_facet(const flow_form& F, int nc,
                                              const double* __restrict__ xy, int c,
                                              int lf) {
-  const Geom g = load_geom(xy, nc, c);
-  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
-  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
-  double U[NF > 0 ? NF : 1][6];
-  load_form_fields<NF>(F, nc, c, U);
-  // (selects, not g.gl[lf]: a run-time index would put g in scratch memory)
-  const double gx = lf == 0 ? g.gl[0][0] : (lf == 1 ? g.gl[1][0] : g.gl[2][0]);
-  const double gy = lf == 0 ? g.gl[0][1] : (lf == 1 ? g.gl[1][1] : g.gl[2][1]);
-  const double gn = sqrt(gx * gx + gy * gy);
-  const double n0 = -gx / gn, n1 = -gy / gn;
-  const double len = g.adet * gn;
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
+  const FacetFrame f = facet_frame(C.g, lf);
   double total = 0.0;
   for (int j = 0; j < F.nq; ++j) {
     const int row = lf * F.nq + j;
     const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
     const double L[3] = {1.0 - xi - eta, xi, eta};
     double out0 = 0.0, out1 = 0.0;
-    form_point<NF, true, EXT>(F, U, X, Y, g, L, row, nc, c, n0, n1, out0, out1);
-    total += F.rule[3 * row + 2] * len * out0;
+    form_point<NF, true, EXT>(F, C.U, C.X, C.Y, C.g, L, row, nc, c, f.n0, f.n1, out0,
+                              out1);
+    total += F.rule[3 * row + 2] * f.len * out0;
   }
   return total;
 }
@@ -539,16 +559,9 @@ __global__ __launch_bounds__(kBlock) void form_facet_values_kernel(
     }
     return;
   }
-  const Geom g = load_geom(xy, nc, c);
-  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
-  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
-  double U[NF > 0 ? NF : 1][6];
-  load_form_fields<NF>(F, nc, c, U);
-  const double gx = lf == 0 ? g.gl[0][0] : (lf == 1 ? g.gl[1][0] : g.gl[2][0]);
-  const double gy = lf == 0 ? g.gl[0][1] : (lf == 1 ? g.gl[1][1] : g.gl[2][1]);
-  const double gn = sqrt(gx * gx + gy * gy);
-  const double n0 = -gx / gn, n1 = -gy / gn;
-  const double len = g.adet * gn;
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
+  const FacetFrame f = facet_frame(C.g, lf);
   double total0 = 0.0, total1 = 0.0;
   // (one loop for the sample and the integral: the interpreter is inlined once)
   for (int q = j, qe = whole ? m : j + 1; q < qe; ++q) {
@@ -556,13 +569,14 @@ __global__ __launch_bounds__(kBlock) void form_facet_values_kernel(
     const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
     const double L[3] = {1.0 - xi - eta, xi, eta};
     double out0 = 0.0, out1 = 0.0;
-    form_point<NF, true, EXT>(F, U, X, Y, g, L, row, nc, c, n0, n1, out0, out1);
+    form_point<NF, true, EXT>(F, C.U, C.X, C.Y, C.g, L, row, nc, c, f.n0, f.n1, out0,
+                              out1);
     if (q == j) {
       val[0] = out0;
       if (F.nout == 2) val[np] = out1;
     }
-    total0 += F.rule[3 * row + 2] * len * out0;
-    total1 += F.rule[3 * row + 2] * len * out1;
+    total0 += F.rule[3 * row + 2] * f.len * out0;
+    total1 += F.rule[3 * row + 2] * f.len * out1;
   }
   if (whole) {
     integrals[d] = total0;
@@ -801,16 +815,13 @@ __global__ __launch_bounds__(kBlock) void form_points_kernel(
   const int c = cell[i];
   double out0 = __builtin_nan(""), out1 = out0;
   if (c >= 0 && c < nc) {
-    const Geom g = load_geom(xy, nc, c);
-    const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
-    const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
-    double U[NF > 0 ? NF : 1][6];
-    load_form_fields<NF>(F, nc, c, U);
+    FormCell<NF> C;
+    load_form_cell<NF>(F, nc, xy, c, C);
     const double L[3] = {bary[i], bary[static_cast<size_t>(n) + i],
                          bary[2 * static_cast<size_t>(n) + i]};
     out0 = 0.0;
     out1 = 0.0;
-    form_point<NF, false, EXT>(F, U, X, Y, g, L, 0, nc, c, 0.0, 0.0, out0, out1);
+    form_point<NF, false, EXT>(F, C.U, C.X, C.Y, C.g, L, 0, nc, c, 0.0, 0.0, out0, out1);
   }
   out[i] = out0;
   if (F.nout == 2) out[static_cast<size_t>(n) + i] = out1;
@@ -832,6 +843,61 @@ __device__ __forceinline__ double arg_basis(int a, const double (&phi)[NL],
   return a == 0 ? phi[t] : gphi[t][a == 2 ? 1 : 0];
 }
 
+// The rank-2 accumulation of one point, shared by form_matrix_kernel and the
+// facet kernel (form_newton_kernel restates it; the bit-for-bit tests check
+// that copy).  m is the mask of live slots, w the point's weight, slots the
+// program's outputs; `base` is the position of the table in both.
+//
+// t_j = sum_a w c_ba D_a phi_j for one test derivative b, whose three slots
+// (a = 0, 1, 2) start at `first`
+template <int NL, int NS>
+__device__ __forceinline__ void trial_sums(int m, int first, double w,
+                                           const double (&slots)[NS],
+                                           const double (&phi)[NL],
+                                           const double (&gphi)[NL][2], double (&t)[NL]) {
+#pragma unroll
+  for (int j = 0; j < NL; ++j) t[j] = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (((m >> (first + a)) & 1) == 0) continue;
+    const double s = w * slots[first + a];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) t[j] += s * arg_basis<NL>(a, phi, gphi, j);
+  }
+}
+
+// rank 2: per test derivative b, t_j first, then Ke[i][j] += D_b phi_i t_j
+template <int NL, int NS>
+__device__ __forceinline__ void add_matrix_terms(int m, int base, double w,
+                                                 const double (&slots)[NS],
+                                                 const double (&phi)[NL],
+                                                 const double (&gphi)[NL][2],
+                                                 double (&Ke)[NL][NL]) {
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    if (((m >> (base + 3 * b)) & 7) == 0) continue;
+    double t[NL];
+    trial_sums<NL>(m, base + 3 * b, w, slots, phi, gphi, t);
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+      const double di = arg_basis<NL>(b, phi, gphi, i);
+#pragma unroll
+      for (int j = 0; j < NL; ++j) Ke[i][j] += di * t[j];
+    }
+  }
+}
+
+// D_b of the basis function `own`, which the lane knows at run time only
+// (selects: a run-time index would put the tables in scratch memory)
+template <int NL>
+__device__ __forceinline__ double own_basis(int b, const double (&phi)[NL],
+                                            const double (&gphi)[NL][2], int own) {
+  double d = 0.0;
+#pragma unroll
+  for (int t = 0; t < NL; ++t) d = t == own ? arg_basis<NL>(b, phi, gphi, t) : d;
+  return d;
+}
+
 // Ke[i][j] = sum_q w_q |det J| sum_ba c_ba(x_q) D_a phi_j D_b phi_i, to
 // scratch[(i*NL + j)*nc + c] (the layout of scalar_matrix_kernel: the gather
 // over cptr / csrc sums it into a value plane).  All NL*NL entries are held
@@ -848,11 +914,8 @@ __global__ __launch_bounds__(kBlock) void form_matrix_kernel(
   // (the lane's own address: the base pointer need not stay in scalar
   // registers across the interpreter loop, which is short of them)
   double* const dst = scratch + c;
-  const Geom g = load_geom(xy, nc, c);
-  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
-  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
-  double U[NF > 0 ? NF : 1][6];
-  load_form_fields<NF>(F, nc, c, U);
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
   double Ke[NL][NL];
 #pragma unroll
   for (int i = 0; i < NL; ++i)
@@ -860,40 +923,22 @@ __global__ __launch_bounds__(kBlock) void form_matrix_kernel(
     for (int j = 0; j < NL; ++j) Ke[i][j] = 0.0;
   for (int q = 0; q < F.nq; ++q) {
     const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
-    const double w = F.rule[3 * q + 2] * g.adet;
+    const double w = F.rule[3 * q + 2] * C.g.adet;
     const double L[3] = {1.0 - xi - eta, xi, eta};
     FormSlots<FLOW_FORM_SLOTS> out;
 #pragma unroll
     for (int k = 0; k < FLOW_FORM_SLOTS; ++k) out.v[k] = 0.0;
-    form_point_n<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    form_point_n<NF, false, EXT>(F, C.U, C.X, C.Y, C.g, L, q, nc, c, 0.0, 0.0, out);
     double phi[NL], dphi[NL][3], gphi[NL][2];
     basis<DEG>(L, phi, dphi);
-    phys_grad<NL>(g, dphi, gphi);
-    // (the mask through an empty asm: otherwise the twelve tests below are
-    // hoisted out of the loop and their results held in scalar registers
-    // across the interpreter, which then spills two of its own)
+    phys_grad<NL>(C.g, dphi, gphi);
+    // (the mask through an empty asm: otherwise the twelve tests of the
+    // accumulation are hoisted out of the loop and their results held in
+    // scalar registers across the interpreter, which then spills two of its
+    // own)
     int m = live;
     asm volatile("" : "+s"(m));
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      if (((m >> (3 * b)) & 7) == 0) continue;
-      double t[NL];
-#pragma unroll
-      for (int j = 0; j < NL; ++j) t[j] = 0.0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        if (((m >> (3 * b + a)) & 1) == 0) continue;
-        const double s = w * out.v[3 * b + a];
-#pragma unroll
-        for (int j = 0; j < NL; ++j) t[j] += s * arg_basis<NL>(a, phi, gphi, j);
-      }
-#pragma unroll
-      for (int i = 0; i < NL; ++i) {
-        const double di = arg_basis<NL>(b, phi, gphi, i);
-#pragma unroll
-        for (int j = 0; j < NL; ++j) Ke[i][j] += di * t[j];
-      }
-    }
+    add_matrix_terms<NL>(m, 0, w, out.v, phi, gphi, Ke);
   }
 #pragma unroll
   for (int i = 0; i < NL; ++i)
@@ -911,6 +956,9 @@ __global__ __launch_bounds__(kBlock) void form_vector_kernel(
   constexpr int NL = Elem<DEG>::NL;
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
+  // (this kernel keeps its own statement of the cell prologue and of its
+  // accumulation: built from load_form_cell and a routine for the loop, two
+  // of its 28 instances take more registers)
   const Geom g = load_geom(xy, nc, c);
   const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
   const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
@@ -948,10 +996,10 @@ __global__ __launch_bounds__(kBlock) void form_vector_kernel(
 // newton_program): ONE program writes the 9 slots of the Jacobian's table and,
 // at 9 + b, the 3 of the residual's; geometry, field values, basis tables and
 // the subtrees the two tables share are loaded / computed once per point.  Ke
-// and be are accumulated with the arithmetic of form_matrix_kernel and
-// form_vector_kernel, in their order; Ke goes to scratch[(i*NL + j)*nc + c],
-// be behind it to scratch[(NL*NL + i)*nc + c].  live: bits 0..8 the Jacobian's
-// slots, 9..11 the residual's.
+// and be are accumulated with the arithmetic of form_matrix_kernel
+// (add_matrix_terms) and form_vector_kernel, in their order; Ke goes to
+// scratch[(i*NL + j)*nc + c], be behind it to scratch[(NL*NL + i)*nc + c].
+// live: bits 0..8 the Jacobian's slots, 9..11 the residual's.
 template <int NF, int DEG, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_newton_kernel(
     int nc, const double* __restrict__ xy, const flow_form F, int live,
@@ -960,6 +1008,9 @@ __global__ __launch_bounds__(kBlock) void form_newton_kernel(
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
   double* const dst = scratch + c;
+  // (this kernel keeps its own statement of the cell prologue and of the two
+  // accumulations: built from load_form_cell and add_matrix_terms its P2
+  // instances measured 1.4 % slower in the block Newton pass)
   const Geom g = load_geom(xy, nc, c);
   const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
   const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
@@ -976,7 +1027,7 @@ __global__ __launch_bounds__(kBlock) void form_newton_kernel(
     const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
     const double w = F.rule[3 * q + 2] * g.adet;
     const double L[3] = {1.0 - xi - eta, xi, eta};
-    FormSlotsNewton out;
+    FormSlots<FLOW_FORM_NEWTON_SLOTS> out;
 #pragma unroll
     for (int k = 0; k < FLOW_FORM_NEWTON_SLOTS; ++k) out.v[k] = 0.0;
     form_point_n<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
@@ -1057,61 +1108,46 @@ __global__ __launch_bounds__(kBlock) void form_facet_arguments_kernel(
       dst[static_cast<size_t>(j) * nfacets] = __builtin_nan("");
     return;
   }
-  const Geom g = load_geom(xy, nc, c);
-  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
-  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
-  double U[NF > 0 ? NF : 1][6];
-  load_form_fields<NF>(F, nc, c, U);
-  // (selects, not g.gl[lf]: a run-time index would put g in scratch memory)
-  const double gx = lf == 0 ? g.gl[0][0] : (lf == 1 ? g.gl[1][0] : g.gl[2][0]);
-  const double gy = lf == 0 ? g.gl[0][1] : (lf == 1 ? g.gl[1][1] : g.gl[2][1]);
-  const double gn = sqrt(gx * gx + gy * gy);
-  const double n0 = -gx / gn, n1 = -gy / gn;
-  const double len = g.adet * gn;
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
+  const FacetFrame f = facet_frame(C.g, lf);
   double acc[NR];
 #pragma unroll
   for (int j = 0; j < NR; ++j) acc[j] = 0.0;
   for (int q = 0; q < F.nq; ++q) {
     const int row = lf * F.nq + q;
     const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
-    const double w = F.rule[3 * row + 2] * len;
+    const double w = F.rule[3 * row + 2] * f.len;
     const double L[3] = {1.0 - xi - eta, xi, eta};
     FormSlots<RANK == 2 ? FLOW_FORM_SLOTS : 3> out;
 #pragma unroll
     for (int s = 0; s < (RANK == 2 ? FLOW_FORM_SLOTS : 3); ++s) out.v[s] = 0.0;
-    form_point_n<NF, true, EXT>(F, U, X, Y, g, L, row, nc, c, n0, n1, out);
+    form_point_n<NF, true, EXT>(F, C.U, C.X, C.Y, C.g, L, row, nc, c, f.n0, f.n1, out);
     double phi[NL], dphi[NL][3], gphi[NL][2];
     basis<DEG>(L, phi, dphi);
-    phys_grad<NL>(g, dphi, gphi);
+    phys_grad<NL>(C.g, dphi, gphi);
     // (the mask through an empty asm, as in form_matrix_kernel)
     int m = live;
     asm volatile("" : "+s"(m));
+    if constexpr (RANK == 2) {
+      // row i of add_matrix_terms
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      if constexpr (RANK == 2) {
+      for (int b = 0; b < 3; ++b) {
         if (((m >> (3 * b)) & 7) == 0) continue;
-      } else {
-        if (((m >> b) & 1) == 0) continue;
-      }
-      // D_b phi_i of the lane's own test function (selects: a run-time index
-      // would put the tables in scratch memory)
-      double di = 0.0;
-#pragma unroll
-      for (int t = 0; t < NL; ++t) di = t == i ? arg_basis<NL>(b, phi, gphi, t) : di;
-      if constexpr (RANK == 2) {
+        const double di = own_basis<NL>(b, phi, gphi, i);
         double t[NL];
-#pragma unroll
-        for (int j = 0; j < NL; ++j) t[j] = 0.0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          if (((m >> (3 * b + a)) & 1) == 0) continue;
-          const double s = w * out.v[3 * b + a];
-#pragma unroll
-          for (int j = 0; j < NL; ++j) t[j] += s * arg_basis<NL>(a, phi, gphi, j);
-        }
+        trial_sums<NL>(m, 3 * b, w, out.v, phi, gphi, t);
 #pragma unroll
         for (int j = 0; j < NL; ++j) acc[j] += di * t[j];
-      } else {
+      }
+    } else {
+      // entry i of the loop of form_vector_kernel (stated here: through a
+      // routine two of the 28 rank-1 instances change their register counts,
+      // DESIGN.md)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        if (((m >> b) & 1) == 0) continue;
+        const double di = own_basis<NL>(b, phi, gphi, i);
         acc[0] += (w * out.v[b]) * di;
       }
     }
@@ -1255,64 +1291,78 @@ static int check_form_mesh(const flow_mesh* mesh) {
   return FLOW_OK;
 }
 
-template <int TD>
-static int launch_cells(const flow_mesh* mesh, const flow_form* F, int cb, int ce,
-                       double* scratch, hipStream_t st) {
-  const dim3 grid((ce - cb + kBlock - 1) / kBlock);
+// what every entry point of a form of arguments asks of its mesh and space:
+// the whole mesh, a space of degree 1 or 2 with the gather maps of the
+// element matrices (need_matrix) and / or vectors (need_vector)
+static int check_argument_space(const flow_mesh* mesh, const flow_space* V,
+                                bool need_matrix, bool need_vector) {
+  const int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 &&
+                   (!need_matrix || (V->nnz > 0 && V->cptr && V->csrc)) &&
+                   (!need_vector || (V->vptr && V->vsrc)),
+               "space");
+  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
+  return FLOW_OK;
+}
+
+// The instance of a form kernel is chosen here and nowhere else: launch(NF,
+// EXT) is called with the number of the form's fields (0..6) and whether its
+// program holds an extended opcode, as std::integral_constants; it launches
+// the one kernel <NF(), ..., EXT()>.
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+template <class Launch>
+static int dispatch_form(const flow_form* F, Launch&& launch) {
   const bool ext = form_is_extended(F);
+  const auto with_ext = [&](auto NF) {
+    if (ext) launch(NF, std::true_type{});
+    else launch(NF, std::false_type{});
+  };
   switch (F->nfield) {
-#define FLOW_FORM_LOAD_CASE(NF)                                                  \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_cell_kernel<NF, TD, true>), grid, dim3(kBlock), \
-                           0, st, mesh->nc, cb, ce, mesh->xy, *F, scratch);     \
-      else                                                                       \
-        hipLaunchKernelGGL((form_cell_kernel<NF, TD, false>), grid, dim3(kBlock),\
-                           0, st, mesh->nc, cb, ce, mesh->xy, *F, scratch);     \
-      break;
-    FLOW_FORM_LOAD_CASE(0)
-    FLOW_FORM_LOAD_CASE(1)
-    FLOW_FORM_LOAD_CASE(2)
-    FLOW_FORM_LOAD_CASE(3)
-    FLOW_FORM_LOAD_CASE(4)
-    FLOW_FORM_LOAD_CASE(5)
-    default:
-    FLOW_FORM_LOAD_CASE(6)
-#undef FLOW_FORM_LOAD_CASE
+    case 0: with_ext(Int<0>{}); break;
+    case 1: with_ext(Int<1>{}); break;
+    case 2: with_ext(Int<2>{}); break;
+    case 3: with_ext(Int<3>{}); break;
+    case 4: with_ext(Int<4>{}); break;
+    case 5: with_ext(Int<5>{}); break;
+    default: with_ext(Int<6>{}); break;
   }
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
+}
+
+// ... and launch(NF, EXT, DEG) for the kernels of a space of degree 1 or 2
+template <class Launch>
+static int dispatch_form(const flow_form* F, int deg, Launch&& launch) {
+  if (deg == 1)
+    return dispatch_form(F, [&](auto NF, auto EXT) { launch(NF, EXT, Int<1>{}); });
+  return dispatch_form(F, [&](auto NF, auto EXT) { launch(NF, EXT, Int<2>{}); });
+}
+
+// td = 0: the functional; the degree of the space: the load vector
+static int launch_cells(const flow_mesh* mesh, const flow_form* F, int td, int cb, int ce,
+                        double* scratch, hipStream_t st) {
+  const dim3 grid((ce - cb + kBlock - 1) / kBlock);
+  const auto launch = [&](auto NF, auto EXT, auto TD) {
+    hipLaunchKernelGGL((form_cell_kernel<NF(), TD(), EXT()>), grid, dim3(kBlock), 0, st,
+                       mesh->nc, cb, ce, mesh->xy, *F, scratch);
+  };
+  if (td == 0)
+    return dispatch_form(F, [&](auto NF, auto EXT) { launch(NF, EXT, Int<0>{}); });
+  return dispatch_form(F, td, launch);
 }
 
 static int launch_facets(const flow_mesh* mesh, const flow_form* F, int nfacets,
                          const int* fcell, const int* flocal, double* scratch,
                          hipStream_t st) {
   const dim3 grid((nfacets + kBlock - 1) / kBlock);
-  const bool ext = form_is_extended(F);
-  switch (F->nfield) {
-#define FLOW_FORM_FACET_CASE(NF)                                                 \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_facet_kernel<NF, true>), grid, dim3(kBlock), 0, \
-                           st, mesh->nc, nfacets, fcell, flocal, mesh->xy, *F,  \
-                           scratch);                                             \
-      else                                                                       \
-        hipLaunchKernelGGL((form_facet_kernel<NF, false>), grid, dim3(kBlock), 0,\
-                           st, mesh->nc, nfacets, fcell, flocal, mesh->xy, *F,  \
-                           scratch);                                             \
-      break;
-    FLOW_FORM_FACET_CASE(0)
-    FLOW_FORM_FACET_CASE(1)
-    FLOW_FORM_FACET_CASE(2)
-    FLOW_FORM_FACET_CASE(3)
-    FLOW_FORM_FACET_CASE(4)
-    FLOW_FORM_FACET_CASE(5)
-    default:
-    FLOW_FORM_FACET_CASE(6)
-#undef FLOW_FORM_FACET_CASE
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
+  return dispatch_form(F, [&](auto NF, auto EXT) {
+    hipLaunchKernelGGL((form_facet_kernel<NF(), EXT()>), grid, dim3(kBlock), 0, st,
+                       mesh->nc, nfacets, fcell, flocal, mesh->xy, *F, scratch);
+  });
 }
 
 static int launch_facet_values(const flow_mesh* mesh, const flow_form* F, int nfacets,
@@ -1320,185 +1370,58 @@ static int launch_facet_values(const flow_mesh* mesh, const flow_form* F, int nf
                                const int* fflip, double* values, double* integrals,
                                hipStream_t st) {
   const dim3 grid((nfacets * F->nq + kBlock - 1) / kBlock);
-  const bool ext = form_is_extended(F);
-  switch (F->nfield) {
-#define FLOW_FORM_VALUES_CASE(NF)                                                \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_facet_values_kernel<NF, true>), grid,           \
-                           dim3(kBlock), 0, st, mesh->nc, nfacets, fcell, flocal,\
-                           fdest, fflip, mesh->xy, *F, values, integrals);       \
-      else                                                                       \
-        hipLaunchKernelGGL((form_facet_values_kernel<NF, false>), grid,          \
-                           dim3(kBlock), 0, st, mesh->nc, nfacets, fcell, flocal,\
-                           fdest, fflip, mesh->xy, *F, values, integrals);       \
-      break;
-    FLOW_FORM_VALUES_CASE(0)
-    FLOW_FORM_VALUES_CASE(1)
-    FLOW_FORM_VALUES_CASE(2)
-    FLOW_FORM_VALUES_CASE(3)
-    FLOW_FORM_VALUES_CASE(4)
-    FLOW_FORM_VALUES_CASE(5)
-    default:
-    FLOW_FORM_VALUES_CASE(6)
-#undef FLOW_FORM_VALUES_CASE
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
+  return dispatch_form(F, [&](auto NF, auto EXT) {
+    hipLaunchKernelGGL((form_facet_values_kernel<NF(), EXT()>), grid, dim3(kBlock), 0, st,
+                       mesh->nc, nfacets, fcell, flocal, fdest, fflip, mesh->xy, *F,
+                       values, integrals);
+  });
 }
 
 static int launch_points(const flow_mesh* mesh, const flow_form* F, int n,
                          const int* cell, const double* bary, double* out,
                          hipStream_t st) {
   const dim3 grid((n + kBlock - 1) / kBlock);
-  const bool ext = form_is_extended(F);
-  switch (F->nfield) {
-#define FLOW_FORM_POINTS_CASE(NF)                                                \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_points_kernel<NF, true>), grid, dim3(kBlock), 0,\
-                           st, mesh->nc, mesh->xy, *F, n, cell, bary, out);     \
-      else                                                                       \
-        hipLaunchKernelGGL((form_points_kernel<NF, false>), grid, dim3(kBlock),  \
-                           0, st, mesh->nc, mesh->xy, *F, n, cell, bary, out);  \
-      break;
-    FLOW_FORM_POINTS_CASE(0)
-    FLOW_FORM_POINTS_CASE(1)
-    FLOW_FORM_POINTS_CASE(2)
-    FLOW_FORM_POINTS_CASE(3)
-    FLOW_FORM_POINTS_CASE(4)
-    FLOW_FORM_POINTS_CASE(5)
-    default:
-    FLOW_FORM_POINTS_CASE(6)
-#undef FLOW_FORM_POINTS_CASE
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
+  return dispatch_form(F, [&](auto NF, auto EXT) {
+    hipLaunchKernelGGL((form_points_kernel<NF(), EXT()>), grid, dim3(kBlock), 0, st,
+                       mesh->nc, mesh->xy, *F, n, cell, bary, out);
+  });
 }
 
-template <int DEG>
-static int launch_matrix(const flow_mesh* mesh, const flow_form* F, int live,
-                         double* scratch, hipStream_t st) {
+// the element kernels of a form of arguments on a space of degree deg
+enum class Element { matrix, vector, newton };
+
+static int launch_element(Element what, const flow_mesh* mesh, int deg,
+                          const flow_form* F, int live, double* scratch, hipStream_t st) {
   const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
-  const bool ext = form_is_extended(F);
-  switch (F->nfield) {
-#define FLOW_FORM_MATRIX_CASE(NF)                                                \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_matrix_kernel<NF, DEG, true>), grid,            \
-                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
-                           scratch);                                             \
-      else                                                                       \
-        hipLaunchKernelGGL((form_matrix_kernel<NF, DEG, false>), grid,           \
-                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
-                           scratch);                                             \
-      break;
-    FLOW_FORM_MATRIX_CASE(0)
-    FLOW_FORM_MATRIX_CASE(1)
-    FLOW_FORM_MATRIX_CASE(2)
-    FLOW_FORM_MATRIX_CASE(3)
-    FLOW_FORM_MATRIX_CASE(4)
-    FLOW_FORM_MATRIX_CASE(5)
+  switch (what) {
+    case Element::matrix:
+      return dispatch_form(F, deg, [&](auto NF, auto EXT, auto DEG) {
+        hipLaunchKernelGGL((form_matrix_kernel<NF(), DEG(), EXT()>), grid, dim3(kBlock), 0,
+                           st, mesh->nc, mesh->xy, *F, live, scratch);
+      });
+    case Element::vector:
+      return dispatch_form(F, deg, [&](auto NF, auto EXT, auto DEG) {
+        hipLaunchKernelGGL((form_vector_kernel<NF(), DEG(), EXT()>), grid, dim3(kBlock), 0,
+                           st, mesh->nc, mesh->xy, *F, live, scratch);
+      });
     default:
-    FLOW_FORM_MATRIX_CASE(6)
-#undef FLOW_FORM_MATRIX_CASE
+      return dispatch_form(F, deg, [&](auto NF, auto EXT, auto DEG) {
+        hipLaunchKernelGGL((form_newton_kernel<NF(), DEG(), EXT()>), grid, dim3(kBlock), 0,
+                           st, mesh->nc, mesh->xy, *F, live, scratch);
+      });
   }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
 }
 
-template <int DEG>
-static int launch_vector(const flow_mesh* mesh, const flow_form* F, int live,
-                         double* scratch, hipStream_t st) {
-  const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
-  const bool ext = form_is_extended(F);
-  switch (F->nfield) {
-#define FLOW_FORM_VECTOR_CASE(NF)                                                \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_vector_kernel<NF, DEG, true>), grid,            \
-                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
-                           scratch);                                             \
-      else                                                                       \
-        hipLaunchKernelGGL((form_vector_kernel<NF, DEG, false>), grid,           \
-                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
-                           scratch);                                             \
-      break;
-    FLOW_FORM_VECTOR_CASE(0)
-    FLOW_FORM_VECTOR_CASE(1)
-    FLOW_FORM_VECTOR_CASE(2)
-    FLOW_FORM_VECTOR_CASE(3)
-    FLOW_FORM_VECTOR_CASE(4)
-    FLOW_FORM_VECTOR_CASE(5)
-    default:
-    FLOW_FORM_VECTOR_CASE(6)
-#undef FLOW_FORM_VECTOR_CASE
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-template <int DEG>
-static int launch_newton(const flow_mesh* mesh, const flow_form* F, int live,
-                         double* scratch, hipStream_t st) {
-  const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
-  const bool ext = form_is_extended(F);
-  switch (F->nfield) {
-#define FLOW_FORM_NEWTON_CASE(NF)                                                \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_newton_kernel<NF, DEG, true>), grid,            \
-                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
-                           scratch);                                             \
-      else                                                                       \
-        hipLaunchKernelGGL((form_newton_kernel<NF, DEG, false>), grid,           \
-                           dim3(kBlock), 0, st, mesh->nc, mesh->xy, *F, live,   \
-                           scratch);                                             \
-      break;
-    FLOW_FORM_NEWTON_CASE(0)
-    FLOW_FORM_NEWTON_CASE(1)
-    FLOW_FORM_NEWTON_CASE(2)
-    FLOW_FORM_NEWTON_CASE(3)
-    FLOW_FORM_NEWTON_CASE(4)
-    FLOW_FORM_NEWTON_CASE(5)
-    default:
-    FLOW_FORM_NEWTON_CASE(6)
-#undef FLOW_FORM_NEWTON_CASE
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-template <int DEG, int RANK>
-static int launch_facet_arguments(const flow_mesh* mesh, const flow_form* F, int live,
-                                  int nfacets, const int* fcell, const int* flocal,
-                                  double* scratch, hipStream_t st) {
-  const dim3 grid((nfacets * (DEG == 1 ? 3 : 6) + kBlock - 1) / kBlock);
-  const bool ext = form_is_extended(F);
-  switch (F->nfield) {
-#define FLOW_FORM_FACET_ARGS_CASE(NF)                                            \
-    case NF:                                                                     \
-      if (ext)                                                                   \
-        hipLaunchKernelGGL((form_facet_arguments_kernel<NF, DEG, true, RANK>),   \
-                           grid, dim3(kBlock), 0, st, mesh->nc, nfacets, fcell,  \
-                           flocal, mesh->xy, *F, live, scratch);                 \
-      else                                                                       \
-        hipLaunchKernelGGL((form_facet_arguments_kernel<NF, DEG, false, RANK>),  \
-                           grid, dim3(kBlock), 0, st, mesh->nc, nfacets, fcell,  \
-                           flocal, mesh->xy, *F, live, scratch);                 \
-      break;
-    FLOW_FORM_FACET_ARGS_CASE(0)
-    FLOW_FORM_FACET_ARGS_CASE(1)
-    FLOW_FORM_FACET_ARGS_CASE(2)
-    FLOW_FORM_FACET_ARGS_CASE(3)
-    FLOW_FORM_FACET_ARGS_CASE(4)
-    FLOW_FORM_FACET_ARGS_CASE(5)
-    default:
-    FLOW_FORM_FACET_ARGS_CASE(6)
-#undef FLOW_FORM_FACET_ARGS_CASE
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
+template <int RANK>
+static int launch_facet_arguments(const flow_mesh* mesh, int deg, const flow_form* F,
+                                  int live, int nfacets, const int* fcell,
+                                  const int* flocal, double* scratch, hipStream_t st) {
+  const dim3 grid((nfacets * (deg == 1 ? 3 : 6) + kBlock - 1) / kBlock);
+  return dispatch_form(F, deg, [&](auto NF, auto EXT, auto DEG) {
+    hipLaunchKernelGGL((form_facet_arguments_kernel<NF(), DEG(), EXT(), RANK>), grid,
+                       dim3(kBlock), 0, st, mesh->nc, nfacets, fcell, flocal, mesh->xy, *F,
+                       live, scratch);
+  });
 }
 
 // flow_form_facet_matrix (RANK 2) / flow_form_facet_vector (RANK 1)
@@ -1508,16 +1431,15 @@ static int facet_arguments(const flow_mesh* mesh, const flow_space* V,
                            const int* facet_local, int ntargets, const int* map_targets,
                            const int* map_ptr, const int* map_src, double* scratch,
                            double* out, void* stream) {
-  int rc = check_form_mesh(mesh);
+  // (the gather runs over the facet map, not over the space's own maps: the
+  // helper asks for neither, and the second "space" requirement adds what
+  // this entry point needs of the space instead)
+  int rc = check_argument_space(mesh, V, false, false);
   if (rc) return rc;
-  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
+  FLOW_REQUIRE((RANK == 1 || V->nnz > 0) && V->cell_dofs, "space");
   int live = 0;
   if ((rc = check_form(form, 3, true, false, RANK == 2 ? FLOW_FORM_SLOTS : 3, &live)))
     return rc;
-  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 &&
-                   (RANK == 1 || V->nnz > 0) && V->cell_dofs,
-               "space");
-  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(nfacets >= 0 && ntargets >= 0, "facet / target count");
   if (nfacets == 0 || ntargets == 0) return FLOW_OK;
   const int nl = V->deg == 1 ? 3 : 6;
@@ -1529,12 +1451,9 @@ static int facet_arguments(const flow_mesh* mesh, const flow_space* V,
   FLOW_REQUIRE(map_targets && map_ptr && map_src, "facet contribution map");
   FLOW_REQUIRE(scratch && out, "pointers");
   hipStream_t st = as_stream(stream);
-  rc = V->deg == 1
-           ? launch_facet_arguments<1, RANK>(mesh, form, live, nfacets, facet_cell,
-                                             facet_local, scratch, st)
-           : launch_facet_arguments<2, RANK>(mesh, form, live, nfacets, facet_cell,
-                                             facet_local, scratch, st);
-  if (rc) return rc;
+  if ((rc = launch_facet_arguments<RANK>(mesh, V->deg, form, live, nfacets, facet_cell,
+                                         facet_local, scratch, st)))
+    return rc;
   hipLaunchKernelGGL(facet_gather_kernel, dim3((ntargets + kBlock - 1) / kBlock),
                      dim3(kBlock), 0, st, ntargets, map_targets, map_ptr, map_src,
                      static_cast<int>(nsrc), scratch, RANK == 2 ? V->nnz : V->n, out);
@@ -1556,9 +1475,33 @@ struct BlockPlanes {
   long long off[4];
 };
 
-// out[p*out_stride + k] = sum of scratch[off[p] + src[e]], e in [ptr[k],
-// ptr[k+1]), added in that order from 0.0 as gather_kernel adds them (the
-// same bits); 0.0 for an absent block
+// s[p] = sum of scratch[off[p] + src[e]], e in [a, b), for NP planes over one
+// index list: added in that order from 0.0 as gather_kernel adds them (the
+// same bits); 0.0 for an absent plane
+template <int NP>
+__device__ __forceinline__ void block_sum(const int* __restrict__ src, int a, int b,
+                                          const double* __restrict__ scratch,
+                                          const long long* off, double (&s)[NP]) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) s[p] = 0.0;
+  for (int t = a; t < b; t += 4) {
+    int idx[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) idx[j] = t + j < b ? src[t + j] : -1;
+    double w[NP][4];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w[p][j] = (off[p] >= 0 && idx[j] >= 0) ? scratch[off[p] + idx[j]] : 0.0;
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[p] += w[p][j];
+  }
+}
+
+// out[p*out_stride + k] = block_sum over [ptr[k], ptr[k+1]) of plane p
 template <int NP>
 __global__ __launch_bounds__(kBlock) void block_gather_kernel(
     int nout, const int* __restrict__ ptr, const int* __restrict__ src,
@@ -1566,26 +1509,8 @@ __global__ __launch_bounds__(kBlock) void block_gather_kernel(
     double* __restrict__ out) {
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nout;
        k += gridDim.x * blockDim.x) {
-    const int a = ptr[k];
-    const int b = ptr[k + 1];
     double s[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) s[p] = 0.0;
-    for (int t = a; t < b; t += 4) {
-      int idx[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) idx[j] = t + j < b ? src[t + j] : -1;
-      double w[NP][4];
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          w[p][j] = (P.off[p] >= 0 && idx[j] >= 0) ? scratch[P.off[p] + idx[j]] : 0.0;
-#pragma unroll
-      for (int p = 0; p < NP; ++p)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[p] += w[p][j];
-    }
+    block_sum<NP>(src, ptr[k], ptr[k + 1], scratch, P.off, s);
 #pragma unroll
     for (int p = 0; p < NP; ++p) out[static_cast<size_t>(p) * out_stride + k] = s[p];
   }
@@ -1599,20 +1524,29 @@ __global__ __launch_bounds__(kBlock) void plane_add_kernel(
     dst[i] += src[i];
 }
 
+// One element kernel of a block form: the first program of a block writes
+// the block's own plane, a further one the spare plane, which is then added
+// to the own one.
+static int launch_block_program(Element what, const flow_mesh* mesh, int deg,
+                                const flow_form* F, int live, bool first, double* own,
+                                double* spare, size_t plane, hipStream_t st) {
+  const int rc = launch_element(what, mesh, deg, F, live, first ? own : spare, st);
+  if (rc || first) return rc;
+  hipLaunchKernelGGL(plane_add_kernel, dim3(grid_for(plane, kBlock, 1 << 20)),
+                     dim3(kBlock), 0, st, plane, spare, own);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
 // flow_form_block_matrix (RANK 2) / flow_form_block_vector (RANK 1)
 template <int RANK>
 static int block_arguments(const flow_mesh* mesh, const flow_space* V, int nprog,
                            const flow_form* forms, const int* blocks, double* scratch,
                            double* out, size_t out_stride, void* stream) {
   constexpr int NB = RANK == 2 ? 4 : 2;
-  int rc = check_form_mesh(mesh);
+  int rc = check_argument_space(mesh, V, RANK == 2, RANK == 1);
   if (rc) return rc;
-  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(nprog >= 1 && nprog <= 64 && forms && blocks, "block programs");
-  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 &&
-                   (RANK == 2 ? (V->nnz > 0 && V->cptr && V->csrc) : (V->vptr && V->vsrc)),
-               "space");
-  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(scratch && out, "pointers");
   FLOW_REQUIRE(out_stride >= static_cast<size_t>(RANK == 2 ? V->nnz : V->n),
                "plane stride");
@@ -1638,20 +1572,10 @@ static int block_arguments(const flow_mesh* mesh, const flow_space* V, int nprog
   int seen[NB] = {};
   for (int k = 0; k < nprog; ++k) {
     const int p = blocks[k];
-    double* const own = scratch + P.off[p];
-    double* const dst = seen[p]++ ? spare : own;
-    if (RANK == 2)
-      rc = V->deg == 1 ? launch_matrix<1>(mesh, forms + k, live[k], dst, st)
-                       : launch_matrix<2>(mesh, forms + k, live[k], dst, st);
-    else
-      rc = V->deg == 1 ? launch_vector<1>(mesh, forms + k, live[k], dst, st)
-                       : launch_vector<2>(mesh, forms + k, live[k], dst, st);
-    if (rc) return rc;
-    if (dst == spare) {
-      hipLaunchKernelGGL(plane_add_kernel, dim3(grid_for(plane, kBlock, 1 << 20)),
-                         dim3(kBlock), 0, st, plane, spare, own);
-      FLOW_CHECK_LAUNCH();
-    }
+    if ((rc = launch_block_program(RANK == 2 ? Element::matrix : Element::vector, mesh,
+                                   V->deg, forms + k, live[k], seen[p]++ == 0,
+                                   scratch + P.off[p], spare, plane, st)))
+      return rc;
   }
   const int nout = RANK == 2 ? V->nnz : V->n;
   const int* ptr = RANK == 2 ? V->cptr : V->vptr;
@@ -1679,31 +1603,6 @@ struct NewtonPlanes {
   long long mat[4];
   long long vec[2];
 };
-
-// the sum of block_gather_kernel for one output entry: NP planes over one
-// index list, added in its order from 0.0 (the same bits)
-template <int NP>
-__device__ __forceinline__ void block_sum(const int* __restrict__ src, int a, int b,
-                                          const double* __restrict__ scratch,
-                                          const long long (&off)[NP], double (&s)[NP]) {
-#pragma unroll
-  for (int p = 0; p < NP; ++p) s[p] = 0.0;
-  for (int t = a; t < b; t += 4) {
-    int idx[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) idx[j] = t + j < b ? src[t + j] : -1;
-    double w[NP][4];
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        w[p][j] = (off[p] >= 0 && idx[j] >= 0) ? scratch[off[p] + idx[j]] : 0.0;
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[p] += w[p][j];
-  }
-}
 
 // vals[p*vals_stride + k], k < nnz, and b[r*n + i], i < n, in one launch;
 // consecutive lanes take consecutive k (i): the stores coalesce, the index
@@ -1735,14 +1634,9 @@ static int block_newton(const flow_mesh* mesh, const flow_space* V, int nprog,
                         const flow_form* forms, const int* kinds, const int* tags,
                         double* scratch, size_t nscratch, double* vals,
                         size_t plane_stride, double* b, void* stream) {
-  int rc = check_form_mesh(mesh);
+  int rc = check_argument_space(mesh, V, true, true);
   if (rc) return rc;
-  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(nprog >= 1 && nprog <= 64 && forms && kinds && tags, "block programs");
-  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->nnz > 0 && V->cptr &&
-                   V->csrc && V->vptr && V->vsrc,
-               "space");
-  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(scratch && vals && b, "pointers");
   FLOW_REQUIRE(plane_stride >= static_cast<size_t>(V->nnz), "plane stride");
   int live[64];
@@ -1807,28 +1701,17 @@ static int block_newton(const flow_mesh* mesh, const flow_space* V, int nprog,
     if (kind == FLOW_BLOCK_NEWTON) {
       ++mseen[tag];
       ++vseen[tag >> 1];
-      double* const dst = scratch + P.mat[tag];
-      rc = V->deg == 1 ? launch_newton<1>(mesh, F, live[k], dst, st)
-                       : launch_newton<2>(mesh, F, live[k], dst, st);
-      if (rc) return rc;
+      if ((rc = launch_element(Element::newton, mesh, V->deg, F, live[k],
+                               scratch + P.mat[tag], st)))
+        return rc;
       continue;
     }
     const bool mat = kind == FLOW_BLOCK_MATRIX;
-    double* const own = scratch + (mat ? P.mat[tag] : P.vec[tag]);
-    double* const dst = (mat ? mseen[tag]++ : vseen[tag]++) ? spare : own;
-    if (mat)
-      rc = V->deg == 1 ? launch_matrix<1>(mesh, F, live[k], dst, st)
-                       : launch_matrix<2>(mesh, F, live[k], dst, st);
-    else
-      rc = V->deg == 1 ? launch_vector<1>(mesh, F, live[k], dst, st)
-                       : launch_vector<2>(mesh, F, live[k], dst, st);
-    if (rc) return rc;
-    if (dst == spare) {
-      const size_t plane = mat ? mplane : vplane;
-      hipLaunchKernelGGL(plane_add_kernel, dim3(grid_for(plane, kBlock, 1 << 20)),
-                         dim3(kBlock), 0, st, plane, spare, own);
-      FLOW_CHECK_LAUNCH();
-    }
+    if ((rc = launch_block_program(mat ? Element::matrix : Element::vector, mesh, V->deg,
+                                   F, live[k], (mat ? mseen[tag]++ : vseen[tag]++) == 0,
+                                   scratch + (mat ? P.mat[tag] : P.vec[tag]), spare,
+                                   mat ? mplane : vplane, st)))
+      return rc;
   }
   hipLaunchKernelGGL(
       block_newton_gather_kernel,
@@ -1854,7 +1737,7 @@ extern "C" int flow_form_functional(const flow_mesh* mesh, const flow_form* form
   hipStream_t st = as_stream(stream);
   const int cb = mesh->c1 > 0 ? mesh->c0 : 0;
   const int ce = mesh->c1 > 0 ? mesh->c1 : mesh->nc;
-  if ((rc = launch_cells<0>(mesh, form, cb, ce, scratch, st))) return rc;
+  if ((rc = launch_cells(mesh, form, 0, cb, ce, scratch, st))) return rc;
   const int nparts = grid_for(ce - cb, kBlock, kRedBlocks);
   hipLaunchKernelGGL(form_sum_kernel, dim3(nparts), dim3(kBlock), 0, st, cb, ce,
                      scratch, work);
@@ -1876,9 +1759,7 @@ extern "C" int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
   hipStream_t st = as_stream(stream);
   const int cb = mesh->c1 > 0 ? mesh->c0 : 0;
   const int ce = mesh->c1 > 0 ? mesh->c1 : mesh->nc;
-  rc = V->deg == 1 ? launch_cells<1>(mesh, form, cb, ce, scratch, st)
-                   : launch_cells<2>(mesh, form, cb, ce, scratch, st);
-  if (rc) return rc;
+  if ((rc = launch_cells(mesh, form, V->deg, cb, ce, scratch, st))) return rc;
   const int nl = V->deg == 1 ? 3 : 6;
   return gather(V->n, form->nout, V->vptr, V->vsrc, scratch,
                 static_cast<size_t>(nl) * mesh->nc, b, st, 0, V->r0, V->r1);
@@ -2053,39 +1934,28 @@ extern "C" int flow_form_points(const flow_mesh* mesh, const flow_form* form, in
 extern "C" int flow_form_matrix(const flow_mesh* mesh, const flow_space* V,
                                 const flow_form* form, double* scratch,
                                 double* vals, void* stream) {
-  int rc = check_form_mesh(mesh);
+  int rc = check_argument_space(mesh, V, true, false);
   if (rc) return rc;
-  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
   int live = 0;
   if ((rc = check_form(form, 1, false, false, FLOW_FORM_SLOTS, &live))) return rc;
-  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->nnz > 0 &&
-                   V->cptr && V->csrc,
-               "space");
-  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(scratch && vals, "pointers");
   hipStream_t st = as_stream(stream);
-  rc = V->deg == 1 ? launch_matrix<1>(mesh, form, live, scratch, st)
-                   : launch_matrix<2>(mesh, form, live, scratch, st);
-  if (rc) return rc;
+  if ((rc = launch_element(Element::matrix, mesh, V->deg, form, live, scratch, st)))
+    return rc;
   return gather(V->nnz, 1, V->cptr, V->csrc, scratch, 0, vals, st);
 }
 
 extern "C" int flow_form_vector(const flow_mesh* mesh, const flow_space* V,
                                 const flow_form* form, double* scratch, double* b,
                                 void* stream) {
-  int rc = check_form_mesh(mesh);
+  int rc = check_argument_space(mesh, V, false, true);
   if (rc) return rc;
-  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
   int live = 0;
   if ((rc = check_form(form, 1, false, false, 3, &live))) return rc;
-  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->vptr && V->vsrc,
-               "space");
-  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(scratch && b, "pointers");
   hipStream_t st = as_stream(stream);
-  rc = V->deg == 1 ? launch_vector<1>(mesh, form, live, scratch, st)
-                   : launch_vector<2>(mesh, form, live, scratch, st);
-  if (rc) return rc;
+  if ((rc = launch_element(Element::vector, mesh, V->deg, form, live, scratch, st)))
+    return rc;
   return gather(V->n, 1, V->vptr, V->vsrc, scratch,
                 static_cast<size_t>(V->deg == 1 ? 3 : 6) * mesh->nc, b, st);
 }
@@ -2093,20 +1963,14 @@ extern "C" int flow_form_vector(const flow_mesh* mesh, const flow_space* V,
 extern "C" int flow_form_newton(const flow_mesh* mesh, const flow_space* V,
                                 const flow_form* form, double* scratch, double* vals,
                                 double* b, void* stream) {
-  int rc = check_form_mesh(mesh);
+  int rc = check_argument_space(mesh, V, true, true);
   if (rc) return rc;
-  FLOW_REQUIRE(mesh->c1 == 0, "forms of arguments on strips");
   int live = 0;
   if ((rc = check_form(form, 1, false, false, FLOW_FORM_NEWTON_SLOTS, &live))) return rc;
-  FLOW_REQUIRE(V && (V->deg == 1 || V->deg == 2) && V->n > 0 && V->nnz > 0 &&
-                   V->cptr && V->csrc && V->vptr && V->vsrc,
-               "space");
-  FLOW_REQUIRE(V->r1 == 0, "forms of arguments on strips");
   FLOW_REQUIRE(scratch && vals && b, "pointers");
   hipStream_t st = as_stream(stream);
-  rc = V->deg == 1 ? launch_newton<1>(mesh, form, live, scratch, st)
-                   : launch_newton<2>(mesh, form, live, scratch, st);
-  if (rc) return rc;
+  if ((rc = launch_element(Element::newton, mesh, V->deg, form, live, scratch, st)))
+    return rc;
   const int nl = V->deg == 1 ? 3 : 6;
   if ((rc = gather(V->nnz, 1, V->cptr, V->csrc, scratch, 0, vals, st))) return rc;
   return gather(V->n, 1, V->vptr, V->vsrc,
