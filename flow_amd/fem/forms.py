@@ -1014,7 +1014,25 @@ def _argument(V, number):
     return FormExpr(('arg', number, 0, V), (), V.degree, V.mesh())
 
 
-class vector_arguments(object):
+class _Switch(object):
+    '''An opt-in switch of the process: `switch(True)` takes effect at
+    construction, `.previous` is the setting it replaced, and as a context
+    manager it restores that on exit.  Every subclass owns its `enabled`.'''
+    enabled = False
+
+    def __init__(self, on=True):
+        self.previous = type(self).enabled
+        type(self).enabled = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        type(self).enabled = self.previous
+        return False
+
+
+class vector_arguments(_Switch):
     '''The switch of test and trial functions on vector spaces (2x2-block
     forms: elasticity, grad-div, the vector Laplacian).  Off by default:
     TestFunction(W) on a VectorFunctionSpace stays the NotImplementedError it
@@ -1024,19 +1042,8 @@ class vector_arguments(object):
     setting.'''
     enabled = False
 
-    def __init__(self, on=True):
-        self.previous = vector_arguments.enabled
-        vector_arguments.enabled = bool(on)
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        vector_arguments.enabled = self.previous
-        return False
-
-
-class vector_derivatives(object):
+class vector_derivatives(_Switch):
     '''The switch of derivative() with respect to a Function of a P1 / P2
     VectorFunctionSpace and of solve(F == 0) there (block Newton).  Off by
     default: both stay the NotImplementedError they were.
@@ -1046,17 +1053,6 @@ class vector_derivatives(object):
     setting.  The derivative is a form of vector arguments, so
     vector_arguments(True) is needed as well.'''
     enabled = False
-
-    def __init__(self, on=True):
-        self.previous = vector_derivatives.enabled
-        vector_derivatives.enabled = bool(on)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        vector_derivatives.enabled = self.previous
-        return False
 
 
 _VECTOR_ARGUMENTS_OFF = (
@@ -1304,7 +1300,7 @@ def _is_mesh(obj):
     return hasattr(obj, 'num_cells') and hasattr(obj, 'bfacets')
 
 
-class facet_arguments(object):
+class facet_arguments(_Switch):
     '''The switch of test and trial functions under ds (Neumann, Robin and
     Nitsche terms).  Off by default: `v*ds` and derivative() of a ds part stay
     the NotImplementedError they were.  `facet_arguments(True)` switches them
@@ -1312,17 +1308,6 @@ class facet_arguments(object):
     as a context manager it restores that on exit.  `facet_arguments.enabled`
     is the current setting.'''
     enabled = False
-
-    def __init__(self, on=True):
-        self.previous = facet_arguments.enabled
-        facet_arguments.enabled = bool(on)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        facet_arguments.enabled = self.previous
-        return False
 
 
 _FACET_ARGUMENTS_OFF = (

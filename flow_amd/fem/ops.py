@@ -13,7 +13,10 @@ flow_form_block_newton).
 Everything numerical is a call into libflow_hip.so (flow_amd/_hip.py); torch
 only owns the HBM buffers.
 '''
+import collections
 import ctypes
+import functools
+import itertools
 import numbers
 
 import numpy
@@ -920,13 +923,12 @@ def _form_struct(prog, mesh, q, facet=False, scheme='default'):
     the cells).  Returns (struct, keepalive).'''
     fs = _hip.FormS()
     fs.nprog = len(prog.code)
+    # (a field of a ctypes struct is a new view at every access: taken once)
+    code = fs.prog
     for i, ins in enumerate(prog.code):
-        for j in range(4):
-            fs.prog[4 * i + j] = int(ins[j])
-    vals = prog.constant_values()
-    fs.nconst = len(vals)
-    for i, v in enumerate(vals):
-        fs.consts[i] = v
+        code[4 * i], code[4 * i + 1], code[4 * i + 2], code[4 * i + 3] = \
+            int(ins[0]), int(ins[1]), int(ins[2]), int(ins[3])
+    fs.nconst = _refresh_constants(prog, fs.consts)
     keep = []
     nc = mesh.num_cells()
     fs.nfield = len(prog.fields)
@@ -982,7 +984,10 @@ def assemble(form, form_compiler_parameters=None):
     TestFunction, a Vector.  2: forms of a TrialFunction and a TestFunction,
     a Matrix of kind 0 on the space's pattern.  Arguments of a vector space
     (forms.vector_arguments(True) allows them): a Vector of 2N, a Matrix of
-    kind 2 (_assemble_blocks).  Parts of rank 1 and 2 over ds
+    kind 2.  Ranks 1 and 2 go part by part through _assemble_arguments (on a
+    vector space _block_part) and the launches of _launch_dx /
+    _launch_block_dx, which NewtonAssembler issues too.  Parts of rank 1 and 2
+    over ds
     (Neumann, Robin, Nitsche terms: forms.facet_arguments(True) allows them)
     go through flow_form_facet_vector / flow_form_facet_matrix and the facet contribution map (facet_map); an
     empty selection, ds(99), contributes zero.  The parts of a sum
@@ -1037,26 +1042,25 @@ def assemble(form, form_compiler_parameters=None):
 
 def _assemble_arguments(form, rank, form_compiler_parameters=None):
     '''assemble() of a form, or of a signed sum of forms, of rank 1 (a
-    Vector) or 2 (a Matrix): flow_form_vector / flow_form_matrix per dx
-    part, flow_form_facet_vector / flow_form_facet_matrix per ds part (per
-    program of a part whose table needs several).'''
+    Vector) or 2 (a Matrix; on a vector space a vector of 2N, a Matrix of
+    kind 2), part by part: the programs of a part are compiled while the
+    kernels of the part before run.  Scalar space: one launch per program
+    (_launch_dx, _facet_arguments), each result added at once; vector space:
+    _block_part.  The first result of sign +1 IS the total, ds included.'''
     from . import forms
     from .function import Vector
-    lib = _hip.lib()
     V = form.arguments()[0]
-    if V.dim == 2:
-        return _assemble_blocks(form, rank, form_compiler_parameters)
-    lay = V.layout
-    mesh = V.mesh()
-    nc = mesh.num_cells()
-    total = None
+    lay, mesh = V.layout, V.mesh()
+    total = _Sum()
     for sign, part in form.terms():
+        _check_part_mesh(part, mesh)
         facet = part.integral_type == 'exterior_facet'
-        if forms.form_mesh(part.integrand, part.mesh) is not mesh:
-            raise ValueError('the form is integrated over another mesh than '
-                             'the one of its arguments')
         _, table = part.argument_table()
         q, scheme = _part_rule(part, form_compiler_parameters)
+        if V.dim == 2:
+            total.add(sign, _block_part(part, table, rank, q, scheme, lay,
+                                        mesh), True)
+            continue
         # (one program, or several whose results add up where the table
         # exceeds the limits of flow_form: forms.argument_programs)
         for prog in forms.argument_programs(table, rank, facet):
@@ -1068,113 +1072,56 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
                                  part.subdomain_id, out)
             elif rank == 2:
                 out = value_plane(lay)
-                buf = scratch(mesh, lay.nloc**2 * nc)
-                _hip.check(lib.flow_form_matrix(
-                    ctypes.byref(mesh_struct(mesh)),
-                    ctypes.byref(space_struct(lay)), ctypes.byref(fs),
-                    _hip.f64(buf, lay.nloc**2 * nc, 'scratch'),
-                    _hip.f64(out, lay.nnz, 'vals'), _hip.stream()
-                    ))
+                _launch_dx(mesh, lay, 'matrix', fs, out, None)
             else:
                 out = device.empty(lay.N)
-                buf = scratch(mesh, lay.nloc * nc)
-                _hip.check(lib.flow_form_vector(
-                    ctypes.byref(mesh_struct(mesh)),
-                    ctypes.byref(space_struct(lay)), ctypes.byref(fs),
-                    _hip.f64(buf, lay.nloc * nc, 'scratch'),
-                    _hip.f64(out, lay.N, 'b'), _hip.stream()
-                    ))
+                _launch_dx(mesh, lay, 'vector', fs, None, out)
             del keep
-            if total is None and sign == 1.0:
-                total = out
-            else:
-                if total is None:
-                    total = _hip.fill(device.empty(out.numel()), 0.0)
-                axpby(sign, out, 1.0, total)
-    if total is None:
+            total.add(sign, out, True)
+    if total.total is None:
         raise ValueError('an empty sum of forms has no rank')
-    return Matrix(lay, 0, total) if rank == 2 else Vector(total)
+    if rank == 2:
+        return Matrix(lay, 2 if V.dim == 2 else 0, total.total)
+    return Vector(total.total)
 
 
-def _assemble_blocks(form, rank, form_compiler_parameters=None):
-    '''assemble() of a form, or of a signed sum of forms, of arguments on a
-    vector space W: a Matrix of kind 2 (rank 2; plane 2 r + s the block of
-    test component r and trial component s) or a Vector of 2N (rank 1).  A dx
-    part is ONE call of flow_form_block_matrix / flow_form_block_vector with
-    the programs of all its blocks; a ds part goes block by block (program
-    by program) through flow_form_facet_matrix / flow_form_facet_vector with
-    the scalar layout's facet_map, into the block's plane or component.'''
+def _block_part(part, table, rank, q, scheme, lay, mesh):
+    '''One part of a form of arguments on a vector space into a fresh buffer:
+    four planes (rank 2; plane 2 r + s the block of test component r and
+    trial component s) or a vector of 2N.  A dx part is ONE block launch with
+    the programs of all its blocks (_launch_block_dx); a ds part goes block
+    by block, program by program, through _facet_arguments with the scalar
+    layout's facet_map into the block's plane or component (a further program
+    of a block into a zeroed buffer of its own, then added).'''
     from . import forms
-    from .function import Vector
-    lib = _hip.lib()
-    W = form.arguments()[0]
-    lay = W.layout
-    mesh = W.mesh()
-    nc = mesh.num_cells()
+    facet = part.integral_type == 'exterior_facet'
     stride = plane_stride(lay) if rank == 2 else lay.N
     nblocks = 4 if rank == 2 else 2
-    width = lay.nnz if rank == 2 else lay.N       # entries of a block
-    total = None
-    for sign, part in form.terms():
-        facet = part.integral_type == 'exterior_facet'
-        if forms.form_mesh(part.integrand, part.mesh) is not mesh:
-            raise ValueError('the form is integrated over another mesh than '
-                             'the one of its arguments')
-        _, table = part.argument_table()
-        q, scheme = _part_rule(part, form_compiler_parameters)
-        progs = [(p, prog) for p, block in forms.block_items(table, rank)
-                 for prog in forms.argument_programs(block, rank, facet)]
-        if facet:
-            # (the facet gather writes its targets only: the rest stays zero)
-            out = device.zeros(nblocks * stride)
-            seen = set()
-            for p, prog in progs:
-                fs, keep = _form_struct(prog, mesh, q, True, scheme)
-                dst = out[p * stride:p * stride + width]
-                tmp = device.zeros(width) if p in seen else dst
-                _facet_arguments(mesh, lay, rank, fs, part.subdomain_data,
-                                 part.subdomain_id, tmp)
-                if p in seen:
-                    axpby(1.0, tmp, 1.0, dst)
-                seen.add(p)
-                del keep
-        else:
-            structs = (_hip.FormS * len(progs))()
-            keeps = []
-            for k, (p, prog) in enumerate(progs):
-                fs, keep = _form_struct(prog, mesh, q, False, scheme)
-                structs[k] = fs
-                keeps.append(keep)
-            tags = (ctypes.c_int * len(progs))(*[p for p, _ in progs])
-            present = len(set(p for p, _ in progs))
-            several = len(progs) > present
-            ns = (present + several) * lay.nloc**rank * nc
-            buf = scratch(mesh, ns)
-            out = device.empty(nblocks * stride)
-            if rank == 2:
-                if stride != lay.nnz:       # (the entry behind every plane)
-                    _hip.fill(out, 0.0)
-                _hip.check(lib.flow_form_block_matrix(
-                    ctypes.byref(mesh_struct(mesh)),
-                    ctypes.byref(space_struct(lay)), len(progs), structs, tags,
-                    _hip.f64(buf, ns, 'scratch'),
-                    _hip.f64(out, 4 * stride, 'vals'), stride, _hip.stream()))
-            else:
-                _hip.check(lib.flow_form_block_vector(
-                    ctypes.byref(mesh_struct(mesh)),
-                    ctypes.byref(space_struct(lay)), len(progs), structs, tags,
-                    _hip.f64(buf, ns, 'scratch'), _hip.f64(out, 2 * lay.N, 'b'),
-                    _hip.stream()))
-            del keeps
-        if total is None and sign == 1.0:
-            total = out
-        else:
-            if total is None:
-                total = _hip.fill(device.empty(out.numel()), 0.0)
-            axpby(sign, out, 1.0, total)
-    if total is None:
-        raise ValueError('an empty sum of forms has no rank')
-    return Matrix(lay, 2, total) if rank == 2 else Vector(total)
+    progs = [(p, prog) for p, block in forms.block_items(table, rank)
+             for prog in forms.argument_programs(block, rank, facet)]
+    tags = tuple(p for p, _ in progs)
+    structs, keeps = _program_structs(
+        [(prog, q, scheme, facet) for _, prog in progs], mesh)
+    if not facet:
+        out = device.empty(nblocks * stride)
+        if rank == 2 and stride != lay.nnz:   # (the entry behind every plane)
+            _hip.fill(out, 0.0)
+        _launch_block_dx(mesh, lay, structs,
+                         ('matrix' if rank == 2 else 'vector',) * len(tags),
+                         tags, out if rank == 2 else None, stride,
+                         out if rank == 1 else None)
+        return out
+    # (the facet gather writes its targets only: the rest stays zero)
+    out = device.zeros(nblocks * stride)
+    width = lay.nnz if rank == 2 else lay.N
+    for k, p in enumerate(tags):
+        dst = out[p * stride:p * stride + width]
+        tmp = device.zeros(width) if p in tags[:k] else dst
+        _facet_arguments(mesh, lay, rank, structs[k], part.subdomain_data,
+                         part.subdomain_id, tmp)
+        if tmp is not dst:
+            axpby(1.0, tmp, 1.0, dst)
+    return out
 
 
 def _scalar_bcs(bcs, V):
@@ -1428,86 +1375,43 @@ def _part_rule(part, form_compiler_parameters):
     return q, scheme
 
 
-def _fusable(tj, fparts, rules, used, rule, origin):
-    '''(index of the part of F to fuse a part of J with, their Program): the
-    first unused part of the same rule, the one J's part was derived from
-    first, whose combined program fits the limits of flow_form; (None, None)
-    without one.'''
+def _check_part_mesh(part, mesh):
     from . import forms
-    for i in sorted(range(len(fparts)),
-                    key=lambda i: fparts[i][1] is not origin):
-        if used[i] or rules[i] != rule \
-                or fparts[i][1].integral_type != 'cell':
-            continue
-        try:
-            return i, forms.newton_program(
-                tj, fparts[i][1].argument_table()[1])
-        except ValueError:          # over a limit of flow_form
-            continue
-    return None, None
+    if forms.form_mesh(part.integrand, part.mesh) is not mesh:
+        raise ValueError('the form is integrated over another mesh than the '
+                         'one of its arguments')
 
 
-def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
-    '''The launches that assemble (J, F) at one state, as a list of
-    (kind, sign of the matrix part, sign of the vector part, Program,
-    degree, scheme), kind 'newton' | 'matrix' | 'vector' | 'facet_matrix' |
-    'facet_vector'; a facet job carries its part as a seventh entry (the
-    facet selection is the part's subdomain data and id).  ds parts are never
-    fused.  A dx part of J is fused with a part of F of the same degree and
-    rule (the one it was derived from first) where forms.newton_program fits the limits of
-    flow_form; what is left goes through flow_form_matrix / flow_form_vector
-    part by part (program by program where a table needs several:
-    forms.argument_programs).  Forms on a vector space: the jobs of
-    _block_newton_jobs.  Host only.'''
-    from . import forms
-    if F.arguments()[0].dim == 2:
-        return _block_newton_jobs(J, F, form_compiler_parameters, fuse)
-    fparts = F.terms()
-    rules = [_part_rule(p, form_compiler_parameters) for _, p in fparts]
-    used = [False] * len(fparts)
-    jobs = []
-    for sj, pj in J.terms():
-        rule = _part_rule(pj, form_compiler_parameters)
-        tj = pj.argument_table()[1]
-        if pj.integral_type == 'exterior_facet':
-            jobs.extend(('facet_matrix', sj, 0.0, prog) + rule + (pj,)
-                        for prog in forms.argument_programs(tj, 2, True))
-            continue
-        i, prog = _fusable(tj, fparts, rules, used, rule,
-                           getattr(pj, 'derived_from', None)) \
-            if fuse else (None, None)
-        if prog is not None:
-            used[i] = True
-            jobs.append(('newton', sj, fparts[i][0], prog) + rule)
-        else:
-            jobs.extend(('matrix', sj, 0.0, prog) + rule
-                        for prog in forms.argument_programs(tj, 2))
-    for i, (sf, pf) in enumerate(fparts):
-        if pf.integral_type == 'exterior_facet':
-            jobs.extend(('facet_vector', 0.0, sf, prog) + rules[i] + (pf,)
-                        for prog in forms.argument_programs(
-                            pf.argument_table()[1], 1, True))
-        elif not used[i]:
-            jobs.extend(('vector', 0.0, sf, prog) + rules[i]
-                        for prog in forms.argument_programs(
-                            pf.argument_table()[1], 1))
-    return jobs
+# -- the jobs of an assembly --------------------------------------------------
+# One launch's worth of one Program.  kind: 'newton' | 'matrix' | 'vector' |
+# 'facet_matrix' | 'facet_vector'; msign, vsign: the signs of the matrix and of
+# the vector part (0.0 where the kind has none); part: the ds part of a facet
+# job (its subdomain data and id are the facet selection), else None; tag: the
+# block plane p = 2 r + s ('newton', 'matrix', 'facet_matrix') or the component
+# r ('vector', 'facet_vector') on a vector space -- a 'newton' job assembles
+# block p and component p // 2 --, 0 on a scalar space; call: (index of the
+# part of J or None, index of the part of F or None).
+Job = collections.namedtuple(
+    'Job', 'kind msign vsign program degree scheme part tag call')
 
 
-def _block_rows(tj, tf):
+def _block_rows(tj, tf, dim=2):
     '''The dx jobs [(kind, Program, tag)] of one part of J (block table tj)
     taken together with one part of F (block table tf), row by row (r = the
     test component): block (r, s) and component r fuse into a 'newton' job
-    (tag p = 2 r + s) where forms.newton_program fits the limits of flow_form,
-    s = r first, else the other block of the row; the other blocks of the row
-    are 'matrix' jobs (tag p), a component that did not fuse 'vector' jobs
-    (tag r), program by program (forms.argument_programs).'''
+    (tag p = dim r + s) where forms.newton_program fits the limits of
+    flow_form, s = r first, else the other block of the row; the other blocks
+    of the row are 'matrix' jobs (tag p), a component that did not fuse
+    'vector' jobs (tag r), program by program (forms.argument_programs).  A
+    scalar space (dim 1) is the single row of the single block.'''
     from . import forms
+    if dim == 1:
+        tj, tf = [[tj]], [tf]
     rows = []
-    for r in range(2):
+    for r in range(dim):
         fused = None
         if tf[r] is not None:
-            for s in (r, 1 - r):
+            for s in [r] + [s for s in range(dim) if s != r]:
                 if tj[r][s] is None:
                     continue
                 try:
@@ -1516,10 +1420,10 @@ def _block_rows(tj, tf):
                 except ValueError:      # over a limit of flow_form
                     continue
         if fused is not None:
-            rows.append(('newton', fused[1], 2 * r + fused[0]))
-        for s in range(2):
+            rows.append(('newton', fused[1], dim * r + fused[0]))
+        for s in range(dim):
             if tj[r][s] is not None and (fused is None or s != fused[0]):
-                rows.extend(('matrix', prog, 2 * r + s)
+                rows.extend(('matrix', prog, dim * r + s)
                             for prog in forms.argument_programs(tj[r][s], 2))
         if tf[r] is not None and fused is None:
             rows.extend(('vector', prog, r)
@@ -1527,32 +1431,35 @@ def _block_rows(tj, tf):
     return rows
 
 
-def _block_newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
-    '''newton_jobs for forms on a vector space W: (kind, sign of the matrix
-    part, sign of the vector part, Program, degree, scheme, part, tag, call).
-    kind as in newton_jobs; part: the ds part of a facet job, else None; tag:
-    the block plane p = 2 r + s ('newton', 'matrix', 'facet_matrix') or the
-    component r ('vector', 'facet_vector') -- a 'newton' job assembles block
-    p and component p // 2; call = (index of the part of J or None, index of
-    the part of F or None): the dx jobs of one call are ONE launch of
+def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
+    '''The launches that assemble (J, F) at one state, as a list of Job
+    records, on a scalar space (one block, tag 0) and on a vector space
+    alike.  ds parts are never fused: 'facet_matrix' / 'facet_vector' jobs
+    block by block, program by program.  A dx part of J is taken together
+    with the first unused dx part of F of the same degree and rule (the one it
+    was derived from first) with which at least one row fuses (_block_rows);
+    without one, and with fuse=False, its blocks are 'matrix' jobs and the
+    parts of F 'vector' jobs, in the order written: the pair assemble(J),
+    assemble(F).  The dx jobs of one call on a vector space are ONE launch of
     flow_form_block_newton (both indices), flow_form_block_matrix or
-    flow_form_block_vector.  A dx part of J is taken together with the first
-    unused dx part of F of the same degree and rule (the one it was derived
-    from first) with which at least one row fuses (_block_rows); without one,
-    and with fuse=False, its blocks are 'matrix' jobs and the parts of F
-    'vector' jobs: the pair assemble(J), assemble(F).'''
+    flow_form_block_vector; on a scalar space every job is a launch
+    (flow_form_newton / flow_form_matrix / flow_form_vector).  Host only.'''
     from . import forms
-    fparts = F.terms()
+    dim = F.arguments()[0].dim
+    # [(tag, table)] of the present blocks of a part's table; a scalar space
+    # is the 1 x 1 case: the table itself, tag 0
+    blocks = forms.block_items if dim == 2 else lambda table, rank: [(0, table)]
+    jparts, fparts = J.terms(), F.terms()
     rules = [_part_rule(p, form_compiler_parameters) for _, p in fparts]
     used = [False] * len(fparts)
     jobs = []
-    for ji, (sj, pj) in enumerate(J.terms()):
+    for ji, (sj, pj) in enumerate(jparts):
         rule = _part_rule(pj, form_compiler_parameters)
         tj = pj.argument_table()[1]
         if pj.integral_type == 'exterior_facet':
-            jobs.extend(('facet_matrix', sj, 0.0, prog) + rule
-                        + (pj, p, (ji, None))
-                        for p, block in forms.block_items(tj, 2)
+            jobs.extend(Job('facet_matrix', sj, 0.0, prog, rule[0], rule[1],
+                            pj, p, (ji, None))
+                        for p, block in blocks(tj, 2)
                         for prog in forms.argument_programs(block, 2, True))
             continue
         fi, rows = None, None
@@ -1562,56 +1469,68 @@ def _block_newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
             if not fuse or used[i] or rules[i] != rule \
                     or fparts[i][1].integral_type != 'cell':
                 continue
-            found = _block_rows(tj, fparts[i][1].argument_table()[1])
+            found = _block_rows(tj, fparts[i][1].argument_table()[1], dim)
             if any(kind == 'newton' for kind, _, _ in found):
                 fi, rows = i, found
                 break
         if fi is None:
-            rows = [('matrix', prog, p)
-                    for p, block in forms.block_items(tj, 2)
+            rows = [('matrix', prog, p) for p, block in blocks(tj, 2)
                     for prog in forms.argument_programs(block, 2)]
         else:
             used[fi] = True
         sf = 0.0 if fi is None else fparts[fi][0]
-        jobs.extend((kind, 0.0 if kind == 'vector' else sj,
-                     0.0 if kind == 'matrix' else sf, prog) + rule
-                    + (None, tag, (ji, fi)) for kind, prog, tag in rows)
+        jobs.extend(Job(kind, 0.0 if kind == 'vector' else sj,
+                        0.0 if kind == 'matrix' else sf, prog, rule[0],
+                        rule[1], None, tag, (ji, fi))
+                    for kind, prog, tag in rows)
     for i, (sf, pf) in enumerate(fparts):
         facet = pf.integral_type == 'exterior_facet'
         if used[i]:
             continue
-        jobs.extend(('facet_vector' if facet else 'vector', 0.0, sf, prog)
-                    + rules[i] + (pf if facet else None, r, (None, i))
-                    for r, block in forms.block_items(
-                        pf.argument_table()[1], 1)
+        jobs.extend(Job('facet_vector' if facet else 'vector', 0.0, sf, prog,
+                        rules[i][0], rules[i][1], pf if facet else None, r,
+                        (None, i))
+                    for r, block in blocks(pf.argument_table()[1], 1)
                     for prog in forms.argument_programs(block, 1, facet))
     return jobs
 
 
+# NewtonInfo.fused: two rules, on purpose.  On a scalar space a job list is
+# fused where no dx part of J needed a 'matrix' job; on a vector space a fused
+# row keeps 'matrix' jobs (its other block), so the rule there asks for more.
+def _scalar_jobs_fused(jobs):
+    '''NewtonInfo.fused of jobs on a scalar space: every dx part of J went
+    into a 'newton' job.  ds jobs do not count.'''
+    return all(j.kind != 'matrix' for j in jobs)
+
+
 def block_jobs_fused(jobs):
-    '''NewtonInfo.fused of the jobs of _block_newton_jobs: there is a 'newton'
-    job, no dx residual component needed a 'vector' job, and every block of a
-    row that has a 'newton' job in its call is ONE program (no table of such a
-    row was split).  ds jobs do not count.'''
-    if not any(j[0] == 'newton' for j in jobs) \
-            or any(j[0] == 'vector' for j in jobs):
+    '''NewtonInfo.fused of jobs on a vector space: there is a 'newton' job, no
+    dx residual component needed a 'vector' job, and every block of a row that
+    has a 'newton' job in its call is ONE program (no table of such a row was
+    split).  ds jobs do not count.'''
+    if not any(j.kind == 'newton' for j in jobs) \
+            or any(j.kind == 'vector' for j in jobs):
         return False
     for j in jobs:
-        if j[0] != 'newton':
+        if j.kind != 'newton':
             continue
-        row = [k[7] for k in jobs if k[8] == j[8]
-               and k[0] in ('newton', 'matrix') and k[7] // 2 == j[7] // 2]
+        row = [k.tag for k in jobs if k.call == j.call
+               and k.kind in ('newton', 'matrix') and k.tag // 2 == j.tag // 2]
         if len(row) != len(set(row)):
             return False
     return True
 
 
+# -- the launch layer: all size arithmetic, ctypes packing and _hip.check -----
 _BLOCK_KINDS = {'newton': 0, 'matrix': 1, 'vector': 2}     # include/flow_hip.h
 
 
 def _block_newton_scratch(kinds, tags, nl, nc):
     '''Doubles of scratch flow_form_block_newton needs for these jobs
-    (include/flow_hip.h).'''
+    (include/flow_hip.h); with 'matrix' jobs or 'vector' jobs only, what
+    flow_form_block_matrix / flow_form_block_vector need: (blocks present + 1
+    where a block has several programs) * nl**rank * nc.'''
     blocks = [t for k, t in zip(kinds, tags) if k != 'vector']
     comps = [t if k == 'vector' else t // 2
              for k, t in zip(kinds, tags) if k != 'matrix']
@@ -1623,274 +1542,306 @@ def _block_newton_scratch(kinds, tags, nl, nc):
     return n
 
 
-class _BlockNewton(object):
-    '''NewtonAssembler for forms on a vector space W: a kind-2 Matrix and a
-    vector of 2N.  Every part of J owns four value planes and every part of F
-    a vector of 2N, held as long as the object; a call (the dx jobs of a part
-    of J and the part of F it is taken with) is one launch of
-    flow_form_block_newton, a part on its own one of flow_form_block_matrix /
-    flow_form_block_vector; ds parts go block by block, program by program,
-    through the facet kernels into their part's zeroed buffer (a further
-    program of a block into a zeroed buffer of its own, then added).  The
-    parts are then added in the order written, as assemble() adds them: A and
-    b have the bits of assemble(J) and assemble(F).'''
+def _launch_dx(mesh, lay, kind, fs, vals, vec):
+    '''The dx launch of one program on a scalar space: flow_form_newton (into
+    the plane `vals` and the vector `vec`), flow_form_matrix (`vals`) or
+    flow_form_vector (`vec`).'''
+    lib = _hip.lib()
+    nl = lay.nloc
+    ms, ss = ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay))
+    if kind == 'newton':
+        n = (nl * nl + nl) * mesh.num_cells()
+        _hip.check(lib.flow_form_newton(
+            ms, ss, ctypes.byref(fs), _hip.f64(scratch(mesh, n), n, 'scratch'),
+            _hip.f64(vals, lay.nnz, 'vals'), _hip.f64(vec, lay.N, 'b'),
+            _hip.stream()))
+    elif kind == 'matrix':
+        n = nl * nl * mesh.num_cells()
+        _hip.check(lib.flow_form_matrix(
+            ms, ss, ctypes.byref(fs), _hip.f64(scratch(mesh, n), n, 'scratch'),
+            _hip.f64(vals, lay.nnz, 'vals'), _hip.stream()))
+    else:
+        n = nl * mesh.num_cells()
+        _hip.check(lib.flow_form_vector(
+            ms, ss, ctypes.byref(fs), _hip.f64(scratch(mesh, n), n, 'scratch'),
+            _hip.f64(vec, lay.N, 'b'), _hip.stream()))
 
-    def __init__(self, owner, J, F, form_compiler_parameters, fuse):
-        self.V = V = owner.V
-        self.mesh = owner.mesh
-        lay = V.layout
-        self.jobs = _block_newton_jobs(J, F, form_compiler_parameters, fuse)
-        self.fused = block_jobs_fused(self.jobs)
-        self.stride = plane_stride(lay)
-        self.jparts, self.fparts = J.terms(), F.terms()
-        if not self.jparts or not self.fparts:
-            raise ValueError('an empty sum of forms has no rank')
-        # (zeroed once: the launches write the nnz entries of a plane, not
-        # the one behind them)
-        self.jbuf = [device.zeros(4 * self.stride) for _ in self.jparts]
-        self.fbuf = [device.zeros(2 * lay.N) for _ in self.fparts]
-        self.A = Matrix(lay, 2, self._total(self.jparts, self.jbuf, 4 * self.stride))
-        self.b = self._total(self.fparts, self.fbuf, 2 * lay.N)
-        # the calls, in the order of the jobs: [call, kind of launch, job
-        # numbers, struct array, keepalives]
-        self.calls = []
-        for jn, job in enumerate(self.jobs):
-            facet = job[0].startswith('facet')
-            if self.calls and self.calls[-1][0] == job[8] and not facet \
-                    and self.calls[-1][1] != 'facet':
-                self.calls[-1][2].append(jn)
-            else:
-                self.calls.append([job[8], 'facet' if facet else None, [jn]])
-        for call in self.calls:
-            js = [self.jobs[jn] for jn in call[2]]
-            if call[1] is None:
-                call[1] = 'newton' if None not in call[0] else \
-                    'matrix' if call[0][1] is None else 'vector'
-            structs = (_hip.FormS * len(js))()
-            keeps = []
-            for k, j in enumerate(js):
-                fs, keep = _form_struct(j[3], self.mesh, j[4],
-                                        call[1] == 'facet', j[5])
-                structs[k] = fs
-                keeps.append(keep)
-            call.extend([structs, keeps])
-        # per further ds program of a block: [buffer]; per ds job: the map it
-        # was last gathered over
-        self._facet_tmp = {}
-        self._facet_map = {}
 
-    def _total(self, parts, bufs, n):
-        '''Where the parts are summed: the first part's own buffer where
-        nothing has to be added to it (one dx part of sign 1), else a buffer
-        of its own.'''
-        if len(parts) == 1 and parts[0][0] == 1.0 \
-                and parts[0][1].integral_type == 'cell':
-            return bufs[0]
-        return device.zeros(n)
+@functools.lru_cache(maxsize=256)
+def _block_call(kinds, tags, nl, nc):
+    '''(kinds, tags as C int arrays, doubles of scratch) of one block launch;
+    the arrays are only read, so the calls of a held assembler share them.'''
+    n = len(kinds)
+    return ((ctypes.c_int * n)(*[_BLOCK_KINDS[k] for k in kinds]),
+            (ctypes.c_int * n)(*tags),
+            _block_newton_scratch(kinds, tags, nl, nc))
 
-    def assemble(self):
-        lib = _hip.lib()
-        lay, mesh = self.V.layout, self.mesh
-        nc, nl, N, stride = mesh.num_cells(), lay.nloc, lay.N, self.stride
-        ms, ss = ctypes.byref(mesh_struct(mesh)), ctypes.byref(
-            space_struct(lay))
-        for (ji, fi), launch, jns, structs, _ in self.calls:
-            js = [self.jobs[jn] for jn in jns]
-            for k, j in enumerate(js):
-                for i, value in enumerate(j[3].constant_values()):
-                    structs[k].consts[i] = value
-            if launch == 'facet':
-                self._facet(jns[0], js[0], structs[0])
-                continue
-            kinds = [j[0] for j in js]
-            tags = [j[7] for j in js]
-            ctags = (ctypes.c_int * len(js))(*tags)
-            ns = _block_newton_scratch(kinds, tags, nl, nc)
-            buf = _hip.f64(scratch(mesh, ns), ns, 'scratch')
-            if launch == 'newton':
-                ckinds = (ctypes.c_int * len(js))(
-                    *[_BLOCK_KINDS[k] for k in kinds])
-                _hip.check(lib.flow_form_block_newton(
-                    ms, ss, len(js), structs, ckinds, ctags, buf, ns,
-                    _hip.f64(self.jbuf[ji], 4 * stride, 'vals'), stride,
-                    _hip.f64(self.fbuf[fi], 2 * N, 'b'), _hip.stream()))
-            elif launch == 'matrix':
-                _hip.check(lib.flow_form_block_matrix(
-                    ms, ss, len(js), structs, ctags, buf,
-                    _hip.f64(self.jbuf[ji], 4 * stride, 'vals'), stride,
-                    _hip.stream()))
-            else:
-                _hip.check(lib.flow_form_block_vector(
-                    ms, ss, len(js), structs, ctags, buf,
-                    _hip.f64(self.fbuf[fi], 2 * N, 'b'), _hip.stream()))
-        self._sum(self.jparts, self.jbuf, self.A.vals)
-        self._sum(self.fparts, self.fbuf, self.b)
-        return self.A, self.b
 
-    @staticmethod
-    def _sum(parts, bufs, total):
-        if total is bufs[0]:
-            return
-        _hip.fill(total, 0.0)
-        for (sign, _), buf in zip(parts, bufs):
-            axpby(sign, buf, 1.0, total)
+def _launch_block_dx(mesh, lay, structs, kinds, tags, vals, stride, vec):
+    '''The dx launch of the programs of one call on a vector space (kinds,
+    tags: tuples): flow_form_block_newton (into the four planes `vals` and
+    the vector `vec` of 2N), flow_form_block_matrix (vec None) or
+    flow_form_block_vector (vals None).'''
+    lib = _hip.lib()
+    ckinds, ctags, ns = _block_call(kinds, tags, lay.nloc, mesh.num_cells())
+    ms, ss = ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay))
+    buf = _hip.f64(scratch(mesh, ns), ns, 'scratch')
+    if vec is None:
+        _hip.check(lib.flow_form_block_matrix(
+            ms, ss, len(kinds), structs, ctags, buf,
+            _hip.f64(vals, 4 * stride, 'vals'), stride, _hip.stream()))
+    elif vals is None:
+        _hip.check(lib.flow_form_block_vector(
+            ms, ss, len(kinds), structs, ctags, buf,
+            _hip.f64(vec, 2 * lay.N, 'b'), _hip.stream()))
+    else:
+        _hip.check(lib.flow_form_block_newton(
+            ms, ss, len(kinds), structs, ckinds, ctags, buf, ns,
+            _hip.f64(vals, 4 * stride, 'vals'), stride,
+            _hip.f64(vec, 2 * lay.N, 'b'), _hip.stream()))
 
-    def _facet(self, jn, job, fs):
-        '''One ds program into the plane or component of its block in its
-        part's buffer.'''
-        lay = self.V.layout
-        kind, part, tag, (ji, fi) = job[0], job[6], job[7], job[8]
-        rank = 2 if kind == 'facet_matrix' else 1
-        width = lay.nnz if rank == 2 else lay.N
-        step = self.stride if rank == 2 else lay.N
-        buf = self.jbuf[ji] if rank == 2 else self.fbuf[fi]
-        dst = buf[tag * step:tag * step + width]
-        first = not any(k[0] == kind and k[7] == tag and k[8] == job[8]
-                        for k in self.jobs[:jn])
-        out = dst
-        if not first:
-            if jn not in self._facet_tmp:
-                self._facet_tmp[jn] = device.zeros(width)
-            out = self._facet_tmp[jn]
-        fmap = facet_map(self.mesh, lay, rank, part.subdomain_data,
+
+def _program_structs(items, mesh):
+    '''(flow_form structs of [(Program, degree, scheme, facet)] as one ctypes
+    array, which the block launches take whole; keep-alives).  The structs
+    hold pointers to the fields' data, which Newton updates in place.'''
+    structs = (_hip.FormS * len(items))()
+    keeps = []
+    for k, (prog, q, scheme, facet) in enumerate(items):
+        structs[k], keep = _form_struct(prog, mesh, q, facet, scheme)
+        keeps.append(keep)
+    return structs, keeps
+
+
+def _refresh_constants(program, consts):
+    '''The current values of a Program's Constants into the `consts` of its
+    struct (the field's view, taken once: a held assembler keeps it);
+    returns their number.'''
+    values = program.constant_values()
+    for i, value in enumerate(values):
+        consts[i] = value
+    return len(values)
+
+
+class _FacetTarget(object):
+    '''Where a held assembler gathers a ds program: a zeroed buffer (N | nnz
+    doubles) the gather writes the same entries of at every call -- its map's
+    targets --, zeroed again where facet_map returns another tuple (the facet
+    markers were changed: other targets).  `into`: where a further program of
+    a block is added afterwards, else None.'''
+
+    def __init__(self, buf, into=None):
+        self.buf = buf
+        self.into = into
+        self.fmap = None
+
+    def gather(self, mesh, lay, rank, fs, part):
+        fmap = facet_map(mesh, lay, rank, part.subdomain_data,
                          part.subdomain_id)
-        if self._facet_map.setdefault(jn, fmap) is not fmap:
-            # re-marked: other targets
-            _hip.fill(out, 0.0)
-            self._facet_map[jn] = fmap
-        _facet_arguments(self.mesh, lay, rank, fs, part.subdomain_data,
-                         part.subdomain_id, out)
-        if not first:
-            axpby(1.0, out, 1.0, dst)
+        if self.fmap is not None and self.fmap is not fmap:
+            _hip.fill(self.buf, 0.0)
+        self.fmap = fmap
+        _facet_arguments(mesh, lay, rank, fs, part.subdomain_data,
+                         part.subdomain_id, self.buf)
+        if self.into is not None:
+            axpby(1.0, self.buf, 1.0, self.into)
+        return self.buf
+
+
+class _Sum(object):
+    '''A signed sum of contributions, added in the order given: `total` a
+    held buffer, or None (the first contribution decides).  `direct`, the
+    caller's rule: the first contribution may land in the total as it is, if
+    its sign is +1 -- no fill, no axpby, and x stays x where 0.0 + 1.0*x would
+    turn a -0.0 into 0.0.  Every other first contribution is added to zeros.
+    The entry points differ in what they pass, on purpose: their bits and
+    their launch counts are kept.'''
+
+    def __init__(self, total=None):
+        self.total = total
+        self.first = True
+
+    def target(self, sign, direct):
+        '''The held total where the next contribution may be written straight
+        into it, else None (a buffer of the caller's, then add()).'''
+        return self.total if self.first and direct and sign == 1.0 else None
+
+    def add(self, sign, out, direct=False):
+        if out is not self.total:
+            if self.total is None and self.first and direct and sign == 1.0:
+                self.total = out
+            else:
+                if self.total is None:
+                    self.total = device.empty(out.numel())
+                if self.first:
+                    _hip.fill(self.total, 0.0)
+                axpby(sign, out, 1.0, self.total)
+        self.first = False
 
 
 class NewtonAssembler(object):
     '''(J, F) at the current values of the fields, into buffers that live as
-    long as the object: the value plane `A.vals`, the vector `b`, one more of
-    each where a sum of parts needs it, and the mesh's scratch.  `fused`:
-    every dx part of J goes through flow_form_newton.  A ds job owns a zeroed
-    buffer that its gather writes the same entries of at every call (zeroed
-    again where the facet markers were changed).  V a vector space: `A` of
-    kind 2, `b` of 2N, `fused` by block_jobs_fused (_BlockNewton).'''
+    long as the object: a Matrix `A` (kind 0; V a vector space: kind 2) and a
+    vector `b` (N; 2N), through the jobs of newton_jobs.  The structs are
+    built once; the Constants' values are refreshed by every assemble().
+    `fused`: _scalar_jobs_fused / block_jobs_fused of the jobs.
+
+    Scalar space: every job is a launch, added to the total program by
+    program; the first dx result of sign +1 lands in the total, any other
+    goes to a spare buffer first, and a ds result is always added (to zeros
+    where it is the first).  Vector space: every part of J owns four value
+    planes and every part of F a vector of 2N; the dx jobs of a call are one
+    launch into them, a ds part goes block by block, program by program, into
+    the plane or component of its part's buffer (a further program of a block
+    into a zeroed buffer of its own, then added); after all launches the
+    parts are added in the order written, as assemble() adds them -- the
+    total IS the first buffer only where a single dx part of sign +1 makes
+    the sum.  A ds program owns a _FacetTarget.  A and b have the bits of
+    assemble(J) and assemble(F).'''
 
     def __init__(self, J, F, V, form_compiler_parameters=None, fuse=True):
-        from . import forms
         self.V = V
-        self.mesh = V.mesh()
-        for _, part in J.terms() + F.terms():
-            if forms.form_mesh(part.integrand, part.mesh) is not self.mesh:
-                raise ValueError('the form is integrated over another mesh '
-                                 'than the one of its arguments')
-        self._blocks = None
-        if V.dim == 2:
-            # forms on a vector space: a kind-2 Matrix, a vector of 2N
-            self._blocks = _BlockNewton(self, J, F, form_compiler_parameters,
-                                        fuse)
-            self.jobs, self.fused = self._blocks.jobs, self._blocks.fused
-            self.A, self.b = self._blocks.A, self._blocks.b
-            return
-        self.jobs = newton_jobs(J, F, form_compiler_parameters, fuse)
-        self.fused = all(j[0] != 'matrix' for j in self.jobs)
+        self.mesh = mesh = V.mesh()
         lay = V.layout
-        self.A = Matrix(lay, 0, value_plane(lay))
-        self.b = device.empty(lay.N)
-        self._plane = self._vector = None
-        # (the structs hold pointers to the fields' data, which Newton updates
-        # in place; the constants' values are refreshed by every assemble())
-        self.structs = [_form_struct(j[3], self.mesh, j[4],
-                                     j[0].startswith('facet'), j[5])
-                        for j in self.jobs]
-        # per ds job: [buffer, the map it was last gathered over]
-        self._facet = {}
+        self.parts = (J.terms(), F.terms())
+        for parts in self.parts:
+            for _, part in parts:
+                _check_part_mesh(part, mesh)
+        self.jobs = jobs = newton_jobs(J, F, form_compiler_parameters, fuse)
+        self._targets = {}          # per ds job: its _FacetTarget
+        if V.dim == 1:
+            self.fused = _scalar_jobs_fused(jobs)
+            self.A = Matrix(lay, 0, value_plane(lay))
+            self.b = device.empty(lay.N)
+            self._spares = {}
+            self._keep = _program_structs(
+                [(j.program, j.degree, j.scheme, j.part is not None)
+                 for j in jobs], mesh)
+            self._steps = [(j, fs, fs.consts)
+                           for j, fs in zip(jobs, self._keep[0])]
+            return
+        self.fused = block_jobs_fused(jobs)
+        if not self.parts[0] or not self.parts[1]:
+            raise ValueError('an empty sum of forms has no rank')
+        # (zeroed once: the launches write the nnz entries of a plane, not
+        # the one behind them)
+        sizes = (4 * plane_stride(lay), 2 * lay.N)
+        self._bufs = [[device.zeros(n) for _ in parts]
+                      for n, parts in zip(sizes, self.parts)]
+        totals = [bufs[0] if self._single_dx(parts) and parts[0][0] == 1.0
+                  else device.zeros(n)
+                  for n, parts, bufs in zip(sizes, self.parts, self._bufs)]
+        self.A, self.b = Matrix(lay, 2, totals[0]), totals[1]
+        # the launches: the jobs of a call (a part of J, of F, or a fused
+        # pair) as [call, job numbers, kinds, tags, structs, keep-alives]
+        self._calls = []
+        for call, g in itertools.groupby(range(len(jobs)),
+                                         key=lambda n: jobs[n].call):
+            jns = list(g)
+            js = [jobs[n] for n in jns]
+            structs, keeps = _program_structs(
+                [(j.program, j.degree, j.scheme, j.part is not None)
+                 for j in js], mesh)
+            self._calls.append(
+                (call, jns, tuple(j.kind for j in js),
+                 tuple(j.tag for j in js), structs,
+                 [(j.program, fs.consts) for j, fs in zip(js, structs)],
+                 keeps))
+
+    @staticmethod
+    def _single_dx(parts):
+        return len(parts) == 1 and parts[0][1].integral_type == 'cell'
 
     def assemble(self):
-        if self._blocks is not None:
-            return self._blocks.assemble()
-        lib = _hip.lib()
+        if self.V.dim == 2:
+            self._by_parts()
+        else:
+            self._by_programs()
+        return self.A, self.b
+
+    def _by_programs(self):
         lay, mesh = self.V.layout, self.mesh
-        nc = mesh.num_cells()
-        nl = lay.nloc
-        ms, ss = ctypes.byref(mesh_struct(mesh)), ctypes.byref(
-            space_struct(lay))
-        first_m = first_v = True
-        for jn, (job, (fs, _)) in enumerate(zip(self.jobs, self.structs)):
-            kind, sm, sv, prog = job[:4]
-            for i, value in enumerate(prog.constant_values()):
-                fs.consts[i] = value
+        msum, vsum = _Sum(self.A.vals), _Sum(self.b)
+        for jn, (job, fs, consts) in enumerate(self._steps):
+            _refresh_constants(job.program, consts)
+            kind = job.kind
             vals = vec = None
-            if kind.startswith('facet'):
+            if job.part is not None:
+                # (a ds result is never the total itself)
                 rank = 2 if kind == 'facet_matrix' else 1
-                out = self._facet_out(jn, rank, job[6])
-                _facet_arguments(mesh, lay, rank, fs, job[6].subdomain_data,
-                                 job[6].subdomain_id, out)
+                target = self._targets.get(jn)
+                if target is None:
+                    target = self._targets[jn] = _FacetTarget(
+                        value_plane(lay) if rank == 2 else device.zeros(lay.N))
+                out = target.gather(mesh, lay, rank, fs, job.part)
                 if rank == 2:
                     vals = out
                 else:
                     vec = out
-            elif kind != 'vector':
-                vals = self.A.vals if first_m and sm == 1.0 else self._tmp(0)
-            if kind in ('newton', 'vector'):
-                vec = self.b if first_v and sv == 1.0 else self._tmp(1)
-            if kind.startswith('facet'):
-                pass
-            elif kind == 'newton':
-                n = (nl * nl + nl) * nc
-                _hip.check(lib.flow_form_newton(
-                    ms, ss, ctypes.byref(fs),
-                    _hip.f64(scratch(mesh, n), n, 'scratch'),
-                    _hip.f64(vals, lay.nnz, 'vals'), _hip.f64(vec, lay.N, 'b'),
-                    _hip.stream()))
-            elif kind == 'matrix':
-                n = nl * nl * nc
-                _hip.check(lib.flow_form_matrix(
-                    ms, ss, ctypes.byref(fs),
-                    _hip.f64(scratch(mesh, n), n, 'scratch'),
-                    _hip.f64(vals, lay.nnz, 'vals'), _hip.stream()))
             else:
-                n = nl * nc
-                _hip.check(lib.flow_form_vector(
-                    ms, ss, ctypes.byref(fs),
-                    _hip.f64(scratch(mesh, n), n, 'scratch'),
-                    _hip.f64(vec, lay.N, 'b'), _hip.stream()))
+                if kind != 'vector':
+                    vals = msum.target(job.msign, True)
+                    if vals is None:
+                        vals = self._spare(2)
+                if kind != 'matrix':
+                    vec = vsum.target(job.vsign, True)
+                    if vec is None:
+                        vec = self._spare(1)
+                _launch_dx(mesh, lay, kind, fs, vals, vec)
             if vals is not None:
-                self._add(first_m, sm, vals, self.A.vals)
-                first_m = False
+                msum.add(job.msign, vals)
             if vec is not None:
-                self._add(first_v, sv, vec, self.b)
-                first_v = False
-        if first_m or first_v:
+                vsum.add(job.vsign, vec)
+        if msum.first or vsum.first:
             raise ValueError('an empty sum of forms has no rank')
-        return self.A, self.b
 
-    def _facet_out(self, jn, rank, part):
+    def _spare(self, rank):
+        '''Where a dx result goes that cannot land in the total.'''
+        buf = self._spares.get(rank)
+        if buf is None:
+            lay = self.V.layout
+            buf = self._spares[rank] = value_plane(lay) if rank == 2 else \
+                device.empty(lay.N)
+        return buf
+
+    def _by_parts(self):
+        lay, mesh = self.V.layout, self.mesh
+        stride = plane_stride(lay)
+        for (ji, fi), jns, kinds, tags, structs, consts, _ in self._calls:
+            for program, view in consts:
+                _refresh_constants(program, view)
+            vals = None if ji is None else self._bufs[0][ji]
+            vec = None if fi is None else self._bufs[1][fi]
+            if kinds[0].startswith('facet'):
+                rank = 2 if vec is None else 1
+                self._facet_blocks(jns, tags, structs, rank,
+                                   vals if rank == 2 else vec)
+            else:
+                _launch_block_dx(mesh, lay, structs, kinds, tags, vals,
+                                 stride, vec)
+        for parts, bufs, total in zip(self.parts, self._bufs,
+                                      (self.A.vals, self.b)):
+            total = _Sum(total)
+            direct = self._single_dx(parts)
+            for (sign, _), buf in zip(parts, bufs):
+                total.add(sign, buf, direct)
+
+    def _facet_blocks(self, jns, tags, structs, rank, buf):
+        '''The ds programs of one part into the planes or components of its
+        buffer: the first program of a block straight into it, a further one
+        into a zeroed buffer of its own, then added.'''
         lay = self.V.layout
-        fmap = facet_map(self.mesh, lay, rank, part.subdomain_data,
-                         part.subdomain_id)
-        held = self._facet.get(jn)
-        if held is None:
-            held = self._facet[jn] = [
-                value_plane(lay) if rank == 2 else device.zeros(lay.N), fmap]
-        elif held[1] is not fmap:       # re-marked: other targets
-            _hip.fill(held[0], 0.0)
-            held[1] = fmap
-        return held[0]
-
-    def _tmp(self, which):
-        if which == 0:
-            if self._plane is None:
-                self._plane = value_plane(self.V.layout)
-            return self._plane
-        if self._vector is None:
-            self._vector = device.empty(self.V.N)
-        return self._vector
-
-    @staticmethod
-    def _add(first, sign, out, total):
-        if out is total:
-            return
-        if first:
-            _hip.fill(total, 0.0)
-        axpby(sign, out, 1.0, total)
+        for k, jn in enumerate(jns):
+            target = self._targets.get(jn)
+            if target is None:
+                width = lay.nnz if rank == 2 else lay.N
+                step = plane_stride(lay) if rank == 2 else lay.N
+                dst = buf[tags[k] * step:tags[k] * step + width]
+                target = self._targets[jn] = _FacetTarget(dst) \
+                    if tags[k] not in tags[:k] \
+                    else _FacetTarget(device.zeros(width), dst)
+            target.gather(self.mesh, lay, rank, structs[k],
+                          self.jobs[jn].part)
 
 
 def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
@@ -1914,7 +1865,7 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
     'error_on_nonconvergence' is False.  Not on strips.  F on a vector space
     W (forms.vector_derivatives(True)): the same loop with a kind-2 matrix and
     vectors of 2N -- (J, F) by flow_form_block_newton where rows fuse
-    (_block_newton_jobs), conditions on W and W.sub(i), the elimination of
+    (newton_jobs, _block_rows), conditions on W and W.sub(i), the elimination of
     flow_bc_symmetric_blocks.'''
     from . import forms
     from ..message import info as say

@@ -288,8 +288,11 @@ def test_solve_parameters_and_refusals(monkeypatch):
     J = derivative(F, u)
     jobs = ops.newton_jobs(J, F)
     assert [j[0] for j in jobs] == ['newton', 'vector']
-    assert jobs[0][3].nout == forms.NEWTON_SLOTS and jobs[0][4:] == (
+    assert jobs[0][3].nout == forms.NEWTON_SLOTS and jobs[0][4:6] == (
         2, 'default')       # (P1: degree 2 of 1 + u^2, the gradients 0)
+    # (the record of a scalar job: no ds part, tag 0, the fused pair of parts)
+    assert jobs[0].part is None and jobs[0].tag == 0
+    assert jobs[0].call == (0, 0) and jobs[1].call == (None, 1)
     assert [j[0] for j in ops.newton_jobs(J, F, fuse=False)] == [
         'matrix', 'vector', 'vector']
     # another degree on the residual's part: no partner, the pair

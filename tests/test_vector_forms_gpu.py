@@ -20,6 +20,7 @@ from flow_amd.fem import (
     )
 
 import vector_form_reference as vref
+from form_assembly_cases import long_integrands
 
 pytestmark = pytest.mark.gpu
 
@@ -173,30 +174,6 @@ def test_action_consistency(hip):
                         % (m, W.degree)) < 1e-12
 
 
-def _long(X, k):
-    """A coefficient of about twenty instructions, different for every k."""
-    return (sin((1.0 + 0.25 * k) * X[0]) * cos(X[1] - 0.5 * k)
-            + (0.5 + k) * X[0] * X[1] + 1.0 / (2.0 + k + X[1] * X[1]))
-
-
-def _long_integrands(mesh, W):
-    """(rank-2, rank-1) integrands whose block (0, 0) / 0 has nine / three
-    long coefficients, more than one program holds (FLOW_FORM_MAX_PROGRAM),
-    next to blocks of one program."""
-    X = SpatialCoordinate(mesh)
-    u, v = TrialFunction(W), TestFunction(W)
-    c = [_long(X, k) for k in range(9)]
-    K = as_vector([[3.0 + c[0], c[1]], [c[2], 3.0 + c[3]]])
-    a = (dot(dot(K, grad(u[0])), grad(v[0]))
-         + dot(as_vector([c[4], c[5]]), grad(u[0])) * v[0]
-         + u[0] * dot(as_vector([c[6], c[7]]), grad(v[0]))
-         + c[8] * u[0] * v[0] + c[1] * u[1] * v[1] + c[2] * u[0].dx(1) * v[1])
-    L = (c[0] * c[6] * v[0]
-         + dot(as_vector([c[1] * c[2], c[3] * c[4]]), grad(v[0]))
-         + c[5] * v[1])
-    return a, L
-
-
 def test_blocks_of_several_programs(hip):
     """The further programs of a block: the spare scratch plane and
     plane_add_kernel under dx, the zeroed plane and the sum under ds."""
@@ -204,7 +181,7 @@ def test_blocks_of_several_programs(hip):
     mesh = fem.UnitSquareMesh(12, 9)
     dsm = Measure('ds', domain=mesh, subdomain_data=_square_markers(mesh))
     for W, _ in _pairs(mesh):
-        ia, iL = _long_integrands(mesh, W)
+        ia, iL = long_integrands(mesh, W)
         for name, form, rank in (('dx matrix', ia * dx, 2),
                                  ('dx vector', iL * dx, 1),
                                  ('ds matrix', ia * dsm(2), 2),

@@ -79,7 +79,7 @@ def main():
                 asm = ops.NewtonAssembler(J, F, V, fuse=fuse)
                 assert asm.fused == fuse
                 row.append(timed(asm.assemble))
-                lens = [len(j[3].code) for j in asm.jobs]
+                lens = [len(j.program.code) for j in asm.jobs]
                 print('  P%d %-22s %-6s %.3f ms (%.3f - %.3f)  programs %s'
                       % (degree, name, 'fused' if fuse else 'pair',
                          row[-1][0], row[-1][1], row[-1][2], lens))

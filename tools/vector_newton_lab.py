@@ -77,7 +77,7 @@ def main():
             best = {k: min(v) for k, v in med.items()}
             print('  P%d %-12s programs %s; pair / fused = %.2f, assemble(J) + '
                   'assemble(F) / fused = %.2f'
-                  % (degree, name, [len(j[3].code) for j in fused.jobs],
+                  % (degree, name, [len(j.program.code) for j in fused.jobs],
                      best['pair'] / best['fused'],
                      best['assemble(J), assemble(F)'] / best['fused']))
 
