@@ -32,8 +32,8 @@ void set_error(const char* fmt, ...);
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
 
 // ilu_kernels.hip
-// stop: a solver's sticky "done" flag (la_kernels.hip) -- every kernel returns
-// at once when it is set
+// stop: a solver's sticky "done" flag (la_kernels.hip, krylov_kernels.hip) --
+// every kernel returns at once when it is set
 int ilu_apply(const flow_ilu* ilu, const double* in, double* out, double* work,
               hipStream_t st, const double* stop = nullptr);
 int ilu_check(const flow_ilu* ilu, int op_size);
@@ -47,7 +47,8 @@ int pmg_check(const flow_pmg* M, int op_size);
 int tl_apply(const flow_tl* T, const double* r, double* z, hipStream_t st,
              const double* stop = nullptr);
 int tl_check(const flow_tl* T, int op_size);
-// la_kernels.hip
+// la_kernels.hip (what its sibling units krylov_, shard_ and profile_kernels.hip
+// share with it: la_internal.h)
 // y = A x for any operator kind (vectors of operator_size(A) entries)
 int operator_apply(const flow_operator* A, const double* x, double* y,
                    hipStream_t st, const double* stop = nullptr);
@@ -70,11 +71,11 @@ enum Slot {
   kBreak, kTarget2, kDone, kConvIt, kIter, kNumSlots = 16
 };
 int read_state(const double* S, double* host, hipStream_t st);
-// K15 (la_kernels.hip): argument checks and the one collective
+// K15 (shard_kernels.hip): argument checks and the one collective
 int check_comm(const flow_comm* c, long long need);
 int check_rows(const flow_rows* R);
 int exchange(const flow_comm* c, int count);
-// [sums | ... | halo at hoff]: see la_kernels.hip
+// [sums | ... | halo at hoff]: see shard_kernels.hip
 int exchange_halo(const flow_comm* C, const flow_rows* R, int ncomp, int sum_count,
                   int hoff, hipStream_t st);
 

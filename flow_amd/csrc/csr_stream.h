@@ -1,4 +1,5 @@
-// CSR-stream tiles of the fp64 SpMV kernels (la_kernels.hip) and of the kernels
+// CSR-stream tiles of the fp64 SpMV kernels (la_kernels.hip), of the multigrid
+// level kernels (krylov_kernels.hip) and of the kernels
 // that carry a product with an epilogue of their own (mass_kernels.hip): a
 // 256-thread workgroup owns <= 256 consecutive rows holding <= kTile - 2
 // nonzeros, streams their values / column indices fully coalesced (every lane

@@ -303,7 +303,7 @@ __global__ __launch_bounds__(kBlock) void ilu_sweep_kernel(
 // instead of 16 B per gather, 20 instead of 28 B per factor entry all told; the
 // row sums still accumulate in fp64, every finished row is rounded once.  The
 // application is then no longer exactly linear in its input (rounding), which
-// only a FLEXIBLE Krylov method may use: the GMRES of la_kernels.hip is one --
+// only a FLEXIBLE Krylov method may use: the GMRES of krylov_kernels.hip is one --
 // it keeps Z_j = M^-1 V_j, multiplies THAT by A and updates x with it, so the
 // Arnoldi relation A Z = V H holds whatever produced Z_j.
 template <int NB>

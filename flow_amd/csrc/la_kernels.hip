@@ -1,5 +1,8 @@
 // Sparse linear algebra of the hot path on gfx950: CSR-stream SpMV (K8), fused
-// BLAS-1 (K9), Jacobi (K10) and the device-resident Krylov drivers (K12).
+// BLAS-1 (K9), Jacobi (K10), the read-backs and the small vector utilities.
+// The device-resident Krylov drivers (K12) built on them: krylov_kernels.hip;
+// the domain decomposition (K15): shard_kernels.hip; what the units share:
+// la_internal.h.
 //
 // Replaces PETSc MatMult / VecDot / VecAXPY / KSPCG inside dolfin's `solve`
 // (reference: flow/navier_stokes/pressure_correction.py:326-339, 419-432,
@@ -16,10 +19,9 @@
 //    finisher => bitwise reproducible.
 //  * Krylov scalars (alpha, beta, ...) live in HBM; the host only reads the
 //    residual norm every `check_every` iterations.
-#include <cstring>
-
 #include "common.h"
 #include "csr_stream.h"
+#include "la_internal.h"
 
 namespace flow {
 
@@ -86,96 +88,6 @@ __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(
   if (DOT) {
     t = block_sum_once(t);
     if (threadIdx.x == 0) dpart[blockIdx.y * gridDim.x + blockIdx.x] = t;
-  }
-}
-
-// The two kernels of a multigrid level (flow_mg) on the same tiles:
-//   UP = 0:  y = c - A x                     (A = Ah, x = c = r:  t = r - Ah r)
-//   UP = 1:  y = A x + w dinv (c + t)        (A = Ps, x = x_{l+1}, c = r)
-//            DOTS: the workgroup's shares of c.y and y.y -> gpart / rpart
-template <int UP, bool DOTS>
-__global__ __launch_bounds__(kBlock) void mg_level_kernel(
-    const int* __restrict__ rowptr, const int* __restrict__ cols,
-    const double* __restrict__ vals, const int* __restrict__ rowblocks,
-    const double* __restrict__ x, const double* __restrict__ c,
-    const double* __restrict__ t, const double* __restrict__ dinv, double omega,
-    double* __restrict__ y, double* __restrict__ gpart,
-    double* __restrict__ rpart, const double* __restrict__ stop) {
-  __shared__ double prod[kTile];
-  if (stopped(stop)) return;
-  int r, r1;
-  const double s =
-      stream_tile_row_sum(rowptr, cols, vals, rowblocks, x, prod, r, r1);
-  double g = 0.0, rr = 0.0;
-  if (r < r1) {
-    const double ci = c[r];
-    if (UP) {
-      const double yi = s + omega * dinv[r] * (ci + t[r]);
-      y[r] = yi;
-      if (DOTS) {
-        g = ci * yi;
-        rr = yi * yi;
-      }
-    } else {
-      y[r] = ci - s;
-    }
-  }
-  if (DOTS) {
-    g = block_sum(g);
-    rr = block_sum(rr);
-    if (threadIdx.x == 0) {
-      gpart[blockIdx.x] = g;
-      rpart[blockIdx.x] = rr;
-    }
-  }
-}
-
-// The up-sweep of a multigrid level in ONE launch (flow_mg's two-launch form):
-//   y = Ps x' + w dinv (2 c - Ah c)
-// -- both products of the workgroup's rows, over row blocks that hold at most a
-// tile of nonzeros of Ps AND of Ah; DOTS as in mg_level_kernel.  y must not be c.
-template <bool DOTS>
-__global__ __launch_bounds__(kBlock) void mg_up2_kernel(
-    const int* __restrict__ rowblocks, const int* __restrict__ p_rowptr,
-    const int* __restrict__ p_cols, const double* __restrict__ p_vals,
-    const int* __restrict__ a_rowptr, const int* __restrict__ a_cols,
-    const double* __restrict__ a_vals, const double* __restrict__ xc,
-    const double* __restrict__ c, const double* __restrict__ dinv, double omega,
-    double* __restrict__ y, double* __restrict__ gpart,
-    double* __restrict__ rpart, const double* __restrict__ stop,
-    int own_lo = 0, int own_hi = 0x7fffffff) {
-  __shared__ double prod_p[kTile];
-  __shared__ double prod_a[kTile];
-  if (stopped(stop)) return;
-  const int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int r0 = rowblocks[tile];
-  const int r1 = rowblocks[tile + 1];
-  const int r = r0 + threadIdx.x;
-  double ci = 0.0, di = 0.0;       // (early: with the tiles' own loads)
-  if (r < r1) {
-    ci = c[r];
-    di = dinv[r];
-  }
-  const double sp = stream_rows_sum(r0, r1, p_rowptr, p_cols, p_vals, xc, prod_p);
-  const double sa = stream_rows_sum(r0, r1, a_rowptr, a_cols, a_vals, c, prod_a);
-  double g = 0.0, rr = 0.0;
-  if (r < r1) {
-    const double yi = sp + omega * di * (2.0 * ci - sa);
-    y[r] = yi;
-    // (K15: a rank that also forms y on its first ghost layer counts its OWN
-    // rows only; the ghost rows are counted by their owners)
-    if (DOTS && r >= own_lo && r < own_hi) {
-      g = ci * yi;
-      rr = yi * yi;
-    }
-  }
-  if (DOTS) {
-    g = block_sum(g);
-    rr = block_sum(rr);
-    if (threadIdx.x == 0) {
-      gpart[blockIdx.x] = g;
-      rpart[blockIdx.x] = rr;
-    }
   }
 }
 
@@ -301,25 +213,8 @@ int check_operator(const flow_operator* A) {
   return FLOW_OK;
 }
 
-static inline int op_size(const flow_operator* A) {
-  return A->kind == 0 ? A->n : 2 * A->n;
-}
-
-// number of x.Ax partials apply() leaves in dpart
-static inline int dot_parts(const flow_operator* A) {
-  return A->kind == 1 ? 2 * A->nblocks : A->nblocks;
-}
-
-// Per-kernel timing of the in-solver SpMV (flow_profile_spmv_begin / _end in
-// include/flow_hip.h): while it is on, every launch of the fused-dot SpMV of a
-// scalar operator with `rows` rows -- the product with A inside a CG iteration,
-// in the cache state the solver leaves -- is bracketed by a pair of HIP events
-// on the launch stream.
-struct SpmvProfile {
-  int rows = 0, cap = 0, used = 0;
-  hipEvent_t* ev = nullptr;   // 2 * cap events
-};
-static SpmvProfile g_spmv_profile;
+// (op_size, dot_parts, SpmvProfile: la_internal.h)
+SpmvProfile g_spmv_profile;
 
 // every value of an operator that reaches a kernel (graph_replay.hip)
 void key_operator(KeyHash& k, const flow_operator* A, bool skip_prm) {
@@ -331,13 +226,10 @@ void key_operator(KeyHash& k, const flow_operator* A, bool skip_prm) {
   }
 }
 
-// y = A x; with dpart != nullptr also the dot_parts(A) workgroup shares of x.y
-// vec_stride: component stride of x and y for the two-component kinds 3 and 4
-// (0: A->n); x and y are indexed by global row either way
-static int apply(const flow_operator* A, const double* x, double* y,
-                 hipStream_t st, double* dpart = nullptr,
-                 const double* stop = nullptr, int vec_stride = 0,
-                 int out_stride = 0, const double* jvp_prm = nullptr) {
+// y = A x [and the shares of x.y]: see la_internal.h
+int apply(const flow_operator* A, const double* x, double* y, hipStream_t st,
+          double* dpart, const double* stop, int vec_stride, int out_stride,
+          const double* jvp_prm) {
   if (A->kind == 3) {
     FLOW_REQUIRE(dpart == nullptr, "matrix-free operators carry no fused dot");
     return momentum_jvp_apply(static_cast<const flow_momentum_jvp*>(A->matfree),
@@ -482,7 +374,7 @@ int fill(int n, double value, double* y, hipStream_t st) {
 
 // out = a * x .* y  (masks, diagonal scalings; out may alias x or y)
 __global__ void vmul_kernel(int n, double a, const double* x, const double* y,
-                            double* out, const double* stop = nullptr) {
+                            double* out, const double* stop) {
   if (stopped(stop)) return;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += gridDim.x * blockDim.x)
@@ -502,394 +394,9 @@ __global__ void residual_kernel(int n, const double* __restrict__ b,
   }
 }
 
-// Chronopoulos-Gear CG scalars from (gamma_new, delta, z.z) partials
-// gamma = r.z and z.z: nparts partials each in gpart / rpart;
-// delta = z.w: ndelta partials in dpart (left there by the SpMV itself)
-constexpr int kScalarBlock = 1024;   // 16 wavefronts: many partials, one block
-__global__ __launch_bounds__(kScalarBlock) void cg_scalar_kernel(
-    int nparts, int ndelta, int first, const double* __restrict__ gpart,
-    const double* __restrict__ rpart, const double* __restrict__ dpart,
-    double rtol2, double atol2, double* __restrict__ S) {
-  __shared__ double wsum[3][kScalarBlock / 64];
-  if (stopped(S + kDone)) return;
-  double g = 0.0, rr = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += kScalarBlock) {
-    g += load_scalar(gpart + i);
-    rr += load_scalar(rpart + i);
-  }
-  // four independent chains keep the loads of the long list in flight
-  double d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0;
-  int i = threadIdx.x;
-  for (; i + 3 * kScalarBlock < ndelta; i += 4 * kScalarBlock) {
-    d0 += load_scalar(dpart + i);
-    d1 += load_scalar(dpart + i + kScalarBlock);
-    d2 += load_scalar(dpart + i + 2 * kScalarBlock);
-    d3 += load_scalar(dpart + i + 3 * kScalarBlock);
-  }
-  for (; i < ndelta; i += kScalarBlock) d0 += load_scalar(dpart + i);
-  double d = (d0 + d1) + (d2 + d3);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    g += __shfl_down(g, off, 64);
-    d += __shfl_down(d, off, 64);
-    rr += __shfl_down(rr, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    wsum[0][threadIdx.x >> 6] = g;
-    wsum[1][threadIdx.x >> 6] = d;
-    wsum[2][threadIdx.x >> 6] = rr;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    g = d = rr = 0.0;
-    for (int w = 0; w < kScalarBlock / 64; ++w) {
-      g += wsum[0][w];
-      d += wsum[1][w];
-      rr += wsum[2][w];
-    }
-  }
-  if (threadIdx.x == 0) {
-    double alpha, beta;
-    if (first) {
-      beta = 0.0;
-      alpha = (d != 0.0) ? g / d : 0.0;
-      // the stopping test of the whole solve, in the PRECONDITIONED norm like
-      // PETSc's KSPCG (its default, which the reference's `solve` runs with):
-      // |B r| <= max(rtol |B b|, atol), z = B r, S[kB2] = |B b|^2
-      const double b2 = load_scalar(S + kB2);
-      store_scalar(S + kTarget2, fmax(rtol2 * b2, atol2));
-      store_scalar(S + kIter, 0.0);
-      // a guarded start (first == 2: flow_cg_solve_guarded) that leaves a
-      // LARGER preconditioned residual than the zero start would, |B r0| >
-      // |B b|, is rejected: S[kDone] = 5 turns everything behind this kernel
-      // into no-ops -- x still holds the start --, the host swaps in the
-      // fallback.  (What a far start costs these recurrences is attainable
-      // accuracy: the recurrence residual drifts from the true one in
-      // proportion to the largest residual seen, and from zero -- the
-      // reference's start -- that is |b|.)
-      if (first == 2 && rr > b2) {
-        store_scalar(S + kConvIt, 0.0);
-        store_scalar(S + kRes2, rr);
-        store_scalar(S + kDone, 5.0);
-        return;
-      }
-    } else {
-      const double g_old = load_scalar(S + kGamma);
-      const double a_old = load_scalar(S + kAlpha);
-      beta = (g_old != 0.0) ? g / g_old : 0.0;
-      const double den = (a_old != 0.0) ? d - beta * g / a_old : 0.0;
-      alpha = (den != 0.0) ? g / den : 0.0;
-    }
-    // rr = z.z belongs to the iterate x_k, k = S[kIter] updates behind the
-    // start: the first one that passes the test (or is not a number) stops
-    // the iteration for good
-    const double k = load_scalar(S + kIter);
-    const bool nan = !(rr == rr);
-    if (nan || rr <= load_scalar(S + kTarget2)) {
-      store_scalar(S + kConvIt, k);
-      store_scalar(S + kDone, nan ? 2.0 : 1.0);
-      alpha = beta = 0.0;
-    }
-    store_scalar(S + kIter, k + 1.0);
-    store_scalar(S + kGamma, g);
-    store_scalar(S + kAlpha, alpha);
-    store_scalar(S + kBeta, beta);
-    store_scalar(S + kRes2, rr);
-  }
-}
-
-// p = z + beta p ; s = w + beta s ; x += alpha p ; r -= alpha s ; z = dinv r
-// (want_z = 0: z is produced afterwards by the two-level preconditioner)
-// DOTS (needs want_z, gridDim.x <= kRedBlocks): the block's shares of r.z and
-// z.z go to partial[blockIdx.x] / partial[2*kRedBlocks + blockIdx.x].
-// own != nullptr (sharded solves: the vectors cover ghost rows too): the dots
-// only count the entries with own[i] = 1
-template <bool DOTS>
-__global__ __launch_bounds__(kBlock) void cg_update_kernel(
-    int n, const double* __restrict__ S, const double* __restrict__ dinv,
-    const double* __restrict__ w, double* __restrict__ z, double* __restrict__ p,
-    double* __restrict__ s, double* __restrict__ x, double* __restrict__ r,
-    int want_z, double* __restrict__ partial,
-    const double* __restrict__ own) {
-  if (stopped(S + kDone)) return;
-  const double alpha = load_scalar(S + kAlpha);
-  const double beta = load_scalar(S + kBeta);
-  double g = 0.0, rr = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    const double pi = z[i] + beta * p[i];
-    const double si = w[i] + beta * s[i];
-    p[i] = pi;
-    s[i] = si;
-    x[i] += alpha * pi;
-    const double ri = r[i] - alpha * si;
-    r[i] = ri;
-    if (want_z) {
-      const double zi = dinv ? dinv[i] * ri : ri;
-      z[i] = zi;
-      if (DOTS && (!own || own[i] != 0.0)) {   // (select, not multiply:
-        g += ri * zi;                            // ghost entries may be NaN)
-        rr += zi * zi;
-      }
-    }
-  }
-  if (DOTS) {
-    g = block_sum(g);
-    rr = block_sum(rr);
-    if (threadIdx.x == 0) {
-      partial[blockIdx.x] = g;
-      partial[2 * kRedBlocks + blockIdx.x] = rr;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// two-level additive preconditioner  z = D^-1 r + P Ac^-1 P^T r
-// (Jacobi + piecewise-constant aggregate coarse space, dense coarse inverse)
-// ---------------------------------------------------------------------------
-// rc[a] = sum of r over the dofs of aggregate a that lie in [r0, r1): one
-// wavefront per aggregate, fixed order => reproducible
-__global__ __launch_bounds__(kBlock) void coarse_restrict_kernel(
-    int nc, const int* __restrict__ agg_ptr, const int* __restrict__ agg_dofs,
-    const double* __restrict__ r, int r0, int r1, double* __restrict__ rc,
-    const double* __restrict__ stop) {
-  if (stopped(stop)) return;
-  const int lane = threadIdx.x & 63;
-  for (int a = blockIdx.x * 4 + (threadIdx.x >> 6); a < nc; a += gridDim.x * 4) {
-    double sum = 0.0;
-    for (int k = agg_ptr[a] + lane; k < agg_ptr[a + 1]; k += 64) {
-      const int d = agg_dofs[k];
-      if (d >= r0 && d < r1) sum += r[d];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
-    if (lane == 0) rc[a] = sum;
-  }
-}
-
-// zc = Ainv rc (dense fp32 rows of lda floats, fp64 accumulation): one
-// wavefront per row, float4 loads; rc 16-byte aligned, nc entries.  (rc and zc
-// are per-lane -- vector -- loads: the stale reads common.h describes were
-// only ever observed on wave-uniform loads, which go through the scalar cache.)
-__global__ __launch_bounds__(kBlock) void coarse_gemv_kernel(
-    int nc, int lda, const float* __restrict__ Ainv,
-    const double* __restrict__ rc, double* __restrict__ zc,
-    const double* __restrict__ stop) {
-  if (stopped(stop)) return;
-  const int lane = threadIdx.x & 63;
-  const int nq = lda >> 2;
-  for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < nc;
-       row += gridDim.x * 4) {
-    const float4* __restrict__ a =
-        reinterpret_cast<const float4*>(Ainv + static_cast<size_t>(row) * lda);
-    const double2* __restrict__ x = reinterpret_cast<const double2*>(rc);
-    double s0 = 0.0, s1 = 0.0;
-    for (int q = lane; q < nq; q += 64) {
-      const float4 v = a[q];
-      double2 x0, x1;
-      if (4 * q + 3 < nc) {
-        x0 = x[2 * q];
-        x1 = x[2 * q + 1];
-      } else {   // last quad of a row whose length is not a multiple of 4
-        const int j = 4 * q;
-        x0.x = rc[j];
-        x0.y = (j + 1 < nc) ? rc[j + 1] : 0.0;
-        x1.x = (j + 2 < nc) ? rc[j + 2] : 0.0;
-        x1.y = 0.0;
-      }
-      s0 += static_cast<double>(v.x) * x0.x + static_cast<double>(v.z) * x1.x;
-      s1 += static_cast<double>(v.y) * x0.y + static_cast<double>(v.w) * x1.y;
-    }
-    double sum = s0 + s1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
-    if (lane == 0) zc[row] = sum;
-  }
-}
-
-// z = dinv r + zc[agg_of]  on dofs [0, n) of pre-offset arrays
-// DOTS (gridDim.x <= kRedBlocks): also the block's shares of r.z and z.z, as
-// in cg_update_kernel
-template <bool DOTS>
-__global__ __launch_bounds__(kBlock) void coarse_prolong_kernel(
-    int n, const int* __restrict__ agg_of, const double* __restrict__ dinv,
-    const double* __restrict__ r, const double* __restrict__ zc,
-    double* __restrict__ z, double* __restrict__ partial,
-    const double* __restrict__ stop) {
-  if (stopped(stop)) return;
-  double g = 0.0, rr = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    const int a = agg_of[i];
-    const double ri = r[i];
-    const double zi = dinv[i] * ri + (a >= 0 ? zc[a] : 0.0);
-    z[i] = zi;
-    if (DOTS) {
-      g += ri * zi;
-      rr += zi * zi;
-    }
-  }
-  if (DOTS) {
-    g = block_sum(g);
-    rr = block_sum(rr);
-    if (threadIdx.x == 0) {
-      partial[blockIdx.x] = g;
-      partial[2 * kRedBlocks + blockIdx.x] = rr;
-    }
-  }
-}
-
-static int check_coarse(const flow_coarse* C, int n) {
-  FLOW_REQUIRE(C->nc > 0 && C->n == n, "coarse space size");
-  FLOW_REQUIRE(C->agg_ptr && C->agg_dofs && C->agg_of && C->Ainv,
-               "coarse space pointers");
-  FLOW_REQUIRE(C->lda >= C->nc && C->lda % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(C->Ainv) % 16 == 0,
-               "coarse inverse: row stride must be a multiple of 4 floats, "
-               "base 16-byte aligned");
-  return FLOW_OK;
-}
-
-// z = M^-1 r with the two-level preconditioner; rc, zc: lda doubles each.
-// partial != nullptr: the prolongation also leaves the shares of r.z and z.z
-// of its *nparts workgroups there.
-static int two_level(const flow_coarse* C, const double* dinv, const double* r,
-                     double* z, double* rc, double* zc, hipStream_t st,
-                     double* partial = nullptr, int* nparts = nullptr,
-                     const double* stop = nullptr) {
-  const int g = grid_for(C->nc, 4, kMaxGrid);
-  hipLaunchKernelGGL(coarse_restrict_kernel, dim3(g), dim3(kBlock), 0, st, C->nc,
-                     C->agg_ptr, C->agg_dofs, r, 0, C->n, rc, stop);
-  hipLaunchKernelGGL(coarse_gemv_kernel, dim3(g), dim3(kBlock), 0, st, C->nc,
-                     C->lda, C->Ainv, rc, zc, stop);
-  if (partial) {
-    const int gp = grid_for(C->n, kBlock, kRedBlocks);
-    hipLaunchKernelGGL(coarse_prolong_kernel<true>, dim3(gp), dim3(kBlock), 0,
-                       st, C->n, C->agg_of, dinv, r, zc, z, partial, stop);
-    *nparts = gp;
-  } else {
-    hipLaunchKernelGGL(coarse_prolong_kernel<false>, dim3(grid_for(C->n)),
-                       dim3(kBlock), 0, st, C->n, C->agg_of, dinv, r, zc, z,
-                       partial, stop);
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// ---------------------------------------------------------------------------
-// smoothed-aggregation multigrid V(1,1) cycle (flow_mg, include/flow_hip.h)
-// ---------------------------------------------------------------------------
-// multigrid V-cycle (flow_mg)
-static int check_mg(const flow_mg* M, int n) {
-  FLOW_REQUIRE(M->nlevels >= 1 && M->nlevels <= FLOW_MG_MAX_LEVELS, "mg levels");
-  FLOW_REQUIRE(M->omega > 0.0 && M->omega < 2.0, "mg damping");
-  int rows = n;
-  for (int l = 0; l + 1 < M->nlevels; ++l) {
-    int rc = check_operator(&M->Ah[l]);
-    if (rc) return rc;
-    if ((rc = check_operator(&M->Ps[l]))) return rc;
-    if ((rc = check_operator(&M->R[l]))) return rc;
-    FLOW_REQUIRE(M->Ah[l].kind == 0 && M->Ps[l].kind == 0 && M->R[l].kind == 0,
-                 "mg operators are scalar");
-    FLOW_REQUIRE(M->Ah[l].n == rows && M->Ps[l].n == rows, "mg level sizes");
-    FLOW_REQUIRE(M->dinv[l] && M->t[l], "mg level vectors");
-    FLOW_REQUIRE(l == 0 || (M->r[l] && M->x[l]), "mg level vectors");
-    if (M->C[0].rowptr) {     // the two-launch form: every level carries it
-      if ((rc = check_operator(&M->C[l]))) return rc;
-      FLOW_REQUIRE(M->C[l].kind == 0 && M->C[l].n == M->R[l].n &&
-                       M->up_rowblocks[l] && M->up_nblocks[l] > 0,
-                   "mg two-launch form: C and the common row blocks");
-    }
-    rows = M->R[l].n;
-  }
-  const int last = M->nlevels - 1;
-  FLOW_REQUIRE(M->nc == rows && M->Ainv && M->lda >= M->nc && M->lda % 4 == 0 &&
-                   reinterpret_cast<uintptr_t>(M->Ainv) % 16 == 0,
-               "mg coarsest level");
-  FLOW_REQUIRE(last == 0 || (M->r[last] && M->x[last] &&
-                             reinterpret_cast<uintptr_t>(M->r[last]) % 16 == 0),
-               "mg coarsest vectors");
-  return FLOW_OK;
-}
-
-// z = V-cycle(r) from level l0 down (l0 = 0: the whole hierarchy; the sharded
-// pressure solve runs the levels >= 1 replicated: l0 = 1, r0 = the summed
-// coarse residual).  gpart != nullptr (l0 = 0 only): the last kernel also
-// leaves the *nparts (= Ps[0].nblocks) workgroup shares of r.z in gpart and z.z
-// in rpart
-static int vcycle(const flow_mg* M, const double* r0, double* z0, hipStream_t st,
-                  double* gpart = nullptr, double* rpart = nullptr,
-                  int* nparts = nullptr, const double* stop = nullptr,
-                  int l0 = 0) {
-  const int L = M->nlevels;
-  int rc;
-  double* const none = nullptr;
-  const bool fused = M->C[0].rowptr != nullptr;
-  for (int l = l0; l + 1 < L; ++l) {
-    const double* r = l == l0 ? r0 : M->r[l];
-    if (fused) {
-      // r_{l+1} = C r,  C = R (I - Ah)
-      if ((rc = apply(&M->C[l], r, M->r[l + 1], st, nullptr, stop))) return rc;
-      continue;
-    }
-    const flow_operator* A = &M->Ah[l];
-    // t = r - Ah r ; r_{l+1} = R t
-    hipLaunchKernelGGL((mg_level_kernel<0, false>), dim3(A->nblocks), dim3(kBlock),
-                       0, st, A->rowptr, A->cols, A->vals[0], A->rowblocks, r, r,
-                       none, none, M->omega, M->t[l], none, none, stop);
-    if ((rc = apply(&M->R[l], M->t[l], M->r[l + 1], st, nullptr, stop)))
-      return rc;
-  }
-  {
-    const double* r = l0 == L - 1 ? r0 : M->r[L - 1];
-    double* x = l0 == L - 1 ? z0 : M->x[L - 1];
-    hipLaunchKernelGGL(coarse_gemv_kernel, dim3(grid_for(M->nc, 4, kMaxGrid)),
-                       dim3(kBlock), 0, st, M->nc, M->lda, M->Ainv, r, x, stop);
-  }
-  for (int l = L - 2; l >= l0; --l) {
-    const double* r = l == l0 ? r0 : M->r[l];
-    double* x = l == l0 ? z0 : M->x[l];
-    const flow_operator* P = &M->Ps[l];
-    const bool with_dots = l == 0 && gpart;
-    if (fused) {
-      // x = Ps x_{l+1} + w D^-1 (2 r - Ah r)
-      const flow_operator* A = &M->Ah[l];
-      const dim3 grid(M->up_nblocks[l]);
-      if (with_dots)
-        hipLaunchKernelGGL(mg_up2_kernel<true>, grid, dim3(kBlock), 0, st,
-                           M->up_rowblocks[l], P->rowptr, P->cols, P->vals[0],
-                           A->rowptr, A->cols, A->vals[0], M->x[l + 1], r,
-                           M->dinv[l], M->omega, x, gpart, rpart, stop);
-      else
-        hipLaunchKernelGGL(mg_up2_kernel<false>, grid, dim3(kBlock), 0, st,
-                           M->up_rowblocks[l], P->rowptr, P->cols, P->vals[0],
-                           A->rowptr, A->cols, A->vals[0], M->x[l + 1], r,
-                           M->dinv[l], M->omega, x, none, none, stop);
-      if (with_dots) *nparts = M->up_nblocks[l];
-      continue;
-    }
-    // x = Ps x_{l+1} + w D^-1 (r + t)
-    if (with_dots) {
-      hipLaunchKernelGGL((mg_level_kernel<1, true>), dim3(P->nblocks),
-                         dim3(kBlock), 0, st, P->rowptr, P->cols, P->vals[0],
-                         P->rowblocks, M->x[l + 1], r, M->t[l], M->dinv[l],
-                         M->omega, x, gpart, rpart, stop);
-      *nparts = P->nblocks;
-    } else {
-      hipLaunchKernelGGL((mg_level_kernel<1, false>), dim3(P->nblocks),
-                         dim3(kBlock), 0, st, P->rowptr, P->cols, P->vals[0],
-                         P->rowblocks, M->x[l + 1], r, M->t[l], M->dinv[l],
-                         M->omega, x, none, none, stop);
-    }
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-static int dots(int n, int nd, const double* a0, const double* b0,
-                const double* a1, const double* b1, const double* a2,
-                const double* b2, double* partial, int* nparts,
-                hipStream_t st) {
+int dots(int n, int nd, const double* a0, const double* b0, const double* a1,
+         const double* b1, const double* a2, const double* b2, double* partial,
+         int* nparts, hipStream_t st) {
   const int g = grid_for(n, kBlock * 4, kRedBlocks);
   hipLaunchKernelGGL(dot3_kernel, dim3(g), dim3(kBlock), 0, st, n, nd, a0, b0,
                      a1, b1, a2, b2, partial);
@@ -918,7 +425,6 @@ __global__ void mailbox_kernel(const double* __restrict__ src0,
 }
 
 // the calling thread's mailbox: kMailbox doubles of pinned, mapped host memory
-constexpr int kMailbox = 64;
 static int mailbox_of_thread(double** host, double** dev) {
   static thread_local double* mailbox = nullptr;
   if (!mailbox)
@@ -981,364 +487,24 @@ int sum_partials_host(double* work, int nparts, double* host, hipStream_t st) {
   return read_slot(S, 0, host, st);
 }
 
-// Work of cg(): [reductions | r z w p s | z.w partials of the SpMV | rc zc |
-// r.z, z.z partials of the V-cycle's last kernel]
-// partials the V-cycle's last kernel leaves (r.z and z.z each)
-static inline int mg_parts(const flow_mg* M) {
-  if (!M || M->nlevels < 2) return 0;
-  return M->C[0].rowptr ? M->up_nblocks[0] : M->Ps[0].nblocks;
+// n doubles of device memory -> the host mailbox
+__global__ void mailbox_copy_kernel(int n, const double* __restrict__ src,
+                                    volatile double* __restrict__ mailbox) {
+  if (threadIdx.x < n) mailbox[threadIdx.x] = load_scalar(src + threadIdx.x);
+  __threadfence_system();
 }
 
-static inline size_t cg_work_len(const flow_operator* A, const flow_coarse* C,
-                                 const flow_mg* M) {
-  const size_t N = op_size(A);
-  return FLOW_REDUCE_WORK + 5 * N + dot_parts(A) + 2 +
-         (C ? 2 * static_cast<size_t>(C->lda) : 0) +
-         2 * static_cast<size_t>(mg_parts(M));
-}
-
-// Chronopoulos-Gear CG.  Per iteration: update (x, r, p, s) -> preconditioner
-// -> SpMV -> scalars; the three dot products ride in those kernels (r.z and z.z
-// in whichever kernel produces z, z.w in the SpMV), so no vector is re-read for
-// a reduction.
-static int cg(const flow_operator* A, const double* dinv,
-              const flow_coarse* C, const flow_mg* M, const double* b,
-              double* x, double rtol, double atol, int maxit, int check_every,
-              int first_check, double* work, int* iters_host,
-              double* resid_host, hipStream_t st, bool* rejected = nullptr) {
-  // rejected != nullptr: the start vector is guarded (cg_scalar_kernel); when
-  // it is rejected, *rejected = true, x is the start still, FLOW_OK
-  if (rejected) *rejected = false;
-  const int N = op_size(A);
-  const int nd = dot_parts(A);
-  double* partial = work;
-  double* S = work + 3 * kRedBlocks;
-  double* r = work + FLOW_REDUCE_WORK;
-  double* z = r + N;
-  double* w = z + N;
-  double* p = w + N;
-  double* s = p + N;
-  double* dpart = s + N;
-  // coarse vectors (two-level only), 16-byte aligned
-  double* crc = dpart + nd + ((N + nd) & 1);
-  double* czc = crc + (C ? C->lda : 0);
-  double* mpart = czc + (C ? C->lda : 0);     // V-cycle partials (multigrid only)
-  const int nm = mg_parts(M);
-  const double* gpart = M ? mpart : partial;
-  const double* rpart = M ? mpart + nm : partial + 2 * kRedBlocks;
-  const int gv = grid_for(N);
-  const int gu = grid_for(N, kBlock, kRedBlocks);   // update with fused dots
-  int np = 0, rc;
-
-  const double* stop = S + kDone;
-  double* const r_ = r;     // (for the lambdas below, whose `r` is a status)
-  const double rtol2 = rtol * rtol, atol2 = atol * atol;
-  if ((rc = fill(kNumSlots, 0.0, S, st))) return rc;
-  if ((rc = fill(2 * N, 0.0, p, st))) return rc;      // p, s
-  // |B b|^2, B the preconditioner (z is free until the start below)
-  if (C) {
-    if ((rc = two_level(C, dinv, b, z, crc, czc, st))) return rc;
-  } else if (M) {
-    if ((rc = vcycle(M, b, z, st))) return rc;
-  } else if (dinv) {
-    hipLaunchKernelGGL(vmul_kernel, dim3(gv), dim3(kBlock), 0, st, N, 1.0, dinv,
-                       b, z);
-  }
-  const double* Bb = (C || M || dinv) ? z : b;
-  if ((rc = dots(N, 1, Bb, Bb, Bb, Bb, Bb, Bb, partial, &np, st))) return rc;
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kBlock), 0, st, np, 1, 0,
-                     partial, S + kB2);
-  // r = b - A x ; z = B r ; w = A z
-  if ((rc = apply(A, x, w, st))) return rc;
-  hipLaunchKernelGGL(residual_kernel, dim3(gv), dim3(kBlock), 0, st, N, b, w,
-                     dinv, r, z);
-  if (C && (rc = two_level(C, dinv, r, z, crc, czc, st))) return rc;
-  if (M && (rc = vcycle(M, r, z, st))) return rc;
-  if ((rc = apply(A, z, w, st, dpart))) return rc;
-  if ((rc = dots(N, 3, r, z, z, w, z, z, partial, &np, st))) return rc;
-  hipLaunchKernelGGL(cg_scalar_kernel, dim3(1), dim3(kScalarBlock), 0, st, np,
-                     nd, rejected ? 2 : 1, partial, partial + 2 * kRedBlocks,
-                     dpart, rtol2, atol2, S);
+int read_values(const double* dev, int n, double* host, hipStream_t st) {
+  double *mailbox = nullptr, *dev_view = nullptr;
+  int rc = mailbox_of_thread(&mailbox, &dev_view);
+  if (rc) return rc;
+  FLOW_REQUIRE(n <= kMailbox, "mailbox size");
+  hipLaunchKernelGGL(mailbox_copy_kernel, dim3(1), dim3(64), 0, st, n, dev,
+                     dev_view);
   FLOW_CHECK_LAUNCH();
-
-  // one iteration: the same launches with the same arguments every time (the
-  // tolerances only enter the FIRST scalar kernel above)
-  auto body = [&]() -> int {
-    int r;
-    if (C) {
-      hipLaunchKernelGGL(cg_update_kernel<false>, dim3(gv), dim3(kBlock), 0,
-                         st, N, S, dinv, w, z, p, s, x, r_, 0, partial,
-                         static_cast<const double*>(nullptr));
-      if ((r = two_level(C, dinv, r_, z, crc, czc, st, partial, &np, stop)))
-        return r;
-    } else if (M) {
-      hipLaunchKernelGGL(cg_update_kernel<false>, dim3(gv), dim3(kBlock), 0,
-                         st, N, S, dinv, w, z, p, s, x, r_, 0, partial,
-                         static_cast<const double*>(nullptr));
-      if ((r = vcycle(M, r_, z, st, mpart, mpart + nm, &np, stop))) return r;
-    } else {
-      hipLaunchKernelGGL(cg_update_kernel<true>, dim3(gu), dim3(kBlock), 0, st,
-                         N, S, dinv, w, z, p, s, x, r_, 1, partial,
-                         static_cast<const double*>(nullptr));
-      np = gu;
-    }
-    if ((r = apply(A, z, w, st, dpart, stop))) return r;
-    hipLaunchKernelGGL(cg_scalar_kernel, dim3(1), dim3(kScalarBlock), 0, st,
-                       np, nd, 0, gpart, rpart, dpart, 0.0, 0.0, S);
-    FLOW_CHECK_LAUNCH();
-    return FLOW_OK;
-  };
-  // ... replayed as a HIP graph where the launch rate bounds the iteration
-  // (graph_replay.hip; never while the SpMV is being timed with events)
-  hipGraphExec_t graph = nullptr;
-  int graph_nodes = 0;
-  if (replay_wanted(N, kReplayCg) && g_spmv_profile.ev == nullptr) {
-    KeyHash key;
-    key.pod(0x6367ull);       // "cg"
-    key_operator(key, A);
-    key.obj(C).obj(M).pod(dinv).pod(x).pod(work).pod(N);
-    if ((rc = replay_prepare(key.h, kReplayCg, st, body, &graph, &graph_nodes))) return rc;
-  }
-
-  // Iterations are enqueued in batches; the device decides which iterate
-  // passes the stopping test (cg_scalar_kernel) and turns everything behind it
-  // into no-ops, so a batch may overshoot: the first one is `first_check`
-  // iterations (the caller's guess of what the solve needs), later ones
-  // `check_every`; the start is only read back with the first batch.
-  double state[kNumSlots];
-  int launched = 0;
-  while (true) {
-    const int batch = (launched == 0 && first_check > 0) ? first_check
-                                                         : check_every;
-    const int todo = (maxit - launched < batch) ? maxit - launched : batch;
-    for (int k = 0; k < todo; ++k) {
-      if (graph) {
-        if ((rc = replay_launch(graph, graph_nodes, st))) return rc;
-      } else if ((rc = body())) {
-        return rc;
-      }
-    }
-    FLOW_CHECK_LAUNCH();
-    launched += todo;
-    if ((rc = read_state(S, state, st))) return rc;
-    const double res2 = state[kRes2];
-    if (state[kDone] == 2.0 || !(res2 == res2)) {
-      *iters_host = static_cast<int>(state[kConvIt]);
-      *resid_host = res2;
-      set_error("CG broke down (NaN residual) at iteration %d", *iters_host);
-      return FLOW_NOT_CONVERGED;
-    }
-    if (state[kDone] == 1.0) {
-      *iters_host = static_cast<int>(state[kConvIt]);
-      *resid_host = sqrt(res2);
-      return FLOW_OK;
-    }
-    if (state[kDone] == 5.0 && rejected) {
-      *rejected = true;
-      *iters_host = 0;
-      *resid_host = sqrt(res2);
-      return FLOW_OK;
-    }
-    if (launched >= maxit) {
-      *iters_host = launched;
-      *resid_host = sqrt(res2);
-      set_error("CG did not converge in %d iterations: |B r| = %.3e > %.3e",
-                launched, sqrt(res2), sqrt(state[kTarget2]));
-      return FLOW_NOT_CONVERGED;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// BiCGStab (right-preconditioned with Jacobi), van der Vorst 1992
-// ---------------------------------------------------------------------------
-// mode 0: rho_new = partial0 ; beta = (rho_new/rho)(alpha/omega)
-// mode 1: alpha = rho_new / partial0 (= rhat.v)
-// mode 2: omega = partial0/partial1 (= t.s / t.t); rho = rho_new;
-//         rho_new = partial2 (= rhat.r of the NEW r needs another pass: see 3)
-// mode 3: rho_new = partial0 (rhat.r), res2 = partial1 (r.r)
-// mode 3 also decides convergence on the device (see `stopped`): first != 0
-// sets the target from |b|^2; the first r that passes the test freezes x, r, p.
-__global__ __launch_bounds__(kBlock) void bicg_scalar_kernel(
-    int nparts, int mode, int first, double rtol2, double atol2,
-    const double* __restrict__ partial, double* __restrict__ S) {
-  if (stopped(S + kDone)) return;
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += kBlock) {
-    a += load_scalar(partial + i);
-    b += load_scalar(partial + kRedBlocks + i);
-  }
-  a = block_sum(a);
-  b = block_sum(b);
-  if (threadIdx.x != 0) return;
-  if (mode == 1) {
-    store_scalar(S + kAlpha, (a != 0.0) ? load_scalar(S + kRhoNew) / a : 0.0);
-    if (a == 0.0) store_scalar(S + kBreak, 1.0);
-  } else if (mode == 2) {
-    store_scalar(S + kOmega, (b != 0.0) ? a / b : 0.0);
-  } else {   // mode 3 (also used for initialisation)
-    const double rho_old = load_scalar(S + kRhoNew);
-    const double omega = load_scalar(S + kOmega);
-    const double alpha = load_scalar(S + kAlpha);
-    store_scalar(S + kRho, rho_old);
-    store_scalar(S + kRhoNew, a);
-    store_scalar(S + kRes2, b);
-    store_scalar(S + kBeta, (rho_old != 0.0 && omega != 0.0)
-                                ? (a / rho_old) * (alpha / omega)
-                                : 0.0);
-    if (first) {
-      store_scalar(S + kTarget2, fmax(rtol2 * load_scalar(S + kB2), atol2));
-      store_scalar(S + kIter, 0.0);
-    }
-    const double k = load_scalar(S + kIter);
-    const bool nan = !(b == b);
-    if (nan || b <= load_scalar(S + kTarget2)) {
-      store_scalar(S + kConvIt, k);
-      store_scalar(S + kDone, nan ? 2.0 : 1.0);
-    }
-    store_scalar(S + kIter, k + 1.0);
-  }
-}
-
-// p = r + beta (p - omega v) ; y = dinv p
-__global__ void bicg_p_kernel(int n, const double* __restrict__ S,
-                              const double* __restrict__ dinv,
-                              const double* __restrict__ r,
-                              const double* __restrict__ v,
-                              double* __restrict__ p, double* __restrict__ y) {
-  if (stopped(S + kDone)) return;
-  const double beta = load_scalar(S + kBeta);
-  const double omega = load_scalar(S + kOmega);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    const double pi = r[i] + beta * (p[i] - omega * v[i]);
-    p[i] = pi;
-    y[i] = dinv ? dinv[i] * pi : pi;
-  }
-}
-
-// s = r - alpha v (in place in r) ; z = dinv s
-__global__ void bicg_s_kernel(int n, const double* __restrict__ S,
-                              const double* __restrict__ dinv,
-                              const double* __restrict__ v,
-                              double* __restrict__ r, double* __restrict__ z) {
-  if (stopped(S + kDone)) return;
-  const double alpha = load_scalar(S + kAlpha);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    const double si = r[i] - alpha * v[i];
-    r[i] = si;
-    z[i] = dinv ? dinv[i] * si : si;
-  }
-}
-
-// x += alpha y + omega z ; r = s - omega t
-__global__ void bicg_x_kernel(int n, const double* __restrict__ S,
-                              const double* __restrict__ y,
-                              const double* __restrict__ z,
-                              const double* __restrict__ t,
-                              double* __restrict__ x, double* __restrict__ r) {
-  if (stopped(S + kDone)) return;
-  const double alpha = load_scalar(S + kAlpha);
-  const double omega = load_scalar(S + kOmega);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    x[i] += alpha * y[i] + omega * z[i];
-    r[i] -= omega * t[i];
-  }
-}
-
-static int bicgstab(const flow_operator* A, const double* dinv,
-                    const flow_ilu* ilu, const double* b,
-                    double* x, double rtol, double atol, int maxit,
-                    int check_every, int first_check, double* work,
-                    int* iters_host, double* resid_host, hipStream_t st) {
-  const int N = op_size(A);
-  double* partial = work;
-  double* S = work + 3 * kRedBlocks;
-  double* r = work + FLOW_REDUCE_WORK;
-  double* rhat = r + N;
-  double* p = rhat + N;
-  double* v = p + N;
-  double* y = v + N;
-  double* z = y + N;
-  double* t = z + N;
-  double* iwork = t + N;                  // ILU sweep buffer (ilu only)
-  if (ilu) dinv = nullptr;                // y = ILU(p), z = ILU(s) below
-  const int gv = grid_for(N);
-  int np = 0, rc;
-
-  if ((rc = fill(kNumSlots, 0.0, S, st))) return rc;
-  if ((rc = fill(2 * N, 0.0, p, st))) return rc;      // p, v
-  if ((rc = dots(N, 1, b, b, b, b, b, b, partial, &np, st))) return rc;
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kBlock), 0, st, np, 1, 0,
-                     partial, S + kB2);
-  if ((rc = apply(A, x, t, st))) return rc;
-  hipLaunchKernelGGL(residual_kernel, dim3(gv), dim3(kBlock), 0, st, N, b, t,
-                     static_cast<const double*>(nullptr), r,
-                     static_cast<double*>(nullptr));
-  hipLaunchKernelGGL(axpby_kernel, dim3(gv), dim3(kBlock), 0, st, N, 1.0, r, 0.0,
-                     rhat);                           // rhat = r0
-  // rho_new = rhat.r, res2 = r.r ; beta = 0 because rho_old = omega = 0
-  const double rtol2 = rtol * rtol, atol2 = atol * atol;
-  if ((rc = dots(N, 2, rhat, r, r, r, r, r, partial, &np, st))) return rc;
-  hipLaunchKernelGGL(bicg_scalar_kernel, dim3(1), dim3(kBlock), 0, st, np, 3, 1,
-                     rtol2, atol2, partial, S);
-  FLOW_CHECK_LAUNCH();
-
-  // batches of iterations; the device freezes x, r, p at the first residual
-  // that passes the stopping test (bicg_scalar_kernel mode 3), see cg()
-  double state[kNumSlots];
-  int launched = 0;
-  while (true) {
-    const int batch = (launched == 0 && first_check > 0) ? first_check
-                                                         : check_every;
-    const int todo = (maxit - launched < batch) ? maxit - launched : batch;
-    for (int k = 0; k < todo; ++k) {
-      hipLaunchKernelGGL(bicg_p_kernel, dim3(gv), dim3(kBlock), 0, st, N, S,
-                         dinv, r, v, p, y);
-      if (ilu && (rc = ilu_apply(ilu, p, y, iwork, st))) return rc;
-      if ((rc = apply(A, y, v, st))) return rc;
-      if ((rc = dots(N, 1, rhat, v, v, v, v, v, partial, &np, st))) return rc;
-      hipLaunchKernelGGL(bicg_scalar_kernel, dim3(1), dim3(kBlock), 0, st, np,
-                         1, 0, rtol2, atol2, partial, S);
-      hipLaunchKernelGGL(bicg_s_kernel, dim3(gv), dim3(kBlock), 0, st, N, S,
-                         dinv, v, r, z);
-      if (ilu && (rc = ilu_apply(ilu, r, z, iwork, st))) return rc;
-      if ((rc = apply(A, z, t, st))) return rc;
-      if ((rc = dots(N, 2, t, r, t, t, t, t, partial, &np, st))) return rc;
-      hipLaunchKernelGGL(bicg_scalar_kernel, dim3(1), dim3(kBlock), 0, st, np,
-                         2, 0, rtol2, atol2, partial, S);
-      hipLaunchKernelGGL(bicg_x_kernel, dim3(gv), dim3(kBlock), 0, st, N, S, y,
-                         z, t, x, r);
-      if ((rc = dots(N, 2, rhat, r, r, r, r, r, partial, &np, st))) return rc;
-      hipLaunchKernelGGL(bicg_scalar_kernel, dim3(1), dim3(kBlock), 0, st, np,
-                         3, 0, rtol2, atol2, partial, S);
-    }
-    FLOW_CHECK_LAUNCH();
-    launched += todo;
-    if ((rc = read_state(S, state, st))) return rc;
-    const double res2 = state[kRes2];
-    if (state[kDone] == 2.0 || !(res2 == res2)) {
-      *iters_host = static_cast<int>(state[kConvIt]);
-      *resid_host = res2;
-      set_error("BiCGStab broke down (NaN residual) at iteration %d",
-                *iters_host);
-      return FLOW_NOT_CONVERGED;
-    }
-    if (state[kDone] == 1.0) {
-      *iters_host = static_cast<int>(state[kConvIt]);
-      *resid_host = sqrt(res2);
-      return FLOW_OK;
-    }
-    if (launched >= maxit) {
-      *iters_host = launched;
-      *resid_host = sqrt(res2);
-      set_error("BiCGStab did not converge in %d iterations: |r| = %.3e > %.3e",
-                launched, sqrt(res2), sqrt(state[kTarget2]));
-      return FLOW_NOT_CONVERGED;
-    }
-  }
+  FLOW_CHECK_HIP(hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i) host[i] = static_cast<volatile double*>(mailbox)[i];
+  return FLOW_OK;
 }
 
 }  // namespace flow
@@ -1360,162 +526,13 @@ extern "C" int flow_launch_count(unsigned long long* count_host) {
   return FLOW_OK;
 }
 
-// nonzeros a CSR-stream row block of an operator of `kind` may hold (the host
-// builds the row blocks: flow_amd/fem/space.py)
-extern "C" int flow_spmv_tile_nnz(int kind) {
-  return (kind == 2 || kind == 4) ? kTile2 - 2 : kTile - 2;
-}
-
-// the workgroup -> tile mapping of the CSR-stream kernels, for host-side tests
-extern "C" int flow_xcd_tile_host(int block, int nblocks) {
-  return xcd_tile(block, nblocks);
-}
-
-extern "C" int flow_profile_spmv_begin(int rows, int max_launches) {
-  SpmvProfile& pf = g_spmv_profile;
-  FLOW_REQUIRE(rows > 0 && max_launches > 0 && max_launches <= 100000,
-               "profile arguments");
-  FLOW_REQUIRE(pf.ev == nullptr, "a profile is already running");
-  pf.ev = new hipEvent_t[2 * static_cast<size_t>(max_launches)];
-  for (int i = 0; i < 2 * max_launches; ++i)
-    FLOW_CHECK_HIP(hipEventCreate(&pf.ev[i]));
-  pf.rows = rows;
-  pf.used = 0;
-  pf.cap = max_launches;
-  return FLOW_OK;
-}
-
-__global__ void profile_null_kernel() {}
-
-// keeps the chip busy for ~20 us (constant 100 MHz counter; bounded loop), so
-// that the launch behind it is dispatched while it runs -- as inside a solver
-__global__ void profile_busy_kernel() {
-  const unsigned long long t0 = wall_clock64();
-  for (int i = 0; i < 100000; ++i) {
-    if (wall_clock64() - t0 > 2000ull) break;
-    __builtin_amdgcn_s_sleep(8);
-  }
-}
-
-// What an event pair measures around NOTHING: the dispatch latency that every
-// bracketed launch above includes on top of the kernel's own execution time
-// (rocprofv3's kernel duration does not).  Median of 33 null launches, each
-// behind a kernel that is still running when it is enqueued, microseconds.
-extern "C" int flow_profile_event_overhead(double* overhead_us, void* stream) {
-  FLOW_REQUIRE(overhead_us != nullptr, "overhead result");
-  hipStream_t st = as_stream(stream);
-  constexpr int kN = 33;
-  hipEvent_t ev[2 * kN];
-  for (int i = 0; i < 2 * kN; ++i) FLOW_CHECK_HIP(hipEventCreate(&ev[i]));
-  for (int i = 0; i < kN; ++i) {
-    // (a running kernel in front, as in the solver: the stream is never idle
-    // and the bracketed launch is dispatched while its predecessor executes)
-    hipLaunchKernelGGL(profile_busy_kernel, dim3(256), dim3(64), 0, st);
-    FLOW_CHECK_HIP(hipEventRecord(ev[2 * i], st));
-    hipLaunchKernelGGL(profile_null_kernel, dim3(1), dim3(64), 0, st);
-    FLOW_CHECK_HIP(hipEventRecord(ev[2 * i + 1], st));
-  }
-  FLOW_CHECK_HIP(hipStreamSynchronize(st));
-  double t[kN];
-  for (int i = 0; i < kN; ++i) {
-    float ms = 0.0f;
-    FLOW_CHECK_HIP(hipEventElapsedTime(&ms, ev[2 * i], ev[2 * i + 1]));
-    t[i] = 1.0e3 * ms;
-  }
-  for (int i = 0; i < 2 * kN; ++i) (void)hipEventDestroy(ev[i]);
-  for (int i = 1; i < kN; ++i)          // insertion sort, median
-    for (int j = i; j > 0 && t[j] < t[j - 1]; --j) {
-      const double tmp = t[j];
-      t[j] = t[j - 1];
-      t[j - 1] = tmp;
-    }
-  *overhead_us = t[kN / 2];
-  return FLOW_OK;
-}
-
-extern "C" int flow_profile_spmv_end(double* total_us, int* launches) {
-  SpmvProfile& pf = g_spmv_profile;
-  FLOW_REQUIRE(total_us && launches, "profile results");
-  FLOW_REQUIRE(pf.ev != nullptr, "no profile is running");
-  double total = 0.0;
-  int rc = FLOW_OK;
-  for (int i = 0; i < pf.used && rc == FLOW_OK; ++i) {
-    float ms = 0.0f;
-    if (hipEventSynchronize(pf.ev[2 * i + 1]) != hipSuccess ||
-        hipEventElapsedTime(&ms, pf.ev[2 * i], pf.ev[2 * i + 1]) != hipSuccess) {
-      set_error("reading the SpMV profile events failed");
-      rc = FLOW_HIP_ERROR;
-    }
-    total += 1.0e3 * ms;
-  }
-  for (int i = 0; i < 2 * pf.cap; ++i) (void)hipEventDestroy(pf.ev[i]);
-  delete[] pf.ev;
-  *total_us = total;
-  *launches = pf.used;
-  pf = SpmvProfile();
-  return rc;
-}
-
-// ---- flow_peer: the blocks and their IPC handles ---------------------------
-extern "C" int flow_peer_alloc(int land_cap, void** base_out, char* handle_out) {
-  FLOW_REQUIRE(land_cap > 0 && base_out && handle_out, "flow_peer_alloc arguments");
-  static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-  const size_t bytes = sizeof(unsigned long long) * FLOW_PEER_FLAGS +
-                       2 * sizeof(double) * static_cast<size_t>(land_cap);
-  void* base = nullptr;
-  // fine-grained where the runtime grants it (flag words polled across GPUs);
-  // plain device memory otherwise -- all flag and landing traffic is system
-  // scope either way
-  if (hipExtMallocWithFlags(&base, bytes, hipDeviceMallocFinegrained) != hipSuccess) {
-    (void)hipGetLastError();
-    FLOW_CHECK_HIP(hipMalloc(&base, bytes));
-  }
-  FLOW_CHECK_HIP(hipMemset(base, 0, bytes));
-  FLOW_CHECK_HIP(hipDeviceSynchronize());
-  hipIpcMemHandle_t h;
-  hipError_t err = hipIpcGetMemHandle(&h, base);
-  if (err != hipSuccess) {
-    // (some runtimes refuse to export fine-grained memory: plain memory then)
-    (void)hipGetLastError();
-    (void)hipFree(base);
-    FLOW_CHECK_HIP(hipMalloc(&base, bytes));
-    FLOW_CHECK_HIP(hipMemset(base, 0, bytes));
-    FLOW_CHECK_HIP(hipDeviceSynchronize());
-    FLOW_CHECK_HIP(hipIpcGetMemHandle(&h, base));
-  }
-  memcpy(handle_out, &h, sizeof(h));
-  *base_out = base;
-  return FLOW_OK;
-}
-
-extern "C" int flow_peer_open(const char* handle, void** base_out) {
-  FLOW_REQUIRE(handle && base_out, "flow_peer_open arguments");
-  hipIpcMemHandle_t h;
-  memcpy(&h, handle, sizeof(h));
-  FLOW_CHECK_HIP(hipIpcOpenMemHandle(base_out, h, hipIpcMemLazyEnablePeerAccess));
-  return FLOW_OK;
-}
-
-extern "C" int flow_peer_close(void* mapped_base) {
-  FLOW_REQUIRE(mapped_base != nullptr, "flow_peer_close argument");
-  FLOW_CHECK_HIP(hipIpcCloseMemHandle(mapped_base));
-  return FLOW_OK;
-}
-
-extern "C" int flow_peer_free(void* base) {
-  FLOW_REQUIRE(base != nullptr, "flow_peer_free argument");
-  FLOW_CHECK_HIP(hipFree(base));
-  return FLOW_OK;
-}
-
-extern "C" int flow_peer_status(const flow_peer* peer,
-                                unsigned long long* error_host, void* stream) {
-  FLOW_REQUIRE(peer && peer->flags && error_host, "flow_peer_status arguments");
-  hipStream_t st = as_stream(stream);
-  FLOW_CHECK_HIP(hipMemcpyAsync(error_host, peer->flags + 4, sizeof(*error_host),
-                                hipMemcpyDeviceToHost, st));
-  FLOW_CHECK_HIP(hipStreamSynchronize(st));
-  return FLOW_OK;
+// n <= 64 doubles of device memory -> the host, in stream order (one
+// synchronisation through the calling thread's mailbox)
+extern "C" int flow_read_doubles(const double* dev, int n, double* host,
+                                 void* stream) {
+  FLOW_REQUIRE(dev && host && n >= 1 && n <= flow::kMailbox,
+               "read_doubles arguments (1..64 values)");
+  return flow::read_values(dev, n, host, flow::as_stream(stream));
 }
 
 extern "C" int flow_operator_apply(const flow_operator* A, const double* x,
@@ -1630,91 +647,6 @@ extern "C" int flow_gather_rows(int ncomp, const int* idx, int m,
   hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(static_cast<long long>(ncomp) * m)),
                      dim3(kBlock), 0, as_stream(stream), ncomp, m, idx, src,
                      src_stride, dst, dst_stride);
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// plain streaming kernels, 16 bytes per lane and load: what this chip's HBM
-// sustains for the simplest possible kernels (bench.py times them with HIP
-// events and quotes the roofline kernel against them as well as against the
-// 8 TB/s of the data sheet).  Variants were timed on the box
-// (tools/micro/copy_ceiling.hip): copy with non-temporal loads and stores, four
-// per lane in flight, 8192 workgroups: 5.17 TB/s (plain: 4.6-4.85); read-only,
-// eight loads in flight, 16384 workgroups: 5.85 TB/s.
-__global__ __launch_bounds__(kBlock) void stream_copy_kernel(
-    size_t n2, const double2* __restrict__ src, double2* __restrict__ dst) {
-  constexpr int U = 4;
-  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  for (; i + (U - 1) * stride < n2; i += U * stride) {
-    double2 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      v[u].x = __builtin_nontemporal_load(&src[i + u * stride].x);
-      v[u].y = __builtin_nontemporal_load(&src[i + u * stride].y);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      __builtin_nontemporal_store(v[u].x, &dst[i + u * stride].x);
-      __builtin_nontemporal_store(v[u].y, &dst[i + u * stride].y);
-    }
-  }
-  for (; i < n2; i += stride) dst[i] = src[i];
-}
-
-__global__ __launch_bounds__(kBlock) void stream_read_kernel(
-    size_t n2, const double2* __restrict__ src, double* __restrict__ sink) {
-  constexpr int U = 8;
-  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  double acc = 0.0;
-  for (; i + (U - 1) * stride < n2; i += U * stride) {
-    double2 v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = src[i + u * stride];
-#pragma unroll
-    for (int u = 0; u < U; ++u) acc += v[u].x + v[u].y;
-  }
-  for (; i < n2; i += stride) acc += src[i].x + src[i].y;
-  // (never true for the buffers bench.py passes; keeps the loads alive)
-  if (acc == 12345.678) sink[0] = acc;
-}
-
-extern "C" int flow_profile_stream_copy(size_t n, const double* src, double* dst,
-                                        void* stream) {
-  FLOW_REQUIRE(n >= 2 && n % 2 == 0 && src != nullptr, "stream copy arguments");
-  FLOW_REQUIRE(reinterpret_cast<uintptr_t>(src) % 16 == 0 &&
-                   reinterpret_cast<uintptr_t>(dst) % 16 == 0 && dst != nullptr,
-               "stream copy: 16-byte aligned buffers");
-  hipLaunchKernelGGL(stream_copy_kernel, dim3(8192), dim3(kBlock), 0,
-                     as_stream(stream), n / 2,
-                     reinterpret_cast<const double2*>(src),
-                     reinterpret_cast<double2*>(dst));
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-extern "C" int flow_profile_stream_read(size_t n, const double* src, double* sink,
-                                        void* stream) {
-  FLOW_REQUIRE(n >= 2 && n % 2 == 0 && src != nullptr && sink != nullptr,
-               "stream read arguments");
-  FLOW_REQUIRE(reinterpret_cast<uintptr_t>(src) % 16 == 0,
-               "stream read: 16-byte aligned buffer");
-  hipLaunchKernelGGL(stream_read_kernel, dim3(16384), dim3(kBlock), 0,
-                     as_stream(stream), n / 2,
-                     reinterpret_cast<const double2*>(src), sink);
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// an empty kernel whose GRID SIZE is the marker id: profiles/summarize.py finds
-// the timed window of bench.py in a rocprofv3 kernel trace by these launches
-__global__ void profile_marker_kernel() {}
-
-extern "C" int flow_profile_marker(int id, void* stream) {
-  FLOW_REQUIRE(id >= 1 && id <= 1024, "marker id");
-  hipLaunchKernelGGL(profile_marker_kernel, dim3(id), dim3(64), 0,
-                     as_stream(stream));
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
 }
@@ -1935,2116 +867,4 @@ extern "C" int flow_vmul(int n, double a, const double* x, const double* y,
                      as_stream(stream), n, a, x, y, out);
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
-}
-
-// ---------------------------------------------------------------------------
-// GMRES(m), right-preconditioned (Saad & Schultz 1986), classical Gram-Schmidt
-// with ONE reduction per Arnoldi step:
-//   w = A M^-1 V_j ; the dots w.V_k (k <= j), w.w and |V_j|^2 are summed
-//   together; h_{j+1,j} follows from Pythagoras, the new basis vector is
-//   formed (and scaled with that estimate) in one fused pass that also leaves
-//   the partial sums of its true norm -- summed with the next step's dots and
-//   put into H then.
-// The Hessenberg matrix, the least-squares problem and the stopping test live
-// ON THE DEVICE (gmres_step_kernel, one workgroup): the kernel that sums the
-// dots also extends H, solves min |beta e1 - H y|, writes the coefficients of
-// the next basis vector and of the solution update into device memory, and
-// sets the solver's sticky done flag -- the Arnoldi steps are enqueued without
-// the host in between (round 1 read every step's dots back: ~25 us of idle GPU
-// per step), as many as the caller expects the solve to need; everything
-// enqueued behind the accepted iterate returns at once.  (The sharded variant
-// further down keeps this algebra on the host: its sums come out of a
-// collective it has to wait for anyway.)
-// Basis vectors are handled eight at a time (compile-time unrolled).
-// ---------------------------------------------------------------------------
-constexpr int kGmresMax = FLOW_GMRES_MAX_RESTART;
-static_assert((kGmresMax + 2) * kRedBlocks == FLOW_GMRES_PARTIALS, "gmres work");
-static_assert(kGmresMax + 2 <= kMailbox, "mailbox size");
-struct Coef8 {
-  double c[8];
-};
-
-// block partials of w.V_k, k < NV (V_k = V + k stride) [and of w.w]
-template <int NV>
-__global__ __launch_bounds__(kBlock) void gmres_dots_kernel(
-    int n, const double* __restrict__ w, const double* __restrict__ V,
-    size_t stride, int with_ww, double* __restrict__ partial,
-    double* __restrict__ ww_partial, const double* __restrict__ stop = nullptr) {
-  if (stopped(stop)) return;
-  double acc[NV];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) acc[k] = 0.0;
-  double ww = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    const double wi = w[i];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) acc[k] += wi * V[k * stride + i];
-    ww += wi * wi;
-  }
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const double a = block_sum(acc[k]);
-    if (threadIdx.x == 0) partial[k * kRedBlocks + blockIdx.x] = a;
-  }
-  if (with_ww) {
-    ww = block_sum(ww);
-    if (threadIdx.x == 0) ww_partial[blockIdx.x] = ww;
-  }
-}
-
-// out = (first ? cw w : out) + sum_{k<NV} c_k V_k ; nn_partial != nullptr: the
-// block partials of |out|^2.  out may be w.
-template <int NV>
-__global__ __launch_bounds__(kBlock) void gmres_combine_kernel(
-    int n, Coef8 coef, double cw, int first, const double* w,
-    const double* __restrict__ V, size_t stride, double* out,
-    double* __restrict__ nn_partial) {
-  double nn = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    double acc = first ? (w ? cw * w[i] : 0.0) : out[i];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) acc += coef.c[k] * V[k * stride + i];
-    out[i] = acc;
-    nn += acc * acc;
-  }
-  if (nn_partial) {
-    nn = block_sum(nn);
-    if (threadIdx.x == 0) nn_partial[blockIdx.x] = nn;
-  }
-}
-
-// block b sums the partials of value b (< nd: w.V_b ; nd: w.w ; nd+1: |V_j|^2)
-// straight into the host-coherent mailbox
-__global__ __launch_bounds__(kBlock) void gmres_finish_kernel(
-    int nparts, int nd, const double* __restrict__ partial,
-    volatile double* __restrict__ mailbox) {
-  const int b = blockIdx.x;
-  const int v = b < nd ? b : kGmresMax + (b - nd);
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += kBlock)
-    s += load_scalar(partial + v * kRedBlocks + i);
-  s = block_sum(s);
-  if (threadIdx.x == 0) {
-    mailbox[b] = s;
-    __threadfence_system();
-  }
-}
-
-// gmres_combine_kernel with the coefficients in device memory: coef[k] (k < NV)
-// and, for the w term, *cw
-template <int NV>
-__global__ __launch_bounds__(kBlock) void gmres_combine_dev_kernel(
-    int n, const double* __restrict__ coef, const double* __restrict__ cw,
-    int first, const double* w, const double* __restrict__ V, size_t stride,
-    double* out, double* __restrict__ nn_partial,
-    const double* __restrict__ stop) {
-  if (stopped(stop)) return;
-  double c[NV];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) c[k] = load_scalar(coef + k);
-  const double c_w = (first && w) ? load_scalar(cw) : 0.0;
-  double nn = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    double acc = first ? (w ? c_w * w[i] : 0.0) : out[i];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) acc += c[k] * V[k * stride + i];
-    out[i] = acc;
-    nn += acc * acc;
-  }
-  if (nn_partial) {
-    nn = block_sum(nn);
-    if (threadIdx.x == 0) nn_partial[blockIdx.x] = nn;
-  }
-}
-
-// device-resident state of one GMRES cycle (doubles, behind the partials)
-constexpr int kGH = 0;                                   // H[col][row]
-constexpr int kGNrm = kGH + kGmresMax * (kGmresMax + 1);  // |V_k|
-constexpr int kGEta = kGNrm + kGmresMax + 1;              // h_{k+1,k} estimates
-constexpr int kGCoef = kGEta + kGmresMax;                 // next vector: c_k
-constexpr int kGCw = kGCoef + kGmresMax;                  //   and the w factor
-constexpr int kGYc = kGCw + 1;                            // update: y_k / |V_k|
-constexpr int kGRot = kGYc + kGmresMax;                   // Givens (cs, sn)[k]
-constexpr int kGRhs = kGRot + 2 * kGmresMax;              // rotated beta e1
-constexpr int kGJvp = kGRhs + kGmresMax + 1;                // momentum_jvp_params
-constexpr int kGState = kGJvp + 3;
-static_assert(kGState <= FLOW_GMRES_STATE, "gmres device state");
-
-// Arnoldi step j of a cycle, the part round 1 did on the host: sums of the
-// partials of w.V_k (k <= j), w.w and |V_j|^2 -> column j of H, the
-// least-squares problem, the stopping test.  One workgroup; the wavefronts sum
-// the value lists, thread 0 does the (tiny, serial) algebra -- O(j) per step:
-// H is kept in its rotated (triangular) form R; a step re-rotates column j-1
-// (its sub-diagonal has just been corrected with the true norm of V_j) and
-// column j with the rotations kept from before; the triangular solve for y
-// only runs behind the step that ends the cycle (`last`) or the solve.
-//   S[kConvIt] = columns of this cycle that are final, S[kRes2] = the residual
-//   estimate, S[kDone] = 1 converged / 2 not a number / 3 the cycle has to end
-//   without a verdict (see below)
-__global__ __launch_bounds__(kBlock) void gmres_step_kernel(
-    int nparts, int j, int last, double beta, double target,
-    const double* __restrict__ partial, double* __restrict__ G,
-    double* __restrict__ S) {
-  // nparts = 0: `partial` holds the nd + 1 [+ 1] values themselves, one after
-  // the other (the sharded solver: summed over the ranks by the collective)
-  constexpr int ld = kGmresMax + 1;
-  __shared__ double val[kGmresMax + 2];
-  // columns < j: rows <= col-1 rotated (R), column j-1 as H left it
-  __shared__ double Hs[kGmresMax * ld];
-  __shared__ double nrm[kGmresMax + 1], eta[kGmresMax];
-  __shared__ double g[kGmresMax + 1], cs[kGmresMax], sn[kGmresMax], y[kGmresMax];
-  if (stopped(S + kDone)) return;
-  // beta < 0: the cycle's |r0| and the target are on the device (left by
-  // gmres_begin_kernel: the single-GPU solver reads nothing back before the
-  // cycle's steps are enqueued)
-  if (beta < 0.0) {
-    beta = load_scalar(S + kBeta);
-    target = load_scalar(S + kTarget2);
-  }
-  const int nd = j + 1;
-  const int nval = nd + 1 + (j > 0 ? 1 : 0);
-  const int lane = threadIdx.x & 63;
-  // the value lists, a wavefront each (per-lane loads, four in flight)
-  // (everything an earlier launch wrote at these same addresses is read with
-  // load_scalar, common.h; the loads of a lane are independent: all in flight)
-  if (nparts == 0 && threadIdx.x < nval)
-    val[threadIdx.x] = load_scalar(partial + threadIdx.x);
-  for (int v = threadIdx.x >> 6; nparts > 0 && v < nval; v += kBlock / 64) {
-    const int list = v < nd ? v : kGmresMax + (v - nd);
-    const double* __restrict__ p = partial + list * kRedBlocks;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int i = lane;
-    for (; i + 192 < nparts; i += 256) {
-      const double a0 = load_scalar(p + i), a1 = load_scalar(p + i + 64);
-      const double a2 = load_scalar(p + i + 128), a3 = load_scalar(p + i + 192);
-      s0 += a0;
-      s1 += a1;
-      s2 += a2;
-      s3 += a3;
-    }
-    for (; i < nparts; i += 64) s0 += load_scalar(p + i);
-    double s = (s0 + s1) + (s2 + s3);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if (lane == 0) val[v] = s;
-  }
-  // the state earlier steps of the cycle left (per-lane loads as well)
-  for (int i = threadIdx.x; i < j * ld; i += kBlock)
-    Hs[i] = load_scalar(G + kGH + i);
-  if (threadIdx.x < j) {
-    nrm[threadIdx.x] = load_scalar(G + kGNrm + threadIdx.x);
-    eta[threadIdx.x] = load_scalar(G + kGEta + threadIdx.x);
-    cs[threadIdx.x] = load_scalar(G + kGRot + 2 * threadIdx.x);
-    sn[threadIdx.x] = load_scalar(G + kGRot + 2 * threadIdx.x + 1);
-    g[threadIdx.x] = load_scalar(G + kGRhs + threadIdx.x);
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  // G holds, for every finished column c: rows 0..c-1 of R (rotated) and, in
-  // rows c and c+1, the UNROTATED pair (h_cc after the earlier rotations, the
-  // sub-diagonal) -- the rotation c is formed from them when column c+1 comes
-  // (then the sub-diagonal is final) or at the end of this step
-  if (j == 0) {
-    nrm[0] = beta;
-    g[0] = beta;
-  }
-  if (j > 0) {
-    // the true norm of V_j (it was scaled with the Pythagoras estimate eta)
-    nrm[j] = sqrt(val[nd + 1]);
-    const int c = j - 1;
-    Hs[c * ld + j] = eta[c] * nrm[j];
-    // rotation c, now final
-    const double a = Hs[c * ld + c], bsub = Hs[c * ld + c + 1];
-    const double d = hypot(a, bsub);
-    cs[c] = d > 0.0 ? a / d : 1.0;
-    sn[c] = d > 0.0 ? bsub / d : 0.0;
-    Hs[c * ld + c] = d;
-    G[kGH + c * ld + c] = d;
-    G[kGRot + 2 * c] = cs[c];
-    G[kGRot + 2 * c + 1] = sn[c];
-    const double gc = g[c];           // (unrotated so far)
-    g[c + 1] = -sn[c] * gc;
-    g[c] = cs[c] * gc;
-    G[kGRhs + c] = g[c];
-  }
-  const double nj = nrm[j];
-  G[kGNrm + j] = nj;
-  const double ww = val[nd] / (nj * nj);
-  double sum = 0.0;
-  double* col = Hs + j * ld;
-  for (int k = 0; k <= j; ++k) {
-    const double h = val[k] / (nj * nrm[k]);
-    y[k] = h;                         // (H[j][k], for the coefficients below)
-    col[k] = h;
-    sum += h * h;
-  }
-  if (!(ww == ww) || !(nj > 0.0)) {
-    store_scalar(S + kConvIt, static_cast<double>(j));
-    store_scalar(S + kDone, 2.0);
-    return;
-  }
-  const double e2 = ww - sum;
-  // h_{j+1,j}^2 = |w|^2 - sum h^2 (Pythagoras: one pass over the basis instead
-  // of two) cancels when w lies in the span of the basis to more than ~6
-  // digits -- an invariant subspace, or simply a preconditioner that is nearly
-  // exact (tiny time steps: A M^-1 ~ I, the first w is parallel to V_0 to 8
-  // digits).  What is left of e2 is then rounding noise and so is the residual
-  // estimate built on it: the cycle ends here, WITHOUT a verdict -- the host
-  // applies the update, computes the true residual and either stops there or
-  // starts the next cycle from it.  (Round 1 took e2 <= 0 for convergence: a
-  // solve could return after one iteration with a true residual of 6e-9 |b|.)
-  const bool lucky = !(e2 > 1.0e-12 * ww);
-  const double et = e2 > 0.0 ? sqrt(e2) : 0.0;
-  G[kGEta + j] = et;
-  // the coefficients of V_{j+1} = (w / nrm_j - sum_k H[j][k] V_k / nrm_k) / eta_j
-  // (unused when the step ends the cycle)
-  if (!lucky) {
-    const double inv = 1.0 / et;
-    for (int k = 0; k <= j; ++k)
-      store_scalar(G + kGCoef + k, -y[k] * inv / nrm[k]);
-    store_scalar(G + kGCw, inv / nj);
-  }
-  // column j through the rotations 0 .. j-1
-  for (int i = 0; i < j; ++i) {
-    const double t = cs[i] * col[i] + sn[i] * col[i + 1];
-    col[i + 1] = -sn[i] * col[i] + cs[i] * col[i + 1];
-    col[i] = t;
-  }
-  col[j + 1] = et;
-  for (int r = 0; r <= j + 1; ++r) G[kGH + j * ld + r] = col[r];
-  G[kGRhs + j] = g[j];                // (before its own rotation)
-  // residual estimate with the Pythagoras sub-diagonal: |g_{j+1}| after
-  // rotation j
-  const double dj = hypot(col[j], et);
-  const double csj = dj > 0.0 ? col[j] / dj : 1.0;
-  const double snj = dj > 0.0 ? et / dj : 0.0;
-  const double resid = fabs(snj * g[j]);
-  store_scalar(S + kRes2, resid);
-  store_scalar(S + kConvIt, static_cast<double>(j + 1));
-  const bool done = resid <= target && !lucky;
-  if (done || lucky || last) {
-    // y from the triangular system R y = g over the j+1 columns
-    const int nc = j + 1;
-    col[j] = dj;
-    g[j] = csj * g[j];
-    for (int i = nc - 1; i >= 0; --i) {
-      double t = g[i];
-      for (int c = i + 1; c < nc; ++c) t -= Hs[c * ld + i] * y[c];
-      const double rii = Hs[i * ld + i];
-      y[i] = rii != 0.0 ? t / rii : 0.0;
-    }
-    // (read by the update kernel with load_scalar: wave-uniform there)
-    for (int k = 0; k < nc; ++k) store_scalar(G + kGYc + k, y[k] / nrm[k]);
-    if (done) store_scalar(S + kDone, 1.0);
-    if (lucky) store_scalar(S + kDone, 3.0);     // end of cycle, no verdict
-  }
-}
-
-// Start of a GMRES cycle, one workgroup: |r0|^2 (list 0 of `partial`) and, the
-// first time, |b|^2 (list 1; have_b2 = 0: b IS r0) -> S[kBeta] = |r0|,
-// S[kTarget2] = the target max(rtol |b|, atol) (NOT squared here), and the
-// verdict on the start itself: S[kDone] = 4 when r0 already passes (accept10:
-// within a factor 10 -- the verification behind a cycle that stopped on the
-// least-squares estimate), 2 when it is not a number.  With it the host
-// enqueues the cycle's Arnoldi steps without having read anything back.
-__global__ __launch_bounds__(kBlock) void gmres_begin_kernel(
-    int nparts, int have_b2, int first, int accept10, double rtol, double atol,
-    const double* __restrict__ partial, double* __restrict__ S) {
-  double r = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += kBlock) {
-    r += load_scalar(partial + i);
-    if (have_b2) b += load_scalar(partial + kRedBlocks + i);
-  }
-  r = block_sum(r);
-  b = block_sum(b);
-  if (threadIdx.x != 0) return;
-  double target;
-  if (first) {
-    const double b2 = have_b2 ? b : r;
-    target = fmax(rtol * sqrt(b2), atol);
-    store_scalar(S + kB2, b2);
-    store_scalar(S + kTarget2, target);
-    // a start vector that leaves a LARGER residual than zero would is dropped:
-    // S[kTmp] = 1 tells gmres_drop_start_kernel to put V_0 = b, x = 0
-    if (have_b2 && r > b2) {
-      store_scalar(S + kTmp, 1.0);
-      r = b2;
-    }
-  } else {
-    target = load_scalar(S + kTarget2);
-  }
-  const double beta = sqrt(r);
-  store_scalar(S + kBeta, beta);
-  store_scalar(S + kRes2, beta);
-  store_scalar(S + kConvIt, 0.0);
-  if (!(r == r))
-    store_scalar(S + kDone, 2.0);
-  else if (beta <= target || (accept10 && beta <= 10.0 * target))
-    store_scalar(S + kDone, 4.0);
-}
-
-// behind gmres_begin_kernel of a solve that was handed a start vector: when that
-// vector was worse than zero (S[kTmp] set), V_0 = b and x = 0
-__global__ void gmres_drop_start_kernel(int n, const double* __restrict__ S,
-                                        const double* __restrict__ b,
-                                        double* __restrict__ v0,
-                                        double* __restrict__ x) {
-  if (load_scalar(S + kTmp) == 0.0) return;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    v0[i] = b[i];
-    x[i] = 0.0;
-  }
-}
-
-#define FLOW_NV_SWITCH(nv, CALL) \
-  switch (nv) {                  \
-    case 1: CALL(1); break;      \
-    case 2: CALL(2); break;      \
-    case 3: CALL(3); break;      \
-    case 4: CALL(4); break;      \
-    case 5: CALL(5); break;      \
-    case 6: CALL(6); break;      \
-    case 7: CALL(7); break;      \
-    default: CALL(8); break;     \
-  }
-
-// out = [accumulate ? out : cw w] + sum_{k<nv} c[k] V_k (w == nullptr: no w
-// term); nn_partial as above
-static int gmres_combine(int N, int nv, const double* c, double cw,
-                         const double* w, const double* V, double* out,
-                         double* nn_partial, bool accumulate, hipStream_t st) {
-  const int g = grid_for(N, kBlock, kRedBlocks);
-  if (nv == 0) {   // only the w term (cannot happen in the Arnoldi loop)
-    FLOW_REQUIRE(w != nullptr, "gmres combine");
-    Coef8 none = {};
-    hipLaunchKernelGGL(gmres_combine_kernel<1>, dim3(g), dim3(kBlock), 0, st, N,
-                       none, cw, 1, w, V, static_cast<size_t>(N), out,
-                       nn_partial);
-  }
-  for (int k0 = 0; k0 < nv; k0 += 8) {
-    const int chunk = nv - k0 < 8 ? nv - k0 : 8;
-    Coef8 coef = {};
-    for (int k = 0; k < chunk; ++k) coef.c[k] = c[k0 + k];
-    double* nnp = (k0 + 8 >= nv) ? nn_partial : nullptr;
-#define FLOW_CALL(NV)                                                          \
-  hipLaunchKernelGGL(gmres_combine_kernel<NV>, dim3(g), dim3(kBlock), 0, st, N, \
-                     coef, cw, (k0 == 0 && !accumulate) ? 1 : 0, w,            \
-                     V + static_cast<size_t>(k0) * N, static_cast<size_t>(N),  \
-                     out, nnp)
-    FLOW_NV_SWITCH(chunk, FLOW_CALL)
-#undef FLOW_CALL
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// the same with the coefficients in device memory (coef[0, nv), *cw)
-static int gmres_combine_dev(int N, int nv, const double* coef, const double* cw,
-                             const double* w, const double* V, double* out,
-                             double* nn_partial, bool accumulate,
-                             const double* stop, hipStream_t st) {
-  const int g = grid_for(N, kBlock, kRedBlocks);
-  for (int k0 = 0; k0 < nv; k0 += 8) {
-    const int chunk = nv - k0 < 8 ? nv - k0 : 8;
-    double* nnp = (k0 + 8 >= nv) ? nn_partial : nullptr;
-#define FLOW_CALL(NV)                                                           \
-  hipLaunchKernelGGL(gmres_combine_dev_kernel<NV>, dim3(g), dim3(kBlock), 0, st, \
-                     N, coef + k0, cw, (k0 == 0 && !accumulate) ? 1 : 0, w,     \
-                     V + static_cast<size_t>(k0) * N, static_cast<size_t>(N),   \
-                     out, nnp, stop)
-    FLOW_NV_SWITCH(chunk, FLOW_CALL)
-#undef FLOW_CALL
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// least squares  min | beta e1 - H y |  for the (j+1) x j Hessenberg matrix H
-// (column-major H[col][row]); returns the residual norm
-static double gmres_least_squares(const double (*H)[kGmresMax + 1], int j,
-                                  double beta, double* y) {
-  double R[kGmresMax][kGmresMax + 1];
-  double g[kGmresMax + 1];
-  double cs[kGmresMax], sn[kGmresMax];
-  g[0] = beta;
-  for (int c = 0; c < j; ++c) {
-    for (int r = 0; r <= c + 1; ++r) R[c][r] = H[c][r];
-    for (int i = 0; i < c; ++i) {
-      const double t = cs[i] * R[c][i] + sn[i] * R[c][i + 1];
-      R[c][i + 1] = -sn[i] * R[c][i] + cs[i] * R[c][i + 1];
-      R[c][i] = t;
-    }
-    const double d = hypot(R[c][c], R[c][c + 1]);
-    cs[c] = d > 0.0 ? R[c][c] / d : 1.0;
-    sn[c] = d > 0.0 ? R[c][c + 1] / d : 0.0;
-    R[c][c] = d;
-    g[c + 1] = -sn[c] * g[c];
-    g[c] = cs[c] * g[c];
-  }
-  for (int i = j - 1; i >= 0; --i) {
-    double t = g[i];
-    for (int c = i + 1; c < j; ++c) t -= R[c][i] * y[c];
-    y[i] = R[i][i] != 0.0 ? t / R[i][i] : 0.0;
-  }
-  return fabs(g[j]);
-}
-
-// work: [reductions | V_0 .. V_m | Z_0 .. Z_{m-1} | sweep buffer | partials |
-// device state]; Z_j = M^-1 V_j is kept, so that the update x += sum_j y_j Z_j
-// needs no further preconditioner application (memory is not the scarce
-// resource).  expected: operator applications the caller expects the solve to
-// need (0: unknown) -- that many Arnoldi steps are enqueued before the host
-// looks at the state for the first time, then one at a time; the result does
-// not depend on it.
-static int gmres(const flow_operator* A, const double* dinv, const flow_ilu* ilu,
-                 const flow_pmg* pmg, const double* b, double* x, double rtol,
-                 double atol, int maxit, int m, int x_is_zero, int expected,
-                 int verify, double* work, int* iters_host, double* resid_host,
-                 hipStream_t st) {
-  const int N = op_size(A);
-  double* partial = work;
-  double* S = work + 3 * kRedBlocks;
-  double* V = work + FLOW_REDUCE_WORK;
-  double* Z = V + static_cast<size_t>(m + 1) * N;
-  double* iwork = Z + static_cast<size_t>(m) * N;
-  double* P = iwork + N;                    // (kGmresMax + 2) x kRedBlocks
-  double* Pww = P + kGmresMax * kRedBlocks;
-  double* Pnn = Pww + kRedBlocks;
-  double* G = P + FLOW_GMRES_PARTIALS;      // device state of the cycle
-  const double* stop = S + kDone;
-  const int gv = grid_for(N);
-  const int gd = grid_for(N, kBlock, kRedBlocks);
-  int np = 0, rc;
-
-  const double* jprm = nullptr;   // (set with the graphs below)
-  // Z_j = M^-1 V_j (without a preconditioner Z_j is V_j itself)
-  const bool precond = pmg || ilu || dinv;
-  const double* Zbase = precond ? Z : V;
-  auto precondition = [&](int j) -> int {
-    const double* in = V + static_cast<size_t>(j) * N;
-    double* out = Z + static_cast<size_t>(j) * N;
-    if (pmg) return pmg_apply(pmg, in, out, st, stop);
-    if (ilu) return ilu_apply(ilu, in, out, iwork, st, stop);
-    if (dinv)
-      hipLaunchKernelGGL(vmul_kernel, dim3(gv), dim3(kBlock), 0, st, N, 1.0, dinv,
-                         in, out, stop);
-    return FLOW_OK;
-  };
-  // Arnoldi step j of the cycle, enqueued without a read-back
-  auto arnoldi = [&](int j, double beta, double target, bool last) -> int {
-    int r;
-    double* w = V + static_cast<size_t>(j + 1) * N;
-    if ((r = precondition(j))) return r;
-    if ((r = apply(A, Zbase + static_cast<size_t>(j) * N, w, st, nullptr, stop, 0,
-                   0, jprm)))
-      return r;
-    for (int k0 = 0; k0 <= j; k0 += 8) {
-      const int chunk = j + 1 - k0 < 8 ? j + 1 - k0 : 8;
-#define FLOW_CALL(NV)                                                         \
-  hipLaunchKernelGGL(gmres_dots_kernel<NV>, dim3(gd), dim3(kBlock), 0, st, N,  \
-                     w, V + static_cast<size_t>(k0) * N,                      \
-                     static_cast<size_t>(N), k0 == 0 ? 1 : 0,                 \
-                     P + k0 * kRedBlocks, Pww, stop)
-      FLOW_NV_SWITCH(chunk, FLOW_CALL)
-#undef FLOW_CALL
-    }
-    hipLaunchKernelGGL(gmres_step_kernel, dim3(1), dim3(kBlock), 0, st, gd, j,
-                       last ? 1 : 0, beta, target, P, G, S);
-    FLOW_CHECK_LAUNCH();
-    // the next basis vector, in place on w (skipped by the flag when the step
-    // kernel has just accepted the iterate; not needed behind the last column)
-    if (!last &&
-        (r = gmres_combine_dev(N, j + 1, G + kGCoef, G + kGCw, w, V, w, Pnn, false,
-                               stop, st)))
-      return r;
-    return FLOW_OK;
-  };
-
-  // Arnoldi step j as a HIP graph where the launch rate bounds it
-  // (graph_replay.hip): one graph per column and `last` flag; the step size
-  // of a matrix-free Jacobian travels through device memory (G + kGJvp), so
-  // the graphs survive the step-size controller
-  const bool replay = replay_wanted(N, kReplayGmres);
-  KeyHash base;
-  if (replay) {
-    base.pod(0x676dull);      // "gm"
-    key_operator(base, A, true);
-    base.pod(dinv).obj(ilu).obj(ilu ? ilu->plan : nullptr).obj(pmg);
-    base.pod(work).pod(N).pod(m);
-    if (A->kind == 3) {
-      jprm = G + kGJvp;
-      if ((rc = momentum_jvp_params(
-               static_cast<const flow_momentum_jvp*>(A->matfree), G + kGJvp, st)))
-        return rc;
-    }
-  }
-  auto arnoldi_replayed = [&](int j, bool last) -> int {
-    if (!replay) return arnoldi(j, -1.0, 0.0, last);
-    KeyHash key = base;
-    key.pod(j).pod(last);
-    hipGraphExec_t graph = nullptr;
-    int nodes = 0, r;
-    if ((r = replay_prepare(key.h, kReplayGmres, st,
-                            [&]() { return arnoldi(j, -1.0, 0.0, last); }, &graph,
-                            &nodes)))
-      return r;
-    return graph ? replay_launch(graph, nodes, st) : arnoldi(j, -1.0, 0.0, last);
-  };
-
-  if ((rc = fill(kNumSlots, 0.0, S, st))) return rc;
-  double resid = 0.0;
-  int it = 0;
-  bool first = true;
-  bool claimed = false;     // the last cycle stopped on the residual estimate
-  double state[kNumSlots];
-  while (true) {
-    // r0 = b - A x -> V_0; |r0|^2 (the first time also |b|^2) in block
-    // partials; beta = |r0|, the target and the verdict on the start itself
-    // are left ON THE DEVICE by gmres_begin_kernel: nothing is read back
-    // before the cycle's Arnoldi steps are enqueued
-    const bool b_is_r0 = x_is_zero && it == 0;
-    if (b_is_r0) {
-      hipLaunchKernelGGL(axpby_kernel, dim3(gv), dim3(kBlock), 0, st, N, 1.0, b,
-                         0.0, V);
-    } else {
-      if ((rc = apply(A, x, iwork, st))) return rc;
-      hipLaunchKernelGGL(residual_kernel, dim3(gv), dim3(kBlock), 0, st, N, b,
-                         iwork,
-                         static_cast<const double*>(nullptr), V,
-                         static_cast<double*>(nullptr));
-    }
-    const int have_b2 = first && !b_is_r0;
-    if ((rc = dots(N, have_b2 ? 2 : 1, V, V, b, b, V, V, partial, &np, st)))
-      return rc;
-    // behind a cycle that stopped on the least-squares ESTIMATE this is the
-    // verification with the true residual b - A x (one operator application):
-    // the one-pass Gram-Schmidt and a reduced-precision preconditioner can
-    // leave the estimate below the target while the true residual stagnates
-    // (seen in principle at rtol 1e-13, flow/heat.py's solves); within a
-    // factor 10 of the target the iterate is accepted and the TRUE norm
-    // reported, beyond it the solve goes on from here
-    hipLaunchKernelGGL(gmres_begin_kernel, dim3(1), dim3(kBlock), 0, st, np,
-                       have_b2, first ? 1 : 0, claimed ? 1 : 0, rtol, atol,
-                       partial, S);
-    if (have_b2)     // (a start vector was handed in: keep it only if it helps)
-      hipLaunchKernelGGL(gmres_drop_start_kernel, dim3(gv), dim3(kBlock), 0, st,
-                         N, S, b, V, x);
-    FLOW_CHECK_LAUNCH();
-    first = false;
-    claimed = false;
-    if (it >= maxit) {
-      if ((rc = read_state(S, state, st))) return rc;
-      resid = state[kBeta];
-      if (state[kDone] == 4.0) break;
-      *iters_host = it;
-      *resid_host = resid;
-      if (state[kDone] == 2.0) {
-        set_error("GMRES broke down (NaN residual) at iteration %d", it);
-      } else {
-        set_error("GMRES did not converge in %d iterations: |r| = %.3e > %.3e",
-                  it, resid, state[kTarget2]);
-      }
-      return FLOW_NOT_CONVERGED;
-    }
-
-    // one cycle: up to m columns; `cols` of them are known to be final
-    const int it0 = it;
-    int enq = 0, cols = 0;
-    bool converged = false, start_passes = false;
-    while (true) {
-      const int room = (m < maxit - it0 ? m : maxit - it0) - enq;
-      if (room <= 0) break;
-      int plan = expected - (it0 + enq);
-      if (plan < 1) plan = 1;
-      if (plan > room) plan = room;
-      for (int k = 0; k < plan; ++k, ++enq) {
-        const bool last = enq + 1 >= m || it0 + enq + 1 >= maxit;
-        if ((rc = arnoldi_replayed(enq, last))) return rc;
-      }
-      if ((rc = read_state(S, state, st))) return rc;
-      cols = static_cast<int>(state[kConvIt]);
-      if (state[kDone] == 2.0) {
-        *iters_host = it0 + cols;
-        *resid_host = state[kRes2];
-        set_error("GMRES broke down (NaN) at iteration %d", it0 + cols);
-        return FLOW_NOT_CONVERGED;
-      }
-      resid = state[kRes2];
-      if (state[kDone] == 4.0) {      // r0 itself passed: nothing was done
-        start_passes = true;
-        break;
-      }
-      if (state[kDone] != 0.0) {
-        converged = state[kDone] == 1.0;   // 3: verify with the true residual
-        break;
-      }
-    }
-    if (start_passes) break;
-    // (a cycle that ends without a final column counts as one iteration: the
-    // loop makes progress towards maxit whatever the device reports)
-    it = it0 + (cols > 0 ? cols : 1);
-    // x += sum_k y_k Z_k / nrm_k (coefficients left by the last step kernel
-    // that ran); the flag is taken down first: it has done its work
-    if ((rc = fill(1, 0.0, S + kDone, st))) return rc;
-    if (cols > 0 &&
-        (rc = gmres_combine_dev(N, cols, G + kGYc, nullptr, nullptr, Zbase, x,
-                                nullptr, true, nullptr, st)))
-      return rc;
-    x_is_zero = 0;
-    if (converged && !verify) break;
-    claimed = converged;
-    // restart from the true residual: verify a claimed convergence there, go
-    // on otherwise (or report non-convergence)
-  }
-  *iters_host = it;
-  *resid_host = resid;
-  return FLOW_OK;
-}
-
-static int check_solver_args(const flow_operator* A, const double* b,
-                             const double* x, double rtol, double atol,
-                             int maxit, int check_every, int first_check,
-                             const double* work, size_t work_len, size_t nvec,
-                             const int* iters_host, const double* resid_host) {
-  int rc = check_operator(A);
-  if (rc) return rc;
-  FLOW_REQUIRE(b && x && work && iters_host && resid_host, "solver pointers");
-  FLOW_REQUIRE(rtol >= 0.0 && atol >= 0.0 && maxit >= 0 && check_every > 0 &&
-                   first_check >= 0,
-               "solver tolerances");
-  FLOW_REQUIRE(work_len >= FLOW_REDUCE_WORK + nvec * (size_t)op_size(A),
-               "solver workspace too small");
-  return FLOW_OK;
-}
-
-extern "C" int flow_cg_solve(const flow_operator* A, const double* dinv,
-                             const flow_coarse* coarse, const flow_mg* mg,
-                             const double* b,
-                             double* x, double rtol, double atol, int maxit,
-                             int check_every, int first_check, double* work,
-                             size_t work_len, int* iters_host,
-                             double* resid_host, void* stream) {
-  int rc = check_solver_args(A, b, x, rtol, atol, maxit, check_every,
-                             first_check, work, work_len, 5, iters_host,
-                             resid_host);
-  if (rc) return rc;
-  FLOW_REQUIRE(A->kind != 3, "CG: assembled (symmetric) operators only");
-  if (coarse) {
-    FLOW_REQUIRE(dinv != nullptr, "two-level preconditioner needs dinv");
-    FLOW_REQUIRE(A->kind == 0, "two-level preconditioner: scalar operators");
-    if ((rc = check_coarse(coarse, A->n))) return rc;
-  }
-  if (mg) {
-    FLOW_REQUIRE(coarse == nullptr, "multigrid and two-level are exclusive");
-    FLOW_REQUIRE(dinv != nullptr && A->kind == 0,
-                 "multigrid preconditioner: scalar operators with dinv");
-    if ((rc = check_mg(mg, A->n))) return rc;
-    FLOW_REQUIRE(mg->nlevels >= 2, "multigrid: at least two levels");
-  }
-  FLOW_REQUIRE(work_len >= cg_work_len(A, coarse, mg),
-               "solver workspace too small (FLOW_REDUCE_WORK + 5 N + SpMV "
-               "workgroups + 2 [+ 2 lda] [+ 2 mg->Ps[0].nblocks])");
-  FLOW_REQUIRE(reinterpret_cast<uintptr_t>(work) % 16 == 0,
-               "solver workspace must be 16-byte aligned");
-  return cg(A, dinv, coarse, mg, b, x, rtol, atol, maxit, check_every,
-            first_check, work, iters_host, resid_host, as_stream(stream));
-}
-
-// The same solve from a GUARDED start vector: a start that leaves a larger
-// preconditioned residual than x = 0 would (|B(b - A x)| > |B b|, decided on
-// the device from the numbers the first iteration forms anyway) is dropped
-// for `x_fallback` (guarded as well; NULL: none), and that for zero -- the
-// reference's start (a fresh Function, pressure_correction.py:313).
-extern "C" int flow_cg_solve_guarded(
-    const flow_operator* A, const double* dinv, const flow_coarse* coarse,
-    const flow_mg* mg, const double* b, double* x, const double* x_fallback,
-    double rtol, double atol, int maxit, int check_every, int first_check,
-    double* work, size_t work_len, int* iters_host, double* resid_host,
-    int* starts_dropped_host, void* stream) {
-  FLOW_REQUIRE(starts_dropped_host != nullptr, "starts_dropped_host is NULL");
-  *starts_dropped_host = 0;
-  // (argument checks: those of the unguarded solve, which does no work before
-  // they have passed)
-  int rc = check_solver_args(A, b, x, rtol, atol, maxit, check_every,
-                             first_check, work, work_len, 5, iters_host,
-                             resid_host);
-  if (rc) return rc;
-  FLOW_REQUIRE(A->kind != 3, "CG: assembled (symmetric) operators only");
-  if (coarse) {
-    FLOW_REQUIRE(dinv != nullptr, "two-level preconditioner needs dinv");
-    FLOW_REQUIRE(A->kind == 0, "two-level preconditioner: scalar operators");
-    if ((rc = check_coarse(coarse, A->n))) return rc;
-  }
-  if (mg) {
-    FLOW_REQUIRE(coarse == nullptr, "multigrid and two-level are exclusive");
-    FLOW_REQUIRE(dinv != nullptr && A->kind == 0,
-                 "multigrid preconditioner: scalar operators with dinv");
-    if ((rc = check_mg(mg, A->n))) return rc;
-    FLOW_REQUIRE(mg->nlevels >= 2, "multigrid: at least two levels");
-  }
-  FLOW_REQUIRE(work_len >= cg_work_len(A, coarse, mg),
-               "solver workspace too small");
-  FLOW_REQUIRE(reinterpret_cast<uintptr_t>(work) % 16 == 0,
-               "solver workspace must be 16-byte aligned");
-  FLOW_REQUIRE(x_fallback != x, "the fallback start must not alias x");
-  hipStream_t st = as_stream(stream);
-  const int N = op_size(A);
-  bool rejected = false;
-  rc = cg(A, dinv, coarse, mg, b, x, rtol, atol, maxit, check_every,
-          first_check, work, iters_host, resid_host, st, &rejected);
-  if (rc || !rejected) return rc;
-  *starts_dropped_host = 1;
-  if (x_fallback) {
-    hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(N)), dim3(kBlock), 0, st, N,
-                       1.0, x_fallback, 0.0, x);
-    FLOW_CHECK_LAUNCH();
-    rc = cg(A, dinv, coarse, mg, b, x, rtol, atol, maxit, check_every, 0, work,
-            iters_host, resid_host, st, &rejected);
-    if (rc || !rejected) return rc;
-    *starts_dropped_host = 2;
-  }
-  if ((rc = fill(N, 0.0, x, st))) return rc;
-  return cg(A, dinv, coarse, mg, b, x, rtol, atol, maxit, check_every, 0, work,
-            iters_host, resid_host, st);
-}
-
-// z = V-cycle(r): one application of the multigrid preconditioner (tests, and
-// callers that drive their own Krylov loop)
-extern "C" int flow_mg_apply(const flow_mg* mg, int n, const double* r,
-                             double* z, void* stream) {
-  FLOW_REQUIRE(mg && r && z && r != z && n > 0, "mg apply");
-  int rc = check_mg(mg, n);
-  if (rc) return rc;
-  return vcycle(mg, r, z, as_stream(stream));
-}
-
-// z = D^-1 r + P Ac^-1 P^T r: one application of the two-level preconditioner
-// (callers that drive their own Krylov loop: the Stokes MINRES)
-extern "C" int flow_two_level_apply(const flow_coarse* coarse,
-                                    const double* dinv, const double* r,
-                                    double* z, double* work, void* stream) {
-  FLOW_REQUIRE(coarse && dinv && r && z && work && r != z, "two-level apply");
-  int rc = check_coarse(coarse, coarse->n);
-  if (rc) return rc;
-  FLOW_REQUIRE(reinterpret_cast<uintptr_t>(work) % 16 == 0,
-               "two-level workspace must be 16-byte aligned");
-  return two_level(coarse, dinv, r, z, work, work + coarse->lda,
-                   as_stream(stream));
-}
-
-extern "C" int flow_bicgstab_solve(const flow_operator* A, const double* dinv,
-                                   const flow_ilu* ilu, const double* b,
-                                   double* x, double rtol, double atol,
-                                   int maxit, int check_every,
-                                   int first_check, double* work,
-                                   size_t work_len, int* iters_host,
-                                   double* resid_host, void* stream) {
-  int rc = check_solver_args(A, b, x, rtol, atol, maxit, check_every,
-                             first_check, work, work_len, 7, iters_host,
-                             resid_host);
-  if (rc) return rc;
-  if (ilu) {
-    if ((rc = ilu_check(ilu, op_size(A)))) return rc;
-    FLOW_REQUIRE(work_len >= FLOW_REDUCE_WORK + 8 * (size_t)op_size(A),
-                 "solver workspace too small for the ILU sweep buffer");
-  }
-  return bicgstab(A, dinv, ilu, b, x, rtol, atol, maxit, check_every,
-                  first_check, work, iters_host, resid_host, as_stream(stream));
-}
-
-extern "C" int flow_gmres_solve(const flow_operator* A, const double* dinv,
-                                const flow_ilu* ilu, const flow_pmg* pmg,
-                                const double* b, double* x,
-                                double rtol, double atol, int maxit, int restart,
-                                int x_is_zero, int expected_its, int verify,
-                                double* work, size_t work_len, int* iters_host,
-                                double* resid_host, void* stream) {
-  int rc = check_solver_args(A, b, x, rtol, atol, maxit, 1, 0, work, work_len, 0,
-                             iters_host, resid_host);
-  if (rc) return rc;
-  FLOW_REQUIRE(restart >= 1 && restart <= FLOW_GMRES_MAX_RESTART,
-               "GMRES restart length");
-  FLOW_REQUIRE(expected_its >= 0, "expected iterations");
-  FLOW_REQUIRE(work_len >= FLOW_REDUCE_WORK +
-                               (2 * static_cast<size_t>(restart) + 2) *
-                                   op_size(A) +
-                               FLOW_GMRES_PARTIALS + FLOW_GMRES_STATE,
-               "solver workspace too small (FLOW_REDUCE_WORK + (2 restart + 2) N "
-               "+ FLOW_GMRES_PARTIALS + FLOW_GMRES_STATE)");
-  FLOW_REQUIRE(!(ilu && pmg), "one preconditioner: ilu or pmg");
-  if (ilu && (rc = ilu_check(ilu, op_size(A)))) return rc;
-  if (pmg && (rc = pmg_check(pmg, op_size(A)))) return rc;
-  return gmres(A, dinv, ilu, pmg, b, x, rtol, atol, maxit, restart, x_is_zero,
-               expected_its, verify, work, iters_host, resid_host,
-               as_stream(stream));
-}
-
-
-// ===========================================================================
-// K15: domain decomposition over the GPUs of one node (include/flow_hip.h).
-// One communication primitive -- comm->allreduce: sum of the head of comm->buf
-// over the ranks -- carries the dot products, the partial coarse residuals AND
-// the halos (own slots filled, all others zero: the sum is the concatenation).
-// ===========================================================================
-namespace flow {
-
-int check_comm(const flow_comm* c, long long need) {
-  FLOW_REQUIRE(c != nullptr && c->allreduce != nullptr && c->buf != nullptr,
-               "communicator");
-  FLOW_REQUIRE(c->world >= 1 && c->world <= kNumSlots && c->rank >= 0 &&
-                   c->rank < c->world,
-               "communicator rank / world (at most 16 ranks)");
-  FLOW_REQUIRE(c->capacity >= need, "exchange buffer too small");
-  FLOW_REQUIRE(reinterpret_cast<uintptr_t>(c->buf) % 16 == 0,
-               "exchange buffer must be 16-byte aligned");
-  return FLOW_OK;
-}
-
-int check_rows(const flow_rows* R) {
-  FLOW_REQUIRE(R != nullptr, "row ranges are NULL");
-  FLOW_REQUIRE(0 <= R->e0 && R->e0 <= R->r0 && R->r0 < R->r1 && R->r1 <= R->e1 &&
-                   R->e1 <= R->n,
-               "row ranges");
-  FLOW_REQUIRE(R->nhalo >= 0, "halo size");
-  for (int i = 0; i < 2; ++i) {
-    FLOW_REQUIRE(R->send_len[i] >= 0 && R->recv_len[i] >= 0, "halo lengths");
-    FLOW_REQUIRE(R->send_len[i] == 0 ||
-                     (R->send_row[i] >= R->r0 &&
-                      R->send_row[i] + R->send_len[i] <= R->r1 &&
-                      R->send_slot[i] >= 0 &&
-                      R->send_slot[i] + R->send_len[i] <= R->nhalo),
-                 "halo send range");
-    FLOW_REQUIRE(R->recv_len[i] == 0 ||
-                     (R->recv_row[i] >= R->e0 &&
-                      R->recv_row[i] + R->recv_len[i] <= R->e1 &&
-                      (R->recv_row[i] + R->recv_len[i] <= R->r0 ||
-                       R->recv_row[i] >= R->r1) &&
-                      R->recv_slot[i] >= 0 &&
-                      R->recv_slot[i] + R->recv_len[i] <= R->nhalo),
-                 "halo receive range");
-  }
-  return FLOW_OK;
-}
-
-int exchange(const flow_comm* c, int count) {
-  const int rc = c->allreduce(c->user, count);
-  if (rc != 0) {
-    set_error("the all-reduce callback failed (code %d, %d doubles)", rc, count);
-    return FLOW_HIP_ERROR;
-  }
-  return FLOW_OK;
-}
-
-// ---- halos from neighbour to neighbour (flow_peer) --------------------------
-// Every rank owns a LANDING area its two neighbours have mapped (hipIpc): two
-// buffers of land_cap doubles (exchange seq uses buffer seq & 1) and a block of
-// 64-bit flags.  One exchange = one push and one pull launch around whatever is
-// really summed:
-//   push  a workgroup per side: wait until that neighbour has pulled exchange
-//         seq - 2 (the landing buffer of this parity is free again: its
-//         `consumed` word in MY block), copy my send slots of the packed
-//         buffer into ITS landing buffer -- same slot numbering on all ranks --,
-//         fence, then write seq into its `arrived` word;
-//   pull  a workgroup per side: wait for my `arrived` word of that side, copy
-//         the landing buffer's receive slots into my packed buffer (where the
-//         unpack kernels look, as after an all-reduce), then write seq into the
-//         neighbour's `consumed` word.
-// Waits are bounded (spin_limit polls with a sleep in between): a neighbour
-// that never arrives sets the error word of this rank's block and the kernel
-// goes on -- nothing can hang the device; the host reads the word
-// (flow_peer_status) behind its next read-back.  All flag traffic is system
-// scope (past L2: the words live in another process, on another GPU).
-constexpr int kPeerBlock = 256;
-enum PeerFlag { kArrived = 0, kConsumed = 2, kPeerError = 4, kPeerFlags = 16 };
-
-__device__ __forceinline__ unsigned long long peer_load(const unsigned long long* p) {
-  return __hip_atomic_load(const_cast<unsigned long long*>(p), __ATOMIC_ACQUIRE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void peer_store(unsigned long long* p,
-                                           unsigned long long v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-// thread 0 waits for *flag >= want; false on time-out (error word set)
-__device__ __forceinline__ bool peer_wait(const unsigned long long* flag,
-                                          unsigned long long want, int limit,
-                                          unsigned long long* err,
-                                          unsigned long long code) {
-  for (int it = 0; it < limit; ++it) {
-    if (peer_load(flag) >= want) return true;
-    __builtin_amdgcn_s_sleep(32);
-  }
-  peer_store(err, code);
-  return false;
-}
-
-// free0 / free1: the exchange in which this rank LAST pushed into the same
-// landing buffer of its left / right neighbour (0: never) -- that one must
-// have been pulled before the buffer is written again
-__global__ __launch_bounds__(kPeerBlock) void peer_push_kernel(
-    flow_rows R, int ncomp, flow_peer P, unsigned long long seq,
-    unsigned long long free0, unsigned long long free1,
-    const double* __restrict__ packed) {
-  const int sd = blockIdx.x;
-  if (R.send_len[sd] <= 0 || P.nb_land[sd] == nullptr) return;
-  const unsigned long long need = sd == 0 ? free0 : free1;
-  if (threadIdx.x == 0 && need > 0)
-    peer_wait(P.flags + kConsumed + sd, need, P.spin_limit, P.flags + kPeerError,
-              (seq << 8) | (1 + sd));
-  __syncthreads();
-  double* land = P.nb_land[sd] + static_cast<size_t>(seq & 1) * P.land_cap;
-  const int len = R.send_len[sd];
-  for (int t = threadIdx.x; t < ncomp * len; t += kPeerBlock) {
-    const int a = t / len, j = t - a * len;
-    const size_t k = static_cast<size_t>(a) * R.nhalo + R.send_slot[sd] + j;
-    __hip_atomic_store(land + k, packed[k], __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  __threadfence_system();
-  __syncthreads();
-  // I am this neighbour's neighbour on its OTHER side
-  if (threadIdx.x == 0) peer_store(P.nb_flags[sd] + kArrived + (1 - sd), seq);
-}
-
-__global__ __launch_bounds__(kPeerBlock) void peer_pull_kernel(
-    flow_rows R, int ncomp, flow_peer P, unsigned long long seq,
-    double* __restrict__ packed) {
-  const int sd = blockIdx.x;
-  if (R.recv_len[sd] <= 0 || P.nb_flags[sd] == nullptr) return;
-  if (threadIdx.x == 0)
-    peer_wait(P.flags + kArrived + sd, seq, P.spin_limit, P.flags + kPeerError,
-              (seq << 8) | (3 + sd));
-  __syncthreads();
-  const double* land = P.land + static_cast<size_t>(seq & 1) * P.land_cap;
-  const int len = R.recv_len[sd];
-  for (int t = threadIdx.x; t < ncomp * len; t += kPeerBlock) {
-    const int a = t / len, j = t - a * len;
-    const size_t k = static_cast<size_t>(a) * R.nhalo + R.recv_slot[sd] + j;
-    packed[k] = __hip_atomic_load(const_cast<double*>(land + k), __ATOMIC_RELAXED,
-                                  __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) peer_store(P.nb_flags[sd] + kConsumed + (1 - sd), seq);
-}
-
-// One exchange of a packed buffer [sums (sum_count doubles) | ... | halo slots
-// at hoff]: the sums through the all-reduce, the halo either with them (the
-// whole buffer is summed: every rank wrote zeros into the others' slots) or,
-// with a flow_peer, from neighbour to neighbour -- then only the first
-// sum_count doubles are a collective, and none at all for a pure halo.
-int exchange_halo(const flow_comm* C, const flow_rows* R, int ncomp, int sum_count,
-                  int hoff, hipStream_t st) {
-  const int nh = ncomp * R->nhalo;
-  const flow_peer* P = C->peer;
-  // (a halo larger than the landing buffers -- the slot numbering spans ALL
-  // ranks' slots -- travels in the all-reduce like without a flow_peer: nh is
-  // the same on every rank, so is this decision)
-  if (P == nullptr || C->world == 1 || nh == 0 || nh > P->land_cap)
-    return (hoff + nh > 0) ? exchange(C, hoff + nh) : FLOW_OK;
-  FLOW_REQUIRE(P->flags && P->land && P->seq_host, "flow_peer pointers");
-  // seq_host[0]: the exchange counter; seq_host[1 + 2 sd + parity]: my last
-  // push into that landing buffer of neighbour sd (what it must have pulled
-  // before this one may overwrite it -- not simply "two exchanges ago": an
-  // exchange of a space that sends nothing to a side skips that side)
-  unsigned long long* H = P->seq_host;
-  const unsigned long long seq = ++H[0];
-  const int par = static_cast<int>(seq & 1);
-  const unsigned long long free0 = H[1 + par], free1 = H[3 + par];
-  hipLaunchKernelGGL(peer_push_kernel, dim3(2), dim3(kPeerBlock), 0, st, *R, ncomp,
-                     *P, seq, free0, free1, C->buf + hoff);
-  for (int sd = 0; sd < 2; ++sd)
-    if (R->send_len[sd] > 0 && P->nb_land[sd] != nullptr) H[1 + 2 * sd + par] = seq;
-  FLOW_CHECK_LAUNCH();
-  if (sum_count > 0) {
-    int rc = exchange(C, sum_count);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(peer_pull_kernel, dim3(2), dim3(kPeerBlock), 0, st, *R, ncomp,
-                     *P, seq, C->buf + hoff);
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// halo[a*nhalo + k] <- the own boundary entries of x (global row index,
-// component stride `stride`), zero in everybody else's slots
-__global__ void shard_pack_kernel(flow_rows R, int ncomp,
-                                  const double* __restrict__ x, int stride,
-                                  double* __restrict__ halo) {
-  const int total = ncomp * R.nhalo;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total;
-       t += gridDim.x * blockDim.x) {
-    const int a = t / R.nhalo, k = t - a * R.nhalo;
-    const double* xa = x + static_cast<size_t>(a) * stride;
-    double v = 0.0;
-#pragma unroll
-    for (int sd = 0; sd < 2; ++sd)
-      if (k >= R.send_slot[sd] && k < R.send_slot[sd] + R.send_len[sd])
-        v = xa[R.send_row[sd] + (k - R.send_slot[sd])];
-    halo[t] = v;
-  }
-}
-
-// ghost rows of x <- the neighbours' slots of the summed buffer
-__global__ void shard_unpack_kernel(flow_rows R, int ncomp,
-                                    const double* __restrict__ halo,
-                                    double* __restrict__ x, int stride) {
-  const int per = R.recv_len[0] + R.recv_len[1];
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ncomp * per;
-       t += gridDim.x * blockDim.x) {
-    const int a = t / per, k = t - a * per;
-    const int sd = k < R.recv_len[0] ? 0 : 1;
-    const int j = sd == 0 ? k : k - R.recv_len[0];
-    x[static_cast<size_t>(a) * stride + R.recv_row[sd] + j] =
-        load_scalar(halo + static_cast<size_t>(a) * R.nhalo + R.recv_slot[sd] + j);
-  }
-}
-
-// x: indexed by global row (x[a*stride + row]); the halo travels at buf + off
-static int halo(const flow_comm* C, const flow_rows* R, int ncomp, double* x,
-                int stride, hipStream_t st) {
-  const int count = ncomp * R->nhalo;
-  if (count == 0) return FLOW_OK;      // a single rank
-  hipLaunchKernelGGL(shard_pack_kernel, dim3(grid_for(count)), dim3(kBlock), 0,
-                     st, *R, ncomp, x, stride, C->buf);
-  FLOW_CHECK_LAUNCH();
-  // (a pure halo: no sums -- with a flow_peer no collective at all)
-  int rc = exchange_halo(C, R, ncomp, 0, 0, st);
-  if (rc) return rc;
-  const int per = R->recv_len[0] + R->recv_len[1];
-  if (per > 0) {
-    hipLaunchKernelGGL(shard_unpack_kernel, dim3(grid_for(ncomp * per)),
-                       dim3(kBlock), 0, st, *R, ncomp, C->buf, x, stride);
-    FLOW_CHECK_LAUNCH();
-  }
-  return FLOW_OK;
-}
-
-// ext-compact <- global-length field (ncomp components), and the ownership mask
-__global__ void shard_compress_kernel(int ncomp, int me, int e0, int n,
-                                      const double* __restrict__ src,
-                                      double* __restrict__ dst) {
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ncomp * me;
-       t += gridDim.x * blockDim.x) {
-    const int a = t / me, i = t - a * me;
-    dst[t] = src[static_cast<size_t>(a) * n + e0 + i];
-  }
-}
-
-__global__ void shard_expand_kernel(int ncomp, int me, int e0, int n,
-                                    const double* __restrict__ src,
-                                    double* __restrict__ dst) {
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ncomp * me;
-       t += gridDim.x * blockDim.x) {
-    const int a = t / me, i = t - a * me;
-    dst[static_cast<size_t>(a) * n + e0 + i] = src[t];
-  }
-}
-
-__global__ void shard_own_kernel(int ncomp, int me, int lo, int hi,
-                                 double* __restrict__ own) {
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ncomp * me;
-       t += gridDim.x * blockDim.x) {
-    const int i = t % me;
-    own[t] = (i >= lo && i < hi) ? 1.0 : 0.0;
-  }
-}
-
-// dst (owned-compact, stride mo, ncomp comps) <-> src (other layout): generic
-// strided 2-D copy  dst[a*ds + i] = src[a*ss + i], i < m
-__global__ void shard_copy2d_kernel(int ncomp, int m, const double* __restrict__ src,
-                                    int ss, double* __restrict__ dst, int ds,
-                                    double scale, int accumulate) {
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ncomp * m;
-       t += gridDim.x * blockDim.x) {
-    const int a = t / m, i = t - a * m;
-    const double v = scale * src[static_cast<size_t>(a) * ss + i];
-    double* d = dst + static_cast<size_t>(a) * ds + i;
-    *d = accumulate ? *d + v : v;
-  }
-}
-
-static int copy2d(int ncomp, int m, const double* src, int ss, double* dst,
-                  int ds, hipStream_t st, double scale = 1.0,
-                  int accumulate = 0) {
-  hipLaunchKernelGGL(shard_copy2d_kernel, dim3(grid_for(ncomp * m)), dim3(kBlock),
-                     0, st, ncomp, m, src, ss, dst, ds, scale, accumulate);
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// n doubles of device memory -> the host mailbox
-__global__ void mailbox_copy_kernel(int n, const double* __restrict__ src,
-                                    volatile double* __restrict__ mailbox) {
-  if (threadIdx.x < n) mailbox[threadIdx.x] = load_scalar(src + threadIdx.x);
-  __threadfence_system();
-}
-
-static int read_values(const double* dev, int n, double* host, hipStream_t st) {
-  double *mailbox = nullptr, *dev_view = nullptr;
-  int rc = mailbox_of_thread(&mailbox, &dev_view);
-  if (rc) return rc;
-  FLOW_REQUIRE(n <= kMailbox, "mailbox size");
-  hipLaunchKernelGGL(mailbox_copy_kernel, dim3(1), dim3(64), 0, st, n, dev,
-                     dev_view);
-  FLOW_CHECK_LAUNCH();
-  FLOW_CHECK_HIP(hipStreamSynchronize(st));
-  for (int i = 0; i < n; ++i) host[i] = static_cast<volatile double*>(mailbox)[i];
-  return FLOW_OK;
-}
-
-}  // namespace flow
-// n <= 64 doubles of device memory -> the host, in stream order (one
-// synchronisation through the calling thread's mailbox)
-extern "C" int flow_read_doubles(const double* dev, int n, double* host,
-                                 void* stream) {
-  FLOW_REQUIRE(dev && host && n >= 1 && n <= flow::kMailbox,
-               "read_doubles arguments (1..64 values)");
-  return flow::read_values(dev, n, host, flow::as_stream(stream));
-}
-namespace flow {
-
-// buf[k] = (k == rank) ? max(v[0..nv)) : 0, k < world
-__global__ void shard_rank_slot_kernel(int world, int rank, int nv,
-                                       const double* __restrict__ v,
-                                       double* __restrict__ buf) {
-  const int k = threadIdx.x;
-  if (k >= world) return;
-  double m = 0.0;
-  if (k == rank)
-    for (int i = 0; i < nv; ++i) m = fmax(m, load_scalar(v + i));
-  buf[k] = m;
-}
-
-// ---------------------------------------------------------------------------
-// sharded CG (Jacobi or multigrid V-cycle), ext-compact vectors
-// ---------------------------------------------------------------------------
-// block 0: the three partial lists -> buf[0..2], buf[3] = *extra (or 0);
-// blocks >= 1: halo slots of w at buf + 4 (own boundary entries, else 0)
-__global__ __launch_bounds__(kScalarBlock) void shard_finish_pack_kernel(
-    flow_rows R, int ncomp, int np, int nd, const double* __restrict__ gpart,
-    const double* __restrict__ rpart, const double* __restrict__ dpart,
-    const double* __restrict__ extra, const double* __restrict__ w, int stride,
-    double* __restrict__ buf, const double* __restrict__ stop, int hoff = 4) {
-  if (stopped(stop)) return;
-  if (blockIdx.x > 0) {
-    const int total = ncomp * R.nhalo;
-    double* halo = buf + hoff;
-    for (int t = (blockIdx.x - 1) * blockDim.x + threadIdx.x; t < total;
-         t += (gridDim.x - 1) * blockDim.x) {
-      const int a = t / R.nhalo, k = t - a * R.nhalo;
-      const double* wa = w + static_cast<size_t>(a) * stride;
-      double v = 0.0;
-#pragma unroll
-      for (int sd = 0; sd < 2; ++sd)
-        if (k >= R.send_slot[sd] && k < R.send_slot[sd] + R.send_len[sd])
-          v = wa[R.send_row[sd] + (k - R.send_slot[sd])];
-      halo[t] = v;
-    }
-    return;
-  }
-  __shared__ double wsum[3][kScalarBlock / 64];
-  double g = 0.0, rr = 0.0, d = 0.0;
-  for (int i = threadIdx.x; i < np; i += kScalarBlock) {
-    g += load_scalar(gpart + i);
-    rr += load_scalar(rpart + i);
-  }
-  for (int i = threadIdx.x; i < nd; i += kScalarBlock) d += load_scalar(dpart + i);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    g += __shfl_down(g, off, 64);
-    d += __shfl_down(d, off, 64);
-    rr += __shfl_down(rr, off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    wsum[0][threadIdx.x >> 6] = g;
-    wsum[1][threadIdx.x >> 6] = d;
-    wsum[2][threadIdx.x >> 6] = rr;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    g = d = rr = 0.0;
-    for (int k = 0; k < kScalarBlock / 64; ++k) {
-      g += wsum[0][k];
-      d += wsum[1][k];
-      rr += wsum[2][k];
-    }
-    buf[0] = g;
-    buf[1] = d;
-    buf[2] = rr;
-    buf[3] = extra ? load_scalar(extra) : 0.0;
-  }
-}
-
-// thread 0 of block 0: Chronopoulos-Gear scalars + the stopping test from the
-// summed buf[0..3] (first: the target from buf[3] = |B b|^2), exactly as
-// cg_scalar_kernel; everybody: ghost rows of w <- the neighbours' slots
-// ncopy > 0: also copy_dst[0, ncopy) <- buf[copy_off, +ncopy) (the summed
-// coarse image C w of the two-collective multigrid CG)
-__global__ void shard_scalar_unpack_kernel(flow_rows R, int ncomp, int first,
-                                           double rtol2, double atol2,
-                                           const double* __restrict__ buf,
-                                           double* __restrict__ S,
-                                           double* __restrict__ w, int stride,
-                                           int ncopy = 0, int copy_off = 0,
-                                           double* __restrict__ copy_dst = nullptr,
-                                           int hoff = 4) {
-  if (stopped(S + kDone)) return;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ncopy;
-       t += gridDim.x * blockDim.x)
-    copy_dst[t] = load_scalar(buf + copy_off + t);
-  const int per = R.recv_len[0] + R.recv_len[1];
-  const double* halo = buf + hoff;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < ncomp * per;
-       t += gridDim.x * blockDim.x) {
-    const int a = t / per, k = t - a * per;
-    const int sd = k < R.recv_len[0] ? 0 : 1;
-    const int j = sd == 0 ? k : k - R.recv_len[0];
-    w[static_cast<size_t>(a) * stride + R.recv_row[sd] + j] =
-        load_scalar(halo + static_cast<size_t>(a) * R.nhalo + R.recv_slot[sd] + j);
-  }
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const double g = load_scalar(buf), d = load_scalar(buf + 1),
-               rr = load_scalar(buf + 2);
-  double alpha, beta;
-  if (first) {
-    beta = 0.0;
-    alpha = (d != 0.0) ? g / d : 0.0;
-    store_scalar(S + kB2, load_scalar(buf + 3));
-    store_scalar(S + kTarget2, fmax(rtol2 * load_scalar(buf + 3), atol2));
-    store_scalar(S + kIter, 0.0);
-    // first == 2: the guarded start of cg_scalar_kernel -- the sums are the
-    // same on every rank, so is the verdict
-    if (first == 2 && rr > load_scalar(buf + 3)) {
-      store_scalar(S + kConvIt, 0.0);
-      store_scalar(S + kRes2, rr);
-      store_scalar(S + kDone, 5.0);
-      return;
-    }
-  } else {
-    const double g_old = load_scalar(S + kGamma);
-    const double a_old = load_scalar(S + kAlpha);
-    beta = (g_old != 0.0) ? g / g_old : 0.0;
-    const double den = (a_old != 0.0) ? d - beta * g / a_old : 0.0;
-    alpha = (den != 0.0) ? g / den : 0.0;
-  }
-  const double k = first ? 0.0 : load_scalar(S + kIter);
-  const double target2 =
-      first ? fmax(rtol2 * load_scalar(buf + 3), atol2) : load_scalar(S + kTarget2);
-  const bool nan = !(rr == rr);
-  if (nan || rr <= target2) {
-    store_scalar(S + kConvIt, k);
-    store_scalar(S + kDone, nan ? 2.0 : 1.0);
-    alpha = beta = 0.0;
-  }
-  store_scalar(S + kIter, k + 1.0);
-  store_scalar(S + kGamma, g);
-  store_scalar(S + kAlpha, alpha);
-  store_scalar(S + kBeta, beta);
-  store_scalar(S + kRes2, rr);
-}
-
-// masked dots of ext-compact vectors: sum own*a0*b0 [, own*a1*b1]
-__global__ __launch_bounds__(kBlock) void shard_dot2_kernel(
-    int n, const double* __restrict__ own, const double* __restrict__ a0,
-    const double* __restrict__ b0, const double* __restrict__ a1,
-    const double* __restrict__ b1, double* __restrict__ p0,
-    double* __restrict__ p1) {
-  double s0 = 0.0, s1 = 0.0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += gridDim.x * blockDim.x) {
-    if (own[i] != 0.0) {      // select, not multiply: ghost entries may be NaN
-      s0 += a0[i] * b0[i];
-      s1 += a1[i] * b1[i];
-    }
-  }
-  s0 = block_sum(s0);
-  s1 = block_sum(s1);
-  if (threadIdx.x == 0) {
-    p0[blockIdx.x] = s0;
-    p1[blockIdx.x] = s1;
-  }
-}
-
-struct ShardCg {
-  const flow_comm* C;
-  const flow_rows* R;
-  const flow_operator* A;
-  const flow_mg_shard* G;     // nullptr: Jacobi
-  int ncomp, me, m, L;
-  double *partial, *S, *r, *z, *w, *p, *s, *xc, *bc, *dc, *own, *t;
-  double *dpart, *mpart;
-  hipStream_t st;
-  template <class T>
-  T* sh(T* v) const { return v - R->e0; }   // index by global row
-};
-
-// the coarse image of CG's recurrences (two-collective form):
-//   rc_s = rc_w + beta rc_s ;  rc_r -= alpha rc_s
-__global__ void shard_rc_update_kernel(int n1, const double* __restrict__ S,
-                                       const double* __restrict__ rc_w,
-                                       double* __restrict__ rc_s,
-                                       double* __restrict__ rc_r) {
-  if (stopped(S + kDone)) return;
-  const double alpha = load_scalar(S + kAlpha);
-  const double beta = load_scalar(S + kBeta);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n1;
-       i += gridDim.x * blockDim.x) {
-    const double si = rc_w[i] + beta * rc_s[i];
-    rc_s[i] = si;
-    rc_r[i] -= alpha * si;
-  }
-}
-
-// iterations between two recomputations of the coarse images (see shard_cg)
-constexpr int kRcRefresh = 8;
-__global__ void shard_rc_refresh_kernel(int n1, const double* __restrict__ buf,
-                                        double* __restrict__ rc_r,
-                                        double* __restrict__ rc_s,
-                                        const double* __restrict__ stop) {
-  if (stopped(stop)) return;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n1;
-       i += gridDim.x * blockDim.x) {
-    rc_r[i] = load_scalar(buf + i);
-    rc_s[i] = load_scalar(buf + n1 + i);
-  }
-}
-
-static inline bool shard_two_launch(const flow_mg_shard* G) {
-  return G && G->Cg.rowptr != nullptr && G->mg->C[0].rowptr != nullptr;
-}
-
-// the up-sweep of level 0 on the owned rows from the coarse solution M->x[1]
-static int shard_up0(const ShardCg& c, const double* r, double* z, double* gpart,
-                     double* rpart, int* nparts, const double* stop) {
-  const flow_mg* M = c.G->mg;
-  const flow_operator* A0 = &c.G->Ah0;
-  const flow_operator* P0 = &c.G->Ps0;
-  double* const none = nullptr;
-  if (shard_two_launch(c.G)) {
-    const dim3 grid(c.G->up_nblocks0);
-    if (gpart)
-      hipLaunchKernelGGL(mg_up2_kernel<true>, grid, dim3(kBlock), 0, c.st,
-                         c.G->up_rowblocks0, P0->rowptr, P0->cols, P0->vals[0],
-                         A0->rowptr, A0->cols, A0->vals[0], M->x[1], c.sh(r),
-                         M->dinv[0], M->omega, c.sh(z), gpart, rpart, stop,
-                         c.R->r0, c.R->r1);
-    else
-      hipLaunchKernelGGL(mg_up2_kernel<false>, grid, dim3(kBlock), 0, c.st,
-                         c.G->up_rowblocks0, P0->rowptr, P0->cols, P0->vals[0],
-                         A0->rowptr, A0->cols, A0->vals[0], M->x[1], c.sh(r),
-                         M->dinv[0], M->omega, c.sh(z), none, none, stop);
-    if (gpart) *nparts = c.G->up_nblocks0;
-  } else if (gpart) {
-    hipLaunchKernelGGL((mg_level_kernel<1, true>), dim3(P0->nblocks), dim3(kBlock),
-                       0, c.st, P0->rowptr, P0->cols, P0->vals[0], P0->rowblocks,
-                       M->x[1], c.sh(r), c.sh(c.t), M->dinv[0], M->omega, c.sh(z),
-                       gpart, rpart, stop);
-    *nparts = P0->nblocks;
-  } else {
-    hipLaunchKernelGGL((mg_level_kernel<1, false>), dim3(P0->nblocks),
-                       dim3(kBlock), 0, c.st, P0->rowptr, P0->cols, P0->vals[0],
-                       P0->rowblocks, M->x[1], c.sh(r), c.sh(c.t), M->dinv[0],
-                       M->omega, c.sh(z), none, none, stop);
-  }
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-// z (owned rows) = V-cycle(r), r ext-compact with current ghosts; two
-// collectives are NOT included: the caller makes z's ghosts current.  One
-// collective here: the partial coarse residuals.  gpart/rpart as vcycle().
-// rc_keep != nullptr (two-launch form): the summed coarse residual C r is also
-// left there (the start of the recurrences of the two-collective loop).
-static int shard_vcycle(const ShardCg& c, const double* r, double* z,
-                        double* gpart, double* rpart, int* nparts,
-                        const double* stop, double* rc_keep = nullptr) {
-  const flow_mg* M = c.G->mg;
-  const flow_operator* A0 = &c.G->Ah0;
-  const flow_operator* Rg = &c.G->Rg;
-  const int n1 = Rg->n;
-  double* const none = nullptr;
-  int rc;
-  if (shard_two_launch(c.G)) {
-    // the rank's share of C r: its owned COLUMNS, no ghost rows involved
-    if ((rc = apply(&c.G->Cg, r + (c.R->r0 - c.R->e0), c.C->buf, c.st, nullptr,
-                    stop)))
-      return rc;
-  } else {
-    // t = r - Ah r on the owned rows
-    hipLaunchKernelGGL((mg_level_kernel<0, false>), dim3(A0->nblocks),
-                       dim3(kBlock), 0, c.st, A0->rowptr, A0->cols, A0->vals[0],
-                       A0->rowblocks, c.sh(r), c.sh(r), none, none, M->omega,
-                       c.sh(c.t), none, none, stop);
-    // the rank's share of the coarse residual -> buf, summed over the ranks
-    if ((rc = apply(Rg, c.t + (c.R->r0 - c.R->e0), c.C->buf, c.st, nullptr, stop)))
-      return rc;
-  }
-  if ((rc = exchange(c.C, n1))) return rc;
-  if (rc_keep) {
-    hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n1)), dim3(kBlock), 0, c.st, n1,
-                       1.0, c.C->buf, 0.0, rc_keep);
-    FLOW_CHECK_LAUNCH();
-  }
-  // levels >= 1: replicated
-  if ((rc = vcycle(M, c.C->buf, M->x[1], c.st, nullptr, nullptr, nullptr, stop,
-                   1)))
-    return rc;
-  return shard_up0(c, r, z, gpart, rpart, nparts, stop);
-}
-
-static size_t shard_cg_work_len(const flow_rows* R, const flow_operator* A,
-                                const flow_mg_shard* G) {
-  const size_t ncomp = A->kind == 4 ? 2 : 1;
-  const size_t L = ncomp * (R->e1 - R->e0);
-  size_t parts = G ? G->Ps0.nblocks : 0;
-  if (G && G->Cg.rowptr && static_cast<size_t>(G->up_nblocks0) > parts)
-    parts = G->up_nblocks0;
-  return FLOW_REDUCE_WORK + (G ? 11 : 10) * L + A->nblocks + 2 + 2 * parts +
-         (G && G->Cg.rowptr ? 3 * static_cast<size_t>(G->Cg.n) + 2 : 0);
-}
-
-static int shard_cg(const flow_comm* C, const flow_rows* R,
-                    const flow_operator* A, const double* dinv,
-                    const flow_mg_shard* G, const double* b, double* x,
-                    double rtol, double atol, int maxit, int check_every,
-                    int first_check, double* work, int* iters_host,
-                    double* resid_host, hipStream_t st,
-                    int* rejected = nullptr) {
-  // rejected != nullptr: the start vector is guarded; when it is rejected,
-  // *rejected = 1, x is untouched, FLOW_OK (the caller swaps in its fallback)
-  if (rejected) *rejected = 0;
-  ShardCg c;
-  c.C = C;
-  c.R = R;
-  c.A = A;
-  c.G = G;
-  c.st = st;
-  c.ncomp = A->kind == 4 ? 2 : 1;
-  c.me = R->e1 - R->e0;
-  c.m = R->r1 - R->r0;
-  c.L = c.ncomp * c.me;
-  const int L = c.L, me = c.me, n = R->n, ncomp = c.ncomp;
-  c.partial = work;
-  c.S = work + 3 * kRedBlocks;
-  double* v = work + FLOW_REDUCE_WORK;
-  c.r = v;
-  c.z = c.r + L;
-  c.w = c.z + L;
-  c.p = c.w + L;
-  c.s = c.p + L;
-  c.xc = c.s + L;
-  c.bc = c.xc + L;
-  c.dc = c.bc + L;
-  c.own = c.dc + L;
-  c.t = c.own + L;                       // MG only (10 L without it)
-  double* tail = c.own + L + (G ? L : 0);
-  c.dpart = tail;
-  c.mpart = c.dpart + A->nblocks + ((L + A->nblocks) & 1);
-  const int nd = A->nblocks;
-  const bool two = shard_two_launch(G);
-  int nm = G ? G->Ps0.nblocks : 0;
-  if (two && G->up_nblocks0 > nm) nm = G->up_nblocks0;
-  // two-collective multigrid CG: the coarse images of r, s, w (replicated)
-  const int n1 = two ? G->Cg.n : 0;
-  double* rc_r = c.mpart + 2 * nm + (nm & 1 ? 0 : 0);
-  rc_r += (reinterpret_cast<uintptr_t>(rc_r) & 15) ? 1 : 0;    // 16-byte aligned
-  double* rc_s = rc_r + n1;
-  double* rc_w = rc_s + n1;
-  const int gl = grid_for(L);
-  const int gu = grid_for(L, kBlock, kRedBlocks);
-  const double rtol2 = rtol * rtol, atol2 = atol * atol;
-  const double* stop = c.S + kDone;
-  double* const none = nullptr;
-  int rc, np = 0;
-
-  // ext-compact copies; ownership mask
-  hipLaunchKernelGGL(shard_compress_kernel, dim3(gl), dim3(kBlock), 0, st, ncomp,
-                     me, R->e0, n, b, c.bc);
-  hipLaunchKernelGGL(shard_compress_kernel, dim3(gl), dim3(kBlock), 0, st, ncomp,
-                     me, R->e0, n, x, c.xc);
-  hipLaunchKernelGGL(shard_compress_kernel, dim3(gl), dim3(kBlock), 0, st, ncomp,
-                     me, R->e0, n, dinv, c.dc);
-  hipLaunchKernelGGL(shard_own_kernel, dim3(gl), dim3(kBlock), 0, st, ncomp, me,
-                     R->r0 - R->e0, R->r1 - R->e0, c.own);
-  if ((rc = fill(kNumSlots, 0.0, c.S, st))) return rc;
-  if ((rc = fill(3 * L, 0.0, c.w, st))) return rc;          // w, p, s
-  // one collective per iteration: z is formed on the first ghost layer too and
-  // never exchanged (rows further out stay zero)
-  const bool z_local = G && shard_two_launch(G) && G->z_hi > G->z_lo;
-  if (z_local && (rc = fill(L, 0.0, c.z, st))) return rc;
-  FLOW_CHECK_LAUNCH();
-
-  // |B b|^2 over the owned rows -> S[kB2] (this rank's share)
-  if (G) {
-    if ((rc = halo(C, R, 1, c.sh(c.bc), me, st))) return rc;
-    if ((rc = shard_vcycle(c, c.bc, c.z, none, none, nullptr, nullptr)))
-      return rc;
-  } else {
-    hipLaunchKernelGGL(vmul_kernel, dim3(gl), dim3(kBlock), 0, st, L, 1.0, c.dc,
-                       c.bc, c.z);
-  }
-  hipLaunchKernelGGL(shard_dot2_kernel, dim3(gu), dim3(kBlock), 0, st, L, c.own,
-                     c.z, c.z, c.z, c.z, c.partial, c.partial + kRedBlocks);
-  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kBlock), 0, st, gu, 1, 0,
-                     c.partial, c.S + kB2);
-  FLOW_CHECK_LAUNCH();
-
-  // r = b - A x on the owned rows, then on the ghost rows from their owners
-  if ((rc = halo(C, R, ncomp, c.sh(c.xc), me, st))) return rc;
-  if ((rc = apply(A, c.sh(c.xc), c.sh(c.w), st, nullptr, nullptr, me))) return rc;
-  hipLaunchKernelGGL(residual_kernel, dim3(gl), dim3(kBlock), 0, st, L, c.bc, c.w,
-                     static_cast<const double*>(nullptr), c.r, none);
-  FLOW_CHECK_LAUNCH();
-  if ((rc = halo(C, R, ncomp, c.sh(c.r), me, st))) return rc;
-  // z = B r
-  if (G) {
-    if ((rc = shard_vcycle(c, c.r, c.z, none, none, nullptr, nullptr,
-                           two ? rc_r : nullptr)))
-      return rc;
-    if (!z_local && (rc = halo(C, R, 1, c.sh(c.z), me, st))) return rc;
-    if (two && (rc = fill(n1, 0.0, rc_s, st))) return rc;
-  } else {
-    hipLaunchKernelGGL(vmul_kernel, dim3(gl), dim3(kBlock), 0, st, L, 1.0, c.dc,
-                       c.r, c.z);
-  }
-  // w = A z (owned rows, z.w partials); r.z, z.z over the owned rows
-  if ((rc = apply(A, c.sh(c.z), c.sh(c.w), st, c.dpart, nullptr, me))) return rc;
-  hipLaunchKernelGGL(shard_dot2_kernel, dim3(gu), dim3(kBlock), 0, st, L, c.own,
-                     c.r, c.z, c.z, c.z, c.partial, c.partial + 2 * kRedBlocks);
-  const int gp = 1 + grid_for(ncomp * R->nhalo > 0 ? ncomp * R->nhalo : 1,
-                              kScalarBlock, 64);
-  // [3 sums, |B b|^2 | (two-collective form) this rank's share of the coarse
-  // image C w | halo of w]: everything that is SUMMED is a prefix, the halo
-  // behind it may travel from neighbour to neighbour instead (exchange_halo)
-  const int coff = 4;
-  const int hoff = coff + n1;
-  const int count = hoff + ncomp * R->nhalo;
-  (void)count;
-  // C w: the rank's owned columns
-  auto coarse_image_of_w = [&](const double* flag) -> int {
-    return two ? apply(&G->Cg, c.w + (R->r0 - R->e0), C->buf + coff, st, nullptr,
-                       flag)
-               : FLOW_OK;
-  };
-  if ((rc = coarse_image_of_w(nullptr))) return rc;
-  hipLaunchKernelGGL(shard_finish_pack_kernel, dim3(gp), dim3(kScalarBlock), 0, st,
-                     *R, ncomp, gu, nd, c.partial, c.partial + 2 * kRedBlocks,
-                     c.dpart, c.S + kB2, c.sh(c.w), me, C->buf,
-                     static_cast<const double*>(nullptr), hoff);
-  FLOW_CHECK_LAUNCH();
-  if ((rc = exchange_halo(C, R, ncomp, hoff, hoff, st))) return rc;
-
-  const int per = R->recv_len[0] + R->recv_len[1];
-  int gs = grid_for(ncomp * per > 0 ? ncomp * per : 1);
-  if (two && grid_for(n1) > gs) gs = grid_for(n1);
-  // alpha, beta and the verdict on the start; ghost rows of w; rc_w
-  hipLaunchKernelGGL(shard_scalar_unpack_kernel, dim3(gs), dim3(kBlock), 0, st, *R,
-                     ncomp, rejected ? 2 : 1, rtol2, atol2, C->buf, c.S,
-                     c.sh(c.w), me, n1, coff, rc_w, hoff);
-  FLOW_CHECK_LAUNCH();
-  double state[kNumSlots];
-  int launched = 0;
-  while (true) {
-    const int batch = (launched == 0 && first_check > 0) ? first_check
-                                                         : check_every;
-    const int todo = (maxit - launched < batch) ? maxit - launched : batch;
-    for (int k = 0; k < todo; ++k) {
-      const double *gpart, *rpart;
-      if (G) {
-        hipLaunchKernelGGL(cg_update_kernel<false>, dim3(gl), dim3(kBlock), 0, st,
-                           L, c.S, c.dc, c.w, c.z, c.p, c.s, c.xc, c.r, 0,
-                           c.partial, static_cast<const double*>(nullptr));
-        if (two) {
-          // the coarse residual by recurrence (no collective), the levels
-          // >= 1 replicated, the up-sweep of level 0 on the owned rows
-          hipLaunchKernelGGL(shard_rc_update_kernel, dim3(grid_for(n1)),
-                             dim3(kBlock), 0, st, n1, c.S, rc_w, rc_s, rc_r);
-          // Every kRcRefresh-th iteration the coarse images are recomputed
-          // from the vectors they belong to, C r and C s (one more collective
-          // then): carried by recurrence alone they drift away from the
-          // rank-local r and s, and the preconditioner with them -- seen on a
-          // 2.5 M-DoF start-up step that needs 38 iterations, where CG then
-          // stagnated a factor 2.5 above its target
-          if ((launched + k) % kRcRefresh == kRcRefresh - 1) {
-            const int own0 = R->r0 - R->e0;
-            if ((rc = apply(&G->Cg, c.r + own0, C->buf, st, nullptr, stop)))
-              return rc;
-            if ((rc = apply(&G->Cg, c.s + own0, C->buf + n1, st, nullptr, stop)))
-              return rc;
-            if ((rc = exchange(C, 2 * n1))) return rc;
-            hipLaunchKernelGGL(shard_rc_refresh_kernel, dim3(grid_for(n1)),
-                               dim3(kBlock), 0, st, n1, C->buf, rc_r, rc_s, stop);
-          }
-          if ((rc = vcycle(G->mg, rc_r, G->mg->x[1], st, nullptr, nullptr,
-                           nullptr, stop, 1)))
-            return rc;
-          if ((rc = shard_up0(c, c.r, c.z, c.mpart, c.mpart + nm, &np, stop)))
-            return rc;
-        } else if ((rc = shard_vcycle(c, c.r, c.z, c.mpart, c.mpart + nm, &np,
-                                      stop))) {
-          return rc;
-        }
-        if (!z_local && (rc = halo(C, R, 1, c.sh(c.z), me, st))) return rc;
-        gpart = c.mpart;
-        rpart = c.mpart + nm;
-      } else {
-        hipLaunchKernelGGL(cg_update_kernel<true>, dim3(gu), dim3(kBlock), 0, st,
-                           L, c.S, c.dc, c.w, c.z, c.p, c.s, c.xc, c.r, 1,
-                           c.partial, c.own);
-        np = gu;
-        gpart = c.partial;
-        rpart = c.partial + 2 * kRedBlocks;
-      }
-      if ((rc = apply(A, c.sh(c.z), c.sh(c.w), st, c.dpart, stop, me))) return rc;
-      if ((rc = coarse_image_of_w(stop))) return rc;
-      hipLaunchKernelGGL(shard_finish_pack_kernel, dim3(gp), dim3(kScalarBlock), 0,
-                         st, *R, ncomp, np, nd, gpart, rpart, c.dpart,
-                         static_cast<const double*>(nullptr), c.sh(c.w), me,
-                         C->buf, stop, hoff);
-      FLOW_CHECK_LAUNCH();
-      if ((rc = exchange_halo(C, R, ncomp, hoff, hoff, st))) return rc;
-      hipLaunchKernelGGL(shard_scalar_unpack_kernel, dim3(gs), dim3(kBlock), 0,
-                         st, *R, ncomp, 0, rtol2, atol2, C->buf, c.S, c.sh(c.w),
-                         me, n1, coff, rc_w, hoff);
-    }
-    FLOW_CHECK_LAUNCH();
-    launched += todo;
-    if ((rc = read_state(c.S, state, st))) return rc;
-    const double res2 = state[kRes2];
-    if (state[kDone] == 2.0 || !(res2 == res2)) {
-      *iters_host = static_cast<int>(state[kConvIt]);
-      *resid_host = res2;
-      set_error("sharded CG broke down (NaN residual) at iteration %d",
-                *iters_host);
-      return FLOW_NOT_CONVERGED;
-    }
-    if (state[kDone] == 1.0) {
-      *iters_host = static_cast<int>(state[kConvIt]);
-      *resid_host = sqrt(res2);
-      break;
-    }
-    if (state[kDone] == 5.0 && rejected) {
-      *rejected = 1;
-      *iters_host = 0;
-      *resid_host = sqrt(res2);
-      return FLOW_OK;
-    }
-    if (launched >= maxit) {
-      *iters_host = launched;
-      *resid_host = sqrt(res2);
-      set_error("sharded CG did not converge in %d iterations: |B r| = %.3e > "
-                "%.3e", launched, sqrt(res2), sqrt(state[kTarget2]));
-      return FLOW_NOT_CONVERGED;
-    }
-  }
-  // x on the owned AND ghost rows (the recurrences ran there too; z_local: on
-  // the first ghost layer -- further out the search directions are zero)
-  if (z_local)
-    hipLaunchKernelGGL(shard_expand_kernel, dim3(grid_for(G->z_hi - G->z_lo)),
-                       dim3(kBlock), 0, st, 1, G->z_hi - G->z_lo, G->z_lo, n,
-                       c.xc + (G->z_lo - R->e0), x);
-  else
-    hipLaunchKernelGGL(shard_expand_kernel, dim3(gl), dim3(kBlock), 0, st, ncomp,
-                       me, R->e0, n, c.xc, x);
-  FLOW_CHECK_LAUNCH();
-  return FLOW_OK;
-}
-
-
-// ---------------------------------------------------------------------------
-// sharded GMRES(m): owned-compact Krylov vectors (2 * (r1 - r0) doubles), the
-// operator's input staged ext-compact with its halo, block-Jacobi ILU(0)
-// ---------------------------------------------------------------------------
-static int shard_gmres(const flow_comm* C, const flow_rows* R,
-                       const flow_operator* A, const flow_ilu* ilu,
-                       const flow_pmg* pmg,
-                       const double* b, double* x, double rtol, double atol,
-                       int maxit, int m, int x_is_zero, int expected,
-                       int verify, double* work, int* iters_host,
-                       double* resid_host, hipStream_t st) {
-  const int mo = R->r1 - R->r0;         // owned rows
-  const int me = R->e1 - R->e0;
-  const int n = R->n;
-  // two components (the Newton systems: kind 3) or one (a scalar operator of
-  // kind 0 on the rank's rows: the heat system)
-  const int ncomp = A->kind == 0 ? 1 : 2;
-  const int N = ncomp * mo;
-  double* V = work + FLOW_REDUCE_WORK;
-  double* Z = V + static_cast<size_t>(m + 1) * N;
-  double* iwork = Z + static_cast<size_t>(m) * N;
-  double* xc = iwork + N;
-  double* bc = xc + N;
-  double* stage = bc + N;                    // ncomp * me, ext-compact
-  double* P = stage + 2 * static_cast<size_t>(me);
-  double* Pww = P + kGmresMax * kRedBlocks;
-  double* Pnn = Pww + kRedBlocks;
-  double* G = P + FLOW_GMRES_PARTIALS;      // device state of the cycle
-  double* S = work + 3 * kRedBlocks;
-  const double* stop = S + kDone;
-  const int gv = grid_for(N);
-  const int gd = grid_for(N, kBlock, kRedBlocks);
-  int rc;
-
-  // w (owned-compact) = A v (owned-compact): stage, halo, apply on the strip
-  // (the collective inside runs whatever the flag says: every rank issues the
-  // same sequence)
-  auto apply_owned = [&](const double* v, double* w, const double* flag) -> int {
-    int r;
-    if ((r = copy2d(ncomp, mo, v, mo, stage + (R->r0 - R->e0), me, st))) return r;
-    if ((r = halo(C, R, ncomp, stage - R->e0, me, st))) return r;
-    return apply(A, stage - R->e0, w - R->r0, st, nullptr, flag, me, mo);
-  };
-  // sums of nv partial lists (list k at base + k*kRedBlocks) -> all ranks'
-  // total on the host
-  auto sums_to_host = [&](int nparts, int nd, int extra, double* host) -> int {
-    const int nv = nd + extra;
-    hipLaunchKernelGGL(gmres_finish_kernel, dim3(nv), dim3(kBlock), 0, st, nparts,
-                       nd, P, C->buf);
-    FLOW_CHECK_LAUNCH();
-    int r = exchange(C, nv);
-    if (r) return r;
-    return read_values(C->buf, nv, host, st);
-  };
-
-  if ((rc = copy2d(ncomp, mo, b + R->r0, n, bc, mo, st))) return rc;
-  if (x_is_zero) {
-    if ((rc = fill(N, 0.0, xc, st))) return rc;
-  } else if ((rc = copy2d(ncomp, mo, x + R->r0, n, xc, mo, st))) {
-    return rc;
-  }
-  if ((rc = fill(kNumSlots, 0.0, S, st))) return rc;
-  // Arnoldi step j of the cycle without a read-back: the sums come out of the
-  // collective summed over the ranks, the step kernel takes them from there
-  // (every rank computes the same H, the same verdict)
-  auto arnoldi = [&](int j, double beta, double target, bool last) -> int {
-    int r;
-    double* w = V + static_cast<size_t>(j + 1) * N;
-    double* zj = Z + static_cast<size_t>(j) * N;
-    // block Jacobi: the rank's own preconditioner on its owned rows
-    if ((r = pmg ? pmg_apply(pmg, V + static_cast<size_t>(j) * N, zj, st, stop)
-                 : ilu_apply(ilu, V + static_cast<size_t>(j) * N, zj, iwork, st,
-                             stop)))
-      return r;
-    if ((r = apply_owned(zj, w, stop))) return r;
-    for (int k0 = 0; k0 <= j; k0 += 8) {
-      const int chunk = j + 1 - k0 < 8 ? j + 1 - k0 : 8;
-#define FLOW_CALL(NV)                                                         \
-  hipLaunchKernelGGL(gmres_dots_kernel<NV>, dim3(gd), dim3(kBlock), 0, st, N,  \
-                     w, V + static_cast<size_t>(k0) * N,                      \
-                     static_cast<size_t>(N), k0 == 0 ? 1 : 0,                 \
-                     P + k0 * kRedBlocks, Pww, stop)
-      FLOW_NV_SWITCH(chunk, FLOW_CALL)
-#undef FLOW_CALL
-    }
-    const int nv = j + 2 + (j > 0 ? 1 : 0);
-    hipLaunchKernelGGL(gmres_finish_kernel, dim3(nv), dim3(kBlock), 0, st, gd,
-                       j + 1, P, C->buf);
-    FLOW_CHECK_LAUNCH();
-    if ((r = exchange(C, nv))) return r;
-    hipLaunchKernelGGL(gmres_step_kernel, dim3(1), dim3(kBlock), 0, st, 0, j,
-                       last ? 1 : 0, beta, target, C->buf, G, S);
-    FLOW_CHECK_LAUNCH();
-    if (!last &&
-        (r = gmres_combine_dev(N, j + 1, G + kGCoef, G + kGCw, w, V, w, Pnn, false,
-                               stop, st)))
-      return r;
-    return FLOW_OK;
-  };
-
-  double host[kGmresMax + 2];
-  double target = 0.0, resid = 0.0;
-  int it = 0;
-  bool have_target = false;
-  bool claimed = false;     // the last cycle stopped on the residual estimate
-  while (true) {
-    // r0 = b - A x -> V_0
-    if (x_is_zero && it == 0) {
-      hipLaunchKernelGGL(axpby_kernel, dim3(gv), dim3(kBlock), 0, st, N, 1.0, bc,
-                         0.0, V);
-    } else {
-      if ((rc = apply_owned(xc, iwork, nullptr))) return rc;
-      hipLaunchKernelGGL(residual_kernel, dim3(gv), dim3(kBlock), 0, st, N, bc,
-                         iwork, static_cast<const double*>(nullptr), V,
-                         static_cast<double*>(nullptr));
-    }
-    // |b|^2 and |r0|^2 in one collective (lists 0 and 1 of P)
-    hipLaunchKernelGGL(gmres_dots_kernel<1>, dim3(gd), dim3(kBlock), 0, st, N, bc,
-                       bc, static_cast<size_t>(N), 0, P, Pww,
-                       static_cast<const double*>(nullptr));
-    hipLaunchKernelGGL(gmres_dots_kernel<1>, dim3(gd), dim3(kBlock), 0, st, N, V,
-                       V, static_cast<size_t>(N), 0, P + kRedBlocks, Pww,
-                       static_cast<const double*>(nullptr));
-    FLOW_CHECK_LAUNCH();
-    if ((rc = sums_to_host(gd, 2, 0, host))) return rc;
-    if (!have_target) {
-      target = fmax(rtol * sqrt(host[0]), atol);
-      have_target = true;
-      // a start vector that leaves a larger residual than zero would is
-      // dropped (every rank sees the same sums): V_0 = b, x = 0
-      if (!x_is_zero && host[1] > host[0]) {
-        hipLaunchKernelGGL(axpby_kernel, dim3(gv), dim3(kBlock), 0, st, N, 1.0, bc,
-                           0.0, V);
-        if ((rc = fill(N, 0.0, xc, st))) return rc;
-        host[1] = host[0];
-      }
-    }
-    const double res2 = host[1];
-    const double beta = sqrt(res2);
-    resid = beta;
-    if (!(res2 == res2)) {
-      *iters_host = it;
-      *resid_host = res2;
-      set_error("sharded GMRES broke down (NaN residual) at iteration %d", it);
-      return FLOW_NOT_CONVERGED;
-    }
-    // (behind a cycle that stopped on the estimate: the verification with the
-    // true residual, as gmres() -- every rank sees the same sums)
-    if (beta <= target || (claimed && beta <= 10.0 * target)) break;
-    claimed = false;
-    if (it >= maxit) {
-      *iters_host = it;
-      *resid_host = beta;
-      set_error("sharded GMRES did not converge in %d iterations: |r| = %.3e > "
-                "%.3e", it, beta, target);
-      return FLOW_NOT_CONVERGED;
-    }
-
-    // one cycle (as gmres(): the plan only depends on numbers every rank has)
-    const int it0 = it;
-    int enq = 0, cols = 0;
-    bool converged = false;
-    double state[kNumSlots];
-    while (true) {
-      const int room = (m < maxit - it0 ? m : maxit - it0) - enq;
-      if (room <= 0) break;
-      int plan = expected - (it0 + enq);
-      if (plan < 1) plan = 1;
-      if (plan > room) plan = room;
-      for (int k = 0; k < plan; ++k, ++enq) {
-        const bool last = enq + 1 >= m || it0 + enq + 1 >= maxit;
-        if ((rc = arnoldi(enq, beta, target, last))) return rc;
-      }
-      if ((rc = read_state(S, state, st))) return rc;
-      cols = static_cast<int>(state[kConvIt]);
-      if (state[kDone] == 2.0) {
-        *iters_host = it0 + cols;
-        *resid_host = resid;
-        set_error("sharded GMRES broke down (NaN) at iteration %d", it0 + cols);
-        return FLOW_NOT_CONVERGED;
-      }
-      resid = state[kRes2];
-      if (state[kDone] != 0.0) {
-        converged = state[kDone] == 1.0;   // 3: verify with the true residual
-        break;
-      }
-    }
-    it = it0 + cols;
-    if ((rc = fill(1, 0.0, S + kDone, st))) return rc;
-    if (cols > 0 &&
-        (rc = gmres_combine_dev(N, cols, G + kGYc, nullptr, nullptr, Z, xc,
-                                nullptr, true, nullptr, st)))
-      return rc;
-    x_is_zero = 0;
-    if (converged && !verify) break;
-    claimed = converged;
-  }
-  // the owned rows of x
-  if ((rc = copy2d(ncomp, mo, xc, mo, x + R->r0, n, st))) return rc;
-  *iters_host = it;
-  *resid_host = resid;
-  return FLOW_OK;
-}
-
-}  // namespace flow
-
-extern "C" int flow_shard_halo(const flow_comm* comm, const flow_rows* rows,
-                               int ncomp, double* x, int stride, void* stream) {
-  int rc = check_rows(rows);
-  if (rc) return rc;
-  FLOW_REQUIRE(ncomp == 1 || ncomp == 2, "components");
-  if ((rc = check_comm(comm, static_cast<long long>(ncomp) * rows->nhalo)))
-    return rc;
-  FLOW_REQUIRE(x != nullptr && stride >= rows->e1 - rows->e0, "halo vector");
-  return halo(comm, rows, ncomp, x, stride, as_stream(stream));
-}
-
-extern "C" int flow_shard_reduce_host(const flow_comm* comm,
-                                      const flow_rows* rows, int ncomp,
-                                      const double* x, const double* y,
-                                      int stride, int kind, double* work,
-                                      double* result_host, void* stream) {
-  int rc = check_rows(rows);
-  if (rc) return rc;
-  if ((rc = check_comm(comm, kNumSlots))) return rc;
-  FLOW_REQUIRE(ncomp == 1 || ncomp == 2, "components");
-  FLOW_REQUIRE(x && work && result_host && (kind == 1 || y), "reduce arguments");
-  FLOW_REQUIRE(kind == 0 || kind == 1, "reduce kind");
-  hipStream_t st = as_stream(stream);
-  const int m = rows->r1 - rows->r0;
-  const double* x0 = x + rows->r0;
-  const double* x1 = x0 + (ncomp == 2 ? stride : 0);
-  double host[kNumSlots];
-  if (kind == 0) {
-    const double* y0 = y + rows->r0;
-    const double* y1 = y0 + (ncomp == 2 ? stride : 0);
-    int np = 0;
-    if ((rc = dots(m, ncomp, x0, y0, x1, y1, x0, y0, work, &np, st))) return rc;
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kBlock), 0, st, np, ncomp, 0,
-                       work, comm->buf);
-    FLOW_CHECK_LAUNCH();
-    if ((rc = exchange(comm, ncomp))) return rc;
-    if ((rc = read_values(comm->buf, ncomp, host, st))) return rc;
-    *result_host = host[0] + (ncomp == 2 ? host[1] : 0.0);
-    return FLOW_OK;
-  }
-  double* S = work + 3 * kRedBlocks;
-  const int g = grid_for(m, kBlock * 4, kRedBlocks);
-  for (int a = 0; a < ncomp; ++a) {
-    hipLaunchKernelGGL(absmax_kernel, dim3(g), dim3(kBlock), 0, st, m,
-                       a == 0 ? x0 : x1, work);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kBlock), 0, st, g, 1, 1, work,
-                       S + a);
-  }
-  hipLaunchKernelGGL(shard_rank_slot_kernel, dim3(1), dim3(64), 0, st, comm->world,
-                     comm->rank, ncomp, S, comm->buf);
-  FLOW_CHECK_LAUNCH();
-  if ((rc = exchange(comm, comm->world))) return rc;
-  if ((rc = read_values(comm->buf, comm->world, host, st))) return rc;
-  double mx = 0.0;
-  for (int k = 0; k < comm->world; ++k) mx = fmax(mx, host[k]);
-  *result_host = mx;
-  return FLOW_OK;
-}
-
-static int check_shard_solver(const flow_comm* comm, const flow_rows* rows,
-                              const flow_operator* A, const double* b,
-                              const double* x, double rtol, double atol,
-                              int maxit, const double* work,
-                              const int* iters_host, const double* resid_host) {
-  int rc = check_rows(rows);
-  if (rc) return rc;
-  if ((rc = check_operator(A))) return rc;
-  FLOW_REQUIRE(A->n == rows->n, "operator / row ranges");
-  FLOW_REQUIRE(b && x && work && iters_host && resid_host, "solver pointers");
-  FLOW_REQUIRE(rtol >= 0.0 && atol >= 0.0 && maxit >= 0, "solver tolerances");
-  FLOW_REQUIRE(reinterpret_cast<uintptr_t>(work) % 16 == 0,
-               "solver workspace must be 16-byte aligned");
-  (void)comm;
-  return FLOW_OK;
-}
-
-extern "C" int flow_shard_cg_solve(const flow_comm* comm, const flow_rows* rows,
-                                   const flow_operator* A, const double* dinv,
-                                   const double* b, double* x, double rtol,
-                                   double atol, int maxit, int check_every,
-                                   int first_check, double* work,
-                                   size_t work_len, int* iters_host,
-                                   double* resid_host,
-                                   int* start_rejected_host, void* stream) {
-  int rc = check_shard_solver(comm, rows, A, b, x, rtol, atol, maxit, work,
-                              iters_host, resid_host);
-  if (rc) return rc;
-  FLOW_REQUIRE(A->kind == 0 || A->kind == 4, "sharded CG: operator kind 0 or 4");
-  FLOW_REQUIRE(dinv != nullptr && check_every > 0 && first_check >= 0,
-               "sharded CG arguments");
-  const int ncomp = A->kind == 4 ? 2 : 1;
-  if ((rc = check_comm(comm, 4 + static_cast<long long>(ncomp) * rows->nhalo)))
-    return rc;
-  FLOW_REQUIRE(work_len >= shard_cg_work_len(rows, A, nullptr),
-               "sharded CG workspace too small");
-  return shard_cg(comm, rows, A, dinv, nullptr, b, x, rtol, atol, maxit,
-                  check_every, first_check, work, iters_host, resid_host,
-                  as_stream(stream), start_rejected_host);
-}
-
-extern "C" int flow_shard_mgcg_solve(
-    const flow_comm* comm, const flow_rows* rows, const flow_operator* A,
-    const double* dinv, const flow_mg_shard* mgs, const double* b, double* x,
-    double rtol, double atol, int maxit, int check_every, int first_check,
-    double* work, size_t work_len, int* iters_host, double* resid_host,
-    int* start_rejected_host, void* stream) {
-  int rc = check_shard_solver(comm, rows, A, b, x, rtol, atol, maxit, work,
-                              iters_host, resid_host);
-  if (rc) return rc;
-  FLOW_REQUIRE(A->kind == 0 && dinv != nullptr && check_every > 0 &&
-                   first_check >= 0,
-               "sharded multigrid CG arguments");
-  FLOW_REQUIRE(mgs && mgs->mg, "sharded hierarchy");
-  if ((rc = check_mg(mgs->mg, A->n))) return rc;
-  FLOW_REQUIRE(mgs->mg->nlevels >= 2, "multigrid: at least two levels");
-  if ((rc = check_operator(&mgs->Ah0))) return rc;
-  if ((rc = check_operator(&mgs->Ps0))) return rc;
-  if ((rc = check_operator(&mgs->Rg))) return rc;
-  FLOW_REQUIRE(mgs->Ah0.kind == 0 && mgs->Ps0.kind == 0 && mgs->Rg.kind == 0 &&
-                   mgs->Ah0.n == A->n && mgs->Ps0.n == A->n &&
-                   mgs->Rg.n == mgs->mg->R[0].n,
-               "sharded hierarchy operators");
-  long long need = 4 + rows->nhalo;
-  if (mgs->Cg.rowptr) {
-    if ((rc = check_operator(&mgs->Cg))) return rc;
-    FLOW_REQUIRE(mgs->mg->C[0].rowptr && mgs->Cg.kind == 0 &&
-                     mgs->Cg.n == mgs->Rg.n && mgs->up_rowblocks0 &&
-                     mgs->up_nblocks0 > 0,
-                 "sharded hierarchy: two-launch form");
-    need += mgs->Cg.n;
-    if (2LL * mgs->Cg.n > need) need = 2LL * mgs->Cg.n;
-    FLOW_REQUIRE(mgs->z_hi <= mgs->z_lo ||
-                     (mgs->z_lo >= rows->e0 && mgs->z_lo <= rows->r0 &&
-                      mgs->z_hi >= rows->r1 && mgs->z_hi <= rows->e1),
-                 "sharded hierarchy: [z_lo, z_hi) must hold the owned rows and "
-                 "lie inside the rows' window");
-  }
-  if (mgs->Rg.n > need) need = mgs->Rg.n;
-  if ((rc = check_comm(comm, need))) return rc;
-  FLOW_REQUIRE(work_len >= shard_cg_work_len(rows, A, mgs),
-               "sharded multigrid CG workspace too small");
-  return shard_cg(comm, rows, A, dinv, mgs, b, x, rtol, atol, maxit, check_every,
-                  first_check, work, iters_host, resid_host, as_stream(stream),
-                  start_rejected_host);
-}
-
-extern "C" int flow_shard_gmres_solve(
-    const flow_comm* comm, const flow_rows* rows, const flow_operator* A,
-    const flow_ilu* ilu, const flow_pmg* pmg, const double* b, double* x,
-    double rtol, double atol, int maxit, int restart, int x_is_zero,
-    int expected_its, int verify, double* work, size_t work_len,
-    int* iters_host, double* resid_host, void* stream) {
-  int rc = check_shard_solver(comm, rows, A, b, x, rtol, atol, maxit, work,
-                              iters_host, resid_host);
-  if (rc) return rc;
-  FLOW_REQUIRE(A->kind == 3 || A->kind == 0,
-               "sharded GMRES: the matrix-free Jacobian action (kind 3) or a "
-               "scalar operator on the rank's rows (kind 0)");
-  FLOW_REQUIRE(expected_its >= 0, "expected iterations");
-  FLOW_REQUIRE(restart >= 1 && restart <= FLOW_GMRES_MAX_RESTART,
-               "GMRES restart length");
-  const int ncomp = A->kind == 0 ? 1 : 2;
-  if (A->kind == 3) {
-    const flow_momentum_jvp* J =
-        static_cast<const flow_momentum_jvp*>(A->matfree);
-    FLOW_REQUIRE(J->W->r0 == rows->r0 && J->W->r1 == rows->r1,
-                 "the operator's row range must be the rank's owned rows");
-  }
-  const int mo = rows->r1 - rows->r0, me = rows->e1 - rows->e0;
-  FLOW_REQUIRE((ilu != nullptr) != (pmg != nullptr),
-               "sharded GMRES needs ONE block-Jacobi preconditioner: ilu or pmg");
-  FLOW_REQUIRE(pmg == nullptr || ncomp == 2,
-               "the p-multigrid cycle is a two-component preconditioner");
-  if (ilu && (rc = ilu_check(ilu, ncomp * mo))) return rc;
-  if (pmg && (rc = pmg_check(pmg, 2 * mo))) return rc;
-  long long need = static_cast<long long>(ncomp) * rows->nhalo;
-  if (need < FLOW_GMRES_MAX_RESTART + 2) need = FLOW_GMRES_MAX_RESTART + 2;
-  if ((rc = check_comm(comm, need))) return rc;
-  FLOW_REQUIRE(work_len >= FLOW_REDUCE_WORK +
-                               (2 * static_cast<size_t>(restart) + 4) * ncomp * mo +
-                               2 * static_cast<size_t>(me) + FLOW_GMRES_PARTIALS +
-                               FLOW_GMRES_STATE,
-               "sharded GMRES workspace too small");
-  return shard_gmres(comm, rows, A, ilu, pmg, b, x, rtol, atol, maxit, restart,
-                     x_is_zero, expected_its, verify, work, iters_host,
-                     resid_host, as_stream(stream));
 }

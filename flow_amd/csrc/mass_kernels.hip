@@ -4,7 +4,7 @@
 // Replaces, for the velocity correction (flow/navier_stokes/
 // pressure_correction.py:436-465: CG + hypre_amg on the vector mass system) and
 // the callers' L2 projections (tests/test_karman_vortex_street.py:262-267), the
-// Jacobi-CG of la_kernels.hip: 11-14 iterations of [fp64 product 12 B/nnz +
+// Jacobi-CG of krylov_kernels.hip: 11-14 iterations of [fp64 product 12 B/nnz +
 // 5-vector update + scalar kernel] become 3-4 defect corrections of [one fp64
 // product whose epilogue leaves the scaled residual in fp32 + k-1 products with
 // an fp16 copy of D^-1 M at 6 B/nnz, no dot products, one launch each].  The

@@ -4,7 +4,7 @@
 // Stands in -- like the multicolour ILU(0) of ilu_kernels.hip -- for the sparse
 // LU behind the reference's Newton solve (flow/navier_stokes/
 // pressure_correction.py:224-254) as the right preconditioner of the flexible
-// GMRES of la_kernels.hip.  Why another one: the ILU(0) sweeps are a chain of
+// GMRES of krylov_kernels.hip.  Why another one: the ILU(0) sweeps are a chain of
 // ~15 dependent launches bound by gather latency (0.30 of the HBM roofline) and
 // a multicolour factorisation is a weak one (33 applications per solve at
 // CFL-sized steps on the 10 M-DoF workload; this one: 13).  It consists of

@@ -22,7 +22,7 @@ import numpy
 
 from . import reference
 
-# CSR-stream tiling (must match flow_amd/csrc/la_kernels.hip)
+# CSR-stream tiling (must match flow_amd/csrc/csr_stream.h)
 SPMV_ROWS_PER_BLOCK = 256
 SPMV_NNZ_PER_BLOCK = 1022     # LDS tile (1024) minus the alignment slack
 

@@ -165,7 +165,7 @@ class Comm(object):
                 os.environ.get('FLOW_AMD_RCCL_DIRECT', '0') == '1':
             self._bind_rccl()
 
-    # -- halos from neighbour to neighbour (flow_peer, csrc/la_kernels.hip) -----
+    # -- halos from neighbour to neighbour (flow_peer, csrc/shard_kernels.hip) -----
     def enable_peer(self, land_cap=1 << 20, spin_limit=2000000, selftest=24):
         '''Map the neighbours' landing buffers (hipIpc: xGMI peers on a node,
         or processes sharing one device in a rehearsal) and take the halos off

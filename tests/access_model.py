@@ -1,8 +1,8 @@
 # -*- coding: utf-8 -*-
 '''
 Host-side model of WHICH entries of the input vector `x` every CSR-stream kernel
-variant of flow_amd/csrc/la_kernels.hip dereferences, tile by tile (helper, not
-a test).  The strip-sharded solvers hand these kernels `x` as a window
+variant of flow_amd/csrc/la_kernels.hip and krylov_kernels.hip dereferences,
+tile by tile (helper, not a test).  The strip-sharded solvers hand these kernels `x` as a window
 [e0, e1) of a vector, addressed by global row through a base pointer shifted
 by -e0: an index outside the window is an address outside the allocation (a
 GPU memory-access fault when it lands on an unmapped page, a silent read of

@@ -5,7 +5,7 @@ CSR-stream products (helper, not a test): StreamTile / stream_rows_sum /
 stream_tile_pair_row_sum of flow_amd/csrc/csr_stream.h and the hand-inlined
 copy in spmv_stream_block2_kernel, behind flow_operator_apply (kinds 0, 1, 2,
 4), flow_operator_apply_block, the mass residuals (mass_kernels.hip) and the
-multigrid level kernels (la_kernels.hip).  The fp16 sibling is
+multigrid level kernels (krylov_kernels.hip).  The fp16 sibling is
 tests/fp16_stream_reference.py, whose Pattern, StubLayout, xcd_tile and
 comparator are reused here.
 
