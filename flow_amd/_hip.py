@@ -461,6 +461,7 @@ SYMBOLS = {
     'flow_assemble_heat_supg_source': [_P(MeshS), _P(SpaceS), _P(SpaceS), _VP,
                                        _D, _D, _P(CoefS), _VP, _VP, _VP, _VP],
     'flow_form_functional': [_P(MeshS), _P(FormS), _VP, _VP, _P(_D), _VP],
+    'flow_form_cell_values': [_P(MeshS), _P(FormS), _VP, _VP],
     'flow_form_load_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
     'flow_form_matrix': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
     'flow_form_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _VP, _VP, _VP],
@@ -470,6 +471,11 @@ SYMBOLS = {
                                    _P(_D), _VP],
     'flow_form_facet_values': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP, _VP,
                                _VP, _VP, _VP],
+    'flow_form_interior_facet_functional': [_P(MeshS), _P(FormS), _I, _VP, _VP,
+                                            _VP, _VP, _VP, _P(_D), _VP],
+    'flow_form_interior_facet_values': [_P(MeshS), _P(FormS), _I, _VP, _VP,
+                                        _VP, _VP, _VP],
+    'flow_facet_cell_shares': [_P(MeshS), _I, _VP, _VP, _D, _VP, _VP],
     'flow_form_facet_matrix': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _VP,
                                _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_form_facet_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _VP,

@@ -220,13 +220,43 @@ __device__ __forceinline__ double form_ext_op(int op, int a, double ra, double r
   }
 }
 
-template <int NF, bool FACET, bool EXT, class OUT>
+// The '-' cell of an interior facet, next to the '+' cell that the other
+// arguments of form_point_n describe (TWO = true, form_interior_facet_kernel):
+// geometry, vertex coordinates, the point's barycentric coordinates there, the
+// cell's own outward normal and the facet's length.
+struct FormMinus {
+  Geom g;
+  double X[3], Y[3];
+  double L[3];
+  double n0, n1;
+  double len;
+};
+
+// g of the side an instruction names.  Selects of values, entry by entry: the
+// side is wave-uniform, and a selected ADDRESS would be a run-time index
+// (facet_frame)
+__device__ __forceinline__ Geom side_geom(const Geom& p, const Geom& m, bool minus) {
+  Geom g;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    g.gl[i][0] = minus ? +m.gl[i][0] : +p.gl[i][0];
+    g.gl[i][1] = minus ? +m.gl[i][1] : +p.gl[i][1];
+  }
+  g.adet = minus ? +m.adet : +p.adet;
+  return g;
+}
+
+// TWO: the program of an interior facet.  FIELD, NORMAL and CELL carry a side
+// bit (FLOW_FORM_SIDE_*): set, the leaf is evaluated on the '-' cell *M, whose
+// field slots the kernel loaded from that cell; FACET_LEN exists.  Every other
+// instance passes TWO = false and compiles to what it was.
+template <int NF, bool FACET, bool EXT, bool TWO = false, class OUT>
 __device__ __forceinline__ void form_point_n(const flow_form& F,
                                              const double (&U)[NF > 0 ? NF : 1][6],
                                              const double X[3], const double Y[3],
                                              const Geom& g, const double L[3], int row,
                                              int nc, int c, double n0, double n1,
-                                             OUT& out) {
+                                             OUT& out, const FormMinus* M = nullptr) {
   FormRegs R = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int pc = 0; pc < F.nprog; ++pc) {
     int op = F.prog[4 * pc];
@@ -234,6 +264,40 @@ __device__ __forceinline__ void form_point_n(const flow_form& F,
     const int a = F.prog[4 * pc + 2], b = F.prog[4 * pc + 3];
     double v;
     bool tanh_op = false;
+    if constexpr (TWO) {
+      if (op == FLOW_FORM_OP_FACET_LEN) {
+        reg_set(R, dst, M->len);
+        continue;
+      }
+      if (op == FLOW_FORM_OP_FIELD) {
+        const bool minus = (b & FLOW_FORM_SIDE_FIELD) != 0;
+        const Geom gs = side_geom(g, M->g, minus);
+        const double Ls[3] = {minus ? +M->L[0] : +L[0], minus ? +M->L[1] : +L[1],
+                              minus ? +M->L[2] : +L[2]};
+        if constexpr (NF > 0) v = field_at<NF>(F, U, a, b & 3, Ls, gs);
+        else v = 0.0;
+        reg_set(R, dst, v);
+        continue;
+      }
+      if (op == FLOW_FORM_OP_NORMAL) {
+        const bool minus = (a & FLOW_FORM_SIDE_NORMAL) != 0;
+        const double m0 = minus ? +M->n0 : +n0, m1 = minus ? +M->n1 : +n1;
+        reg_set(R, dst, (a & 1) == 0 ? m0 : m1);
+        continue;
+      }
+      if (EXT && op == FLOW_FORM_OP_CELL) {
+        const bool minus = (a & FLOW_FORM_SIDE_CELL) != 0;
+        const Geom gs = side_geom(g, M->g, minus);
+        double Xs[3], Ys[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          Xs[i] = minus ? +M->X[i] : +X[i];
+          Ys[i] = minus ? +M->Y[i] : +Y[i];
+        }
+        reg_set(R, dst, form_ext_op(op, a & 3, 0.0, 0.0, 0.0, Xs, Ys, gs));
+        continue;
+      }
+    }
     if constexpr (EXT) {
       // tanh goes through the exp below; the others have a switch of their own
       tanh_op = op == FLOW_FORM_OP_TANH;
@@ -256,7 +320,8 @@ __device__ __forceinline__ void form_point_n(const flow_form& F,
         break;
       }
       case FLOW_FORM_OP_FIELD:
-        if constexpr (NF > 0) v = field_at<NF>(F, U, a, b, L, g);
+        // (TWO: taken above, with the side's geometry)
+        if constexpr (NF > 0 && !TWO) v = field_at<NF>(F, U, a, b, L, g);
         else v = 0.0;
         break;
       case FLOW_FORM_OP_EXPR: {
@@ -521,6 +586,111 @@ __global__ __launch_bounds__(kBlock) void form_facet_kernel(
     return;
   }
   scratch[k] = form_facet<NF, EXT>(F, nc, xy, c, lf);
+}
+
+// Interior facets (assemble(f*dS), flow_form_interior_facet_*).  A lane holds
+// TWO cells, but one U array: every (field, component, side) the program names
+// is a field slot of its own, and slot k is loaded from the cell of its side
+// (bit k of minus_slots set: the '-' cell).  Two FormCell<6> would be ~150
+// VGPRs of nodal values alone.
+template <int NF>
+__device__ __forceinline__ void load_form_fields_sides(const flow_form& F, int nc, int cp,
+                                                       int cm, int minus_slots,
+                                                       double (&U)[NF > 0 ? NF : 1][6]) {
+  if constexpr (NF > 0) {
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+      const int c = ((minus_slots >> k) & 1) ? cm : cp;
+      const double* f = F.field[k];
+      if (F.field_deg[k] == 1) {
+        const int* cd = F.cell_dofs[0];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) U[k][i] = f[cd[i * nc + c]];
+#pragma unroll
+        for (int i = 3; i < 6; ++i) U[k][i] = 0.0;
+      } else {
+        const int* cd = F.cell_dofs[1];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) U[k][i] = f[cd[i * nc + c]];
+      }
+    }
+  }
+}
+
+// One interior facet per lane: out[k] = the integral over facet k of the
+// list.  fplus / lplus: the '+' cell and the facet's local index in it;
+// fother = (cell- << 3) | (local- << 1) | flip, packed as adapt.facet_table
+// packs a neighbour.  The lane walks the rule's rows of local facet lplus on
+// the '+' cell and scales by that cell's facet length.  On '-' the barycentric
+// coordinates are zero at vertex local- and the '+' facet's pair on the facet's
+// two vertices, swapped where flip is set (the first vertex of the facet in
+// '-' is then the second in '+'); n('-') is the '-' cell's own facet_frame.  An
+// entry outside the mesh gives NaN, not a stray read.
+template <int NF, bool EXT>
+__global__ __launch_bounds__(kBlock) void form_interior_facet_kernel(
+    int nc, int nfacets, const int* __restrict__ fplus, const int* __restrict__ lplus,
+    const int* __restrict__ fother, int minus_slots, const double* __restrict__ xy,
+    const flow_form F, double* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nfacets) return;
+  const int cp = fplus[k], lp = lplus[k], packed = fother[k];
+  const int cm = packed >> 3, lm = (packed >> 1) & 3, flip = packed & 1;
+  if (cp < 0 || cp >= nc || lp < 0 || lp > 2 || packed < 0 || cm >= nc || lm > 2) {
+    out[k] = __builtin_nan("");
+    return;
+  }
+  const Geom gp = load_geom(xy, nc, cp);
+  FormMinus M;
+  M.g = load_geom(xy, nc, cm);
+  double X[3], Y[3];
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    X[v] = xy[v * nc + cp];
+    Y[v] = xy[(3 + v) * nc + cp];
+    M.X[v] = xy[v * nc + cm];
+    M.Y[v] = xy[(3 + v) * nc + cm];
+  }
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields_sides<NF>(F, nc, cp, cm, minus_slots, U);
+  const FacetFrame fp = facet_frame(gp, lp);
+  const FacetFrame fm = facet_frame(M.g, lm);
+  M.n0 = fm.n0;
+  M.n1 = fm.n1;
+  M.len = fp.len;
+  double total = 0.0;
+  for (int j = 0; j < F.nq; ++j) {
+    const int row = lp * F.nq + j;
+    const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    // the weights of the facet's first and second vertex in '+' ...
+    const double a0 = lp == 0 ? +L[1] : +L[0], a1 = lp == 2 ? +L[1] : +L[2];
+    // ... are those of its first and second vertex in '-', or the reverse
+    const double b0 = flip ? a1 : a0, b1 = flip ? a0 : a1;
+    M.L[0] = lm == 0 ? 0.0 : b0;
+    M.L[1] = lm == 0 ? b0 : (lm == 1 ? 0.0 : b1);
+    M.L[2] = lm == 2 ? 0.0 : b1;
+    double out0 = 0.0, out1 = 0.0;
+    FormOut2 o = {out0, out1};
+    form_point_n<NF, true, EXT, true>(F, U, X, Y, gp, L, row, nc, cp, fp.n0, fp.n1, o, &M);
+    total += F.rule[3 * row + 2] * fp.len * out0;
+  }
+  out[k] = total;
+}
+
+// flow_facet_cell_shares: one lane per cell, its three facets in the order
+// 0, 1, 2; a position of -1 (a boundary facet, or one not selected) is skipped
+__global__ __launch_bounds__(kBlock) void facet_cell_shares_kernel(
+    int nc, int nfacets, const int* __restrict__ position,
+    const double* __restrict__ values, double share, double* __restrict__ out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int p = position[static_cast<size_t>(i) * nc + c];
+    if (p >= 0 && p < nfacets) s += values[p];
+  }
+  out[c] = share * s;
 }
 
 // Wall distributions (flow_amd/fem/profile.py, flow_form_facet_values): one
@@ -1191,7 +1361,15 @@ __global__ __launch_bounds__(kBlock) void facet_gather_kernel(
 // slot the program writes (at least one, none twice; 12: at least one of the
 // first 9 and one of the last 3)
 static int check_form(const flow_form* F, int rows = 1, bool facet = false,
-                      bool points = false, int slots = 0, int* live = nullptr) {
+                      bool points = false, int slots = 0, int* live = nullptr,
+                      int* minus_slots = nullptr) {
+  // minus_slots != nullptr: the program of an interior facet (with facet =
+  // true).  There, and only there, FIELD / NORMAL / CELL may carry their side
+  // bit and FACET_LEN exists; EXPR does not (its tables are indexed by the
+  // rule's row of one cell).  *minus_slots = one bit per field slot that is
+  // read on the '-' cell; a slot is read on one side only
+  const bool interior = minus_slots != nullptr;
+  int plus = 0, minus = 0;
   FLOW_REQUIRE(F, "form");
   FLOW_REQUIRE(F->nprog >= 1 && F->nprog <= FLOW_FORM_MAX_PROGRAM,
                "form program length");
@@ -1226,10 +1404,18 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
     const int a = F->prog[4 * pc + 2], b = F->prog[4 * pc + 3];
     FLOW_REQUIRE((op >= FLOW_FORM_OP_CONST && op <= FLOW_FORM_OP_OUT) ||
                      (facet && op == FLOW_FORM_OP_NORMAL) ||
-                     (op >= FLOW_FORM_OP_LT && op <= FLOW_FORM_OP_CELL),
-                 facet ? "form opcode" : "form opcode (NORMAL: facet integrals only)");
+                     (op >= FLOW_FORM_OP_LT && op <= FLOW_FORM_OP_CELL) ||
+                     (interior && op == FLOW_FORM_OP_FACET_LEN),
+                 facet ? "form opcode (FACET_LEN: interior facets only)"
+                       : "form opcode (NORMAL: facet integrals only)");
     FLOW_REQUIRE(!points || op != FLOW_FORM_OP_EXPR,
                  "form opcode (EXPR: not at points)");
+    FLOW_REQUIRE(!interior || op != FLOW_FORM_OP_EXPR,
+                 "form opcode (EXPR: not on interior facets)");
+    // the side bits: legal on interior facets, out of range anywhere else
+    const int side_f = interior ? FLOW_FORM_SIDE_FIELD : 0;
+    const int side_n = interior ? FLOW_FORM_SIDE_NORMAL : 0;
+    const int side_c = interior ? FLOW_FORM_SIDE_CELL : 0;
     const bool reg_a = (op >= FLOW_FORM_OP_MOV && op <= FLOW_FORM_OP_OUT) ||
                        (op >= FLOW_FORM_OP_LT && op <= FLOW_FORM_OP_TANH);
     const bool reg_b = (op >= FLOW_FORM_OP_ADD && op <= FLOW_FORM_OP_POW) ||
@@ -1245,16 +1431,23 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
         FLOW_REQUIRE(a == 0 || a == 1, "form coordinate");
         break;
       case FLOW_FORM_OP_FIELD:
-        FLOW_REQUIRE(a >= 0 && a < F->nfield && b >= 0 && b <= 2, "form field operand");
+        FLOW_REQUIRE(a >= 0 && a < F->nfield && b >= 0 && (b & ~side_f) <= 2,
+                     "form field operand (a side bit: interior facets only)");
+        if (interior) {
+          if (b & side_f) minus |= 1 << a;
+          else plus |= 1 << a;
+        }
         break;
       case FLOW_FORM_OP_EXPR:
         FLOW_REQUIRE(a >= 0 && a < F->nexpr, "form expression index");
         break;
       case FLOW_FORM_OP_NORMAL:
-        FLOW_REQUIRE(a == 0 || a == 1, "form normal component");
+        FLOW_REQUIRE(a >= 0 && (a & ~side_n) <= 1,
+                     "form normal component (a side bit: interior facets only)");
         break;
       case FLOW_FORM_OP_CELL:
-        FLOW_REQUIRE(a >= 0 && a <= 2, "form cell quantity");
+        FLOW_REQUIRE(a >= 0 && (a & ~side_c) <= 2,
+                     "form cell quantity (a side bit: interior facets only)");
         break;
       case FLOW_FORM_OP_OUT:
         FLOW_REQUIRE(b >= 0 && b < F->nout, "form output");
@@ -1272,6 +1465,10 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
     FLOW_REQUIRE((wrote & ((1 << FLOW_FORM_SLOTS) - 1)) != 0 && (wrote >> FLOW_FORM_SLOTS) != 0,
                  "form writes no Jacobian slot or no residual slot");
   if (live) *live = wrote;
+  if (interior) {
+    FLOW_REQUIRE((plus & minus) == 0, "form field slot read on both sides");
+    *minus_slots = minus;
+  }
   return FLOW_OK;
 }
 
@@ -1279,7 +1476,8 @@ static int check_form(const flow_form* F, int rows = 1, bool facet = false,
 // instance of its kernel
 static bool form_is_extended(const flow_form* F) {
   for (int pc = 0; pc < F->nprog; ++pc)
-    if (F->prog[4 * pc] >= FLOW_FORM_OP_LT) return true;
+    if (F->prog[4 * pc] >= FLOW_FORM_OP_LT && F->prog[4 * pc] <= FLOW_FORM_OP_CELL)
+      return true;
   return false;
 }
 
@@ -1362,6 +1560,17 @@ static int launch_facets(const flow_mesh* mesh, const flow_form* F, int nfacets,
   return dispatch_form(F, [&](auto NF, auto EXT) {
     hipLaunchKernelGGL((form_facet_kernel<NF(), EXT()>), grid, dim3(kBlock), 0, st,
                        mesh->nc, nfacets, fcell, flocal, mesh->xy, *F, scratch);
+  });
+}
+
+static int launch_interior_facets(const flow_mesh* mesh, const flow_form* F, int nfacets,
+                                  const int* fplus, const int* lplus, const int* fother,
+                                  int minus_slots, double* out, hipStream_t st) {
+  const dim3 grid((nfacets + kBlock - 1) / kBlock);
+  return dispatch_form(F, [&](auto NF, auto EXT) {
+    hipLaunchKernelGGL((form_interior_facet_kernel<NF(), EXT()>), grid, dim3(kBlock), 0,
+                       st, mesh->nc, nfacets, fplus, lplus, fother, minus_slots,
+                       mesh->xy, *F, out);
   });
 }
 
@@ -1745,6 +1954,17 @@ extern "C" int flow_form_functional(const flow_mesh* mesh, const flow_form* form
   return sum_partials_host(work, nparts, result_host, st);
 }
 
+extern "C" int flow_form_cell_values(const flow_mesh* mesh, const flow_form* form,
+                                     double* out, void* stream) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "per-cell integrals on strips");
+  if ((rc = check_form(form))) return rc;
+  FLOW_REQUIRE(form->nout == 1, "a functional has one output");
+  FLOW_REQUIRE(out, "out pointer");
+  return launch_cells(mesh, form, 0, 0, mesh->nc, out, as_stream(stream));
+}
+
 extern "C" int flow_form_load_vector(const flow_mesh* mesh, const flow_space* V,
                                      const flow_form* form, double* scratch,
                                      double* b, void* stream) {
@@ -1809,6 +2029,71 @@ extern "C" int flow_form_facet_values(const flow_mesh* mesh, const flow_form* fo
   FLOW_REQUIRE(values, "values pointer");
   return launch_facet_values(mesh, form, nfacets, facet_cell, facet_local, facet_dest,
                              facet_flip, values, integrals, as_stream(stream));
+}
+
+// what the two interior-facet entry points ask; *minus_slots as check_form
+static int check_interior_facets(const flow_mesh* mesh, const flow_form* form,
+                                 int nfacets, int* minus_slots) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "interior-facet integrals on strips");
+  if ((rc = check_form(form, 3, true, false, 0, nullptr, minus_slots))) return rc;
+  FLOW_REQUIRE(form->nout == 1, "an interior-facet integrand has one output");
+  FLOW_REQUIRE(nfacets >= 0, "facet count");
+  return FLOW_OK;
+}
+
+extern "C" int flow_form_interior_facet_functional(
+    const flow_mesh* mesh, const flow_form* form, int nfacets, const int* facet_plus,
+    const int* local_plus, const int* facet_other, double* scratch, double* work,
+    double* result_host, void* stream) {
+  int minus_slots = 0;
+  int rc = check_interior_facets(mesh, form, nfacets, &minus_slots);
+  if (rc) return rc;
+  FLOW_REQUIRE(result_host, "result pointer");
+  if (nfacets == 0) {
+    *result_host = 0.0;
+    return FLOW_OK;
+  }
+  FLOW_REQUIRE(facet_plus && local_plus && facet_other, "facet lists");
+  FLOW_REQUIRE(scratch && work, "pointers");
+  hipStream_t st = as_stream(stream);
+  if ((rc = launch_interior_facets(mesh, form, nfacets, facet_plus, local_plus,
+                                   facet_other, minus_slots, scratch, st)))
+    return rc;
+  const int nparts = grid_for(nfacets, kBlock, kRedBlocks);
+  hipLaunchKernelGGL(form_sum_kernel, dim3(nparts), dim3(kBlock), 0, st, 0, nfacets,
+                     scratch, work);
+  FLOW_CHECK_LAUNCH();
+  return sum_partials_host(work, nparts, result_host, st);
+}
+
+extern "C" int flow_form_interior_facet_values(
+    const flow_mesh* mesh, const flow_form* form, int nfacets, const int* facet_plus,
+    const int* local_plus, const int* facet_other, double* out, void* stream) {
+  int minus_slots = 0;
+  const int rc = check_interior_facets(mesh, form, nfacets, &minus_slots);
+  if (rc) return rc;
+  if (nfacets == 0) return FLOW_OK;
+  FLOW_REQUIRE(facet_plus && local_plus && facet_other, "facet lists");
+  FLOW_REQUIRE(out, "out pointer");
+  return launch_interior_facets(mesh, form, nfacets, facet_plus, local_plus, facet_other,
+                                minus_slots, out, as_stream(stream));
+}
+
+extern "C" int flow_facet_cell_shares(const flow_mesh* mesh, int nfacets,
+                                      const int* position, const double* values,
+                                      double share, double* out, void* stream) {
+  const int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "facet shares on strips");
+  FLOW_REQUIRE(nfacets >= 0 && position && out && (nfacets == 0 || values),
+               "facet count / pointers");
+  hipLaunchKernelGGL(facet_cell_shares_kernel, dim3((mesh->nc + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0,
+                     as_stream(stream), mesh->nc, nfacets, position, values, share, out);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
 }
 
 extern "C" int flow_profile_cumsum(int ncurves, const int* curve_facets, int nrows,

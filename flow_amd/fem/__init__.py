@@ -28,6 +28,7 @@ from .forms import (                                            # noqa: F401
     conditional, lt, le, gt, ge, eq, ne, And, Or, Not, max_value, min_value,
     sign, tanh, CellVolume, Circumradius, CellDiameter, facet_arguments,
     vector_arguments, vector_derivatives, sym, tr, transpose, Identity, outer,
+    interior_facets, jump, avg, FacetArea,
     )
 from .points import Probes                                      # noqa: F401
 from .tracers import Tracers                                    # noqa: F401
@@ -59,7 +60,8 @@ def __getattr__(name):
     # host-only parts (meshes, spaces, BC search) work without the library
     if name in ('project', 'interpolate', 'errornorm', 'norm', 'assemble_mass',
                 'assemble_stiffness', 'integral', 'project_magnitude', 'ops',
-                'assemble', 'assemble_system', 'solve'):
+                'assemble', 'assemble_system', 'solve',
+                'interior_facet_integrals', 'cell_indicator'):
         import importlib
         ops = importlib.import_module('.ops', __name__)
         return ops if name == 'ops' else getattr(ops, name)

@@ -42,7 +42,32 @@ SubDomain.mark.  FacetNormal(mesh) (the outward unit normal, degree 0) is
 legal only in ds integrands.  The rule is reference.line_rule(q) on each
 edge (Gauss-Legendre, exact for degree q).  Rank-0 forms add and subtract:
 assemble(f*dx + g*ds(1) - h*ds(2)) sums the parts in the order written.
-No interior facets (dS), no facet integrals on strips.
+No facet integrals on strips.
+
+Interior facets are OFF by default, as they always were (NotImplementedError);
+`interior_facets(True)` switches them on like facet_arguments.  Then `f*dS`,
+dS(mesh), dS(k) and Measure('dS', domain=mesh, subdomain_data=markers)(k) are
+forms of integral_type 'interior_facet' over the edges with two cells (those
+whose marker equals k), f('+') / f('-') restricts any scalar, vector or
+tensor expression to a side -- pushed down to the leaves at once: ('side',
+leaf, s) --, jump(f) = f('+') - f('-'), jump(f, n) = f('+')*n('+') +
+f('-')*n('-') (scalar f: a vector) or the same with dot (vector f: a scalar),
+avg(f) = (f('+') + f('-'))/2, FacetArea(mesh) the facet's length (degree 0).
+'+' is the cell with the SMALLER cell index.  UFL's apply_restrictions rules:
+values of Functions, SpatialCoordinate, Constants, numbers and FacetArea may
+stand unrestricted under dS (continuous: evaluated on '+'); gradients,
+FacetNormal, CellVolume, Circumradius and CellDiameter must be restricted
+(ValueError naming the operand); a restriction under dx / ds, or of a
+restricted expression, is a ValueError.  Every (Function, component, side) is
+one of the MAX_FIELDS field slots of a program: u('+') and u('-') are two.
+Refused (NotImplementedError, switch on or off): test and trial functions
+under dS (restricted arguments need twice the coefficient slots and, for rank
+2, a sparsity pattern wider than the space's), Expression operands and the
+SUPG tau under dS (their tables are indexed by the rule's row of one cell),
+FacetArea under dx / ds, derivative of a dS part, strips.  The degree is
+estimated, and replaced by dS(degree=q) or form_compiler_parameters, as for
+ds.  ops.assemble (a float; signed sums mix dx, ds and dS),
+ops.interior_facet_integrals and ops.cell_indicator are the device calls.
 
 Arguments: `v = TestFunction(V)`, `u = TrialFunction(V)` on a scalar P1 / P2
 space are operands like any other (degree = the space's), so `grad`, `dot`,
@@ -98,7 +123,7 @@ themselves -- derivative() with respect to a vector Function and solve(F ==
 0): `vector_derivatives(True)` switches those on (below).
 Not supported (NotImplementedError): arguments on mixed spaces, test
 and trial functions of different spaces (a vector test function with a scalar
-trial function included), dS, action / adjoint.  lhs / rhs
+trial function included), arguments under dS, action / adjoint.  lhs / rhs
 also split ONE integrand that holds terms of
 both ranks, (source - dot(conv, grad(u))) * tau * dot(conv, grad(v)) * dx, by
 linearity, as UFL does; assembling such an integrand unsplit stays a
@@ -197,7 +222,13 @@ OPS = {name: i for i, name in enumerate((
     'const', 'coord', 'field', 'expr', 'mov', 'add', 'sub', 'mul', 'div', 'pow',
     'neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos', 'out', 'normal',
     # 19 up: conditions (1.0 | 0.0), the select, clips, tanh, cell geometry
-    'lt', 'le', 'eq', 'ne', 'select', 'min', 'max', 'sign', 'tanh', 'cell'))}
+    'lt', 'le', 'eq', 'ne', 'select', 'min', 'max', 'sign', 'tanh', 'cell',
+    # 29: the length of the facet (interior-facet programs only)
+    'facet_len'))}
+# interior-facet programs: the side bit of the leaf instructions ('+' clear,
+# '-' set) -- FIELD in b (beside the derivative 0..2), NORMAL in a (beside the
+# component 0..1), CELL in a (beside the quantity 0..2); include/flow_hip.h
+SIDE_BIT = {'field': 4, 'normal': 2, 'cell': 4}
 UNARY = ('neg', 'abs', 'sqrt', 'exp', 'ln', 'sin', 'cos')
 BINARY = ('add', 'sub', 'mul', 'div', 'pow')
 # the extended vocabulary: nodes like the above that no argument may sit under
@@ -222,6 +253,10 @@ CELL_QUANTITIES = ('volume', 'circumradius', 'diameter')
 # (op, a[, b]) for UNARY_EXT / BINARY_EXT; (op, a, b) for COMPARE, worth 1.0
 # or 0.0 (And = mul, Or = max, Not = 1 - c of those); ('cond', c, t, f), t
 # where c != 0 and f elsewhere -- a select, the untaken value is not read.
+# ('side', leaf, s): the leaf (a field, n, cell or arg leaf) restricted to the
+# '+' (s = 0) or '-' (s = 1) cell of an interior facet -- a leaf itself: the
+# restriction is pushed down to the leaves when it is applied; ('farea',
+# mesh): the length of the facet (dS only).
 # Objects inside compare by identity.
 ZERO = ('num', 0.0)
 ONE = ('num', 1.0)
@@ -291,9 +326,12 @@ def s_cond(c, t, f):
 def s_diff(n, d):
     '''d n / d x_d (d = 0, 1), by the chain rule.'''
     k = n[0]
-    if k in ('num', 'const', 'n', 'cell', 'sign'):
+    if k in ('num', 'const', 'n', 'cell', 'sign', 'farea'):
         # (the normal: constant on a facet; cell geometry: on a cell)
         return ZERO
+    if k == 'side':                     # (grad(u('+')) is grad(u)('+'))
+        inner_d = s_diff(n[1], d)
+        return inner_d if _is_num(inner_d) else ('side', inner_d, n[2])
     if k == 'cond':                     # (the condition is not differentiated)
         return s_cond(n[1], s_diff(n[2], d), s_diff(n[3], d))
     if k in ('max', 'min'):
@@ -549,6 +587,11 @@ class FormExpr(object):
     def T(self):
         return transpose(self)
 
+    def __call__(self, side):
+        '''f('+') / f('-'): the restriction to a side of an interior facet
+        (interior_facets(True)); see restricted().'''
+        return restricted(self, side)
+
     def dx(self, i):
         if i not in (0, 1):
             raise IndexError('dx(%r): the mesh is 2-D' % (i,))
@@ -606,7 +649,7 @@ def _has_lattice(obj):
 
 def is_form_operand(obj):
     return isinstance(obj, (FormExpr, Function, Constant, Expression, Measure,
-                            Condition)) or _has_lattice(obj)
+                            Condition, _InteriorFacets)) or _has_lattice(obj)
 
 
 def _binary(op, a, b):
@@ -1294,10 +1337,182 @@ def quadrature_scheme(*params):
 
 _INTEGRAL_TYPES = {'dx': 'cell', 'cell': 'cell', 'ds': 'exterior_facet',
                    'exterior_facet': 'exterior_facet'}
+_INTERIOR_TYPES = ('dS', 'interior_facet')
+_MEASURE_NAMES = {'cell': 'dx', 'exterior_facet': 'ds', 'interior_facet': 'dS'}
 
 
 def _is_mesh(obj):
     return hasattr(obj, 'num_cells') and hasattr(obj, 'bfacets')
+
+
+class interior_facets(_Switch):
+    '''The switch of interior-facet integrals: dS, Measure('dS'), jump, avg,
+    FacetArea and the restrictions f('+') / f('-').  Off by default: each of
+    them stays the NotImplementedError it was.  `interior_facets(True)`
+    switches them on at once, for the process; `.previous` is the setting it
+    replaced, and as a context manager it restores that on exit.
+    `interior_facets.enabled` is the current setting.'''
+    enabled = False
+
+
+_INTERIOR_FACETS_OFF = (
+    'dS: interior-facet integrals (dS, jump, avg, FacetArea and the '
+    "restrictions ('+') / ('-')) are off by default (dx and ds are "
+    'supported); interior_facets(True) switches them on')
+
+
+def _need_interior_facets():
+    if not interior_facets.enabled:
+        raise NotImplementedError(_INTERIOR_FACETS_OFF)
+
+
+# -- restrictions, jump, avg ---------------------------------------------------
+# The '+' cell of an interior facet is the one with the SMALLER cell index,
+# the '-' cell the other (Mesh.interior_facets).  UFL's apply_restrictions
+# rules: values of P1 / P2 Functions, SpatialCoordinate, Constants, numbers
+# and FacetArea are continuous and may stand unrestricted under dS (they are
+# evaluated on '+'); gradients of fields, FacetNormal, CellVolume,
+# Circumradius and CellDiameter must be restricted.
+_SIDES = {'+': 0, '-': 1}
+_LEAF_NAMES = {'n': 'FacetNormal', 'expr': 'an Expression',
+               'arg': 'a test or trial function'}
+
+
+def _leaf_name(leaf):
+    '''What the user wrote, for a message.'''
+    if leaf[0] == 'field':
+        name = getattr(leaf[1], 'name', None)
+        name = name() if callable(name) else name
+        what = 'a Function' if not name else 'the Function %r' % (name,)
+        return what if leaf[3] == 0 else 'the gradient (grad, div, curl, ' \
+            '.dx) of ' + what
+    if leaf[0] == 'cell':
+        return ('CellVolume', 'Circumradius', 'CellDiameter')[leaf[2]]
+    return _LEAF_NAMES.get(leaf[0], leaf[0])
+
+
+def _restrict(n, s):
+    k = n[0]
+    if k == 'side':
+        raise ValueError('a restriction of a restricted expression: %s is '
+                         "already restricted to ('%s')"
+                         % (_leaf_name(n[1]), '+-'[n[2]]))
+    if k in NONLEAF:
+        return (k,) + tuple(_restrict(c, s) if isinstance(c, tuple) else c
+                            for c in n[1:])
+    if k in ('num', 'const', 'x', 'farea'):
+        return n            # (the same on both sides)
+    return ('side', n, s)
+
+
+def restricted(f, side):
+    '''f('+') / f('-') of a scalar, vector or tensor: every leaf that lives
+    on a cell (field values and gradients, FacetNormal, cell geometry) is
+    restricted to that side of the interior facet; numbers, Constants,
+    SpatialCoordinate and FacetArea are the same on both.'''
+    _need_interior_facets()
+    if side not in _SIDES:
+        raise ValueError("a restriction is ('+') or ('-'), got %r" % (side,))
+    f = as_form(f)
+    s = _SIDES[side]
+    return FormExpr(_map(lambda n: _restrict(n, s), f.comps, f.shape),
+                    f.shape, f.deg, f.mesh)
+
+
+def jump(f, n=None):
+    """jump(f) = f('+') - f('-'); jump(f, n) = f('+')*n('+') + f('-')*n('-')
+    for a scalar f (a vector), dot(f('+'), n('+')) + dot(f('-'), n('-')) for a
+    vector f (a scalar)."""
+    _need_interior_facets()
+    f = as_form(f)
+    if n is None:
+        return restricted(f, '+') - restricted(f, '-')
+    n = as_form(n)
+    if n.shape != (2,):
+        raise ValueError('jump(f, n): n is the FacetNormal')
+    if not f.shape:
+        return restricted(f, '+') * restricted(n, '+') \
+            + restricted(f, '-') * restricted(n, '-')
+    if f.shape != (2,):
+        raise ValueError('jump(f, n) of a tensor of shape %r: f is a scalar '
+                         'or a vector' % (f.shape,))
+    return dot(restricted(f, '+'), restricted(n, '+')) \
+        + dot(restricted(f, '-'), restricted(n, '-'))
+
+
+def avg(f):
+    """(f('+') + f('-')) / 2."""
+    _need_interior_facets()
+    f = as_form(f)
+    return (restricted(f, '+') + restricted(f, '-')) / 2
+
+
+def FacetArea(mesh):
+    '''The length of the facet: a scalar of degree 0, dS integrands only.'''
+    _need_interior_facets()
+    if not _is_mesh(mesh):
+        raise TypeError('FacetArea takes a mesh (got %r)' % (type(mesh),))
+    return FormExpr(('farea', mesh), (), 0, mesh)
+
+
+def side_leaves(n, found=None):
+    '''[(leaf, side)] of a scalar tree: every leaf, with the side (0 | 1) it
+    is restricted to or None.'''
+    found = [] if found is None else found
+    if n[0] == 'side':
+        found.append((n[1], n[2]))
+    elif n[0] in NONLEAF:
+        for c in n[1:]:
+            if isinstance(c, tuple):
+                side_leaves(c, found)
+    else:
+        found.append((n, None))
+    return found
+
+
+def _check_no_sides(tree, where):
+    '''dx, ds, points, projections: no restriction, no FacetArea.'''
+    for leaf, side in side_leaves(tree):
+        if side is not None:
+            raise ValueError(
+                "a restriction ('+') / ('-') is defined on interior facets "
+                'only: %s is restricted in %s' % (_leaf_name(leaf), where))
+        if leaf[0] == 'farea':
+            raise NotImplementedError(
+                'FacetArea in %s: it is provided on interior facets (dS) only'
+                % where)
+
+
+def _interior_integrand(n):
+    '''The tree of a dS integrand with the continuous operands that stand
+    unrestricted evaluated on '+'; ValueError, naming the operand, for one
+    that must be restricted.'''
+    k = n[0]
+    if k == 'side':
+        leaf = n[1]
+    elif k in NONLEAF:
+        return (k,) + tuple(_interior_integrand(c) if isinstance(c, tuple)
+                            else c for c in n[1:])
+    else:
+        leaf = n
+    if leaf[0] == 'arg':
+        raise NotImplementedError(
+            'test and trial functions under dS: restricted arguments need '
+            'twice the coefficient slots and, for rank 2, a sparsity pattern '
+            "wider than the space's (DG and interior-penalty matrices are "
+            'out of scope)')
+    if leaf[0] == 'expr':
+        raise NotImplementedError(
+            'Expression operands and the SUPG tau under dS: their tables are '
+            "indexed by the rule's row of ONE cell; interpolate the "
+            'Expression into a Function')
+    if k == 'side' or leaf[0] in ('num', 'const', 'x', 'farea'):
+        return n
+    if leaf[0] == 'field' and leaf[3] == 0:
+        return ('side', leaf, 0)
+    raise ValueError(
+        "%s is discontinuous across an interior facet: restrict it, ('+') or "
+        "('-'), or use jump / avg, in a dS integrand" % _leaf_name(leaf))
 
 
 class facet_arguments(_Switch):
@@ -1325,11 +1540,15 @@ class Measure(object):
 
     def __init__(self, integral_type='dx', domain=None,
                  subdomain_id='everywhere', metadata=None, subdomain_data=None):
-        if integral_type not in _INTEGRAL_TYPES:
+        if integral_type in _INTERIOR_TYPES and interior_facets.enabled:
+            self.integral_type = 'interior_facet'
+        elif integral_type not in _INTEGRAL_TYPES:
             raise NotImplementedError(
                 'integral type %r: only dx (cells) and ds (exterior facets) '
-                'are supported' % (integral_type,))
-        self.integral_type = _INTEGRAL_TYPES[integral_type]
+                'are supported; dS (interior facets) after '
+                'interior_facets(True)' % (integral_type,))
+        else:
+            self.integral_type = _INTEGRAL_TYPES[integral_type]
         self.mesh = domain
         self.subdomain_id = subdomain_id
         self.metadata = dict(metadata or {})
@@ -1348,7 +1567,7 @@ class Measure(object):
         if degree is not None:
             md['quadrature_degree'] = degree
         return Measure(
-            'dx' if self.integral_type == 'cell' else 'ds',
+            _MEASURE_NAMES[self.integral_type],
             domain if domain is not None else self.mesh,
             self.subdomain_id if subdomain_id is None else subdomain_id, md,
             self.subdomain_data if subdomain_data is None else subdomain_data)
@@ -1358,6 +1577,16 @@ class Measure(object):
         if f.shape:
             raise ValueError('only scalar integrands can be integrated: the '
                              'integrand has shape %r' % (f.shape,))
+        if self.integral_type == 'interior_facet':
+            tree = _interior_integrand(f.comps)
+            mesh = _join_mesh(f.mesh, self.mesh)
+            if self.subdomain_data is not None:
+                mesh = _join_mesh(mesh, self.subdomain_data.mesh)
+            return Form(FormExpr(tree, (), f.deg, f.mesh), mesh,
+                        self.metadata, 'interior_facet', self.subdomain_id,
+                        self.subdomain_data)
+        _check_no_sides(f.comps, 'a %s integral'
+                        % _MEASURE_NAMES[self.integral_type])
         if self.integral_type == 'cell':
             check_no_normal(f, 'a dx integral')
             return Form(f, _join_mesh(f.mesh, self.mesh), self.metadata)
@@ -1380,13 +1609,19 @@ ds = Measure('ds')
 
 
 class _InteriorFacets(object):
-    '''dS: interior-facet integrals are not supported.'''
+    """dS: the measure of the interior facets, Measure('dS'), once
+    interior_facets(True) has switched it on; the NotImplementedError it
+    always was until then."""
 
-    def _refuse(self, *args, **kwargs):
-        raise NotImplementedError('dS: interior-facet integrals are not '
-                                  'supported (dx and ds are)')
+    def _measure(self):
+        _need_interior_facets()
+        return Measure('dS')
 
-    __call__ = __rmul__ = _refuse
+    def __call__(self, *args, **kwargs):
+        return self._measure()(*args, **kwargs)
+
+    def __rmul__(self, other):
+        return self._measure().__rmul__(other)
 
 
 dS = _InteriorFacets()
@@ -1654,6 +1889,10 @@ def derivative(F, u, du=None):
                 % ('TestFunction', 'TrialFunction')[k])
     parts = []
     for sign, part in F.terms():
+        if part.integral_type == 'interior_facet':
+            raise NotImplementedError(
+                'derivative of a dS part: the result would hold test or '
+                'trial functions under dS')
         tree = s_gateaux(part.integrand.comps, u, k, V)
         if _is_num(tree, 0.0):
             continue
@@ -1713,8 +1952,12 @@ class Program(object):
     Expression components (Expression, i), in slot order.'''
 
     def __init__(self, trees, facet=False, point=False, slots=None,
-                 nout=None, shared=()):
-        '''facet: the program runs on exterior facets, where the normal
+                 nout=None, shared=(), interior=False):
+        '''interior: the program runs on interior facets (dS), where a lane
+        holds two cells: restricted leaves and FacetArea exist (ValueError
+        otherwise), Expression leaves do not; every (Function, component,
+        side) takes a field slot of its own, `field_sides` is the side of
+        each.  facet: the program runs on exterior facets, where the normal
         exists (ValueError if a tree reads it otherwise).  point: it runs at
         located points (Probes, u(x)), where neither the normal nor
         Expression leaves exist (their lattices are tabulated at the rule's
@@ -1731,6 +1974,14 @@ class Program(object):
         if point and any(has_leaf(t, 'expr') for t in trees):
             raise ValueError('Expression leaves cannot be evaluated at points: '
                              'interpolate the Expression into a Function')
+        if not interior:
+            for t in trees + [t for _, t in shared]:
+                _check_no_sides(t, 'a program of cells, exterior facets or '
+                                'points')
+        elif any(has_leaf(t, 'expr') for t in trees):
+            raise ValueError('Expression leaves cannot be evaluated on '
+                             'interior facets')
+        facet = facet or interior
         if not facet and any(has_normal(t) for t in trees):
             raise ValueError('FacetNormal is defined on exterior facets only: '
                              'integrate over ds')
@@ -1742,6 +1993,8 @@ class Program(object):
         self.code = []
         self.consts = []
         self.fields = []
+        # (interior: 0 '+' | 1 '-' per field slot; else None)
+        self.field_sides = [] if interior else None
         self.exprs = []
         self.nregs = 0
         for r, t in shared:
@@ -1794,7 +2047,8 @@ class Program(object):
     def need(n):
         '''Registers the tree needs (Sethi-Ullman).'''
         k = n[0]
-        if k in ('num', 'const', 'x', 'field', 'expr', 'n', 'reg', 'cell'):
+        if k in ('num', 'const', 'x', 'field', 'expr', 'n', 'reg', 'cell',
+                 'side', 'farea'):
             return 1
         if k in UNARY + UNARY_EXT:
             return Program.need(n[1])
@@ -1821,6 +2075,8 @@ class Program(object):
             self._emit('normal', base, n[1])
         elif k == 'reg':
             self._emit('mov', base, n[1])
+        elif k == 'field' and self.field_sides is not None:
+            self._gen_side(n, 0, base)      # (unrestricted: evaluated on '+')
         elif k == 'field':
             self._emit('field', base, self._slot(
                 self.fields, (n[1], n[2]), MAX_FIELDS, 'field components'),
@@ -1831,6 +2087,10 @@ class Program(object):
                 'Expression components'))
         elif k == 'cell':
             self._emit('cell', base, n[2])
+        elif k == 'farea':
+            self._emit('facet_len', base)
+        elif k == 'side':
+            self._gen_side(n[1], n[2], base)
         elif k in UNARY + UNARY_EXT:
             self._gen(n[1], base)
             self._emit(k, base, base)
@@ -1870,6 +2130,33 @@ class Program(object):
                 self._gen(b, base)
                 self._gen(a, base + 1)
                 self._emit(k, base, base + 1, base)
+
+    def _gen_side(self, leaf, s, base):
+        '''A leaf restricted to side s: the instruction of the leaf with the
+        side bit in its operand; a field component takes the slot of its
+        (Function, component, side).'''
+        k = leaf[0]
+        if k == 'field':
+            for slot, (key, side) in enumerate(zip(self.fields,
+                                                   self.field_sides)):
+                if key[0] is leaf[1] and key[1] == leaf[2] and side == s:
+                    break
+            else:
+                if len(self.fields) == MAX_FIELDS:
+                    raise ProgramLimit(
+                        'the integrand needs more than %d field components '
+                        "(u('+') and u('-') are two): the limit is %d"
+                        % (MAX_FIELDS, MAX_FIELDS))
+                slot = len(self.fields)
+                self.fields.append((leaf[1], leaf[2]))
+                self.field_sides.append(s)
+            self._emit('field', base, slot, leaf[3] | SIDE_BIT['field'] * s)
+        elif k == 'n':
+            self._emit('normal', base, leaf[1] | SIDE_BIT['normal'] * s)
+        elif k == 'cell':
+            self._emit('cell', base, leaf[2] | SIDE_BIT['cell'] * s)
+        else:
+            raise ValueError('%s cannot be restricted' % _leaf_name(leaf))
 
     def constant_values(self):
         '''The constants' current values (Constants may be re-assigned

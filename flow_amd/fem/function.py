@@ -364,7 +364,12 @@ class Function(_FormOperand):
         '''The value at a point, as dolfin's `u(x, y)`, `u(Point(x, y))`,
         `u((x, y))`, `u(numpy.array([x, y]))`: a float for a scalar field, a
         numpy (2,) array for a vector field; RuntimeError outside the mesh.
-        Through fem.Probes (flow_amd/fem/points.py), on the GPU.'''
+        Through fem.Probes (flow_amd/fem/points.py), on the GPU.
+        `u('+')` / `u('-')` -- one str argument -- is the restriction to a
+        side of an interior facet (forms.restricted; interior_facets(True)).'''
+        if len(x) == 1 and isinstance(x[0], str) and x[0] in ('+', '-'):
+            from . import forms
+            return forms.restricted(self, x[0])
         from .points import evaluate_function
         return evaluate_function(self, x)
 

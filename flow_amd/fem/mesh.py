@@ -215,6 +215,46 @@ class Mesh(object):
     def num_edges(self):
         return len(self.edges)
 
+    # -- interior facets (dS) --------------------------------------------------
+    def interior_facet_lists(self):
+        '''The edges with two cells, as a dict of arrays of one entry per such
+        edge, in ascending edge order: 'facets' (edge ids), 'cell_plus',
+        'local_plus', 'cell_minus', 'local_minus' (each side's cell and the
+        edge's local index in it) and 'flip'.  The '+' cell is the one with
+        the SMALLER cell index.  flip = 0 where the first vertex of the
+        facet in '-' is the first vertex of the facet in '+' (the vertices of
+        local facet k are k == 0 ? 1 : 0 and k == 2 ? 1 : 2), 1 where it is
+        the second -- adapt.facet_table's bit.  Built once per mesh.'''
+        held = self._cache.get('interior_facets')
+        if held is not None:
+            return held
+        nb = self.cell_neighbors.astype(numpy.int64)
+        ce = self.cell_edges.astype(numpy.int64)
+        cv = self.cell_vertices
+        cp, lp = numpy.nonzero(nb > numpy.arange(len(nb))[:, None])
+        edge = ce[cp, lp]
+        order = numpy.argsort(edge, kind='stable')
+        cp, lp, edge = cp[order], lp[order], edge[order]
+        cm = nb[cp, lp]
+        same = ce[cm] == edge[:, None]
+        assert (same.sum(axis=1) == 1).all()
+        lm = same.argmax(axis=1)
+        first = numpy.array([1, 0, 0])
+        flip = cv[cp, first[lp]] != cv[cm, first[lm]]
+        held = {'facets': edge.astype(numpy.int32),
+                'cell_plus': cp.astype(numpy.int32),
+                'local_plus': lp.astype(numpy.int32),
+                'cell_minus': cm.astype(numpy.int32),
+                'local_minus': lm.astype(numpy.int32),
+                'flip': flip.astype(numpy.int32)}
+        self._cache['interior_facets'] = held
+        return held
+
+    @property
+    def interior_facets(self):
+        '''(Ni,) ids of the edges with two incident cells, ascending.'''
+        return self.interior_facet_lists()['facets']
+
     def cell_bfacet_mask(self):
         '''Per cell: bit i set iff local facet i lies on the boundary.'''
         mask = numpy.zeros(self.num_cells(), dtype=numpy.int32)

@@ -1016,6 +1016,21 @@ def assemble(form, form_compiler_parameters=None):
     q = forms.check_degree(form.degree() if q is None else q)
     lib = _hip.lib()
     mesh = forms.form_mesh(form.integrand, form.mesh)
+    if form.integral_type == 'interior_facet':
+        fs, keep, sel = _interior_facet_job(form, mesh, q)
+        if sel.count == 0:          # (dS(99): exactly 0.0, nothing launched)
+            return 0.0
+        res = ctypes.c_double(0.0)
+        _hip.check(lib.flow_form_interior_facet_functional(
+            ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs), sel.count,
+            _hip.i32(sel.plus, sel.count, 'facet + cells'),
+            _hip.i32(sel.local, sel.count, 'facet + local indices'),
+            _hip.i32(sel.other, sel.count, 'facet - cells'),
+            _hip.f64(scratch(mesh, max(sel.count, 1))),
+            _hip.f64(work(_hip.REDUCE_WORK)), ctypes.byref(res), _hip.stream()
+            ))
+        del keep
+        return res.value
     facet = form.integral_type == 'exterior_facet'
     prog = forms.compile_trees([form.integrand.comps], facet=facet)
     fs, keep = _form_struct(prog, mesh, q, facet)
@@ -1991,6 +2006,189 @@ def facet_lists(mesh, markers=None, subdomain_id='everywhere'):
     held = (None if everywhere else markers, version, cells, local, nf)
     cache[key] = held
     return held[2:]
+
+
+InteriorFacetLists = collections.namedtuple(
+    'InteriorFacetLists', 'plus local other count positions cell_positions')
+
+
+def interior_facet_lists(mesh, markers=None, subdomain_id='everywhere'):
+    '''The interior facets a dS integral runs over: device int32 arrays
+    `plus`, `local` (the '+' cell -- the smaller cell index -- and the
+    facet's local index in it) and `other` ((cell- << 3) | (local- << 1) |
+    flip, as adapt.facet_table packs a neighbour), their `count`, and for the
+    cell gather `positions` (host, one entry per EDGE of the mesh: the
+    facet's place in the selection or -1) and `cell_positions` (device
+    (3*nc,): entry [i*nc + c] = positions[cell_edges[c][i]]).  Every interior
+    facet for subdomain_id 'everywhere', else those whose marker equals
+    subdomain_id, in Mesh.interior_facets order.  Cached on the mesh against
+    the markers' version like facet_lists; an empty selection holds no device
+    array.'''
+    everywhere = subdomain_id in (None, 'everywhere')
+    if markers is None and not everywhere:
+        raise ValueError('dS(%r) needs markers: Measure(\'dS\', domain=mesh, '
+                         'subdomain_data=markers)' % (subdomain_id,))
+    if markers is not None and markers.mesh is not mesh:
+        raise ValueError('the facet markers belong to another mesh')
+    cache = mesh._cache.setdefault('interior_facet_lists', {})
+    key = (None if everywhere else id(markers),
+           None if everywhere else subdomain_id, str(device.get()))
+    version = None if everywhere else markers.version
+    held = cache.get(key)
+    if held is not None and held[0] is (None if everywhere else markers) \
+            and held[1] == version:
+        return held[2]
+    lists = mesh.interior_facet_lists()
+    facets = lists['facets']
+    if everywhere:
+        sel = numpy.arange(len(facets))
+    else:
+        sel = numpy.nonzero(markers.array()[facets] == subdomain_id)[0]
+    count = len(sel)
+    positions = numpy.full(mesh.num_edges(), -1, dtype=numpy.int32)
+    positions[facets[sel]] = numpy.arange(count, dtype=numpy.int32)
+    plus = local = other = cellpos = None
+    if count:
+        nc = mesh.num_cells()
+        if nc >= 1 << 28:
+            raise ValueError('the interior facet list packs cell indices '
+                             'below 2**28; the mesh has %d cells' % nc)
+        packed = (lists['cell_minus'][sel].astype(numpy.int64) << 3) \
+            | (lists['local_minus'][sel].astype(numpy.int64) << 1) \
+            | lists['flip'][sel]
+        plus = device.to_device(lists['cell_plus'][sel].astype(numpy.int32))
+        local = device.to_device(lists['local_plus'][sel].astype(numpy.int32))
+        other = device.to_device(packed.astype(numpy.int32))
+        cellpos = device.to_device(numpy.ascontiguousarray(
+            positions[mesh.cell_edges].T.reshape(-1)))
+    if len(cache) >= 32:
+        cache.clear()
+    out = InteriorFacetLists(plus, local, other, count, positions, cellpos)
+    cache[key] = (None if everywhere else markers, version, out)
+    return out
+
+
+def _form_degree(form, form_compiler_parameters=None):
+    from . import forms
+    q = forms._quadrature_degree(form.metadata)
+    if q is None:
+        q = forms._quadrature_degree(form_compiler_parameters)
+    return forms.check_degree(form.degree() if q is None else q)
+
+
+def _interior_facet_job(form, mesh, q):
+    '''(flow_form, keepalive, InteriorFacetLists) of one dS part.'''
+    from . import forms
+    prog = forms.compile_trees([form.integrand.comps], interior=True)
+    fs, keep = _form_struct(prog, mesh, q, True)
+    sel = interior_facet_lists(mesh, form.subdomain_data, form.subdomain_id)
+    return fs, keep, sel
+
+
+def _interior_part(form, what):
+    from . import forms
+    if not isinstance(form, forms.Form) or isinstance(form, forms.FormSum) \
+            or form.integral_type != 'interior_facet':
+        raise TypeError('%s takes one dS form, f*dS (got %r)'
+                        % (what, type(form)))
+
+
+def interior_facet_integrals(form, out=None, form_compiler_parameters=None):
+    '''The integral of a dS form over each interior facet it selects: a
+    device fp64 array with one entry per selected facet, in
+    Mesh.interior_facets order (a new one, or `out`, which is returned).  One
+    launch, enqueued on the package's stream: nothing synchronises.  Their
+    sum is assemble(form) up to the order of the additions.'''
+    _interior_part(form, 'interior_facet_integrals')
+    from . import forms
+    _no_strips('interior_facet_integrals')
+    mesh = forms.form_mesh(form.integrand, form.mesh)
+    fs, keep, sel = _interior_facet_job(
+        form, mesh, _form_degree(form, form_compiler_parameters))
+    if out is None:
+        out = device.empty(sel.count)
+    elif getattr(out, 'shape', None) != (sel.count,):
+        raise ValueError('out: a device fp64 tensor of shape (%d,)'
+                         % sel.count)
+    if sel.count:
+        _hip.check(_hip.lib().flow_form_interior_facet_values(
+            ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs), sel.count,
+            _hip.i32(sel.plus, sel.count, 'facet + cells'),
+            _hip.i32(sel.local, sel.count, 'facet + local indices'),
+            _hip.i32(sel.other, sel.count, 'facet - cells'),
+            _hip.f64(out, sel.count, 'out'), _hip.stream()))
+    del keep
+    return out
+
+
+def cell_indicator(form, share=0.5, out=None, form_compiler_parameters=None):
+    '''Per-cell values of a rank-0 form, or signed sum, of dx and dS parts: a
+    device fp64 array (nc,) (a new one, or `out`), which feeds fem.mark
+    unchanged.  A dx part gives every cell its own integral (stage 1 of the
+    functional).  A dS part gives every cell `share` times the integral of
+    each of its selected interior facets, added in the order of its local
+    facets 0, 1, 2: 0.5 is what avg(w)*f*dS gives for a DG0 test function w,
+    1.0 is Kelly's convention (JumpIndicator's).  The parts are added in the
+    order written.  Enqueued; no atomics, the same bits on every call.  ds
+    parts are not provided.'''
+    from . import forms
+    if not isinstance(form, forms.Form):
+        raise TypeError('cell_indicator takes a form (got %r)' % (type(form),))
+    _no_strips('cell_indicator')
+    if form.rank != 0:
+        raise ValueError('cell_indicator takes a form without test or trial '
+                         'functions')
+    lib = _hip.lib()
+    share = float(share)
+    total = mesh = None
+    for sign, part in form.terms():
+        if part.integral_type == 'exterior_facet':
+            raise NotImplementedError(
+                'cell_indicator of a ds part: dx and dS parts only')
+        pmesh = forms.form_mesh(part.integrand, part.mesh)
+        if mesh is not None and pmesh is not mesh:
+            raise ValueError('the parts of the form live on different meshes')
+        mesh = pmesh
+        nc = mesh.num_cells()
+        if total is None:
+            if out is None:
+                out = device.empty(nc)
+            elif getattr(out, 'shape', None) != (nc,):
+                raise ValueError('out: a device fp64 tensor of shape (%d,)'
+                                 % nc)
+        # (a first part of sign +1 lands in `out` itself, the others in a
+        # spare that is added to it)
+        direct = total is None and sign == 1.0
+        dest = out if direct else device.empty(nc)
+        if part.integral_type == 'interior_facet':
+            sel = interior_facet_lists(mesh, part.subdomain_data,
+                                       part.subdomain_id)
+            vals = interior_facet_integrals(
+                part, form_compiler_parameters=form_compiler_parameters)
+            if sel.count == 0:
+                _hip.fill(dest, 0.0)
+            else:
+                _hip.check(lib.flow_facet_cell_shares(
+                    ctypes.byref(mesh_struct(mesh)), sel.count,
+                    _hip.i32(sel.cell_positions, 3 * nc, 'cell positions'),
+                    _hip.f64(vals, sel.count, 'facet integrals'), share,
+                    _hip.f64(dest, nc, 'out'), _hip.stream()))
+        else:
+            q = _form_degree(part, form_compiler_parameters)
+            prog = forms.compile_trees([part.integrand.comps])
+            fs, keep = _form_struct(prog, mesh, q)
+            _hip.check(lib.flow_form_cell_values(
+                ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs),
+                _hip.f64(dest, nc, 'out'), _hip.stream()))
+            del keep
+        if not direct:
+            if total is None:
+                _hip.fill(out, 0.0)
+            axpby(sign, dest, 1.0, out)
+        total = out
+    if total is None:
+        raise ValueError('cell_indicator: the form has no parts')
+    return out
 
 
 def facet_map_host(mesh, layout, rank, markers=None,

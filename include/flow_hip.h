@@ -1152,6 +1152,19 @@ int flow_assemble_magnitude(const flow_mesh* mesh, const flow_space* W, int mode
 #define FLOW_FORM_OP_SIGN 26
 #define FLOW_FORM_OP_TANH 27
 #define FLOW_FORM_OP_CELL 28
+/* Interior facets (flow_form_interior_facet_*): a lane holds the two cells of
+ * its facet, '+' (the smaller cell index) and '-'.  The leaf instructions carry
+ * a side bit -- clear '+', set '-' -- in an operand bit the other entry points
+ * keep at zero (they refuse it): FIELD in b beside the derivative, NORMAL in a
+ * beside the component, CELL in a beside the quantity.  Every (field,
+ * component, side) is a field slot of its own, loaded from the cell of its
+ * side; a slot is read on one side only.  COORD is the point itself.
+ *   facet_len  r[dst] = the length of the facet (interior facets only)
+ * A program without a side bit and without facet_len is what it always was. */
+#define FLOW_FORM_OP_FACET_LEN 29
+#define FLOW_FORM_SIDE_FIELD 4
+#define FLOW_FORM_SIDE_NORMAL 2
+#define FLOW_FORM_SIDE_CELL 4
 typedef struct {
   int nprog;
   int prog[4 * FLOW_FORM_MAX_PROGRAM];     /* (op, dst, a, b) per instruction */
@@ -1181,6 +1194,12 @@ typedef struct {
 int flow_form_functional(const flow_mesh* mesh, const flow_form* form,
                          double* scratch, double* work, double* result_host,
                          void* stream);
+
+/* Stage 1 of flow_form_functional alone: out[c] = the integral of output 0
+ * over cell c (device, nc doubles), not summed.  Enqueued; nothing
+ * synchronises.  Not on strips. */
+int flow_form_cell_values(const flow_mesh* mesh, const flow_form* form, double* out,
+                          void* stream);
 
 /* assemble(f*ds): the integral of output 0 over a list of exterior facets,
  * facet k being local facet facet_local[k] (the edge opposite that vertex)
@@ -1224,6 +1243,47 @@ int flow_form_facet_values(const flow_mesh* mesh, const flow_form* form,
                            const int* facet_local, const int* facet_dest,
                            const int* facet_flip, double* values,
                            double* integrals, void* stream);
+
+/* assemble(f*dS): the integral of output 0 over a list of interior facets.
+ * Facet k is local facet local_plus[k] of its '+' cell facet_plus[k] and
+ * local facet j of its '-' cell n, with facet_other[k] = (n << 3) | (j << 1) |
+ * flip, flip = 0 where the first vertex of the facet in '-' is its first
+ * vertex in '+' (the vertices of local facet i are i == 0 ? 1 : 0 and i == 2 ?
+ * 1 : 2) and 1 where it is the second: what adapt.facet_table packs (device
+ * int32 arrays of nfacets entries).  One lane per facet walks the rows of
+ * local facet local_plus[k] of the rule (that of flow_form_facet_functional, 3*nq
+ * rows), runs the program once per point and scales by the facet's length in
+ * the '+' cell.  A leaf with its side bit set is evaluated on the '-' cell:
+ * barycentric coordinates zero at vertex j, the '+' facet's pair on the other
+ * two (swapped where flip is set), the normal that of the '-' cell itself.
+ * EXPR is refused.  An entry outside the mesh gives NaN for that facet.
+ * Fixed-order reduction as flow_form_functional, no atomics: bitwise
+ * reproducible.  nfacets == 0: 0.0, nothing launched.  Not on strips.
+ * scratch: nfacets doubles (scratch[k] = the integral over facet k); work:
+ * FLOW_REDUCE_WORK doubles. */
+int flow_form_interior_facet_functional(const flow_mesh* mesh, const flow_form* form,
+                                        int nfacets, const int* facet_plus,
+                                        const int* local_plus, const int* facet_other,
+                                        double* scratch, double* work,
+                                        double* result_host, void* stream);
+
+/* The same launch without the sum: out[k] = the integral over facet k (device,
+ * nfacets doubles).  Enqueued; nothing synchronises. */
+int flow_form_interior_facet_values(const flow_mesh* mesh, const flow_form* form,
+                                    int nfacets, const int* facet_plus,
+                                    const int* local_plus, const int* facet_other,
+                                    double* out, void* stream);
+
+/* Per-cell shares of per-facet values: one lane per cell c,
+ *     out[c] = share * sum_{i = 0, 1, 2} values[position[i*nc + c]],
+ * always in the order i = 0, 1, 2, with position[i*nc + c] the index in
+ * `values` of local facet i of cell c (the edge -> position map of a facet
+ * selection, gathered through the cell's edges on the host) or -1 (a boundary
+ * facet, or one not selected), which is skipped.  position: device int32,
+ * 3*nc; values: device, nfacets doubles; out: device, nc doubles.  No atomics. */
+int flow_facet_cell_shares(const flow_mesh* mesh, int nfacets, const int* position,
+                           const double* values, double share, double* out,
+                           void* stream);
 
 /* Running integrals along boundary curves: for every curve c < ncurves and
  * row r < nrows, out[r*nfacets + k] = integrals[r*nfacets + b] + ... +
