@@ -158,6 +158,109 @@ __device__ __forceinline__ double stream_tile_row_sum(
   return stream_rows_sum(r0, r1, rowptr, cols, vals, x, prod, early);
 }
 
+// The rows [r0, r1) of one workgroup on the tiles of the kernels that park two
+// products per nonzero (<= kTile2 - 2 nonzeros), for a 2x2-block operator (kind
+// 2: four value planes over the scalar pattern), as the lanes hold them between
+// the tile's own loads and a product with a component-blocked vector (x then y,
+// n apart): load() fetches the column pairs and the four planes' value pairs
+// once; gather(), park(), a barrier and sum() may then follow for several
+// vectors, each with two LDS planes of its own (the block product of
+// eigen_kernels.hip).  The per-nonzero expressions, the "own columns only" select
+// and the order of the row sums are those of spmv_stream_block2_kernel
+// (la_kernels.hip), so every vector has the bits of that kernel's product.
+struct StreamTile2 {
+  double2 vxx[kPairs2], vxy[kPairs2], vyx[kPairs2], vyy[kPairs2];
+  int2 c[kPairs2];   // the columns to gather: the tile's own, else its first
+  int a, b;          // the lane's row in the LDS planes: [a, b)
+  int npair;         // pairs of the tile
+
+  __device__ __forceinline__ void load(int r0, int r1, const int* __restrict__ rowptr,
+                                       const int* __restrict__ cols,
+                                       const double* __restrict__ pxx,
+                                       const double* __restrict__ pxy,
+                                       const double* __restrict__ pyx,
+                                       const double* __restrict__ pyy) {
+    const int k0 = rowptr[r0];
+    const int k1 = rowptr[r1];
+    const int ka = k0 & ~1;
+    const int r = r0 + threadIdx.x;
+    a = 0;
+    b = 0;
+    if (r < r1) {
+      a = rowptr[r] - ka;
+      b = rowptr[r + 1] - ka;
+    }
+    npair = (k1 - ka + 1) >> 1;
+    // (only the tile's own columns are dereferenced: StreamTile::gather)
+    const int safe = cols[k0 < k1 ? k0 : (k0 > 0 ? k0 - 1 : 0)];
+    const int2* __restrict__ c2p = reinterpret_cast<const int2*>(cols + ka);
+    const double2* __restrict__ qxx = reinterpret_cast<const double2*>(pxx + ka);
+    const double2* __restrict__ qxy = reinterpret_cast<const double2*>(pxy + ka);
+    const double2* __restrict__ qyx = reinterpret_cast<const double2*>(pyx + ka);
+    const double2* __restrict__ qyy = reinterpret_cast<const double2*>(pyy + ka);
+    const double2 zero = make_double2(0.0, 0.0);
+#pragma unroll
+    for (int j = 0; j < kPairs2; ++j) {
+      const int p = threadIdx.x + j * kBlock;
+      const bool ok = p < npair;
+      const int2 cc = ok ? c2p[p] : make_int2(safe, safe);
+      vxx[j] = ok ? qxx[p] : zero;
+      vxy[j] = ok ? qxy[p] : zero;
+      vyx[j] = ok ? qyx[p] : zero;
+      vyy[j] = ok ? qyy[p] : zero;
+      c[j].x = 2 * p >= k0 - ka ? cc.x : safe;
+      c[j].y = 2 * p + 1 < k1 - ka ? cc.y : safe;
+    }
+  }
+
+  // both components of x at the lane's nonzeros (u: the even, w: the odd entry
+  // of each pair; 0: component x, 1: component y)
+  struct Gathered {
+    double u0[kPairs2], u1[kPairs2], w0[kPairs2], w1[kPairs2];
+  };
+  __device__ __forceinline__ Gathered gather(const double* __restrict__ x,
+                                             int n) const {
+    Gathered g;
+#pragma unroll
+    for (int j = 0; j < kPairs2; ++j) {   // all gathers in flight before any use
+      g.u0[j] = x[c[j].x];
+      g.u1[j] = x[n + c[j].x];
+      g.w0[j] = x[c[j].y];
+      g.w1[j] = x[n + c[j].y];
+    }
+    return g;
+  }
+
+  // the lane's products into LDS (prod0, prod1: kTile2 doubles each)
+  __device__ __forceinline__ void park(const Gathered& g, double* __restrict__ prod0,
+                                       double* __restrict__ prod1) const {
+#pragma unroll
+    for (int j = 0; j < kPairs2; ++j) {
+      const int p = threadIdx.x + j * kBlock;
+      if (p < npair) {
+        const double2 axx = vxx[j], axy = vxy[j], ayx = vyx[j], ayy = vyy[j];
+        const double u0 = g.u0[j], u1 = g.u1[j];
+        const double w0 = g.w0[j], w1 = g.w1[j];
+        prod0[2 * p] = axx.x * u0 + axy.x * u1;
+        prod1[2 * p] = ayx.x * u0 + ayy.x * u1;
+        prod0[2 * p + 1] = axx.y * w0 + axy.y * w1;
+        prod1[2 * p + 1] = ayx.y * w0 + ayy.y * w1;
+      }
+    }
+  }
+
+  // the lane's two row sums out of the parked products (behind a barrier)
+  __device__ __forceinline__ double2 sum(const double* __restrict__ prod0,
+                                         const double* __restrict__ prod1) const {
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = a; k < b; ++k) {
+      s0 += prod0[k];
+      s1 += prod1[k];
+    }
+    return make_double2(s0, s1);
+  }
+};
+
 // The same tile with ONE value plane applied to both components of a
 // component-blocked vector (component stride xs): the two components' products
 // side by side as double2 in LDS (prod: kTile2 double2, 16 KB -- with the

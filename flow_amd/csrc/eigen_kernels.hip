@@ -17,6 +17,18 @@
 //                   so column j has the bits flow_operator_apply gives for it.
 //                   Traffic: 12 B per nonzero once instead of m times; the
 //                   gathers and the 8 n m B of Y are unchanged.
+//                   A of kind 2 (2x2 blocks over the scalar pattern, columns of
+//                   2 N entries, component-blocked): the same scheme on the
+//                   rowblocks2 tiles with StreamTile2 (csr_stream.h).  The
+//                   column pairs and the four planes' value pairs are loaded
+//                   once (36 B per nonzero once instead of m times); per chunk
+//                   the gathers of x[c], x[N + c] of all MC columns in flight,
+//                   the two products per nonzero parked in two LDS planes per
+//                   column (2 MC kTile2 doubles: 16 KB per column, so MC is 2
+//                   or 4), one barrier, both row sums per lane and column, one
+//                   barrier.  The expressions and the summation order are those
+//                   of spmv_stream_block2_kernel (la_kernels.hip), so column j
+//                   has the bits flow_operator_apply gives for it.
 //   flow_block_gram out[i*mb + j] = X[:, i] . Y[:, j]: ONE launch over (blocks
 //                   of n, chunks of 8 columns of X, columns of Y) that leaves
 //                   the block sums in work[b*ma*mb + i*mb + j], and the finishing
@@ -37,6 +49,10 @@ constexpr int kBlockMC = 2;     // columns per chunk of flow_operator_apply_bloc
                                 // (the fastest of 2, 4, 8 at every m: 16 KB of
                                 // LDS keeps 8 workgroups per CU; DESIGN.md,
                                 // fem.Eigenmodes)
+constexpr int kBlockMC2 = 2;    // the same for a 2x2-block operator (the faster of
+                                // 2, 4 at every m: 32 KB of LDS and 94 VGPRs
+                                // against 64 KB and 132; DESIGN.md,
+                                // fem.Eigenmodes, tools/eigen_lab.py --vector)
 constexpr int kMaxGridYZ = 65535;
 
 // columns j .. j + C of one tile: prod holds C planes of kTile doubles
@@ -90,6 +106,63 @@ __global__ __launch_bounds__(kBlock) void spmv_block_kernel(
 }
 static_assert(8 * kTile * sizeof(double) <= 65536, "LDS planes of the widest chunk");
 
+// columns j .. j + C of one tile of a 2x2-block operator: prod holds 2 C planes
+// of kTile2 doubles (column c: planes 2c and 2c + 1, the two components' products)
+template <int C>
+__device__ __forceinline__ void block2_chunk(
+    const StreamTile2& t, int n, int r, int r1, int j, const double* __restrict__ X,
+    size_t ldx, double* __restrict__ Y, size_t ldy, double* __restrict__ prod) {
+  StreamTile2::Gathered g[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c)      // every column's gathers before any use
+    g[c] = t.gather(X + static_cast<size_t>(j + c) * ldx, n);
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+    t.park(g[c], prod + 2 * c * kTile2, prod + (2 * c + 1) * kTile2);
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const double2 s = t.sum(prod + 2 * c * kTile2, prod + (2 * c + 1) * kTile2);
+    if (r < r1) {
+      double* __restrict__ y = Y + static_cast<size_t>(j + c) * ldy;
+      y[r] = s.x;
+      y[n + r] = s.y;
+    }
+  }
+}
+
+// full 2x2 blocks over one scalar pattern (kind 2): n rows of the pattern,
+// columns of X and Y of 2 n entries, component-blocked
+template <int MC>
+__global__ __launch_bounds__(kBlock) void spmv_block2_kernel(
+    int n, const int* __restrict__ rowptr, const int* __restrict__ cols,
+    const double* __restrict__ vxx, const double* __restrict__ vxy,
+    const double* __restrict__ vyx, const double* __restrict__ vyy,
+    const int* __restrict__ rowblocks, int m, const double* __restrict__ X,
+    size_t ldx, double* __restrict__ Y, size_t ldy) {
+  __shared__ double prod[2 * MC * kTile2];
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
+  const int r0 = rowblocks[tile];
+  const int r1 = rowblocks[tile + 1];
+  const int r = r0 + threadIdx.x;
+  StreamTile2 t;
+  t.load(r0, r1, rowptr, cols, vxx, vxy, vyx, vyy);
+  int j = 0;
+  for (; j + MC <= m; j += MC) {
+    block2_chunk<MC>(t, n, r, r1, j, X, ldx, Y, ldy, prod);
+    __syncthreads();   // the planes have been summed
+  }
+  // the last chunk holds fewer columns: its own instance (block-uniform)
+  switch (m - j) {
+    case 1: block2_chunk<1>(t, n, r, r1, j, X, ldx, Y, ldy, prod); break;
+    case 2: if (MC > 2) block2_chunk<2>(t, n, r, r1, j, X, ldx, Y, ldy, prod); break;
+    case 3: if (MC > 3) block2_chunk<3>(t, n, r, r1, j, X, ldx, Y, ldy, prod); break;
+    default: break;
+  }
+}
+static_assert(2 * 4 * kTile2 * sizeof(double) <= 65536,
+              "LDS planes of the widest chunk of a 2x2-block operator");
+
 // columns blockIdx.y*kChunk .. of X against column blockIdx.z of Y
 __global__ __launch_bounds__(kBlock) void block_gram_kernel(
     int n, int ma, const double* __restrict__ X, size_t ldx, int mb,
@@ -121,6 +194,14 @@ void launch_block(const flow_operator* A, int m, const double* X, size_t ldx, do
                      A->rowptr, A->cols, A->vals[0], A->rowblocks, m, X, ldx, Y, ldy);
 }
 
+template <int MC>
+void launch_block2(const flow_operator* A, int m, const double* X, size_t ldx,
+                   double* Y, size_t ldy, hipStream_t st) {
+  hipLaunchKernelGGL((spmv_block2_kernel<MC>), dim3(A->nblocks), dim3(kBlock), 0, st,
+                     A->n, A->rowptr, A->cols, A->vals[0], A->vals[1], A->vals[2],
+                     A->vals[3], A->rowblocks, m, X, ldx, Y, ldy);
+}
+
 }  // namespace
 }  // namespace flow
 
@@ -131,12 +212,15 @@ extern "C" int flow_operator_apply_block_chunk(const flow_operator* A, int m,
                                                size_t ldy, int mc, void* stream) {
   int rc = check_operator(A);
   if (rc) return rc;
-  FLOW_REQUIRE(A->kind == 0, "block product: a scalar operator (kind 0)");
+  FLOW_REQUIRE(A->kind == 0 || A->kind == 2,
+               "block product: a scalar or a 2x2-block operator (kind 0 or 2)");
+  const bool block2 = A->kind == 2;
   FLOW_REQUIRE(m >= 0, "block product: m");
-  FLOW_REQUIRE(mc == 0 || mc == 2 || mc == 4 || mc == 8, "block product: chunk");
+  FLOW_REQUIRE(mc == 0 || mc == 2 || mc == 4 || (mc == 8 && !block2),
+               "block product: chunk (2, 4; 8 for a scalar operator only)");
   if (m == 0) return FLOW_OK;
   FLOW_REQUIRE(X && Y, "block product pointers");
-  const size_t n = static_cast<size_t>(A->n);
+  const size_t n = static_cast<size_t>(A->n) * (block2 ? 2 : 1);
   FLOW_REQUIRE(ldx >= n && ldx % 2 == 0 && ldy >= n && ldy % 2 == 0,
                "block product: ldx, ldy >= n, even");
   FLOW_REQUIRE(aligned16(X) && aligned16(Y), "block product: X and Y 16-byte aligned");
@@ -144,6 +228,14 @@ extern "C" int flow_operator_apply_block_chunk(const flow_operator* A, int m,
                         static_cast<size_t>(m - 1) * ldx + n),
                "block product: Y overlaps X");
   hipStream_t st = as_stream(stream);
+  if (block2) {
+    if ((mc ? mc : kBlockMC2) == 2)
+      launch_block2<2>(A, m, X, ldx, Y, ldy, st);
+    else
+      launch_block2<4>(A, m, X, ldx, Y, ldy, st);
+    FLOW_CHECK_LAUNCH();
+    return FLOW_OK;
+  }
   switch (mc ? mc : kBlockMC) {
     case 2: launch_block<2>(A, m, X, ldx, Y, ldy, st); break;
     case 4: launch_block<4>(A, m, X, ldx, Y, ldy, st); break;

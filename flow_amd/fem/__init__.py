@@ -40,7 +40,7 @@ from .recovery import (                                         # noqa: F401
     GradientRecovery, recover_gradient, zz_indicator,
     )
 from .snapshots import Snapshots                                # noqa: F401
-from .eigen import Eigenmodes, eigensolve                       # noqa: F401
+from .eigen import Eigenmodes, eigensolve, vector_eigenmodes    # noqa: F401
 from .statistics import Statistics                              # noqa: F401
 from .distance import Distance, wall_distance                   # noqa: F401
 from .isolines import Isolines, isolines                        # noqa: F401

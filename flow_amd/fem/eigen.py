@@ -6,7 +6,9 @@ Poincare and Friedrichs constants -- dolfin's SLEPcEigenSolver, for the case
 it is mostly used for.
 
     E = Eigenmodes(a, m=None, bcs=None)     # rank-2 forms on one scalar P1 / P2
-    E = Eigenmodes.from_matrices(A, M, isbc=None)     # kind-0 Matrix objects
+                                            # (or vector: "Vector spaces" below)
+    E = Eigenmodes.from_matrices(A, M, isbc=None)     # Matrix objects, kind 0
+                                                      # (or both kind 2)
     r = E.solve(k, rtol=1e-8, maxit=200, guard=None, preconditioner='jacobi',
                 initial=None, error_on_nonconvergence=True)
     r.values, r.modes, r.residuals, r.iterations, r.converged
@@ -62,8 +64,34 @@ not accept is refused unless symmetric=True vouches for it), the smallest
 eigenvalues only (no shift-invert), b <= 32, not on strips.  Eigenvectors of
 clustered eigenvalues are accurate as a subspace, not one by one: compare
 subspaces (principal angles) there.
+
+Vector spaces.  vector_eigenmodes(True) (a process switch like
+vector_arguments, which the forms need as well; off: the NotImplementedError
+there was) lets a and m live on one P1 / P2 VectorFunctionSpace W: vibration
+modes of an elastic body, the vector Laplacian, Korn constants.  Component
+views and mixed spaces stay refused.  A and M are then kind-2 matrices (four
+value planes over the scalar pattern), every vector has 2N entries,
+component-blocked, and the column stride is 2N.  m=None is dot(u, v)*dx.
+bcs are conditions on W and on W.sub(i); both matrices go through
+symmetric_bc_blocks, and isbc / free have 2N entries in operator numbering.
+Matrix.apply_block streams all four planes once per launch (36 B per
+nonzero once instead of per column), every column with the bits of
+flow_operator_apply.  modes are vector Functions on W; initial takes vector
+Functions; rayleigh(u) takes 2N entries.  'jacobi' is the inverse diagonal of
+the planes A_xx and A_yy.  'two_level' is component-wise: z = [T_xx r_x ; T_yy
+r_y], each T_cc flow_two_level_apply with a CoarseSpace of the plane A_cc of
+the eliminated matrix, that component's half of the Dirichlet mask, and
+singular= "the component has no Dirichlet dof"; it is block-diagonal and SPD
+and ignores the coupling planes A_xy, A_yx.  Limits there: the mass matrix of
+dot(u, v)*dx is a kind-2 matrix whose off-diagonal planes are zero and are
+streamed all the same (the cost is accepted and not measured); a free body
+returns its three rigid-body modes as (numerically) zero eigenvalues;
+symmetric problems and the smallest eigenvalues only, k + guard <= 32, not on
+strips.
 '''
 import numpy
+
+from .forms import _Switch
 
 MAX_BLOCK = 32
 SEED = 20011
@@ -273,17 +301,21 @@ def host_eigensolve(A, M, free, k, rtol=1e-8, maxit=200, guard=None,
 # -- the device backend ---------------------------------------------------------------
 class DeviceBackend(object):
     '''The block operations of lobpcg on the device (see the module's text).
-    A, M: kind-0 Matrix objects after symmetric_bc_matrix; free: host boolean
-    mask; precondition(r, z): one column, device tensors of N entries.'''
+    A, M: Matrix objects of one kind (0, or 2 on a vector space) after the
+    symmetric elimination; free: host boolean mask; precondition(r, z): one
+    column, device tensors of A.size entries.'''
 
     # Matrix.apply_block against one flow_operator_apply per column: the
-    # block product is used from this many columns on (measured: DESIGN.md)
+    # block product is used from this many columns on (measured: DESIGN.md);
+    # BLOCK_FROM_2: the same for kind 2 (measured too: 0.95 at m = 1, 1.65 at
+    # m = 2, tools/eigen_lab.py --vector)
     BLOCK_FROM = 2
+    BLOCK_FROM_2 = 2
 
     def __init__(self, A, M, free, b, precondition):
         from .. import _hip, device
         self.A, self.M, self.b = A, M, b
-        self.n = n = A.layout.N
+        self.n = n = A.size
         self.ld = ld = n + (n & 1)
         self._T = precondition
         cols = 3 * b
@@ -312,7 +344,7 @@ class DeviceBackend(object):
         S, AS, MS = self.sets[self.cur]
         ld, o = self.ld, j0 * self.ld
         for Mat, Y in ((self.A, AS), (self.M, MS)):
-            if m >= self.BLOCK_FROM:
+            if m >= (self.BLOCK_FROM_2 if Mat.kind == 2 else self.BLOCK_FROM):
                 Mat.apply_block(S[o:], ld, m, Y[o:], ld)
             else:
                 for j in range(j0, j0 + m):
@@ -380,6 +412,18 @@ class DeviceBackend(object):
 
 
 # -- the public interface ---------------------------------------------------------------
+class vector_eigenmodes(_Switch):
+    '''The switch of Eigenmodes on a P1 / P2 VectorFunctionSpace (2x2-block
+    operators: vibration modes of an elastic body, the vector Laplacian).  Off
+    by default: Eigenmodes of forms on a vector space stays the
+    NotImplementedError it was.  `vector_eigenmodes(True)` switches it on at
+    once, for the process; `.previous` is the setting it replaced, and as a
+    context manager it restores that on exit.  `vector_eigenmodes.enabled` is
+    the current setting.  The forms are written with test and trial functions
+    on the vector space, so vector_arguments(True) is needed as well.'''
+    enabled = False
+
+
 def _no_strips():
     from .. import parallel
     if parallel.active():
@@ -413,13 +457,16 @@ def _check_forms(a, m, symmetric):
                     'written; LOBPCG takes symmetric problems only (pass '
                     'symmetric=True for a form that is symmetric all the '
                     'same)' % name)
-    if getattr(V, 'component', None) is None and V.dim == 2:
+    vector = getattr(V, 'component', None) is None and V.dim == 2
+    if vector and not vector_eigenmodes.enabled:
         raise NotImplementedError(
             'Eigenmodes of forms on a vector space (2x2-block operators) is '
-            'not implemented: LOBPCG runs on scalar matrices only')
-    if getattr(V, 'component', None) is not None or V.dim != 1 \
-            or V.degree not in (1, 2):
-        raise ValueError('a, m: forms on one scalar P1 or P2 space')
+            'not implemented unless fem.vector_eigenmodes(True) switches it '
+            'on: LOBPCG runs on scalar matrices only without it')
+    if getattr(V, 'component', None) is not None \
+            or (V.dim != 1 and not vector) or V.degree not in (1, 2):
+        raise ValueError('a, m: forms on one scalar P1 or P2 space, or with '
+                         'vector_eigenmodes(True) on one P1 or P2 vector space')
     return V
 
 
@@ -435,15 +482,20 @@ class EigenResult(object):
 
 
 class Eigenmodes(object):
-    '''The smallest eigenpairs of a == lambda m on one scalar P1 / P2 space;
-    see the module's text.'''
+    '''The smallest eigenpairs of a == lambda m on one scalar P1 / P2 space,
+    or with vector_eigenmodes(True) on one P1 / P2 VectorFunctionSpace (m
+    None: dot(u, v)*dx; conditions on W and on W.sub(i)); see the module's
+    text.'''
 
     def __init__(self, a, m=None, bcs=None, form_compiler_parameters=None,
                  symmetric=False):
         from . import forms, ops
         _no_strips()
         V = _check_forms(a, m, symmetric)
-        if m is None:
+        if m is None and V.dim == 2:
+            m = forms.dot(forms.TrialFunction(V), forms.TestFunction(V)) \
+                * forms.dx
+        elif m is None:
             m = forms.TrialFunction(V) * forms.TestFunction(V) * forms.dx
         _, _, mask = ops._scalar_bcs(bcs, V)
         A = ops.assemble(a, form_compiler_parameters)
@@ -452,13 +504,16 @@ class Eigenmodes(object):
 
     @classmethod
     def from_matrices(cls, A, M, isbc=None):
-        '''From assembled kind-0 Matrix objects of one layout; isbc: the
-        Dirichlet dofs as a boolean / 0-1 array of N entries (host or device),
-        or None.'''
+        '''From assembled Matrix objects of one layout, both scalar (kind 0)
+        or both 2x2-block (kind 2); isbc: the Dirichlet dofs as a boolean /
+        0-1 array of A.size entries (N, or 2N in operator numbering; host or
+        device), or None.'''
         from .. import device
         _no_strips()
-        if getattr(A, 'kind', None) != 0 or getattr(M, 'kind', None) != 0:
-            raise ValueError('A, M: scalar matrices (kind 0)')
+        kinds = (getattr(A, 'kind', None), getattr(M, 'kind', None))
+        if kinds not in ((0, 0), (2, 2)):
+            raise ValueError('A, M: two scalar matrices (kind 0) or two '
+                             '2x2-block matrices (kind 2)')
         if A.layout is not M.layout:
             raise ValueError('A, M: matrices of different layouts')
         mask = None
@@ -467,7 +522,7 @@ class Eigenmodes(object):
                 isinstance(isbc, (list, tuple)) else \
                 device.to_host(isbc).numpy()
             host = numpy.asarray(host).astype(bool)
-            if host.shape != (A.layout.N,):
+            if host.shape != (A.size,):
                 raise ValueError('isbc: one entry per dof')
             if host.any():
                 mask = device.to_device(host.astype(numpy.uint8))
@@ -480,14 +535,16 @@ class Eigenmodes(object):
         from . import ops
         self.V = V
         self.layout = A.layout
-        n = A.layout.N
+        n = A.size
         if mask is None:
             self.isbc = numpy.zeros(n, dtype=bool)
             self.A, self.M = A, M
         else:
             self.isbc = device.to_host(mask).numpy().astype(bool)
-            self.A = ops.symmetric_bc_matrix(A, mask)
-            self.M = ops.symmetric_bc_matrix(M, mask)
+            eliminate = ops.symmetric_bc_blocks if A.kind == 2 else \
+                ops.symmetric_bc_matrix
+            self.A = eliminate(A, mask)
+            self.M = eliminate(M, mask)
         self.free = ~self.isbc
         self._free_d = device.to_device(self.free.astype(numpy.float64))
         self._dinv = None
@@ -507,19 +564,31 @@ class Eigenmodes(object):
         from .. import _hip, device
         from . import ops
         self._jacobi()
+        n = self.layout.N
         if self._coarse is None:
-            C = ops.CoarseSpace(
-                self.A, isbc=self.isbc if self.isbc.any() else None,
-                singular=not self.isbc.any())
-            self._coarse = (C, device.zeros(2 * C.struct.lda + 2))
-        C, cwork = self._coarse
-        dinv, n = self._dinv, self.layout.N
+            # one scalar coarse space per component: on a vector space the
+            # diagonal planes A_xx (0) and A_yy (3) of the eliminated matrix,
+            # each with its half of the Dirichlet mask (the coupling planes
+            # are ignored: z = [T_xx r_x ; T_yy r_y], block-diagonal and SPD)
+            self._coarse = []
+            for c, p in enumerate((0, 3) if self.A.kind == 2 else (0,)):
+                Ac = self.A if self.A.kind == 0 else ops.Matrix(
+                    self.layout, 0, self.A.vals[p * self.A.stride:
+                                                (p + 1) * self.A.stride])
+                isbc = self.isbc[c * n:(c + 1) * n]
+                C = ops.CoarseSpace(Ac, isbc=isbc if isbc.any() else None,
+                                    singular=not isbc.any())
+                self._coarse.append((C, device.zeros(2 * C.struct.lda + 2)))
+        coarse, dinv = self._coarse, self._dinv
         lib = _hip.lib()
 
         def apply(r, z):
-            _hip.check(lib.flow_two_level_apply(
-                ctypes.byref(C.struct), _hip.f64(dinv, n), _hip.f64(r, n),
-                _hip.f64(z, n), _hip.f64(cwork), _hip.stream()))
+            for c, (C, cwork) in enumerate(coarse):
+                lo, hi = c * n, (c + 1) * n
+                _hip.check(lib.flow_two_level_apply(
+                    ctypes.byref(C.struct), _hip.f64(dinv[lo:hi], n),
+                    _hip.f64(r[lo:hi], n), _hip.f64(z[lo:hi], n),
+                    _hip.f64(cwork), _hip.stream()))
         return apply
 
     # -- the solve -------------------------------------------------------------------
@@ -535,7 +604,7 @@ class Eigenmodes(object):
         if preconditioner not in ('jacobi', 'two_level'):
             raise ValueError("preconditioner: 'jacobi' or 'two_level', not %r"
                              % (preconditioner,))
-        n = self.layout.N
+        n = self.A.size
         k, guard, b = check_block(k, guard, int(self.free.sum()))
         start = []
         for u in initial or []:
@@ -573,11 +642,12 @@ class Eigenmodes(object):
 
     def rayleigh(self, u):
         '''The Rayleigh quotient u^T A u / u^T M u of a Function (or a device
-        tensor of N entries) with the eliminated matrices.'''
+        tensor of N entries; 2N on a vector space) with the eliminated
+        matrices.'''
         from .. import device
         from . import ops
         x = getattr(u, 'data', u)
-        n = self.layout.N
+        n = self.A.size
         y = device.empty(n)
         num = ops.dot(x, self.A.apply(x, y))
         den = ops.dot(x, self.M.apply(x, y))

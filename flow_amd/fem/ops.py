@@ -186,19 +186,22 @@ class Matrix(object):
 
     def apply_block(self, X, ldx, m, Y, ldy, chunk=0):
         '''Y[:, j] = A X[:, j] for the first m columns of the column stores X
-        and Y (tensors, column strides ldx and ldy: >= N and even, the stores
-        16-byte aligned, Y not overlapping X): one launch that reads the
-        matrix once; every column has the bits of apply() on that column
-        (flow_operator_apply_block; scalar matrices only).  chunk: columns a
-        workgroup takes at a time (2, 4, 8; 0: the library's choice).'''
+        and Y (tensors, column strides ldx and ldy: >= self.size and even, the
+        stores 16-byte aligned, Y not overlapping X): one launch that reads
+        the matrix once; every column has the bits of apply() on that column
+        (flow_operator_apply_block).  Scalar matrices (kind 0: columns of N
+        entries) and 2x2-block matrices (kind 2: columns of 2N entries,
+        component-blocked, all four value planes read once); other kinds are
+        a ValueError.  chunk: columns a workgroup takes at a time (2, 4, and
+        for kind 0 also 8; 0: the library's choice).'''
         lib = _hip.lib()
-        if self.kind != 0:
-            raise ValueError('apply_block: a scalar matrix (kind 0), not kind '
-                             '%d' % self.kind)
+        if self.kind not in (0, 2):
+            raise ValueError('apply_block: a scalar or a 2x2-block matrix '
+                             '(kind 0 or 2), not kind %d' % self.kind)
         m = int(m)
         if m == 0:
             return Y
-        n = self.layout.N
+        n = self.size
         _hip.check(lib.flow_operator_apply_block_chunk(
             ctypes.byref(self.operator()), m,
             _hip.f64(X, (m - 1) * ldx + n, 'X'), ldx,

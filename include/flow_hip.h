@@ -1822,16 +1822,23 @@ int flow_combine(int n, int m, const double* X, size_t ldx, int r,
  * X + j*ldx, ld >= n and even, the store 16-byte aligned, the padding (entries
  * at and past n of a column) never read or written.
  *
- * Y[:, j] = A X[:, j], j < m, for a scalar operator (kind 0; other kinds are
- * refused).  ONE launch: a workgroup loads its CSR-stream tile of A once and
- * runs over the columns in chunks, so the 12 B per nonzero of A are read once
- * instead of m times.  Column j has exactly the bits flow_operator_apply gives
- * for that column (the same products, the same summation order per row).  Y
- * must not overlap X (refused).  m == 0: nothing is launched. */
+ * Y[:, j] = A X[:, j], j < m, for a scalar operator (kind 0: n = A->n) or a
+ * 2x2-block operator (kind 2: n = 2 * A->n in every size check, a column holds
+ * component x then component y, A->rowblocks the tiles of the kernels that park
+ * two products per nonzero, as for flow_operator_apply); kinds 1, 3 and 4 are
+ * refused.  ONE launch: a workgroup loads its CSR-stream tile of A once and
+ * runs over the columns in chunks, so the 12 B per nonzero of A (kind 2: the
+ * 36 B of the four value planes and the columns) are read once instead of m
+ * times.  Column j has exactly the bits flow_operator_apply gives for that
+ * column (the same products, the same summation order per row).  No atomics:
+ * two calls give the same bits.  Y must not overlap X (refused).  m == 0:
+ * nothing is launched.  A refusal (code 2) launches nothing. */
 int flow_operator_apply_block(const flow_operator* A, int m, const double* X,
                               size_t ldx, double* Y, size_t ldy, void* stream);
 /* The same with the chunk width chosen by the caller (2, 4 or 8 columns; 0: the
- * library's own): for tools/eigen_lab.py.  The bits do not depend on it. */
+ * library's own): for tools/eigen_lab.py.  Kind 2 parks two LDS planes per
+ * column (16 KB): 2 or 4 columns, 8 is refused.  The bits do not depend on
+ * it. */
 int flow_operator_apply_block_chunk(const flow_operator* A, int m, const double* X,
                                     size_t ldx, double* Y, size_t ldy, int mc,
                                     void* stream);
