@@ -480,6 +480,13 @@ SYMBOLS = {
                                _I, _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_form_facet_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _VP,
                                _I, _VP, _VP, _VP, _VP, _VP, _VP],
+    'flow_form_cells_functional': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP,
+                                   _P(_D), _VP],
+    'flow_form_cells_values': [_P(MeshS), _P(FormS), _I, _VP, _VP, _VP],
+    'flow_form_cells_matrix': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _I,
+                               _VP, _VP, _VP, _VP, _VP, _VP],
+    'flow_form_cells_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _I,
+                               _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_form_block_matrix': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),
                                _VP, _VP, ctypes.c_size_t, _VP],
     'flow_form_block_vector': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),

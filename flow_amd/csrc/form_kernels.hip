@@ -1074,6 +1074,8 @@ __device__ __forceinline__ double own_basis(int b, const double (&phi)[NL],
 // in one pass over the rule (measured faster than a row or three
 // at a time with the program re-run per pass).  Per point and test derivative
 // b, t_j = sum_a w c_ba D_a phi_j first, then Ke[i][j] += D_b phi_i t_j.
+// (form_cells_matrix_kernel below restates this kernel over a cell list and
+// must give its bits: an edit here is an edit there)
 template <int NF, int DEG, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_matrix_kernel(
     int nc, const double* __restrict__ xy, const flow_form F, int live,
@@ -1118,7 +1120,9 @@ __global__ __launch_bounds__(kBlock) void form_matrix_kernel(
 }
 
 // be[i] = sum_q w_q |det J| sum_b c_b(x_q) D_b phi_i, to scratch[i*nc + c]
-// (the gather over vptr / vsrc sums it into the vector)
+// (the gather over vptr / vsrc sums it into the vector; form_cells_vector_kernel
+// below restates this kernel over a cell list and must give its bits: an edit
+// here is an edit there)
 template <int NF, int DEG, bool EXT>
 __global__ __launch_bounds__(kBlock) void form_vector_kernel(
     int nc, const double* __restrict__ xy, const flow_form F, int live,
@@ -1350,6 +1354,134 @@ __global__ __launch_bounds__(kBlock) void facet_gather_kernel(
     }
   }
   out[tg] = s;
+}
+
+// ---------------------------------------------------------------------------
+// Cell subdomains (assemble(f*dx(k)), flow_form_cells_*): the cell-list forms
+// of form_cell_kernel (TD = 0), form_matrix_kernel and form_vector_kernel.
+// Lane k of nsel takes c = cells[k], runs the arithmetic of the whole-mesh
+// kernel on cell c -- the same rule order, add_matrix_terms, the same handling
+// of the live mask -- and stores with stride nsel at position k; a list that
+// holds every cell in ascending order gives the bits of the whole-mesh kernel.
+// They are kernels of their own, not a parameter of the whole-mesh ones:
+// those are short of scalar registers (see the comments there), and a list
+// pointer and a count more would change their instances.  A list
+// entry outside [0, nc) gives NaN, not a stray read.
+// ---------------------------------------------------------------------------
+// BY_CELL = false: out[k] = the integral over cell cells[k] (the functional's
+// stage 1); true: out[cells[k]] (flow_form_cells_values: the caller zeroed
+// out, an entry outside the mesh is skipped)
+template <int NF, bool EXT, bool BY_CELL>
+__global__ __launch_bounds__(kBlock) void form_cells_kernel(
+    int nc, int nsel, const int* __restrict__ cells, const double* __restrict__ xy,
+    const flow_form F, double* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nsel) return;
+  const int c = cells[k];
+  if (c < 0 || c >= nc) {
+    if constexpr (!BY_CELL) out[k] = __builtin_nan("");
+    return;
+  }
+  double acc[2][6];
+#pragma unroll
+  for (int o = 0; o < 2; ++o)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[o][i] = 0.0;
+  out[BY_CELL ? c : k] = form_cell<NF, 0, EXT>(F, nc, xy, c, acc);
+}
+
+// Ke of cell cells[k] to scratch[(i*NL + j)*nsel + k]: form_matrix_kernel
+// over a list
+template <int NF, int DEG, bool EXT>
+__global__ __launch_bounds__(kBlock) void form_cells_matrix_kernel(
+    int nc, int nsel, const int* __restrict__ cells, const double* __restrict__ xy,
+    const flow_form F, int live, double* __restrict__ scratch) {
+  constexpr int NL = Elem<DEG>::NL;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nsel) return;
+  double* const dst = scratch + k;
+  const int c = cells[k];
+  if (c < 0 || c >= nc) {
+#pragma unroll
+    for (int ij = 0; ij < NL * NL; ++ij)
+      dst[static_cast<size_t>(ij) * nsel] = __builtin_nan("");
+    return;
+  }
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
+  double Ke[NL][NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i)
+#pragma unroll
+    for (int j = 0; j < NL; ++j) Ke[i][j] = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
+    const double w = F.rule[3 * q + 2] * C.g.adet;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlots<FLOW_FORM_SLOTS> out;
+#pragma unroll
+    for (int s = 0; s < FLOW_FORM_SLOTS; ++s) out.v[s] = 0.0;
+    form_point_n<NF, false, EXT>(F, C.U, C.X, C.Y, C.g, L, q, nc, c, 0.0, 0.0, out);
+    double phi[NL], dphi[NL][3], gphi[NL][2];
+    basis<DEG>(L, phi, dphi);
+    phys_grad<NL>(C.g, dphi, gphi);
+    // (the mask through an empty asm, as in form_matrix_kernel)
+    int m = live;
+    asm volatile("" : "+s"(m));
+    add_matrix_terms<NL>(m, 0, w, out.v, phi, gphi, Ke);
+  }
+#pragma unroll
+  for (int i = 0; i < NL; ++i)
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+      dst[static_cast<size_t>(i * NL + j) * nsel] = Ke[i][j];
+}
+
+// be of cell cells[k] to scratch[i*nsel + k]: form_vector_kernel over a list
+template <int NF, int DEG, bool EXT>
+__global__ __launch_bounds__(kBlock) void form_cells_vector_kernel(
+    int nc, int nsel, const int* __restrict__ cells, const double* __restrict__ xy,
+    const flow_form F, int live, double* __restrict__ scratch) {
+  constexpr int NL = Elem<DEG>::NL;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nsel) return;
+  const int c = cells[k];
+  if (c < 0 || c >= nc) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i)
+      scratch[static_cast<size_t>(i) * nsel + k] = __builtin_nan("");
+    return;
+  }
+  const Geom g = load_geom(xy, nc, c);
+  const double X[3] = {xy[0 * nc + c], xy[1 * nc + c], xy[2 * nc + c]};
+  const double Y[3] = {xy[3 * nc + c], xy[4 * nc + c], xy[5 * nc + c]};
+  double U[NF > 0 ? NF : 1][6];
+  load_form_fields<NF>(F, nc, c, U);
+  double be[NL];
+#pragma unroll
+  for (int i = 0; i < NL; ++i) be[i] = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
+    const double w = F.rule[3 * q + 2] * g.adet;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlots<3> out = {{0.0, 0.0, 0.0}};
+    form_point_n<NF, false, EXT>(F, U, X, Y, g, L, q, nc, c, 0.0, 0.0, out);
+    double phi[NL], dphi[NL][3], gphi[NL][2];
+    basis<DEG>(L, phi, dphi);
+    phys_grad<NL>(g, dphi, gphi);
+    // (EXT: the mask through an empty asm, as in form_vector_kernel)
+    int m = live;
+    if constexpr (EXT) asm volatile("" : "+s"(m));
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (((m >> b) & 1) == 0) continue;
+      const double s = w * out.v[b];
+#pragma unroll
+      for (int i = 0; i < NL; ++i) be[i] += s * arg_basis<NL>(b, phi, gphi, i);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NL; ++i) scratch[static_cast<size_t>(i) * nsel + k] = be[i];
 }
 
 // rows: the rule holds rows * nq points (1: cells; 3: the three local
@@ -1663,6 +1795,73 @@ static int facet_arguments(const flow_mesh* mesh, const flow_space* V,
   if ((rc = launch_facet_arguments<RANK>(mesh, V->deg, form, live, nfacets, facet_cell,
                                          facet_local, scratch, st)))
     return rc;
+  hipLaunchKernelGGL(facet_gather_kernel, dim3((ntargets + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, st, ntargets, map_targets, map_ptr, map_src,
+                     static_cast<int>(nsrc), scratch, RANK == 2 ? V->nnz : V->n, out);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+template <bool BY_CELL>
+static int launch_cell_list(const flow_mesh* mesh, const flow_form* F, int ncells,
+                            const int* cells, double* out, hipStream_t st) {
+  const dim3 grid((ncells + kBlock - 1) / kBlock);
+  return dispatch_form(F, [&](auto NF, auto EXT) {
+    hipLaunchKernelGGL((form_cells_kernel<NF(), EXT(), BY_CELL>), grid, dim3(kBlock), 0, st,
+                       mesh->nc, ncells, cells, mesh->xy, *F, out);
+  });
+}
+
+// what the two rank-0 cell-list entry points ask
+static int check_cell_list(const flow_mesh* mesh, const flow_form* form, int ncells) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "cell subdomains on strips");
+  if ((rc = check_form(form))) return rc;
+  FLOW_REQUIRE(form->nout == 1, "a functional has one output");
+  FLOW_REQUIRE(ncells >= 0, "cell count");
+  return FLOW_OK;
+}
+
+// flow_form_cells_matrix (RANK 2) / flow_form_cells_vector (RANK 1)
+template <int RANK>
+static int cells_arguments(const flow_mesh* mesh, const flow_space* V,
+                           const flow_form* form, int ncells, const int* cells,
+                           int ntargets, const int* map_targets, const int* map_ptr,
+                           const int* map_src, double* scratch, double* out,
+                           void* stream) {
+  // (the gather runs over the cell map, not over the space's own maps, as in
+  // facet_arguments)
+  int rc = check_argument_space(mesh, V, false, false);
+  if (rc) return rc;
+  FLOW_REQUIRE((RANK == 1 || V->nnz > 0) && V->cell_dofs, "space");
+  int live = 0;
+  if ((rc = check_form(form, 1, false, false, RANK == 2 ? FLOW_FORM_SLOTS : 3, &live)))
+    return rc;
+  FLOW_REQUIRE(ncells >= 0 && ntargets >= 0, "cell / target count");
+  if (ncells == 0 || ntargets == 0) return FLOW_OK;
+  const int nl = V->deg == 1 ? 3 : 6;
+  const long long nsrc = static_cast<long long>(ncells) * nl * (RANK == 2 ? nl : 1);
+  FLOW_REQUIRE(nsrc < (1LL << 31) - kBlock, "cell count (scratch entries)");
+  FLOW_REQUIRE(ntargets <= (RANK == 2 ? V->nnz : V->n) && ntargets <= nsrc,
+               "target count");
+  FLOW_REQUIRE(cells, "cell list");
+  FLOW_REQUIRE(map_targets && map_ptr && map_src, "cell contribution map");
+  FLOW_REQUIRE(scratch && out, "pointers");
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((ncells + kBlock - 1) / kBlock);
+  if constexpr (RANK == 2) {
+    rc = dispatch_form(form, V->deg, [&](auto NF, auto EXT, auto DEG) {
+      hipLaunchKernelGGL((form_cells_matrix_kernel<NF(), DEG(), EXT()>), grid, dim3(kBlock),
+                         0, st, mesh->nc, ncells, cells, mesh->xy, *form, live, scratch);
+    });
+  } else {
+    rc = dispatch_form(form, V->deg, [&](auto NF, auto EXT, auto DEG) {
+      hipLaunchKernelGGL((form_cells_vector_kernel<NF(), DEG(), EXT()>), grid, dim3(kBlock),
+                         0, st, mesh->nc, ncells, cells, mesh->xy, *form, live, scratch);
+    });
+  }
+  if (rc) return rc;
   hipLaunchKernelGGL(facet_gather_kernel, dim3((ntargets + kBlock - 1) / kBlock),
                      dim3(kBlock), 0, st, ntargets, map_targets, map_ptr, map_src,
                      static_cast<int>(nsrc), scratch, RANK == 2 ? V->nnz : V->n, out);
@@ -2281,6 +2480,57 @@ extern "C" int flow_form_facet_vector(const flow_mesh* mesh, const flow_space* V
                                       double* scratch, double* b, void* stream) {
   return facet_arguments<1>(mesh, V, form, nfacets, facet_cell, facet_local, ntargets,
                             map_targets, map_ptr, map_src, scratch, b, stream);
+}
+
+extern "C" int flow_form_cells_functional(const flow_mesh* mesh, const flow_form* form,
+                                          int ncells, const int* cells, double* scratch,
+                                          double* work, double* result_host,
+                                          void* stream) {
+  int rc = check_cell_list(mesh, form, ncells);
+  if (rc) return rc;
+  FLOW_REQUIRE(result_host, "result pointer");
+  if (ncells == 0) {
+    *result_host = 0.0;
+    return FLOW_OK;
+  }
+  FLOW_REQUIRE(cells, "cell list");
+  FLOW_REQUIRE(scratch && work, "pointers");
+  hipStream_t st = as_stream(stream);
+  if ((rc = launch_cell_list<false>(mesh, form, ncells, cells, scratch, st))) return rc;
+  const int nparts = grid_for(ncells, kBlock, kRedBlocks);
+  hipLaunchKernelGGL(form_sum_kernel, dim3(nparts), dim3(kBlock), 0, st, 0, ncells,
+                     scratch, work);
+  FLOW_CHECK_LAUNCH();
+  return sum_partials_host(work, nparts, result_host, st);
+}
+
+extern "C" int flow_form_cells_values(const flow_mesh* mesh, const flow_form* form,
+                                      int ncells, const int* cells, double* out,
+                                      void* stream) {
+  const int rc = check_cell_list(mesh, form, ncells);
+  if (rc) return rc;
+  if (ncells == 0) return FLOW_OK;
+  FLOW_REQUIRE(cells, "cell list");
+  FLOW_REQUIRE(out, "out pointer");
+  return launch_cell_list<true>(mesh, form, ncells, cells, out, as_stream(stream));
+}
+
+extern "C" int flow_form_cells_matrix(const flow_mesh* mesh, const flow_space* V,
+                                      const flow_form* form, int ncells, const int* cells,
+                                      int ntargets, const int* map_targets,
+                                      const int* map_ptr, const int* map_src,
+                                      double* scratch, double* vals, void* stream) {
+  return cells_arguments<2>(mesh, V, form, ncells, cells, ntargets, map_targets, map_ptr,
+                            map_src, scratch, vals, stream);
+}
+
+extern "C" int flow_form_cells_vector(const flow_mesh* mesh, const flow_space* V,
+                                      const flow_form* form, int ncells, const int* cells,
+                                      int ntargets, const int* map_targets,
+                                      const int* map_ptr, const int* map_src,
+                                      double* scratch, double* b, void* stream) {
+  return cells_arguments<1>(mesh, V, form, ncells, cells, ntargets, map_targets, map_ptr,
+                            map_src, scratch, b, stream);
 }
 
 extern "C" int flow_form_block_matrix(const flow_mesh* mesh, const flow_space* V,

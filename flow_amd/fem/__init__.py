@@ -9,7 +9,7 @@ GPU box, so the counterpart drivers import these names from here instead.
 from .mesh import (                                             # noqa: F401
     Mesh, Point, RectangleMesh, UnitSquareMesh, rectangle_with_hole,
     karman_channel, karman_channel_graded, heater_box, heater_box_coarse,
-    MeshFunction, FacetFunction,
+    MeshFunction, FacetFunction, CellFunction,
     )
 from .space import (                                            # noqa: F401
     FunctionSpace, VectorFunctionSpace, FiniteElement, VectorElement,
@@ -27,6 +27,7 @@ from .forms import (                                            # noqa: F401
     lhs, rhs, system, dS, derivative, action, adjoint,
     conditional, lt, le, gt, ge, eq, ne, And, Or, Not, max_value, min_value,
     sign, tanh, CellVolume, Circumradius, CellDiameter, facet_arguments,
+    cell_subdomains,
     vector_arguments, vector_derivatives, sym, tr, transpose, Identity, outer,
     interior_facets, jump, avg, FacetArea,
     )
@@ -35,7 +36,9 @@ from .tracers import Tracers                                    # noqa: F401
 from .transfer import Transfer                                  # noqa: F401
 from .projection import Projection, project_onto               # noqa: F401
 from .supermesh import Supermesh, mesh_errornorm                # noqa: F401
-from .adapt import JumpIndicator, jump_indicator, mark, refine  # noqa: F401
+from .adapt import (                                            # noqa: F401
+    JumpIndicator, jump_indicator, mark, refine, refined_markers,
+    )
 from .recovery import (                                         # noqa: F401
     GradientRecovery, recover_gradient, zz_indicator,
     )

@@ -339,6 +339,29 @@ def refine(mesh, markers=None):
     return out
 
 
+def refined_markers(markers, fine_mesh):
+    '''The cell MeshFunction `markers` of a mesh carried to the mesh
+    refine() made of it: every child cell gets its parent's value
+    (fine_mesh.parent_cell), so a material map survives estimate -> mark ->
+    refine.  Host only; needs forms.cell_subdomains(True) like every cell
+    MeshFunction.'''
+    from .mesh import MeshFunction
+    if getattr(markers, 'dim', None) != 2:
+        raise ValueError('refined_markers takes a cell MeshFunction (dim 2)')
+    parent = getattr(fine_mesh, 'parent_cell', None)
+    if parent is None:
+        raise ValueError('refined_markers: the fine mesh has no parent_cell '
+                         '(it is not the result of refine())')
+    if len(parent) != fine_mesh.num_cells() or (
+            len(parent) and parent.max() >= markers.size()):
+        raise ValueError('refined_markers: the fine mesh was not refined '
+                         'from the mesh of the markers')
+    out = MeshFunction(markers.value_type, fine_mesh, 2)
+    out.set_where(numpy.ones(fine_mesh.num_cells(), dtype=bool),
+                  markers.array()[parent])
+    return out
+
+
 def _snap_to_hole(mesh, points, cells, orient, split, nv):
     '''The midpoints of split boundary edges with both end points on the
     hole's circle, moved radially onto it; a midpoint some child cell of

@@ -24,8 +24,18 @@ class SubDomain(object):
     def mark(self, markers, value):
         '''Set `value` on the facets of a facet MeshFunction where `inside`
         holds at both vertices and the midpoint (facet_marked): on_boundary
-        is True on the exterior facets and False on the interior ones.'''
+        is True on the exterior facets and False on the interior ones.  On a
+        cell MeshFunction: the cells where `inside(x, False)` holds at the
+        three vertices and at the midpoint (dolfin's rule; a cell the
+        interface cuts stays as it was).'''
         mesh = markers.mesh
+        if markers.dim == 2:
+            p = mesh.points[mesh.cell_vertices]             # (nc, 3, 2)
+            sel = _eval_inside(self, p.mean(axis=1), False)
+            for v in range(3):
+                sel &= _eval_inside(self, p[:, v], False)
+            markers.set_where(sel, value)
+            return
         sel = numpy.zeros(mesh.num_edges(), dtype=bool)
         bf = mesh.bfacets
         interior = numpy.ones(mesh.num_edges(), dtype=bool)

@@ -1531,12 +1531,48 @@ _FACET_ARGUMENTS_OFF = (
     'facet_arguments(True); they are off by default')
 
 
+class cell_subdomains(_Switch):
+    '''The switch of cell subdomains: cell MeshFunctions (dim 2, CellFunction),
+    SubDomain.mark on them, and `dx(k)` / `dx(subdomain_data=markers)` /
+    Measure('dx', domain=mesh, subdomain_data=markers)(k) for forms of every
+    rank.  Off by default: each of them stays the NotImplementedError it was.
+    `cell_subdomains(True)` switches them on at once, for the process;
+    `.previous` is the setting it replaced, and as a context manager it
+    restores that on exit.  `cell_subdomains.enabled` is the current
+    setting.'''
+    enabled = False
+
+
+def _check_markers(integral_type, subdomain_id, markers):
+    '''ValueError for markers of the wrong kind (a facet MeshFunction under
+    dx, a cell one under ds / dS) and for a subdomain id that is not one
+    integer.'''
+    name = _MEASURE_NAMES[integral_type]
+    if markers is not None:
+        dim = getattr(markers, 'dim', None)
+        want = 2 if integral_type == 'cell' else 1
+        if dim != want and (want == 2 or dim == 2):
+            raise ValueError(
+                '%s takes a %s MeshFunction (dim %d) as subdomain_data: got '
+                '%s' % (name, 'cell' if want == 2 else 'facet', want,
+                        'a %s MeshFunction (dim %d)'
+                        % ('cell' if dim == 2 else 'facet', dim)
+                        if dim in (1, 2) else repr(type(markers))))
+    if integral_type == 'cell' and subdomain_id != 'everywhere' and (
+            isinstance(subdomain_id, bool)
+            or not isinstance(subdomain_id, numbers.Integral)):
+        raise ValueError('dx(%r): a cell subdomain id is one integer (tuples '
+                         'of ids are not provided)' % (subdomain_id,))
+
+
 class Measure(object):
     '''`dx` over the cells, `ds` over the exterior facets (UFL's
     Measure(integral_type, domain, subdomain_id, metadata, subdomain_data)).
     Calls: `dx(mesh)`, `dx(domain=mesh)`, `dx(metadata={...})`, `dx(degree=q)`;
     `ds` also takes a subdomain id, `ds(1)` / `ds(subdomain_id=1)`, which
-    selects the facets its subdomain_data (a facet MeshFunction) marks 1.'''
+    selects the facets its subdomain_data (a facet MeshFunction) marks 1.
+    With cell_subdomains(True) `dx` takes one too: `dx(1)` selects the cells
+    its subdomain_data (a cell MeshFunction) marks 1.'''
 
     def __init__(self, integral_type='dx', domain=None,
                  subdomain_id='everywhere', metadata=None, subdomain_data=None):
@@ -1554,9 +1590,11 @@ class Measure(object):
         self.metadata = dict(metadata or {})
         self.subdomain_data = subdomain_data
         if self.integral_type == 'cell' and (
-                subdomain_id != 'everywhere' or subdomain_data is not None):
+                subdomain_id != 'everywhere' or subdomain_data is not None) \
+                and not cell_subdomains.enabled:
             raise NotImplementedError('cell subdomains: dx integrates over '
                                       'the whole mesh')
+        _check_markers(self.integral_type, subdomain_id, subdomain_data)
 
     def __call__(self, subdomain_id=None, metadata=None, domain=None,
                  subdomain_data=None, degree=None):
@@ -1589,7 +1627,14 @@ class Measure(object):
                         % _MEASURE_NAMES[self.integral_type])
         if self.integral_type == 'cell':
             check_no_normal(f, 'a dx integral')
-            return Form(f, _join_mesh(f.mesh, self.mesh), self.metadata)
+            mesh = _join_mesh(f.mesh, self.mesh)
+            if self.subdomain_data is not None:
+                if mesh is not None and self.subdomain_data.mesh is not mesh:
+                    raise ValueError('the cell markers of dx belong to '
+                                     'another mesh than the integrand')
+                mesh = self.subdomain_data.mesh
+            return Form(f, mesh, self.metadata, 'cell', self.subdomain_id,
+                        self.subdomain_data)
         if has_leaf(f.comps, 'arg') and not facet_arguments.enabled:
             raise NotImplementedError(_FACET_ARGUMENTS_OFF)
         if has_leaf(f.comps, 'arg') and quadrature_scheme(

@@ -273,20 +273,29 @@ class MeshFunction(object):
     (dim = 1): one value per edge, in `mesh.edges` order.  SubDomain.mark
     fills it; `ds` reads it as subdomain_data.  `array()` is a read-only view:
     changes go through set_all / mark / item assignment, which bump
-    `version` (the device facet lists of ops.assemble are cached against it).'''
+    `version` (the device facet lists of ops.assemble are cached against it).
+    With forms.cell_subdomains(True) also for cells (dim = 2): one value per
+    cell, in cell order, which `dx` reads as subdomain_data (ops.cell_lists);
+    the same contract.'''
 
     def __init__(self, value_type, mesh, dim, value=0):
         if value_type not in _MESH_FUNCTION_TYPES:
             raise ValueError('MeshFunction value type %r: one of %s'
                              % (value_type, sorted(_MESH_FUNCTION_TYPES)))
-        if dim != 1:
+        if dim == 2:
+            from . import forms
+            cells = forms.cell_subdomains.enabled
+        else:
+            cells = False
+        if dim != 1 and not cells:
             raise NotImplementedError('MeshFunction of dimension %r: only '
                                       'facet markers (dim 1)' % (dim,))
         self.mesh = mesh
         self.dim = dim
         self.value_type = value_type
-        self._values = numpy.full(mesh.num_edges(), value,
-                                  dtype=_MESH_FUNCTION_TYPES[value_type])
+        self._values = numpy.full(
+            mesh.num_cells() if cells else mesh.num_edges(), value,
+            dtype=_MESH_FUNCTION_TYPES[value_type])
         self.version = 0
 
     def size(self):
@@ -309,7 +318,8 @@ class MeshFunction(object):
         self.version += 1
 
     def set_where(self, mask, value):
-        '''Set `value` on the facets of a boolean mask over the edges.'''
+        '''Set `value` on the facets of a boolean mask over the edges (on
+        the cells of a mask over the cells).'''
         self._values[mask] = value
         self.version += 1
 
@@ -317,6 +327,12 @@ class MeshFunction(object):
 def FacetFunction(value_type, mesh, value=0):
     '''MeshFunction(value_type, mesh, 1, value) under its older name.'''
     return MeshFunction(value_type, mesh, 1, value)
+
+
+def CellFunction(value_type, mesh, value=0):
+    '''MeshFunction(value_type, mesh, 2, value) under its older name
+    (forms.cell_subdomains(True) switches cell markers on).'''
+    return MeshFunction(value_type, mesh, 2, value)
 
 
 def _quad_cells(nx, ny, diagonal, vid, mid=None):

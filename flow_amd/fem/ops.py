@@ -1038,7 +1038,17 @@ def assemble(form, form_compiler_parameters=None):
     prog = forms.compile_trees([form.integrand.comps], facet=facet)
     fs, keep = _form_struct(prog, mesh, q, facet)
     res = ctypes.c_double(0.0)
-    if facet:
+    if is_cell_subdomain(form):
+        cells, nsel = cell_lists(mesh, form.subdomain_data, form.subdomain_id)
+        if nsel == 0:               # (dx(99): exactly 0.0, nothing launched)
+            return 0.0
+        _hip.check(lib.flow_form_cells_functional(
+            ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs), nsel,
+            _hip.i32(cells, nsel, 'cell list'),
+            _hip.f64(scratch(mesh, nsel)),
+            _hip.f64(work(_hip.REDUCE_WORK)), ctypes.byref(res), _hip.stream()
+            ))
+    elif facet:
         cells, local, nf = facet_lists(mesh, form.subdomain_data,
                                        form.subdomain_id)
         _hip.check(lib.flow_form_facet_functional(
@@ -1063,7 +1073,8 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
     Vector) or 2 (a Matrix; on a vector space a vector of 2N, a Matrix of
     kind 2), part by part: the programs of a part are compiled while the
     kernels of the part before run.  Scalar space: one launch per program
-    (_launch_dx, _facet_arguments), each result added at once; vector space:
+    (_launch_dx; a ds or dx(k) part: _facet_arguments / _cell_arguments into
+    a zeroed buffer), each result added at once; vector space:
     _block_part.  The first result of sign +1 IS the total, ds included.'''
     from . import forms
     from .function import Vector
@@ -1083,11 +1094,10 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
         # exceeds the limits of flow_form: forms.argument_programs)
         for prog in forms.argument_programs(table, rank, facet):
             fs, keep = _form_struct(prog, mesh, q, facet, scheme)
-            if facet:
+            if facet or is_cell_subdomain(part):
                 # (the gather writes its targets only: the rest stays zero)
                 out = value_plane(lay) if rank == 2 else device.zeros(lay.N)
-                _facet_arguments(mesh, lay, rank, fs, part.subdomain_data,
-                                 part.subdomain_id, out)
+                _selection_arguments(mesh, lay, rank, fs, part, out)
             elif rank == 2:
                 out = value_plane(lay)
                 _launch_dx(mesh, lay, 'matrix', fs, out, None)
@@ -1107,9 +1117,10 @@ def _block_part(part, table, rank, q, scheme, lay, mesh):
     '''One part of a form of arguments on a vector space into a fresh buffer:
     four planes (rank 2; plane 2 r + s the block of test component r and
     trial component s) or a vector of 2N.  A dx part is ONE block launch with
-    the programs of all its blocks (_launch_block_dx); a ds part goes block
-    by block, program by program, through _facet_arguments with the scalar
-    layout's facet_map into the block's plane or component (a further program
+    the programs of all its blocks (_launch_block_dx); a ds part, and a
+    dx(k) part, goes block by block, program by program, through
+    _facet_arguments / _cell_arguments with the scalar layout's facet_map /
+    cell_map into the block's plane or component (a further program
     of a block into a zeroed buffer of its own, then added).'''
     from . import forms
     facet = part.integral_type == 'exterior_facet'
@@ -1120,7 +1131,7 @@ def _block_part(part, table, rank, q, scheme, lay, mesh):
     tags = tuple(p for p, _ in progs)
     structs, keeps = _program_structs(
         [(prog, q, scheme, facet) for _, prog in progs], mesh)
-    if not facet:
+    if not facet and not is_cell_subdomain(part):
         out = device.empty(nblocks * stride)
         if rank == 2 and stride != lay.nnz:   # (the entry behind every plane)
             _hip.fill(out, 0.0)
@@ -1135,8 +1146,7 @@ def _block_part(part, table, rank, q, scheme, lay, mesh):
     for k, p in enumerate(tags):
         dst = out[p * stride:p * stride + width]
         tmp = device.zeros(width) if p in tags[:k] else dst
-        _facet_arguments(mesh, lay, rank, structs[k], part.subdomain_data,
-                         part.subdomain_id, tmp)
+        _selection_arguments(mesh, lay, rank, structs[k], part, tmp)
         if tmp is not dst:
             axpby(1.0, tmp, 1.0, dst)
     return out
@@ -1362,15 +1372,18 @@ class NewtonInfo(object):
     they go through flow_form_facet_matrix / flow_form_facet_vector one by
     one; on a vector space: there is a 'newton' job, no dx component of the
     residual needed a 'vector' job and no block of a fused row was split into
-    several programs -- block_jobs_fused), `method` (of the linear solves).'''
+    several programs -- block_jobs_fused), `method` (of the linear solves),
+    `route` (NewtonAssembler.route: 'by_parts' where a ds or dx(k) part is
+    gathered on its own, else 'fused' | 'pair').'''
 
-    def __init__(self, fused, method):
+    def __init__(self, fused, method, route=None):
         self.iterations = 0
         self.converged = False
         self.residuals = []
         self.linear_iterations = []
         self.fused = fused
         self.method = method
+        self.route = route or ('fused' if fused else 'pair')
 
     def __repr__(self):
         return 'newton (%s, %s): %d iterations, |F| = %.3e, %s' % (
@@ -1402,11 +1415,13 @@ def _check_part_mesh(part, mesh):
 
 # -- the jobs of an assembly --------------------------------------------------
 # One launch's worth of one Program.  kind: 'newton' | 'matrix' | 'vector' |
-# 'facet_matrix' | 'facet_vector'; msign, vsign: the signs of the matrix and of
-# the vector part (0.0 where the kind has none); part: the ds part of a facet
-# job (its subdomain data and id are the facet selection), else None; tag: the
-# block plane p = 2 r + s ('newton', 'matrix', 'facet_matrix') or the component
-# r ('vector', 'facet_vector') on a vector space -- a 'newton' job assembles
+# 'facet_matrix' | 'facet_vector' | 'cells_matrix' | 'cells_vector'; msign,
+# vsign: the signs of the matrix and of the vector part (0.0 where the kind has
+# none); part: the ds part of a facet job or the dx(k) part of a cells job (its
+# subdomain data and id are the selection), else None; tag: the block plane
+# p = 2 r + s ('newton', 'matrix', 'facet_matrix', 'cells_matrix') or the
+# component r ('vector', 'facet_vector', 'cells_vector') on a vector space -- a
+# 'newton' job assembles
 # block p and component p // 2 --, 0 on a scalar space; call: (index of the
 # part of J or None, index of the part of F or None).
 Job = collections.namedtuple(
@@ -1453,7 +1468,8 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
     '''The launches that assemble (J, F) at one state, as a list of Job
     records, on a scalar space (one block, tag 0) and on a vector space
     alike.  ds parts are never fused: 'facet_matrix' / 'facet_vector' jobs
-    block by block, program by program.  A dx part of J is taken together
+    block by block, program by program; dx(k) parts neither: 'cells_matrix' /
+    'cells_vector' jobs in the same way.  A dx part of J is taken together
     with the first unused dx part of F of the same degree and rule (the one it
     was derived from first) with which at least one row fuses (_block_rows);
     without one, and with fuse=False, its blocks are 'matrix' jobs and the
@@ -1474,18 +1490,21 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
     for ji, (sj, pj) in enumerate(jparts):
         rule = _part_rule(pj, form_compiler_parameters)
         tj = pj.argument_table()[1]
-        if pj.integral_type == 'exterior_facet':
-            jobs.extend(Job('facet_matrix', sj, 0.0, prog, rule[0], rule[1],
-                            pj, p, (ji, None))
+        if pj.integral_type == 'exterior_facet' or is_cell_subdomain(pj):
+            # (a part over a selection is never fused)
+            facet = pj.integral_type == 'exterior_facet'
+            jobs.extend(Job('facet_matrix' if facet else 'cells_matrix', sj,
+                            0.0, prog, rule[0], rule[1], pj, p, (ji, None))
                         for p, block in blocks(tj, 2)
-                        for prog in forms.argument_programs(block, 2, True))
+                        for prog in forms.argument_programs(block, 2, facet))
             continue
         fi, rows = None, None
         origin = getattr(pj, 'derived_from', None)
         for i in sorted(range(len(fparts)),
                         key=lambda i: fparts[i][1] is not origin):
             if not fuse or used[i] or rules[i] != rule \
-                    or fparts[i][1].integral_type != 'cell':
+                    or fparts[i][1].integral_type != 'cell' \
+                    or is_cell_subdomain(fparts[i][1]):
                 continue
             found = _block_rows(tj, fparts[i][1].argument_table()[1], dim)
             if any(kind == 'newton' for kind, _, _ in found):
@@ -1503,11 +1522,13 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
                     for kind, prog, tag in rows)
     for i, (sf, pf) in enumerate(fparts):
         facet = pf.integral_type == 'exterior_facet'
+        cells = is_cell_subdomain(pf)
         if used[i]:
             continue
-        jobs.extend(Job('facet_vector' if facet else 'vector', 0.0, sf, prog,
-                        rules[i][0], rules[i][1], pf if facet else None, r,
-                        (None, i))
+        jobs.extend(Job('facet_vector' if facet else
+                        'cells_vector' if cells else 'vector', 0.0, sf, prog,
+                        rules[i][0], rules[i][1],
+                        pf if facet or cells else None, r, (None, i))
                     for r, block in blocks(pf.argument_table()[1], 1)
                     for prog in forms.argument_programs(block, 1, facet))
     return jobs
@@ -1518,8 +1539,9 @@ def newton_jobs(J, F, form_compiler_parameters=None, fuse=True):
 # row keeps 'matrix' jobs (its other block), so the rule there asks for more.
 def _scalar_jobs_fused(jobs):
     '''NewtonInfo.fused of jobs on a scalar space: every dx part of J went
-    into a 'newton' job.  ds jobs do not count.'''
-    return all(j.kind != 'matrix' for j in jobs)
+    into a 'newton' job.  ds jobs do not count; a dx(k) job is never fused.'''
+    return all(j.kind not in ('matrix', 'cells_matrix', 'cells_vector')
+               for j in jobs)
 
 
 def block_jobs_fused(jobs):
@@ -1528,7 +1550,8 @@ def block_jobs_fused(jobs):
     has a 'newton' job in its call is ONE program (no table of such a row was
     split).  ds jobs do not count.'''
     if not any(j.kind == 'newton' for j in jobs) \
-            or any(j.kind == 'vector' for j in jobs):
+            or any(j.kind in ('vector', 'cells_matrix', 'cells_vector')
+                   for j in jobs):
         return False
     for j in jobs:
         if j.kind != 'newton':
@@ -1642,10 +1665,10 @@ def _refresh_constants(program, consts):
 
 
 class _FacetTarget(object):
-    '''Where a held assembler gathers a ds program: a zeroed buffer (N | nnz
-    doubles) the gather writes the same entries of at every call -- its map's
-    targets --, zeroed again where facet_map returns another tuple (the facet
-    markers were changed: other targets).  `into`: where a further program of
+    '''Where a held assembler gathers a ds or a dx(k) program: a zeroed buffer
+    (N | nnz doubles) the gather writes the same entries of at every call --
+    its map's targets --, zeroed again where facet_map / cell_map returns
+    another tuple (the markers were changed: other targets).  `into`: where a further program of
     a block is added afterwards, else None.'''
 
     def __init__(self, buf, into=None):
@@ -1654,13 +1677,11 @@ class _FacetTarget(object):
         self.fmap = None
 
     def gather(self, mesh, lay, rank, fs, part):
-        fmap = facet_map(mesh, lay, rank, part.subdomain_data,
-                         part.subdomain_id)
+        fmap = _selection_map(mesh, lay, rank, part)
         if self.fmap is not None and self.fmap is not fmap:
             _hip.fill(self.buf, 0.0)
         self.fmap = fmap
-        _facet_arguments(mesh, lay, rank, fs, part.subdomain_data,
-                         part.subdomain_id, self.buf)
+        _selection_arguments(mesh, lay, rank, fs, part, self.buf)
         if self.into is not None:
             axpby(1.0, self.buf, 1.0, self.into)
         return self.buf
@@ -1714,8 +1735,12 @@ class NewtonAssembler(object):
     into a zeroed buffer of its own, then added); after all launches the
     parts are added in the order written, as assemble() adds them -- the
     total IS the first buffer only where a single dx part of sign +1 makes
-    the sum.  A ds program owns a _FacetTarget.  A and b have the bits of
-    assemble(J) and assemble(F).'''
+    the sum.  A ds program, and a dx(k) program, owns a _FacetTarget; `route`
+    is 'by_parts' where the jobs hold one, else 'fused' or 'pair' as `fused`
+    tells -- 'by_parts' names that treatment (a part over a selection is
+    gathered on its own into a zeroed buffer and then added), on scalar and on
+    vector spaces alike, not the method _by_parts, which is the vector-space
+    path.  A and b have the bits of assemble(J) and assemble(F).'''
 
     def __init__(self, J, F, V, form_compiler_parameters=None, fuse=True):
         self.V = V
@@ -1726,19 +1751,25 @@ class NewtonAssembler(object):
             for _, part in parts:
                 _check_part_mesh(part, mesh)
         self.jobs = jobs = newton_jobs(J, F, form_compiler_parameters, fuse)
+        # 'by_parts': a part runs over a selection (ds, dx(k)) and is gathered
+        # on its own into a zeroed buffer; else what `fused` tells
+        self.route = 'by_parts' if any(j.part is not None for j in jobs) \
+            else None
         self._targets = {}          # per ds job: its _FacetTarget
         if V.dim == 1:
             self.fused = _scalar_jobs_fused(jobs)
+            self.route = self.route or ('fused' if self.fused else 'pair')
             self.A = Matrix(lay, 0, value_plane(lay))
             self.b = device.empty(lay.N)
             self._spares = {}
             self._keep = _program_structs(
-                [(j.program, j.degree, j.scheme, j.part is not None)
+                [(j.program, j.degree, j.scheme, j.kind.startswith('facet'))
                  for j in jobs], mesh)
             self._steps = [(j, fs, fs.consts)
                            for j, fs in zip(jobs, self._keep[0])]
             return
         self.fused = block_jobs_fused(jobs)
+        self.route = self.route or ('fused' if self.fused else 'pair')
         if not self.parts[0] or not self.parts[1]:
             raise ValueError('an empty sum of forms has no rank')
         # (zeroed once: the launches write the nnz entries of a plane, not
@@ -1758,7 +1789,7 @@ class NewtonAssembler(object):
             jns = list(g)
             js = [jobs[n] for n in jns]
             structs, keeps = _program_structs(
-                [(j.program, j.degree, j.scheme, j.part is not None)
+                [(j.program, j.degree, j.scheme, j.kind.startswith('facet'))
                  for j in js], mesh)
             self._calls.append(
                 (call, jns, tuple(j.kind for j in js),
@@ -1768,7 +1799,8 @@ class NewtonAssembler(object):
 
     @staticmethod
     def _single_dx(parts):
-        return len(parts) == 1 and parts[0][1].integral_type == 'cell'
+        return len(parts) == 1 and parts[0][1].integral_type == 'cell' \
+            and not is_cell_subdomain(parts[0][1])
 
     def assemble(self):
         if self.V.dim == 2:
@@ -1786,7 +1818,7 @@ class NewtonAssembler(object):
             vals = vec = None
             if job.part is not None:
                 # (a ds result is never the total itself)
-                rank = 2 if kind == 'facet_matrix' else 1
+                rank = 2 if kind.endswith('_matrix') else 1
                 target = self._targets.get(jn)
                 if target is None:
                     target = self._targets[jn] = _FacetTarget(
@@ -1830,7 +1862,7 @@ class NewtonAssembler(object):
                 _refresh_constants(program, view)
             vals = None if ji is None else self._bufs[0][ji]
             vec = None if fi is None else self._bufs[1][fi]
-            if kinds[0].startswith('facet'):
+            if kinds[0].startswith(('facet', 'cells')):
                 rank = 2 if vec is None else 1
                 self._facet_blocks(jns, tags, structs, rank,
                                    vals if rank == 2 else vec)
@@ -1922,7 +1954,7 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
         Abc = Matrix(V.layout, 2 if V.dim == 2 else 0)
     delta = device.empty(V.size())
     ilu = None
-    out = NewtonInfo(asm.fused, method)
+    out = NewtonInfo(asm.fused, method, asm.route)
     rtol, atol = ns['relative_tolerance'], ns['absolute_tolerance']
     maxit = int(ns['maximum_iterations'])
     r0 = None
@@ -2128,7 +2160,8 @@ def cell_indicator(form, share=0.5, out=None, form_compiler_parameters=None):
     '''Per-cell values of a rank-0 form, or signed sum, of dx and dS parts: a
     device fp64 array (nc,) (a new one, or `out`), which feeds fem.mark
     unchanged.  A dx part gives every cell its own integral (stage 1 of the
-    functional).  A dS part gives every cell `share` times the integral of
+    functional); a dx(k) part its selected cells, zeros outside the
+    selection.  A dS part gives every cell `share` times the integral of
     each of its selected interior facets, added in the order of its local
     facets 0, 1, 2: 0.5 is what avg(w)*f*dS gives for a DG0 test function w,
     1.0 is Kelly's convention (JumpIndicator's).  The parts are added in the
@@ -2180,9 +2213,20 @@ def cell_indicator(form, share=0.5, out=None, form_compiler_parameters=None):
             q = _form_degree(part, form_compiler_parameters)
             prog = forms.compile_trees([part.integrand.comps])
             fs, keep = _form_struct(prog, mesh, q)
-            _hip.check(lib.flow_form_cell_values(
-                ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs),
-                _hip.f64(dest, nc, 'out'), _hip.stream()))
+            if is_cell_subdomain(part):
+                # (zeros outside the selection: the launch writes its cells)
+                cells, nsel = cell_lists(mesh, part.subdomain_data,
+                                         part.subdomain_id)
+                _hip.fill(dest, 0.0)
+                if nsel:
+                    _hip.check(lib.flow_form_cells_values(
+                        ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs),
+                        nsel, _hip.i32(cells, nsel, 'cell list'),
+                        _hip.f64(dest, nc, 'out'), _hip.stream()))
+            else:
+                _hip.check(lib.flow_form_cell_values(
+                    ctypes.byref(mesh_struct(mesh)), ctypes.byref(fs),
+                    _hip.f64(dest, nc, 'out'), _hip.stream()))
             del keep
         if not direct:
             if total is None:
@@ -2286,6 +2330,156 @@ def _facet_arguments(mesh, lay, rank, fs, markers, subdomain_id, out):
         _hip.i32(targets, nt, 'map targets'), _hip.i32(ptr, nt + 1, 'map ptr'),
         _hip.i32(src, n, 'map src'), _hip.f64(scratch(mesh, n), n, 'scratch'),
         _hip.f64(out, lay.nnz if rank == 2 else lay.N, 'out'), _hip.stream()))
+
+
+# -- cell subdomains: dx(k) (forms.cell_subdomains) ----------------------------
+def is_cell_subdomain(part):
+    '''Whether a part is a dx(k) part: cells, and a subdomain id.'''
+    return part.integral_type == 'cell' \
+        and part.subdomain_id not in (None, 'everywhere')
+
+
+def _check_cell_markers(mesh, markers, subdomain_id):
+    if markers is None:
+        raise ValueError('dx(%r) needs markers: Measure(\'dx\', domain=mesh, '
+                         'subdomain_data=markers)' % (subdomain_id,))
+    if markers.mesh is not mesh:
+        raise ValueError('the cell markers belong to another mesh')
+    if getattr(markers, 'dim', None) != 2:
+        raise ValueError('dx(%r) takes a cell MeshFunction (dim 2) as '
+                         'subdomain_data' % (subdomain_id,))
+
+
+def _cell_selection(mesh, markers, subdomain_id):
+    '''The cells dx(subdomain_id) selects, ascending.'''
+    if subdomain_id in (None, 'everywhere'):
+        return numpy.arange(mesh.num_cells())
+    return numpy.nonzero(markers.array() == subdomain_id)[0]
+
+
+def cell_lists(mesh, markers=None, subdomain_id='everywhere'):
+    '''The cells a dx(k) integral runs over: a device int32 array of the
+    cells whose marker equals subdomain_id, ascending, and their count.
+    Cached on the mesh against the markers' version like facet_lists: a time
+    loop uploads nothing, re-marking re-selects.  An empty selection holds no
+    device array; for 'everywhere' nothing is built, (None, number of cells)
+    -- the whole-mesh entry points take no list.'''
+    if subdomain_id in (None, 'everywhere'):
+        return None, mesh.num_cells()
+    _check_cell_markers(mesh, markers, subdomain_id)
+    cache = mesh._cache.setdefault('cell_lists', {})
+    key = (id(markers), subdomain_id, str(device.get()))
+    held = cache.get(key)
+    if held is not None and held[0] is markers and held[1] == markers.version:
+        return held[2:]
+    sel = _cell_selection(mesh, markers, subdomain_id)
+    cells = device.to_device(sel.astype(numpy.int32)) if len(sel) else None
+    if len(cache) >= 32:
+        cache.clear()
+    # (the markers are kept alive with the entry: their id stays unique)
+    held = (markers, markers.version, cells, len(sel))
+    cache[key] = held
+    return held[2:]
+
+
+def cell_map_host(mesh, layout, rank, markers=None, subdomain_id='everywhere'):
+    '''The cell contribution map of one (cell selection, space layout, rank)
+    as numpy int32 arrays (targets, ptr, src), of the shape of facet_map_host.
+    The lanes of flow_form_cells_matrix / flow_form_cells_vector write the
+    element entries of cell k of the selection (cell_lists' order) to
+    scratch[(i*NL + j)*nsel + k] (rank 2) or scratch[i*nsel + k] (rank 1), NL
+    = layout.nloc.  targets: the sorted unique indices of the nonzeros of the
+    layout's CSR pattern (rank 2) or of the dofs (rank 1) that a selected
+    cell touches; target t sums scratch[src[e]], e in [ptr[t], ptr[t+1]).
+    ORDER: the sources of a target stand in the order in which the space's
+    own map lists them (cptr / csrc, rank 2; vptr / vsrc, rank 1), restricted
+    to the selected cells -- the space's map is filtered: the cell of each
+    source is decoded, unselected cells are dropped, the rest re-encoded with
+    the cell's position in the list.  A selection that holds every cell
+    therefore gives the bits of plain dx.  Every scratch entry appears exactly
+    once.'''
+    sel = _cell_selection(mesh, markers, subdomain_id)
+    nsel, nc = len(sel), mesh.num_cells()
+    if nsel == 0:
+        return (numpy.zeros(0, numpy.int32), numpy.zeros(1, numpy.int32),
+                numpy.zeros(0, numpy.int32))
+    if rank == 2:
+        ptr, src = layout.pattern('cptr'), layout.pattern('csrc')
+    else:
+        ptr, src = layout.vmap('vptr'), layout.vmap('vsrc')
+    src = src.astype(numpy.int64)
+    position = numpy.full(nc, -1, dtype=numpy.int64)
+    position[sel] = numpy.arange(nsel)
+    pos = position[src % nc]
+    keep = pos >= 0
+    # (kept sources before each row of the space's map: the new row pointers)
+    before = numpy.concatenate([[0], numpy.cumsum(keep)])[ptr]
+    count = numpy.diff(before)
+    targets = numpy.nonzero(count)[0]
+    new_src = (src[keep] // nc) * nsel + pos[keep]
+    assert len(new_src) == layout.nloc**rank * nsel < 2**31
+    return (targets.astype(numpy.int32),
+            numpy.concatenate([before[targets], [len(new_src)]]).astype(
+                numpy.int32),
+            new_src.astype(numpy.int32))
+
+
+def cell_map(mesh, layout, rank, markers=None, subdomain_id='everywhere'):
+    '''cell_map_host on the device: (targets, ptr, src, number of targets),
+    None arrays for an empty selection.  Cached on the mesh against the
+    markers' version like facet_map; the SAME tuple is returned while the
+    entry holds.'''
+    _check_cell_markers(mesh, markers, subdomain_id)
+    cache = mesh._cache.setdefault('cell_maps', {})
+    key = (id(markers), subdomain_id, id(layout), rank, str(device.get()))
+    held = cache.get(key)
+    if held is not None and held[0] is markers \
+            and held[1] == markers.version and held[2] is layout:
+        return held[3]
+    targets, ptr, src = cell_map_host(mesh, layout, rank, markers,
+                                      subdomain_id)
+    nt = len(targets)
+    if nt:
+        cmap = (device.to_device(targets), device.to_device(ptr),
+                device.to_device(src), nt)
+    else:
+        cmap = (None, None, None, 0)
+    if len(cache) >= 32:
+        cache.clear()
+    # (markers and layout are kept alive with the entry: their ids stay unique)
+    cache[key] = (markers, markers.version, layout, cmap)
+    return cmap
+
+
+def _cell_arguments(mesh, lay, rank, fs, markers, subdomain_id, out):
+    '''One dx(k) part of rank 1 | 2 into `out` (N | nnz doubles, zero outside
+    the map's targets): the element launch over the cell list and the gather
+    launch.'''
+    cells, nsel = cell_lists(mesh, markers, subdomain_id)
+    if nsel == 0:
+        return
+    targets, ptr, src, nt = cell_map(mesh, lay, rank, markers, subdomain_id)
+    n = lay.nloc**rank * nsel
+    lib = _hip.lib()
+    fn = lib.flow_form_cells_matrix if rank == 2 else lib.flow_form_cells_vector
+    _hip.check(fn(
+        ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay)),
+        ctypes.byref(fs), nsel, _hip.i32(cells, nsel, 'cell list'), nt,
+        _hip.i32(targets, nt, 'map targets'), _hip.i32(ptr, nt + 1, 'map ptr'),
+        _hip.i32(src, n, 'map src'), _hip.f64(scratch(mesh, n), n, 'scratch'),
+        _hip.f64(out, lay.nnz if rank == 2 else lay.N, 'out'), _hip.stream()))
+
+
+def _selection_map(mesh, lay, rank, part):
+    '''The contribution map of a ds or dx(k) part.'''
+    fn = cell_map if part.integral_type == 'cell' else facet_map
+    return fn(mesh, lay, rank, part.subdomain_data, part.subdomain_id)
+
+
+def _selection_arguments(mesh, lay, rank, fs, part, out):
+    '''One ds or dx(k) part of rank 1 | 2 into `out`.'''
+    fn = _cell_arguments if part.integral_type == 'cell' else _facet_arguments
+    fn(mesh, lay, rank, fs, part.subdomain_data, part.subdomain_id, out)
 
 
 def form_load_vector(expr, V, form_compiler_parameters=None):

@@ -1379,6 +1379,47 @@ int flow_form_facet_vector(const flow_mesh* mesh, const flow_space* V,
                            const int* map_ptr, const int* map_src,
                            double* scratch, double* b, void* stream);
 
+/* Cell subdomains (assemble(f*dx(k)), forms.cell_subdomains): the integrals of
+ * flow_form_functional / flow_form_cell_values / flow_form_matrix /
+ * flow_form_vector over a LIST of cells.  cells: device int32 (ncells), the
+ * selected cells; the program, the rule and the Expression tables are those of
+ * the whole-mesh entry point (1 * nq rows, no NORMAL).  Lane k takes cell
+ * cells[k] and runs the whole-mesh kernel's arithmetic on it: a list that
+ * holds every cell in ascending order gives the whole-mesh entry point's bits.
+ * A list entry outside [0, nc) gives NaN (cells_values: it is skipped).
+ *   flow_form_cells_functional: per-cell integrals to scratch[k] (ncells
+ * doubles), then the fixed-order reduction of flow_form_functional over
+ * [0, ncells) (work: FLOW_REDUCE_WORK doubles) into *result_host.
+ *   flow_form_cells_values: out[cells[k]] = the integral over that cell; every
+ * other entry of out (nc doubles) is left as it is: the caller zeroes it.
+ *   flow_form_cells_matrix / flow_form_cells_vector: lane k writes the element
+ * matrix of its cell to scratch[(i*nloc + j)*ncells + k] (scratch: nloc^2 *
+ * ncells) or its element vector to scratch[i*ncells + k] (nloc * ncells); the
+ * gather of flow_form_facet_matrix then sums them over (map_targets, map_ptr,
+ * map_src) into vals (nnz) / b (n) and leaves every other entry as it is.  For
+ * the bits of the whole-mesh entry point the sources of a target stand in the
+ * order of V's own cptr / csrc (vptr / vsrc) restricted to the list
+ * (ops.cell_map_host).
+ * ncells == 0 (or ntargets == 0): FLOW_OK, nothing launched (the functional:
+ * *result_host = 0.0).  No atomics: two calls give the same bits.  Not on
+ * strips. */
+int flow_form_cells_functional(const flow_mesh* mesh, const flow_form* form,
+                               int ncells, const int* cells, double* scratch,
+                               double* work, double* result_host, void* stream);
+int flow_form_cells_values(const flow_mesh* mesh, const flow_form* form,
+                           int ncells, const int* cells, double* out,
+                           void* stream);
+int flow_form_cells_matrix(const flow_mesh* mesh, const flow_space* V,
+                           const flow_form* form, int ncells, const int* cells,
+                           int ntargets, const int* map_targets,
+                           const int* map_ptr, const int* map_src,
+                           double* scratch, double* vals, void* stream);
+int flow_form_cells_vector(const flow_mesh* mesh, const flow_space* V,
+                           const flow_form* form, int ncells, const int* cells,
+                           int ntargets, const int* map_targets,
+                           const int* map_ptr, const int* map_src,
+                           double* scratch, double* b, void* stream);
+
 /* Forms of a test function v and a trial function u of the VECTOR space on V's
  * scalar pattern (forms.py, vector_arguments): the host rewrites the integrand
  * as  sum_(r,s) sum_(b,a) c^rs_ba D_a u_s D_b v_r  (rank 2) or  sum_r sum_b
