@@ -487,6 +487,16 @@ SYMBOLS = {
                                _VP, _VP, _VP, _VP, _VP, _VP],
     'flow_form_cells_vector': [_P(MeshS), _P(SpaceS), _P(FormS), _I, _VP, _I,
                                _VP, _VP, _VP, _VP, _VP, _VP],
+    'flow_form_rect_matrix': [_P(MeshS), _P(SpaceS), _P(SpaceS), _P(FormS),
+                              _VP, _VP, _VP, _VP, _I, _VP],
+    'flow_form_rect_facet_matrix': [_P(MeshS), _P(SpaceS), _P(SpaceS),
+                                    _P(FormS), _I, _VP, _VP, _I, _VP, _VP,
+                                    _VP, _VP, _VP, _I, _VP],
+    'flow_form_rect_cells_matrix': [_P(MeshS), _P(SpaceS), _P(SpaceS),
+                                    _P(FormS), _I, _VP, _I, _VP, _VP, _VP,
+                                    _VP, _VP, _I, _VP],
+    'flow_bc_rect_mask': [_VP, _VP, _I, _VP, _VP, _VP, _VP],
+    'flow_plane_symmetric_part': [_I, _VP, _VP, _I, _VP, _VP, _VP],
     'flow_form_block_matrix': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),
                                _VP, _VP, ctypes.c_size_t, _VP],
     'flow_form_block_vector': [_P(MeshS), _P(SpaceS), _I, _P(FormS), _P(_I),

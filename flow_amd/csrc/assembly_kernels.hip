@@ -891,6 +891,21 @@ __global__ void bc_symmetric_kernel(int n, const int* __restrict__ rowptr,
   }
 }
 
+// out[e] = (a[e] + b[perm[e]]) / 2: the symmetric part of a value plane, b the
+// plane of the transposed block and perm[e] the position of entry e's mirror
+// image in it.  The sum commutes, so out and the result for the mirrored pair
+// (b, a, inverse perm) hold the same bits.  perm[e] outside [0, nb): NaN.
+__global__ void plane_symmetric_part_kernel(int n, const double* __restrict__ a,
+                                            const double* __restrict__ b, int nb,
+                                            const int* __restrict__ perm,
+                                            double* __restrict__ out) {
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n;
+       e += gridDim.x * blockDim.x) {
+    const int t = perm[e];
+    out[e] = (t >= 0 && t < nb) ? 0.5 * (a[e] + b[t]) : __builtin_nan("");
+  }
+}
+
 // the symmetric elimination of a 2x2-block operator (kind 2), all four planes:
 // entry (i, j) of plane (r, s) belongs to row r*n + i and column s*n + j
 __global__ void bc_symmetric_blocks_kernel(int n, const int* __restrict__ rowptr,
@@ -1546,6 +1561,19 @@ extern "C" int flow_bc_symmetric_matrix(int n, const int* rowptr,
   FLOW_REQUIRE(n > 0 && rowptr && cols && vals_in && isbc && vals_out, "pointers");
   hipLaunchKernelGGL(bc_symmetric_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
                      as_stream(stream), n, rowptr, cols, vals_in, isbc, vals_out);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+extern "C" int flow_plane_symmetric_part(int n, const double* a, const double* b,
+                                         int nb, const int* perm, double* out,
+                                         void* stream) {
+  FLOW_REQUIRE(n > 0 && nb > 0, "entry counts");
+  FLOW_REQUIRE(a && b && perm && out, "pointers");
+  FLOW_REQUIRE(out + n <= a || a + n <= out, "out must not overlap a");
+  FLOW_REQUIRE(out + n <= b || b + nb <= out, "out must not overlap b");
+  hipLaunchKernelGGL(plane_symmetric_part_kernel, dim3(grid_for(n)), dim3(kBlock), 0,
+                     as_stream(stream), n, a, b, nb, perm, out);
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
 }

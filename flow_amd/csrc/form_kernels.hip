@@ -1870,6 +1870,298 @@ static int cells_arguments(const flow_mesh* mesh, const flow_space* V,
 }
 
 // ---------------------------------------------------------------------------
+// Rectangular blocks (forms.py, mixed_arguments: the velocity-pressure
+// coupling of a Taylor-Hood form): a test function of degree DT and a trial
+// function of degree DS.  form_matrix_kernel, form_facet_arguments_kernel
+// (RANK 2) and form_cells_matrix_kernel with two bases: per point and test
+// derivative b, t_j = sum_a w c_ba D_a psi_j over the TRIAL basis first, then
+// Ke[i][j] += D_b phi_i t_j over the TEST basis; the program, the slots, the
+// live mask, the walk over the rule and the form_point_n call are theirs.
+// They are kernels of their own, not a parameter of those: those are short of
+// scalar registers, and their instances stay as they are.  With DT == DS one
+// basis is tabulated and the arithmetic is add_matrix_terms': the bits of the
+// square kernel.  Ke goes to scratch[(i*NLS + j)*n + k], n the cells | facets |
+// list entries, k fastest.
+// ---------------------------------------------------------------------------
+template <int NLT, int NLS, int NS>
+__device__ __forceinline__ void add_rect_terms(int m, double w, const double (&slots)[NS],
+                                               const double (&phi)[NLT],
+                                               const double (&gphi)[NLT][2],
+                                               const double (&psi)[NLS],
+                                               const double (&gpsi)[NLS][2],
+                                               double (&Ke)[NLT][NLS]) {
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    if (((m >> (3 * b)) & 7) == 0) continue;
+    double t[NLS];
+    trial_sums<NLS>(m, 3 * b, w, slots, psi, gpsi, t);
+#pragma unroll
+    for (int i = 0; i < NLT; ++i) {
+      const double di = arg_basis<NLT>(b, phi, gphi, i);
+#pragma unroll
+      for (int j = 0; j < NLS; ++j) Ke[i][j] += di * t[j];
+    }
+  }
+}
+
+// one point of a cell: both bases at L, then add_rect_terms
+template <int DT, int DS, int NS>
+__device__ __forceinline__ void rect_point(const Geom& g, const double (&L)[3], int m,
+                                           double w, const double (&slots)[NS],
+                                           double (&Ke)[Elem<DT>::NL][Elem<DS>::NL]) {
+  constexpr int NLT = Elem<DT>::NL, NLS = Elem<DS>::NL;
+  double phi[NLT], dphi[NLT][3], gphi[NLT][2];
+  basis<DT>(L, phi, dphi);
+  phys_grad<NLT>(g, dphi, gphi);
+  if constexpr (DT == DS) {
+    add_rect_terms<NLT, NLS>(m, w, slots, phi, gphi, phi, gphi, Ke);
+  } else {
+    double psi[NLS], dpsi[NLS][3], gpsi[NLS][2];
+    basis<DS>(L, psi, dpsi);
+    phys_grad<NLS>(g, dpsi, gpsi);
+    add_rect_terms<NLT, NLS>(m, w, slots, phi, gphi, psi, gpsi, Ke);
+  }
+}
+
+// cell c (LIST: cells[k]) of n = nc (LIST: nsel) lanes
+template <int NF, int DT, int DS, bool EXT, bool LIST>
+__global__ __launch_bounds__(kBlock) void form_rect_matrix_kernel(
+    int nc, int n, const int* __restrict__ cells, const double* __restrict__ xy,
+    const flow_form F, int live, double* __restrict__ scratch) {
+  constexpr int NLT = Elem<DT>::NL, NLS = Elem<DS>::NL;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  double* const dst = scratch + k;
+  int c = k;
+  if constexpr (LIST) {
+    c = cells[k];
+    if (c < 0 || c >= nc) {
+#pragma unroll
+      for (int ij = 0; ij < NLT * NLS; ++ij)
+        dst[static_cast<size_t>(ij) * n] = __builtin_nan("");
+      return;
+    }
+  }
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
+  double Ke[NLT][NLS];
+#pragma unroll
+  for (int i = 0; i < NLT; ++i)
+#pragma unroll
+    for (int j = 0; j < NLS; ++j) Ke[i][j] = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const double xi = F.rule[3 * q], eta = F.rule[3 * q + 1];
+    const double w = F.rule[3 * q + 2] * C.g.adet;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlots<FLOW_FORM_SLOTS> out;
+#pragma unroll
+    for (int s = 0; s < FLOW_FORM_SLOTS; ++s) out.v[s] = 0.0;
+    form_point_n<NF, false, EXT>(F, C.U, C.X, C.Y, C.g, L, q, nc, c, 0.0, 0.0, out);
+    // (the mask through an empty asm, as in form_matrix_kernel)
+    int m = live;
+    asm volatile("" : "+s"(m));
+    rect_point<DT, DS>(C.g, L, m, w, out.v, Ke);
+  }
+#pragma unroll
+  for (int i = 0; i < NLT; ++i)
+#pragma unroll
+    for (int j = 0; j < NLS; ++j)
+      dst[static_cast<size_t>(i * NLS + j) * n] = Ke[i][j];
+}
+
+// one lane per (local test dof i < NLT, facet k), k fastest: row i of the
+// facet's element matrix, as form_facet_arguments_kernel (RANK 2) writes it
+template <int NF, int DT, int DS, bool EXT>
+__global__ __launch_bounds__(kBlock) void form_rect_facet_kernel(
+    int nc, int nfacets, const int* __restrict__ fcell,
+    const int* __restrict__ flocal, const double* __restrict__ xy,
+    const flow_form F, int live, double* __restrict__ scratch) {
+  constexpr int NLT = Elem<DT>::NL, NLS = Elem<DS>::NL;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= nfacets * NLT) return;
+  const int i = idx / nfacets, k = idx - i * nfacets;
+  double* const dst = scratch + static_cast<size_t>(i) * NLS * nfacets + k;
+  const int c = fcell[k], lf = flocal[k];
+  if (c < 0 || c >= nc || lf < 0 || lf > 2) {
+#pragma unroll
+    for (int j = 0; j < NLS; ++j)
+      dst[static_cast<size_t>(j) * nfacets] = __builtin_nan("");
+    return;
+  }
+  FormCell<NF> C;
+  load_form_cell<NF>(F, nc, xy, c, C);
+  const FacetFrame f = facet_frame(C.g, lf);
+  double acc[NLS];
+#pragma unroll
+  for (int j = 0; j < NLS; ++j) acc[j] = 0.0;
+  for (int q = 0; q < F.nq; ++q) {
+    const int row = lf * F.nq + q;
+    const double xi = F.rule[3 * row], eta = F.rule[3 * row + 1];
+    const double w = F.rule[3 * row + 2] * f.len;
+    const double L[3] = {1.0 - xi - eta, xi, eta};
+    FormSlots<FLOW_FORM_SLOTS> out;
+#pragma unroll
+    for (int s = 0; s < FLOW_FORM_SLOTS; ++s) out.v[s] = 0.0;
+    form_point_n<NF, true, EXT>(F, C.U, C.X, C.Y, C.g, L, row, nc, c, f.n0, f.n1, out);
+    double phi[NLT], dphi[NLT][3], gphi[NLT][2];
+    basis<DT>(L, phi, dphi);
+    phys_grad<NLT>(C.g, dphi, gphi);
+    double psi[NLS], dpsi[NLS][3], gpsi[NLS][2];
+    basis<DS>(L, psi, dpsi);
+    phys_grad<NLS>(C.g, dpsi, gpsi);
+    // (the mask through an empty asm, as in form_matrix_kernel)
+    int m = live;
+    asm volatile("" : "+s"(m));
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      if (((m >> (3 * b)) & 7) == 0) continue;
+      const double di = own_basis<NLT>(b, phi, gphi, i);
+      double t[NLS];
+      trial_sums<NLS>(m, 3 * b, w, out.v, psi, gpsi, t);
+#pragma unroll
+      for (int j = 0; j < NLS; ++j) acc[j] += di * t[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NLS; ++j) dst[static_cast<size_t>(j) * nfacets] = acc[j];
+}
+
+// vals[e] = sum of scratch[src[t]], t in [ptr[e], ptr[e+1]), in that order (the
+// order and grouping of gather_kernel: adding its padding zeros changes no
+// bit).  A row of ptr or an entry of src outside the scratch gives NaN, not a
+// stray read.  No atomics: two calls give the same bits.
+__global__ __launch_bounds__(kBlock) void rect_gather_kernel(
+    int nnz, const int* __restrict__ ptr, const int* __restrict__ src, int nsrc,
+    const double* __restrict__ scratch, double* __restrict__ vals) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= nnz) return;
+  const int a = ptr[e], b = ptr[e + 1];
+  double s = 0.0;
+  if (a < 0 || b > nsrc || a > b) {
+    s = __builtin_nan("");
+  } else {
+    for (int t = a; t < b; ++t) {
+      const int x = src[t];
+      s += (x >= 0 && x < nsrc) ? scratch[x] : __builtin_nan("");
+    }
+  }
+  vals[e] = s;
+}
+
+// vals[e] = 0 where the row or the column of entry e is a Dirichlet dof: one
+// lane per row, plain vector stores
+__global__ __launch_bounds__(kBlock) void bc_rect_mask_kernel(
+    int n_rows, const int* __restrict__ rowptr, const int* __restrict__ cols,
+    const unsigned char* __restrict__ row_isbc,
+    const unsigned char* __restrict__ col_isbc, double* __restrict__ vals) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  const bool rb = row_isbc[r] != 0;
+  for (int e = rowptr[r]; e < rowptr[r + 1]; ++e)
+    if (rb || col_isbc[cols[e]]) vals[e] = 0.0;
+}
+
+// launch(NF, EXT, DT, DS) for the kernels of a (test, trial) pair of degrees
+template <class Launch>
+static int dispatch_rect(const flow_form* F, int dt, int ds, Launch&& launch) {
+  return dispatch_form(F, dt, [&](auto NF, auto EXT, auto DT) {
+    if (ds == 1) launch(NF, EXT, DT, Int<1>{});
+    else launch(NF, EXT, DT, Int<2>{});
+  });
+}
+
+// what the three rectangular entry points ask of the mesh, the two spaces and
+// the program (rows = 1: cells, 3: facets, where NORMAL is legal).  Each dof of
+// a space on this mesh lies in a cell, so n <= nloc * nc: a space with more
+// belongs to another mesh.
+static int check_rect(const flow_mesh* mesh, const flow_space* Vt, const flow_space* Vs,
+                      const flow_form* form, int rows, int* live) {
+  int rc = check_form_mesh(mesh);
+  if (rc) return rc;
+  FLOW_REQUIRE(mesh->c1 == 0, "rectangular forms on strips");
+  FLOW_REQUIRE(Vt && Vs, "spaces");
+  FLOW_REQUIRE((Vt->deg == 1 || Vt->deg == 2) && (Vs->deg == 1 || Vs->deg == 2),
+               "space degree (1 or 2)");
+  FLOW_REQUIRE(Vt->r1 == 0 && Vs->r1 == 0, "rectangular forms on strips");
+  FLOW_REQUIRE(Vt->n > 0 && Vs->n > 0 &&
+                   Vt->n <= static_cast<long long>(Vt->deg == 1 ? 3 : 6) * mesh->nc &&
+                   Vs->n <= static_cast<long long>(Vs->deg == 1 ? 3 : 6) * mesh->nc,
+               "space (of another mesh)");
+  return check_form(form, rows, rows == 3, false, FLOW_FORM_SLOTS, live);
+}
+
+static int rect_matrix(const flow_mesh* mesh, const flow_space* Vt, const flow_space* Vs,
+                       const flow_form* form, double* scratch, double* vals,
+                       const int* cptr, const int* csrc, int nnz, void* stream) {
+  int live = 0;
+  int rc = check_rect(mesh, Vt, Vs, form, 1, &live);
+  if (rc) return rc;
+  const long long nsrc = static_cast<long long>(mesh->nc) * (Vt->deg == 1 ? 3 : 6) *
+                         (Vs->deg == 1 ? 3 : 6);
+  FLOW_REQUIRE(nsrc < (1LL << 31) - kBlock, "cell count (scratch entries)");
+  FLOW_REQUIRE(nnz > 0 && nnz <= nsrc &&
+                   nnz <= static_cast<long long>(Vt->n) * Vs->n,
+               "nnz (more entries than the scratch or the block holds)");
+  FLOW_REQUIRE(scratch && vals && cptr && csrc, "pointers");
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((mesh->nc + kBlock - 1) / kBlock);
+  rc = dispatch_rect(form, Vt->deg, Vs->deg, [&](auto NF, auto EXT, auto DT, auto DS) {
+    hipLaunchKernelGGL((form_rect_matrix_kernel<NF(), DT(), DS(), EXT(), false>), grid,
+                       dim3(kBlock), 0, st, mesh->nc, mesh->nc,
+                       static_cast<const int*>(nullptr), mesh->xy, *form, live, scratch);
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(rect_gather_kernel, dim3((nnz + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                     st, nnz, cptr, csrc, static_cast<int>(nsrc), scratch, vals);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+// FACET: n facets (cells = facet_cell, local = facet_local), else n listed cells
+template <bool FACET>
+static int rect_list(const flow_mesh* mesh, const flow_space* Vt, const flow_space* Vs,
+                     const flow_form* form, int n, const int* cells, const int* local,
+                     int ntargets, const int* map_targets, const int* map_ptr,
+                     const int* map_src, double* scratch, double* vals, int nnz,
+                     void* stream) {
+  int live = 0;
+  int rc = check_rect(mesh, Vt, Vs, form, FACET ? 3 : 1, &live);
+  if (rc) return rc;
+  FLOW_REQUIRE(n >= 0 && ntargets >= 0, "list / target count");
+  if (n == 0 || ntargets == 0) return FLOW_OK;
+  const int nlt = Vt->deg == 1 ? 3 : 6;
+  const long long nsrc = static_cast<long long>(n) * nlt * (Vs->deg == 1 ? 3 : 6);
+  FLOW_REQUIRE(nsrc < (1LL << 31) - kBlock, "list length (scratch entries)");
+  FLOW_REQUIRE(nnz > 0 && nnz <= static_cast<long long>(Vt->n) * Vs->n, "nnz");
+  FLOW_REQUIRE(ntargets <= nnz && ntargets <= nsrc, "target count");
+  FLOW_REQUIRE(cells && (!FACET || local), "cell / facet lists");
+  FLOW_REQUIRE(map_targets && map_ptr && map_src, "contribution map");
+  FLOW_REQUIRE(scratch && vals, "pointers");
+  hipStream_t st = as_stream(stream);
+  if constexpr (FACET) {
+    const dim3 grid((n * nlt + kBlock - 1) / kBlock);
+    rc = dispatch_rect(form, Vt->deg, Vs->deg, [&](auto NF, auto EXT, auto DT, auto DS) {
+      hipLaunchKernelGGL((form_rect_facet_kernel<NF(), DT(), DS(), EXT()>), grid,
+                         dim3(kBlock), 0, st, mesh->nc, n, cells, local, mesh->xy, *form,
+                         live, scratch);
+    });
+  } else {
+    const dim3 grid((n + kBlock - 1) / kBlock);
+    rc = dispatch_rect(form, Vt->deg, Vs->deg, [&](auto NF, auto EXT, auto DT, auto DS) {
+      hipLaunchKernelGGL((form_rect_matrix_kernel<NF(), DT(), DS(), EXT(), true>), grid,
+                         dim3(kBlock), 0, st, mesh->nc, n, cells, mesh->xy, *form, live,
+                         scratch);
+    });
+  }
+  if (rc) return rc;
+  hipLaunchKernelGGL(facet_gather_kernel, dim3((ntargets + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, st, ntargets, map_targets, map_ptr, map_src,
+                     static_cast<int>(nsrc), scratch, nnz, vals);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Forms of arguments on a vector space (forms.py, vector_arguments): the table
 // of such a form is one scalar table per block (r, s) = (test, trial
 // component), compiled to the programs of a scalar form.  Every program runs
@@ -2556,4 +2848,42 @@ extern "C" int flow_form_block_newton(const flow_mesh* mesh, const flow_space* V
                                       void* stream) {
   return block_newton(mesh, V, nprog, forms, kinds, tags, scratch, nscratch, vals,
                       plane_stride, b, stream);
+}
+
+extern "C" int flow_form_rect_matrix(const flow_mesh* mesh, const flow_space* V_test,
+                                     const flow_space* V_trial, const flow_form* form,
+                                     double* scratch, double* vals, const int* cptr,
+                                     const int* csrc, int nnz, void* stream) {
+  return rect_matrix(mesh, V_test, V_trial, form, scratch, vals, cptr, csrc, nnz, stream);
+}
+
+extern "C" int flow_form_rect_facet_matrix(
+    const flow_mesh* mesh, const flow_space* V_test, const flow_space* V_trial,
+    const flow_form* form, int nfacets, const int* facet_cell, const int* facet_local,
+    int ntargets, const int* map_targets, const int* map_ptr, const int* map_src,
+    double* scratch, double* vals, int nnz, void* stream) {
+  return rect_list<true>(mesh, V_test, V_trial, form, nfacets, facet_cell, facet_local,
+                         ntargets, map_targets, map_ptr, map_src, scratch, vals, nnz,
+                         stream);
+}
+
+extern "C" int flow_form_rect_cells_matrix(
+    const flow_mesh* mesh, const flow_space* V_test, const flow_space* V_trial,
+    const flow_form* form, int ncells, const int* cells, int ntargets,
+    const int* map_targets, const int* map_ptr, const int* map_src, double* scratch,
+    double* vals, int nnz, void* stream) {
+  return rect_list<false>(mesh, V_test, V_trial, form, ncells, cells, nullptr, ntargets,
+                          map_targets, map_ptr, map_src, scratch, vals, nnz, stream);
+}
+
+extern "C" int flow_bc_rect_mask(const int* rowptr, const int* cols, int n_rows,
+                                 double* vals, const unsigned char* row_isbc,
+                                 const unsigned char* col_isbc, void* stream) {
+  FLOW_REQUIRE(n_rows > 0, "row count");
+  FLOW_REQUIRE(rowptr && cols && vals && row_isbc && col_isbc, "pointers");
+  hipLaunchKernelGGL(bc_rect_mask_kernel, dim3((n_rows + kBlock - 1) / kBlock),
+                     dim3(kBlock), 0, as_stream(stream), n_rows, rowptr, cols, row_isbc,
+                     col_isbc, vals);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
 }

@@ -30,7 +30,10 @@ from .forms import (                                            # noqa: F401
     cell_subdomains,
     vector_arguments, vector_derivatives, sym, tr, transpose, Identity, outer,
     interior_facets, jump, avg, FacetArea,
+    mixed_arguments, TestFunctions, TrialFunctions, split,
     )
+from .space import RectLayout, rect_layout                      # noqa: F401
+from .mixed import MixedMatrix                                  # noqa: F401
 from .points import Probes                                      # noqa: F401
 from .tracers import Tracers                                    # noqa: F401
 from .transfer import Transfer                                  # noqa: F401

@@ -445,6 +445,11 @@ def _check_forms(a, m, symmetric):
             raise ValueError('%s: a bilinear form (rank 2), not rank %d'
                              % (name, f.rank))
         W = f.arguments()[0]
+        if forms.is_mixed_space(W):
+            raise NotImplementedError(
+                'Eigenmodes of forms on a mixed space is not implemented: '
+                'LOBPCG takes positive definite problems on one scalar or '
+                'vector space, a saddle-point operator is indefinite')
         if V is None:
             V = W
         elif not W.same_as(V):

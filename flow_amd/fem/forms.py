@@ -121,7 +121,17 @@ switches.  Refused there (NotImplementedError): W.sub(i) as an argument
 space, Eigenmodes, strips, and -- OFF by default like the arguments
 themselves -- derivative() with respect to a vector Function and solve(F ==
 0): `vector_derivatives(True)` switches those on (below).
-Not supported (NotImplementedError): arguments on mixed spaces, test
+Arguments on a Taylor-Hood space WP = VectorElement(P_kv) * FiniteElement(P_kp),
+kv, kp in {1, 2}, are OFF by default too (NotImplementedError);
+`mixed_arguments(True)` switches them on (it implies no other switch):
+TestFunctions(WP) / TrialFunctions(WP) give (vector, scalar) pairs whose leaves
+are ('arg', number, d, WP, comp), comp 0, 1 (velocity), 2 (pressure);
+argument_table gives a MixedTable of 3 x 3 (rank 1: 3) scalar tables whose
+velocity() corner is the BlockTable of a vector form; is_symmetric_form judges
+symmetry over all parts of a sum; Function(WP), split(w), w.split(), w.sub(i)
+(function.py); assembly and solve: fem/mixed.py.
+Not supported (NotImplementedError): arguments on other mixed spaces, a mixed
+argument together with an argument of another space, test
 and trial functions of different spaces (a vector test function with a scalar
 trial function included), arguments under dS, action / adjoint.  lhs / rhs
 also split ONE integrand that holds terms of
@@ -1041,6 +1051,10 @@ def FacetNormal(mesh):
 def _argument(V, number):
     name = ('TestFunction', 'TrialFunction')[number]
     if not hasattr(V, 'layout') or not hasattr(V, 'dim'):
+        if mixed_arguments.enabled:
+            # (a 3-vector does not exist here: the pair, as TestFunctions)
+            raise NotImplementedError(
+                '%s on a mixed space: take the pair, %ss(W)' % (name, name))
         raise NotImplementedError(
             '%s on a mixed space: only scalar P1 / P2 spaces carry arguments'
             % name)
@@ -1116,12 +1130,88 @@ def TrialFunction(V):
     return _argument(V, 1)
 
 
+class mixed_arguments(_Switch):
+    '''The switch of test and trial functions, and of Functions, on a
+    Taylor-Hood space WP = FunctionSpace(mesh, VectorElement('Lagrange',
+    triangle, kv) * FiniteElement('Lagrange', triangle, kp)), kv, kp in {1,
+    2}: TestFunctions(WP), TrialFunctions(WP), Function(WP), split.  Off by
+    default: each of them stays the error it was.  `mixed_arguments(True)`
+    switches them on at once, for the process; `.previous` is the setting it
+    replaced, and as a context manager it restores that on exit.  It implies
+    no other switch: the forms need vector_arguments(True) as well, their ds
+    parts facet_arguments(True), their dx(k) parts cell_subdomains(True).'''
+    enabled = False
+
+
+_MIXED_MISMATCH = (
+    'an argument of a mixed space together with an argument of another space '
+    'in one form: the test and the trial function of a mixed form both come '
+    'from TestFunctions(W) / TrialFunctions(W) of ONE mixed space')
+
+
+def is_mixed_space(V):
+    '''Whether V is a mixed (velocity-pressure) space.'''
+    return hasattr(V, 'spaces') and not hasattr(V, 'layout')
+
+
+def _mixed_arguments(W, number):
+    name = ('TestFunctions', 'TrialFunctions')[number]
+    if not is_mixed_space(W):
+        raise NotImplementedError(
+            '%s takes a mixed (velocity-pressure) space and returns a pair; '
+            'on a scalar or vector space use %s' % (name, name[:-1]))
+    if not mixed_arguments.enabled:
+        # (the error TestFunction(W) / TrialFunction(W) always was)
+        return _argument(W, number)
+    if not vector_arguments.enabled:
+        raise NotImplementedError(
+            '%s: mixed_arguments(True) is on, but vector_arguments(True) is '
+            'not: the velocity part is a vector argument, which '
+            'vector_arguments switches on' % name)
+    Wv, P = W.taylor_hood()
+    mesh = W.mesh()
+    v = FormExpr([('arg', number, 0, W, c) for c in range(2)], (2,),
+                 Wv.degree, mesh)
+    q = FormExpr(('arg', number, 0, W, 2), (), P.degree, mesh)
+    return v, q
+
+
+def TestFunctions(W):
+    '''(v, q) of the Taylor-Hood space W (mixed_arguments(True)): the vector
+    test function of the velocity part, a FormExpr of shape (2,), and the
+    scalar one of the pressure part.  The leaves are ('arg', 0, d, W, comp),
+    comp 0, 1 (velocity) or 2 (pressure); every component has its own scalar
+    layout: W.sub(0)'s for 0 and 1, W.sub(1)'s for 2.'''
+    return _mixed_arguments(W, 0)
+
+
+def TrialFunctions(W):
+    '''(u, p) of the Taylor-Hood space W: the trial functions (number 1).'''
+    return _mixed_arguments(W, 1)
+
+
+def split(w):
+    '''split(w) of a Function on a mixed space: w.split(), views of its
+    storage as ordinary Functions (coefficients of forms like any other).'''
+    if not isinstance(w, Function) or not is_mixed_space(w.function_space()):
+        raise TypeError('split takes a Function of a mixed space: the pairs '
+                        'of test and trial functions come from '
+                        'TestFunctions(W) / TrialFunctions(W)')
+    return w.split()
+
+
+def _same_space(V, W):
+    if is_mixed_space(V) != is_mixed_space(W):
+        raise NotImplementedError(_MIXED_MISMATCH)
+    return V is W or V.same_as(W)
+
+
 def arguments(n, found=None):
     '''{number: space} of the argument leaves of a scalar tree.'''
     found = {} if found is None else found
     if n[0] == 'arg':
         V = found.setdefault(n[1], n[3])
-        if V is not n[3] and not V.same_as(n[3]):
+        if V is not n[3] and not _same_space(V, n[3]):
             raise NotImplementedError(
                 'two %s functions of different spaces in one form'
                 % ('test', 'trial')[n[1]])
@@ -1208,7 +1298,9 @@ def argument_table(integrand):
     (rank 1) of coefficient trees, None where the term is absent.  With
     arguments of a vector space (callers tell by the space's dim) one such
     table per block: table[r][s][b][a] or table[r][b], None for an absent
-    block.'''
+    block.  Arguments of a mixed space (TestFunctions): a MixedTable of 3 x 3
+    (rank 2) or 3 (rank 1) blocks over the components 0, 1 (velocity), 2
+    (pressure).'''
     tab = {key: c for key, c in extract_arguments(integrand).items()
            if not _is_num(c, 0.0)}
     kinds = set((b is not None, a is not None) for b, a in tab)
@@ -1224,7 +1316,9 @@ def argument_table(integrand):
     if not kinds or kinds == {(False, False)}:
         return 0, None
     if any(isinstance(b, tuple) for b, a in tab):
-        return _block_table(tab, 1 if kinds == {(True, False)} else 2)
+        mixed = any(is_mixed_space(V) for V in arguments(integrand).values())
+        return _block_table(tab, 1 if kinds == {(True, False)} else 2,
+                            3 if mixed else 2)
     if kinds == {(True, False)}:
         return 1, [tab.get((b, None)) for b in range(3)]
     return 2, [[tab.get((b, a)) for a in range(3)] for b in range(3)]
@@ -1236,25 +1330,43 @@ class BlockTable(list):
     a scalar form (is_symmetric_table).'''
 
 
-def _block_table(tab, rank):
+class MixedTable(BlockTable):
+    '''The table of a form of arguments on a Taylor-Hood space: 3 x 3 (rank
+    2) or 3 (rank 1) blocks over the components 0, 1 (velocity) and 2
+    (pressure).  velocity() is its [0:2][0:2] corner (rank 1: [0:2]): exactly
+    the BlockTable of the same terms written on the velocity space alone.'''
+
+    def velocity(self):
+        corner = BlockTable(row[:2] if self.rank == 2 else row
+                            for row in self[:2])
+        corner.rank = self.rank
+        return corner
+
+
+def _block_table(tab, rank, nb=2):
     '''argument_table of vector arguments: table[r] (rank 1) or table[r][s]
     (rank 2), r the test and s the trial component, each the table of a
-    scalar form or None where the block has no term.'''
+    scalar form or None where the block has no term.  nb = 3: the components
+    of a mixed space, a MixedTable.'''
     if any(d is not None and not isinstance(d, tuple)
            for key in tab for d in key):
         raise NotImplementedError(
             'test and trial functions of different spaces (a vector and a '
             'scalar argument in one form)')
+    kind = MixedTable if nb == 3 else BlockTable
     if rank == 1:
         blocks = [[tab.get(((b, r), None)) for b in range(3)]
-                  for r in range(2)]
-        return 1, BlockTable(t if any(c is not None for c in t) else None
-                             for t in blocks)
-    blocks = [[[[tab.get(((b, r), (a, s))) for a in range(3)]
-                for b in range(3)] for s in range(2)] for r in range(2)]
-    return 2, BlockTable(
-        [t if any(c is not None for row in t for c in row) else None
-         for t in row] for row in blocks)
+                  for r in range(nb)]
+        table = kind(t if any(c is not None for c in t) else None
+                     for t in blocks)
+    else:
+        blocks = [[[[tab.get(((b, r), (a, s))) for a in range(3)]
+                    for b in range(3)] for s in range(nb)] for r in range(nb)]
+        table = kind(
+            [t if any(c is not None for row in t for c in row) else None
+             for t in row] for row in blocks)
+    table.rank = rank
+    return rank, table
 
 
 def block_items(table, rank):
@@ -1271,12 +1383,57 @@ def is_symmetric_table(table):
     tree for every (a, b).  A BlockTable (2 x 2 blocks, vector arguments):
     c[r][s][b][a] and c[s][r][a][b] are.'''
     if isinstance(table, BlockTable):
+        nb = len(table)         # (3: the MixedTable of a Taylor-Hood form)
+
         def entry(r, s, b, a):
             return None if table[r][s] is None else table[r][s][b][a]
         return all(entry(r, s, b, a) == entry(s, r, a, b)
-                   for r in range(2) for s in range(2)
+                   for r in range(nb) for s in range(nb)
                    for b in range(3) for a in range(3))
     return all(table[b][a] == table[a][b] for b in range(3) for a in range(b))
+
+
+def is_symmetric_form(form):
+    '''Structural symmetry of a rank-2 form of mixed (or vector) arguments
+    over ALL its parts: the reference writes its Stokes form as three
+    integrals, of which -p*div(v)*dx alone is not symmetric but together with
+    -q*div(u)*dx is.  The signed coefficient trees of entry (r, s, b, a),
+    collected over the parts with their measure (type, subdomain, metadata),
+    must be those of entry (s, r, a, b).'''
+    entries = {}
+    for sign, part in form.terms():
+        _, table = part.argument_table()
+        if not isinstance(table, BlockTable):
+            table = [[table]]
+        where = (part.integral_type, part.subdomain_id,
+                 id(part.subdomain_data), sorted(part.metadata.items()))
+        nb = len(table)
+        for r in range(nb):
+            for s in range(nb):
+                if table[r][s] is None:
+                    continue
+                for b in range(3):
+                    for a in range(3):
+                        c = table[r][s][b][a]
+                        if c is None:
+                            continue
+                        # (one spelling of the sign: a - f and a + (-1)*f)
+                        sg = sign
+                        while c[0] == 'neg':
+                            sg, c = -sg, c[1]
+                        if _is_num(c):
+                            sg, c = 1.0, ('num', sg * c[1])
+                        entries.setdefault((r, s, b, a), []).append(
+                            (sg, c, where))
+    for (r, s, b, a), found in entries.items():
+        other = list(entries.get((s, r, a, b), []))
+        if len(other) != len(found):
+            return False
+        for item in found:
+            if item not in other:
+                return False
+            other.remove(item)
+    return True
 
 
 def has_normal(n):
@@ -1701,7 +1858,8 @@ class Form(object):
         '''{number: space} of the test (0) and trial (1) functions.'''
         if getattr(self, '_arguments', None) is None:
             found = arguments(self.integrand.comps)
-            if 0 in found and 1 in found and not found[0].same_as(found[1]):
+            if 0 in found and 1 in found \
+                    and not _same_space(found[0], found[1]):
                 raise NotImplementedError(
                     'test and trial functions of different spaces or meshes')
             self._arguments = found
@@ -1776,7 +1934,7 @@ class FormSum(Form):
         for _, f in self._terms:
             for number, V in f.arguments().items():
                 W = found.setdefault(number, V)
-                if not W.same_as(V):
+                if not _same_space(W, V):
                     raise NotImplementedError(
                         'test and trial functions of different spaces or '
                         'meshes')

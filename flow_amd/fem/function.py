@@ -277,8 +277,30 @@ class _VectorSlice(object):
         return self.vec.get_local()
 
 
+def _mixed_enabled(V):
+    '''Whether V is a mixed space and forms.mixed_arguments(True) is on.'''
+    from . import forms
+    return forms.mixed_arguments.enabled and forms.is_mixed_space(V)
+
+
 class Function(_FormOperand):
+    # True for a Function of a Taylor-Hood space (made while
+    # forms.mixed_arguments(True) was on; what it is does not change after)
+    _mixed = False
+
     def __init__(self, V, data=None):
+        if _mixed_enabled(V):
+            # (forms.mixed_arguments(True): one vector of 2 Nv + Np doubles,
+            # velocity x, velocity y, pressure -- the numbering of the kind-2
+            # operators on its velocity part)
+            V.taylor_hood()
+            self._V = V
+            self._mixed = True
+            self.data = device.zeros(V.size()) if data is None else data
+            assert self.data.numel() == V.size() \
+                and self.data.dtype == torch.float64
+            self._name = 'f'
+            return
         assert isinstance(V, FunctionSpace)
         assert V.component is None, 'Function on a sub-space view'
         self._V = V
@@ -344,8 +366,18 @@ class Function(_FormOperand):
     def name(self):
         return self._name
 
-    def split(self, deepcopy=True):
-        '''Component functions of a vector field (copies).'''
+    def split(self, deepcopy=None):
+        '''Component functions of a vector field (copies).  Of a Function on
+        a Taylor-Hood space (forms.mixed_arguments): the velocity, a vector
+        Function on W.sub(0), and the pressure, a scalar one on W.sub(1) --
+        views of this Function's storage (deepcopy=False, the default there)
+        or copies (deepcopy=True).'''
+        if self._mixed:
+            W, P = self._V.taylor_hood()
+            parts = (self.data[:W.size()], self.data[W.size():])
+            if deepcopy:
+                parts = tuple(_hip.clone(x) for x in parts)
+            return Function(W, parts[0]), Function(P, parts[1])
         assert self._V.dim == 2
         n = self._V.N
         S = self._V.collapse()
@@ -354,10 +386,22 @@ class Function(_FormOperand):
             for c in range(2)
             )
 
+    def sub(self, i):
+        '''w.sub(i) of a Function on a Taylor-Hood space: w.split()[i], a
+        view.'''
+        if not self._mixed:
+            raise NotImplementedError(
+                'Function.sub: Functions of a mixed space only (after '
+                'forms.mixed_arguments(True)); components of a vector field '
+                'are u[i] in forms and u.split() as Functions')
+        return self.split()[i]
+
     def ufl_element(self):
         return self._V.ufl_element()
 
     def value_dim(self):
+        if self._mixed:
+            return 3
         return self._V.dim
 
     def __call__(self, *x):

@@ -1079,6 +1079,11 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
     from . import forms
     from .function import Vector
     V = form.arguments()[0]
+    if forms.is_mixed_space(V):
+        # (a Taylor-Hood space, forms.mixed_arguments: a MixedMatrix or a
+        # Vector of 2 Nv + Np)
+        from . import mixed
+        return mixed.assemble_form(form, rank, form_compiler_parameters)
     lay, mesh = V.layout, V.mesh()
     total = _Sum()
     for sign, part in form.terms():
@@ -1205,6 +1210,9 @@ def assemble_system(a, L, bcs=None, form_compiler_parameters=None):
     from .function import Vector
     _no_strips('assemble_system')
     V = _form_space(a)
+    if forms.is_mixed_space(V):
+        from . import mixed
+        return mixed.assemble_system(a, L, bcs, form_compiler_parameters)
     A0 = assemble(a, form_compiler_parameters)
     if L is None or (isinstance(L, forms.FormSum) and not L.terms()):
         b = Vector(device.zeros(V.size()))
@@ -1289,6 +1297,11 @@ def solve(equation, u, bcs=None, J=None, solver_parameters=None,
         raise TypeError('solve takes an equation a == L of a bilinear and a '
                         'linear form (got %r)' % (type(equation),))
     if isinstance(equation.rhs, numbers.Real):
+        if isinstance(u, Function) and forms.is_mixed_space(
+                u.function_space()):
+            raise NotImplementedError(
+                'solve(F == 0) on a mixed space: Newton\'s method takes '
+                'scalar and vector spaces only')
         return newton_solve(equation.lhs, u, bcs, J, solver_parameters,
                             form_compiler_parameters)
     if J is not None:
@@ -1301,6 +1314,11 @@ def solve(equation, u, bcs=None, J=None, solver_parameters=None,
             'are %s' % (method, ', '.join(_KRYLOV_METHODS + ('default',))))
     a, L = equation.lhs, equation.rhs
     V = _form_space(a)
+    if forms.is_mixed_space(V):
+        # (symmetric forms only: preconditioned MINRES, fem/mixed.py)
+        from . import mixed
+        return mixed.solve(a, L, u, bcs, solver_parameters,
+                           form_compiler_parameters)
     if not isinstance(u, Function) or not u.function_space().same_as(V):
         raise ValueError('solve writes into a Function of the space of the '
                          'trial function')

@@ -280,7 +280,8 @@ class FunctionSpace(object):
 
     def same_as(self, other):
         return (
-            self._mesh is other._mesh and self.degree == other.degree
+            isinstance(other, FunctionSpace)
+            and self._mesh is other._mesh and self.degree == other.degree
             and self.dim == other.dim
             )
 
@@ -324,6 +325,177 @@ class MixedFunctionSpace(object):
 
     def num_sub_spaces(self):
         return len(self.spaces)
+
+    def same_as(self, other):
+        return (
+            isinstance(other, MixedFunctionSpace)
+            and len(self.spaces) == len(other.spaces)
+            and all(a.same_as(b) for a, b in zip(self.spaces, other.spaces))
+            )
+
+    def taylor_hood(self):
+        '''(velocity space, pressure space) where the pair has the one shape
+        forms of mixed arguments support (forms.mixed_arguments): a P1 / P2
+        vector space times a P1 / P2 scalar space; NotImplementedError for any
+        other mixed space.'''
+        ok = len(self.spaces) == 2 and all(
+            isinstance(S, FunctionSpace) and S.degree in (1, 2)
+            for S in self.spaces) \
+            and self.spaces[0].dim == 2 and self.spaces[1].dim == 1
+        if not ok:
+            raise NotImplementedError(
+                'mixed spaces: only VectorElement(Lagrange, k) * '
+                'FiniteElement(Lagrange, l) with k, l in {1, 2} (the '
+                'Taylor-Hood shape) carries arguments and Functions')
+        return self.spaces[0], self.spaces[1]
+
+    def size(self):
+        '''2 Nv + Np: velocity x, velocity y, pressure.'''
+        W, P = self.taylor_hood()
+        return W.size() + P.size()
+
+    def offsets(self):
+        '''Where the three scalar components start, and the end.'''
+        W, P = self.taylor_hood()
+        return (0, W.N, 2 * W.N, 2 * W.N + P.N)
+
+
+class RectLayout(object):
+    '''The CSR pattern of the pairs (test dof of the scalar layout of degree
+    deg_rows, trial dof of the one of degree deg_cols) that share a cell, and
+    the contribution maps of flow_form_rect_matrix: rowptr, cols (padded on
+    the device like ScalarLayout.dev('cols')), nnz, rowblocks
+    (csr_stream_rowblocks: a kind-0 rectangular flow_operator), cptr / csrc
+    (entry e sums scratch[csrc[t]], t in [cptr[e], cptr[e+1]); the scratch is
+    laid out (i*nloc_cols + j)*nc + c; the sources of a target ascend by
+    cell, as in ScalarLayout._build_pattern).  Use rect_layout(): cached on
+    the mesh.'''
+
+    def __init__(self, mesh, deg_rows, deg_cols):
+        self.mesh = mesh
+        self.rows = scalar_layout(mesh, deg_rows)
+        self.cols_layout = scalar_layout(mesh, deg_cols)
+        self.shape = (self.rows.N, self.cols_layout.N)
+        nlr, nlc = self.rows.nloc, self.cols_layout.nloc
+        nc = len(self.rows.cell_dofs)
+        M = self.cols_layout.N
+        rd = self.rows.cell_dofs.astype(numpy.int64)
+        cd = self.cols_layout.cell_dofs.astype(numpy.int64)
+        key = (rd[:, :, None] * M + cd[:, None, :]).ravel()   # [c][i][j]
+        order = numpy.argsort(key, kind='stable')
+        skey = key[order]
+        new = numpy.empty(len(skey), dtype=bool)
+        new[0] = True
+        numpy.not_equal(skey[1:], skey[:-1], out=new[1:])
+        first = numpy.nonzero(new)[0]
+        ukey = skey[first]
+        rowptr = numpy.zeros(self.rows.N + 1, dtype=numpy.int64)
+        numpy.cumsum(numpy.bincount(ukey // M, minlength=self.rows.N),
+                     out=rowptr[1:])
+        assert nlr * nlc * nc < 2**31
+        self.nnz = len(ukey)
+        self.ukey = ukey
+        self.rowptr = rowptr.astype(numpy.int32)
+        self.cols = (ukey % M).astype(numpy.int32)
+        self.cptr = numpy.concatenate([first, [len(order)]]).astype(
+            numpy.int32)
+        # scratch index of pair p = (cell, ij): ij*nc + cell (cell fastest)
+        self.csrc = ((order % (nlr * nlc)) * nc + order // (nlr * nlc)).astype(
+            numpy.int32)
+        self._rowblocks = None
+        self._dev = {}
+
+    @property
+    def rowblocks(self):
+        if self._rowblocks is None:
+            self._rowblocks = csr_stream_rowblocks(
+                self.rowptr.astype(numpy.int64))
+        return self._rowblocks
+
+    @property
+    def stride(self):
+        '''Distance between two value planes over the pattern (ops.plane_
+        stride's rule: nnz rounded up to even).'''
+        return self.nnz + (self.nnz & 1)
+
+    def dev(self, name):
+        from .. import device
+        if name not in self._dev:
+            arr = getattr(self, name)
+            if name == 'cols':
+                arr = numpy.concatenate([arr, numpy.zeros(4, dtype=arr.dtype)])
+            self._dev[name] = device.to_device(arr)
+        return self._dev[name]
+
+    def _targets(self, cells):
+        '''Entry indices [k][i][j] of the element pairs of the listed cells.'''
+        M = self.cols_layout.N
+        rd = self.rows.cell_dofs[cells].astype(numpy.int64)
+        cd = self.cols_layout.cell_dofs[cells].astype(numpy.int64)
+        key = rd[:, :, None] * M + cd[:, None, :]
+        tgt = numpy.searchsorted(self.ukey, key)
+        assert (self.ukey[tgt] == key).all()
+        return tgt
+
+    def facet_map_host(self, markers=None, subdomain_id='everywhere'):
+        '''ops.facet_map_host for this pattern: (targets, ptr, src) of the
+        facets of the selection, whose lanes write scratch[(i*nloc_cols +
+        j)*nf + k]; sources ascend by facet position, then by ij.'''
+        from . import ops
+        sel = ops._facet_selection(self.mesh, markers, subdomain_id)
+        return self._list_map(self.mesh.bfacet_cell[sel])
+
+    def cell_map_host(self, markers=None, subdomain_id='everywhere'):
+        '''ops.cell_map_host for this pattern: (targets, ptr, src) of the
+        selected cells (ascending), whose lanes write scratch[(i*nloc_cols +
+        j)*nsel + k]; sources ascend by cell, as cptr / csrc list them.'''
+        from . import ops
+        sel = ops._cell_selection(self.mesh, markers, subdomain_id)
+        return self._list_map(sel)
+
+    def _list_map(self, cells):
+        n = len(cells)
+        if n == 0:
+            return (numpy.zeros(0, numpy.int32), numpy.zeros(1, numpy.int32),
+                    numpy.zeros(0, numpy.int32))
+        tgt = self._targets(cells).transpose(1, 2, 0).reshape(-1)  # [ij][k]
+        assert len(tgt) < 2**31
+        scr = numpy.arange(len(tgt), dtype=numpy.int64)
+        order = numpy.lexsort((scr // n, scr % n, tgt))     # (target, k, ij)
+        st = tgt[order]
+        first = numpy.nonzero(
+            numpy.concatenate([[True], st[1:] != st[:-1]]))[0]
+        return (st[first].astype(numpy.int32),
+                numpy.concatenate([first, [len(st)]]).astype(numpy.int32),
+                order.astype(numpy.int32))
+
+
+def transpose_permutation(rowptr, cols, other_rowptr, other_cols):
+    '''perm (int32, one entry per nonzero of the CSR pattern (rowptr,
+    cols)): the position of the mirror image (col, row) of every
+    entry in the pattern (other_rowptr, other_cols) of the transposed block.
+    The patterns here are structurally symmetric to one another: every mirror
+    image exists.'''
+    rowptr = numpy.asarray(rowptr, dtype=numpy.int64)
+    other_rowptr = numpy.asarray(other_rowptr, dtype=numpy.int64)
+    nrows = len(rowptr) - 1
+    rows = numpy.repeat(numpy.arange(nrows, dtype=numpy.int64),
+                        numpy.diff(rowptr))
+    orows = numpy.repeat(numpy.arange(len(other_rowptr) - 1,
+                                      dtype=numpy.int64),
+                         numpy.diff(other_rowptr))
+    okey = orows * nrows + numpy.asarray(other_cols, dtype=numpy.int64)
+    key = numpy.asarray(cols, dtype=numpy.int64) * nrows + rows
+    perm = numpy.searchsorted(okey, key)
+    assert (okey[perm] == key).all()
+    return perm.astype(numpy.int32)
+
+
+def rect_layout(mesh, deg_rows, deg_cols):
+    key = ('rect_layout', deg_rows, deg_cols)
+    if key not in mesh._cache:
+        mesh._cache[key] = RectLayout(mesh, deg_rows, deg_cols)
+    return mesh._cache[key]
 
 
 # pylint: disable=invalid-name

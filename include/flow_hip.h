@@ -1420,6 +1420,58 @@ int flow_form_cells_vector(const flow_mesh* mesh, const flow_space* V,
                            const int* map_ptr, const int* map_src,
                            double* scratch, double* b, void* stream);
 
+/* Rectangular blocks: a test function of the scalar space V_test and a trial
+ * function of the scalar space V_trial on one mesh (degrees 1 | 2, equal or
+ * not) -- the velocity-pressure coupling of a form on a Taylor-Hood space
+ * (forms.py, mixed_arguments).  The program is the coefficient table of
+ * flow_form_matrix (nout = FLOW_FORM_SLOTS: slot 3 b + a multiplies D_a of the
+ * trial and D_b of the test function); the rule and the tables are those of
+ * flow_form_matrix (rect_matrix, rect_cells_matrix) or of
+ * flow_form_facet_matrix (rect_facet_matrix: 3*nq rows, NORMAL legal).
+ *   Element kernels: flow_form_matrix's, flow_form_facet_matrix's and
+ * flow_form_cells_matrix's with two bases -- per point and test derivative b,
+ * t_j = sum_a w c_ba D_a psi_j over the trial basis first, then Ke[i][j] +=
+ * D_b phi_i t_j over the test basis -- into
+ *     scratch[(i*nloc_trial + j)*n + k],  n = nc | nfacets | ncells, k fastest
+ * (scratch: nloc_test * nloc_trial * n doubles).
+ *   flow_form_rect_matrix: the gather sums scratch over cptr (nnz + 1) / csrc
+ * in order into vals (nnz doubles), the pattern of pairs (test dof, trial dof)
+ * that share a cell (space.RectLayout).  With V_test == V_trial and the maps
+ * of that space it gives the bits of flow_form_matrix.
+ *   flow_form_rect_facet_matrix / flow_form_rect_cells_matrix: the gather of
+ * flow_form_facet_matrix over (map_targets, map_ptr, map_src) into vals (nnz);
+ * every other entry is left as it is.  nfacets | ncells == 0 or ntargets == 0:
+ * nothing launched.
+ *   Refused: degrees outside {1, 2}, a space with more dofs than the cells of
+ * the mesh can hold (a space of another mesh), NORMAL in the two cell entry
+ * points, strips, nnz above the scratch entries or above n_test * n_trial,
+ * more targets than nnz.  A map row or source outside the scratch, a list
+ * entry outside the mesh: NaN, not a stray read.  No atomics: two calls give
+ * the same bits. */
+int flow_form_rect_matrix(const flow_mesh* mesh, const flow_space* V_test,
+                          const flow_space* V_trial, const flow_form* form,
+                          double* scratch, double* vals, const int* cptr,
+                          const int* csrc, int nnz, void* stream);
+int flow_form_rect_facet_matrix(const flow_mesh* mesh, const flow_space* V_test,
+                                const flow_space* V_trial, const flow_form* form,
+                                int nfacets, const int* facet_cell,
+                                const int* facet_local, int ntargets,
+                                const int* map_targets, const int* map_ptr,
+                                const int* map_src, double* scratch, double* vals,
+                                int nnz, void* stream);
+int flow_form_rect_cells_matrix(const flow_mesh* mesh, const flow_space* V_test,
+                                const flow_space* V_trial, const flow_form* form,
+                                int ncells, const int* cells, int ntargets,
+                                const int* map_targets, const int* map_ptr,
+                                const int* map_src, double* scratch, double* vals,
+                                int nnz, void* stream);
+/* vals[e] = 0 for every entry e of a rectangular CSR plane (rowptr: n_rows + 1)
+ * whose row (row_isbc, n_rows bytes) or column (col_isbc, one byte per column)
+ * is a Dirichlet dof; the other entries stay.  One lane per row. */
+int flow_bc_rect_mask(const int* rowptr, const int* cols, int n_rows, double* vals,
+                      const unsigned char* row_isbc, const unsigned char* col_isbc,
+                      void* stream);
+
 /* Forms of a test function v and a trial function u of the VECTOR space on V's
  * scalar pattern (forms.py, vector_arguments): the host rewrites the integrand
  * as  sum_(r,s) sum_(b,a) c^rs_ba D_a u_s D_b v_r  (rank 2) or  sum_r sum_b
@@ -1955,6 +2007,14 @@ int flow_bc_set_values(int nbc, const int* dofs, const double* g, double* x,
 int flow_bc_symmetric_matrix(int n, const int* rowptr, const int* cols,
                              const double* vals_in, const unsigned char* isbc,
                              double* vals_out, void* stream);
+/* out[e] = (a[e] + b[perm[e]]) / 2, e < n: the symmetric part of the value
+ * plane a of a block, b (nb entries) being the plane of the transposed block
+ * and perm[e] the position in b of the mirror image of entry e (device int32,
+ * built once per pattern on the host).  The sum commutes: calling it for (a,
+ * b, perm) and for (b, a, inverse perm) gives mirrored entries the same bits.
+ * out overlaps neither input; perm[e] outside [0, nb) gives NaN. */
+int flow_plane_symmetric_part(int n, const double* a, const double* b, int nb,
+                              const int* perm, double* out, void* stream);
 /* The same elimination for the four planes of a kind-2 operator (2x2 blocks
  * over one scalar pattern; plane p = 2 r + s at vals + p*stride, stride >= nnz)
  * in one launch: entry (i, j) of plane (r, s) becomes (r == s && i == j) ? 1 : 0
