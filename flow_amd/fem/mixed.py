@@ -36,6 +36,7 @@ import numpy
 import torch
 
 from . import ops
+from . import selection
 from .function import Function, Vector
 from .space import rect_layout
 from .. import _hip
@@ -194,106 +195,33 @@ class MixedMatrix(object):
 
 
 # -- assembly ---------------------------------------------------------------------
-def _scalar_part(part, table, rank, q, scheme, lay, mesh, total, sign):
-    '''One part of a scalar form (the pressure corner) into the sum `total`:
-    the launches of ops._assemble_arguments on a scalar space.'''
-    from . import forms
-    facet = part.integral_type == 'exterior_facet'
-    for prog in forms.argument_programs(table, rank, facet):
-        fs, keep = ops._form_struct(prog, mesh, q, facet, scheme)
-        if facet or ops.is_cell_subdomain(part):
-            out = ops.value_plane(lay) if rank == 2 else device.zeros(lay.N)
-            ops._selection_arguments(mesh, lay, rank, fs, part, out)
-        elif rank == 2:
-            out = ops.value_plane(lay)
-            ops._launch_dx(mesh, lay, 'matrix', fs, out, None)
-        else:
-            out = device.empty(lay.N)
-            ops._launch_dx(mesh, lay, 'vector', fs, None, out)
-        del keep
-        total.add(sign, out, True)
-
-
-def _rect_map(R, part):
-    '''The contribution map of a ds or dx(k) part over the rectangular
-    pattern R on the device, (targets, ptr, src, number of targets), held on R
-    against the markers' version like ops.facet_map.'''
-    markers, sid = part.subdomain_data, part.subdomain_id
-    cell = part.integral_type == 'cell'
-    everywhere = sid in (None, 'everywhere')
-    if cell:
-        ops._check_cell_markers(R.mesh, markers, sid)
-    elif markers is None and not everywhere:
-        raise ValueError('ds(%r) needs markers: Measure(\'ds\', domain=mesh, '
-                         'subdomain_data=markers)' % (sid,))
-    elif markers is not None and markers.mesh is not R.mesh:
-        raise ValueError('the facet markers belong to another mesh')
-    cache = R._dev.setdefault('maps', {})
-    key = (cell, None if everywhere else id(markers),
-           None if everywhere else sid, str(device.get()))
-    version = None if everywhere else markers.version
-    held = cache.get(key)
-    if held is not None and held[0] is (None if everywhere else markers) \
-            and held[1] == version:
-        return held[2]
-    fn = R.cell_map_host if cell else R.facet_map_host
-    targets, ptr, src = fn(markers, sid)
-    nt = len(targets)
-    rmap = (device.to_device(targets), device.to_device(ptr),
-            device.to_device(src), nt) if nt else (None, None, None, 0)
-    if len(cache) >= 32:
-        cache.clear()
-    cache[key] = (None if everywhere else markers, version, rmap)
-    return rmap
-
-
 def rect_launch(R, part, fs, out):
     '''One program of a coupling block over the pattern R into the plane
     `out` (zero outside a ds / dx(k) part's targets): flow_form_rect_matrix,
-    or its list form over the exterior facets / the cells of the part.'''
+    or its list form over the exterior facets / the cells of the part with
+    the map of selection.rect_map.'''
     lib = _hip.lib()
     mesh = R.mesh
-    nc = mesh.num_cells()
     nl2 = R.rows.nloc * R.cols_layout.nloc
     head = (ctypes.byref(ops.mesh_struct(mesh)),
             ctypes.byref(ops.space_struct(R.rows)),
             ctypes.byref(ops.space_struct(R.cols_layout)), ctypes.byref(fs))
     if part is None or (part.integral_type == 'cell'
                         and not ops.is_cell_subdomain(part)):
-        n = nl2 * nc
+        n = nl2 * mesh.num_cells()
         _hip.check(lib.flow_form_rect_matrix(
             *head, _hip.f64(ops.scratch(mesh, n), n, 'scratch'),
             _hip.f64(out, R.nnz, 'vals'),
             _hip.i32(R.dev('cptr'), R.nnz + 1, 'cptr'),
             _hip.i32(R.dev('csrc'), n, 'csrc'), R.nnz, _hip.stream()))
         return
-    if part.integral_type == 'cell':
-        cells, nsel = ops.cell_lists(mesh, part.subdomain_data,
-                                     part.subdomain_id)
-        if nsel == 0:
-            return
-        targets, ptr, src, nt = _rect_map(R, part)
-        n = nl2 * nsel
-        _hip.check(lib.flow_form_rect_cells_matrix(
-            *head, nsel, _hip.i32(cells, nsel, 'cell list'), nt,
-            _hip.i32(targets, nt, 'map targets'),
-            _hip.i32(ptr, nt + 1, 'map ptr'), _hip.i32(src, n, 'map src'),
-            _hip.f64(ops.scratch(mesh, n), n, 'scratch'),
-            _hip.f64(out, R.nnz, 'vals'), R.nnz, _hip.stream()))
-        return
-    cells, local, nf = ops.facet_lists(mesh, part.subdomain_data,
-                                       part.subdomain_id)
-    if nf == 0:
-        return
-    targets, ptr, src, nt = _rect_map(R, part)
-    n = nl2 * nf
-    _hip.check(lib.flow_form_rect_facet_matrix(
-        *head, nf, _hip.i32(cells, nf, 'facet cells'),
-        _hip.i32(local, nf, 'facet local indices'), nt,
-        _hip.i32(targets, nt, 'map targets'), _hip.i32(ptr, nt + 1, 'map ptr'),
-        _hip.i32(src, n, 'map src'),
-        _hip.f64(ops.scratch(mesh, n), n, 'scratch'),
-        _hip.f64(out, R.nnz, 'vals'), R.nnz, _hip.stream()))
+    cell = part.integral_type == 'cell'
+    ops._list_launch(
+        lib.flow_form_rect_cells_matrix if cell
+        else lib.flow_form_rect_facet_matrix,
+        head, mesh, *ops._selection_lists(mesh, part),
+        selection.rect_map(R, cell, part.subdomain_data, part.subdomain_id),
+        nl2, (out, R.nnz, 'vals'), (R.nnz,))
 
 
 def _rect_part(part, block, q, scheme, R, mesh):
@@ -343,8 +271,8 @@ def assemble_form(form, rank, form_compiler_parameters=None):
                                                  layv, mesh), True)
         pblock = table[2][2] if rank == 2 else table[2]
         if pblock is not None:
-            _scalar_part(part, pblock, rank, q, scheme, layp, mesh,
-                         sums['pp'], sign)
+            ops._scalar_part(part, pblock, rank, q, scheme, layp, mesh,
+                             sums['pp'], sign)
         if rank == 1:
             continue
         for c in range(2):

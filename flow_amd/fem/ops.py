@@ -26,6 +26,11 @@ from . import reference
 from .function import (
     Function, Expression, Constant, as_cell_coefficient, cell_lattice_points,
     )
+from .selection import (        # noqa: F401  (ops' names for them stay)
+    InteriorFacetLists, facet_lists, interior_facet_lists, cell_lists,
+    facet_map_host, facet_map, cell_map_host, cell_map, is_cell_subdomain,
+    _facet_selection, _cell_selection, _check_cell_markers,
+    )
 from .space import mesh_geometry_dev
 from .. import _hip
 from .. import device
@@ -990,16 +995,15 @@ def assemble(form, form_compiler_parameters=None):
     kind 2.  Ranks 1 and 2 go part by part through _assemble_arguments (on a
     vector space _block_part) and the launches of _launch_dx /
     _launch_block_dx, which NewtonAssembler issues too.  Parts of rank 1 and 2
-    over ds
-    (Neumann, Robin, Nitsche terms: forms.facet_arguments(True) allows them)
-    go through flow_form_facet_vector / flow_form_facet_matrix and the facet contribution map (facet_map); an
-    empty selection, ds(99), contributes zero.  The parts of a sum
-    are assembled one by one, each at its own degree, and added in the order
-    written; fixed-order reductions and gathers on the device: the same bits
-    on every call.  form_compiler_parameters: 'quadrature_degree' replaces
-    the estimate (a measure's own metadata comes first), 'quadrature_rule':
-    'vertex' selects the vertex rule for ranks 1 and 2 (functionals do not
-    read that key).'''
+    over ds (Neumann, Robin, Nitsche terms: forms.facet_arguments(True)
+    allows them) go through flow_form_facet_vector / flow_form_facet_matrix
+    and the facet contribution map (facet_map); an empty selection, ds(99),
+    contributes zero.  The parts of a sum are assembled one by one, each at
+    its own degree, and added in the order written; fixed-order reductions
+    and gathers on the device: the same bits on every call.
+    form_compiler_parameters: 'quadrature_degree' replaces the estimate (a
+    measure's own metadata comes first), 'quadrature_rule': 'vertex' selects
+    the vertex rule for ranks 1 and 2 (functionals do not read that key).'''
     from . import forms
     if not isinstance(form, forms.Form):
         raise TypeError('assemble takes a form, f*dx or f*ds (got %r)'
@@ -1013,10 +1017,7 @@ def assemble(form, form_compiler_parameters=None):
         for sign, part in form.terms():
             total += sign * assemble(part, form_compiler_parameters)
         return total
-    q = forms._quadrature_degree(form.metadata)
-    if q is None:
-        q = forms._quadrature_degree(form_compiler_parameters)
-    q = forms.check_degree(form.degree() if q is None else q)
+    q = _form_degree(form, form_compiler_parameters)
     lib = _hip.lib()
     mesh = forms.form_mesh(form.integrand, form.mesh)
     if form.integral_type == 'interior_facet':
@@ -1072,10 +1073,9 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
     '''assemble() of a form, or of a signed sum of forms, of rank 1 (a
     Vector) or 2 (a Matrix; on a vector space a vector of 2N, a Matrix of
     kind 2), part by part: the programs of a part are compiled while the
-    kernels of the part before run.  Scalar space: one launch per program
-    (_launch_dx; a ds or dx(k) part: _facet_arguments / _cell_arguments into
-    a zeroed buffer), each result added at once; vector space:
-    _block_part.  The first result of sign +1 IS the total, ds included.'''
+    kernels of the part before run.  Scalar space: _scalar_part; vector
+    space: _block_part.  The first result of sign +1 IS the total, ds
+    included.'''
     from . import forms
     from .function import Vector
     V = form.arguments()[0]
@@ -1088,34 +1088,43 @@ def _assemble_arguments(form, rank, form_compiler_parameters=None):
     total = _Sum()
     for sign, part in form.terms():
         _check_part_mesh(part, mesh)
-        facet = part.integral_type == 'exterior_facet'
         _, table = part.argument_table()
         q, scheme = _part_rule(part, form_compiler_parameters)
         if V.dim == 2:
             total.add(sign, _block_part(part, table, rank, q, scheme, lay,
                                         mesh), True)
-            continue
-        # (one program, or several whose results add up where the table
-        # exceeds the limits of flow_form: forms.argument_programs)
-        for prog in forms.argument_programs(table, rank, facet):
-            fs, keep = _form_struct(prog, mesh, q, facet, scheme)
-            if facet or is_cell_subdomain(part):
-                # (the gather writes its targets only: the rest stays zero)
-                out = value_plane(lay) if rank == 2 else device.zeros(lay.N)
-                _selection_arguments(mesh, lay, rank, fs, part, out)
-            elif rank == 2:
-                out = value_plane(lay)
-                _launch_dx(mesh, lay, 'matrix', fs, out, None)
-            else:
-                out = device.empty(lay.N)
-                _launch_dx(mesh, lay, 'vector', fs, None, out)
-            del keep
-            total.add(sign, out, True)
+        else:
+            _scalar_part(part, table, rank, q, scheme, lay, mesh, total, sign)
     if total.total is None:
         raise ValueError('an empty sum of forms has no rank')
     if rank == 2:
         return Matrix(lay, 2 if V.dim == 2 else 0, total.total)
     return Vector(total.total)
+
+
+def _scalar_part(part, table, rank, q, scheme, lay, mesh, total, sign):
+    '''One part of a form of arguments on a scalar space (a scalar form's, or
+    the pressure corner of a mixed form's: mixed.assemble_form) into the sum
+    `total`: one launch per program -- one program, or several whose results
+    add up where the table exceeds the limits of flow_form
+    (forms.argument_programs) --, each result added at once.  dx: _launch_dx;
+    a ds or dx(k) part: _selection_arguments into a zeroed buffer (the gather
+    writes its targets only: the rest stays zero).'''
+    from . import forms
+    facet = part.integral_type == 'exterior_facet'
+    for prog in forms.argument_programs(table, rank, facet):
+        fs, keep = _form_struct(prog, mesh, q, facet, scheme)
+        if facet or is_cell_subdomain(part):
+            out = value_plane(lay) if rank == 2 else device.zeros(lay.N)
+            _selection_arguments(mesh, lay, rank, fs, part, out)
+        elif rank == 2:
+            out = value_plane(lay)
+            _launch_dx(mesh, lay, 'matrix', fs, out, None)
+        else:
+            out = device.empty(lay.N)
+            _launch_dx(mesh, lay, 'vector', fs, None, out)
+        del keep
+        total.add(sign, out, True)
 
 
 def _block_part(part, table, rank, q, scheme, lay, mesh):
@@ -1124,9 +1133,9 @@ def _block_part(part, table, rank, q, scheme, lay, mesh):
     trial component s) or a vector of 2N.  A dx part is ONE block launch with
     the programs of all its blocks (_launch_block_dx); a ds part, and a
     dx(k) part, goes block by block, program by program, through
-    _facet_arguments / _cell_arguments with the scalar layout's facet_map /
-    cell_map into the block's plane or component (a further program
-    of a block into a zeroed buffer of its own, then added).'''
+    _selection_arguments with the scalar layout's facet_map / cell_map into
+    the block's plane or component (a further program of a block into a
+    zeroed buffer of its own, then added).'''
     from . import forms
     facet = part.integral_type == 'exterior_facet'
     stride = plane_stride(lay) if rank == 2 else lay.N
@@ -1686,8 +1695,8 @@ class _FacetTarget(object):
     '''Where a held assembler gathers a ds or a dx(k) program: a zeroed buffer
     (N | nnz doubles) the gather writes the same entries of at every call --
     its map's targets --, zeroed again where facet_map / cell_map returns
-    another tuple (the markers were changed: other targets).  `into`: where a further program of
-    a block is added afterwards, else None.'''
+    another tuple (the markers were changed: other targets).  `into`: where a
+    further program of a block is added afterwards, else None.'''
 
     def __init__(self, buf, into=None):
         self.buf = buf
@@ -2018,109 +2027,6 @@ def newton_solve(F, u, bcs=None, J=None, solver_parameters=None,
     return out
 
 
-def _facet_selection(mesh, markers, subdomain_id):
-    '''Positions in mesh.bfacets of the facets ds(subdomain_id) selects.'''
-    if subdomain_id in (None, 'everywhere'):
-        return numpy.arange(len(mesh.bfacets))
-    return numpy.nonzero(markers.array()[mesh.bfacets] == subdomain_id)[0]
-
-
-def facet_lists(mesh, markers=None, subdomain_id='everywhere'):
-    '''The exterior facets a ds integral runs over, as device int32 arrays
-    (owning cell, local facet index) and their count: every boundary facet
-    for subdomain_id 'everywhere', else those whose marker equals
-    subdomain_id, in boundary-facet order.  Cached on the mesh against the
-    markers' version: a time loop uploads nothing, re-marking re-selects.'''
-    everywhere = subdomain_id in (None, 'everywhere')
-    if markers is None and not everywhere:
-        raise ValueError('ds(%r) needs markers: Measure(\'ds\', domain=mesh, '
-                         'subdomain_data=markers)' % (subdomain_id,))
-    if markers is not None and markers.mesh is not mesh:
-        raise ValueError('the facet markers belong to another mesh')
-    cache = mesh._cache.setdefault('facet_lists', {})
-    key = (None if everywhere else id(markers),
-           None if everywhere else subdomain_id, str(device.get()))
-    version = None if everywhere else markers.version
-    held = cache.get(key)
-    if held is not None and held[0] is (None if everywhere else markers) \
-            and held[1] == version:
-        return held[2:]
-    sel = _facet_selection(mesh, markers, subdomain_id)
-    cells = mesh.bfacet_cell[sel].astype(numpy.int32)
-    local = mesh.bfacet_local[sel].astype(numpy.int32)
-    nf = len(sel)
-    if nf:
-        cells, local = device.to_device(cells), device.to_device(local)
-    else:
-        cells = local = None
-    if len(cache) >= 32:
-        cache.clear()
-    # (the markers are kept alive with the entry: their id stays unique)
-    held = (None if everywhere else markers, version, cells, local, nf)
-    cache[key] = held
-    return held[2:]
-
-
-InteriorFacetLists = collections.namedtuple(
-    'InteriorFacetLists', 'plus local other count positions cell_positions')
-
-
-def interior_facet_lists(mesh, markers=None, subdomain_id='everywhere'):
-    '''The interior facets a dS integral runs over: device int32 arrays
-    `plus`, `local` (the '+' cell -- the smaller cell index -- and the
-    facet's local index in it) and `other` ((cell- << 3) | (local- << 1) |
-    flip, as adapt.facet_table packs a neighbour), their `count`, and for the
-    cell gather `positions` (host, one entry per EDGE of the mesh: the
-    facet's place in the selection or -1) and `cell_positions` (device
-    (3*nc,): entry [i*nc + c] = positions[cell_edges[c][i]]).  Every interior
-    facet for subdomain_id 'everywhere', else those whose marker equals
-    subdomain_id, in Mesh.interior_facets order.  Cached on the mesh against
-    the markers' version like facet_lists; an empty selection holds no device
-    array.'''
-    everywhere = subdomain_id in (None, 'everywhere')
-    if markers is None and not everywhere:
-        raise ValueError('dS(%r) needs markers: Measure(\'dS\', domain=mesh, '
-                         'subdomain_data=markers)' % (subdomain_id,))
-    if markers is not None and markers.mesh is not mesh:
-        raise ValueError('the facet markers belong to another mesh')
-    cache = mesh._cache.setdefault('interior_facet_lists', {})
-    key = (None if everywhere else id(markers),
-           None if everywhere else subdomain_id, str(device.get()))
-    version = None if everywhere else markers.version
-    held = cache.get(key)
-    if held is not None and held[0] is (None if everywhere else markers) \
-            and held[1] == version:
-        return held[2]
-    lists = mesh.interior_facet_lists()
-    facets = lists['facets']
-    if everywhere:
-        sel = numpy.arange(len(facets))
-    else:
-        sel = numpy.nonzero(markers.array()[facets] == subdomain_id)[0]
-    count = len(sel)
-    positions = numpy.full(mesh.num_edges(), -1, dtype=numpy.int32)
-    positions[facets[sel]] = numpy.arange(count, dtype=numpy.int32)
-    plus = local = other = cellpos = None
-    if count:
-        nc = mesh.num_cells()
-        if nc >= 1 << 28:
-            raise ValueError('the interior facet list packs cell indices '
-                             'below 2**28; the mesh has %d cells' % nc)
-        packed = (lists['cell_minus'][sel].astype(numpy.int64) << 3) \
-            | (lists['local_minus'][sel].astype(numpy.int64) << 1) \
-            | lists['flip'][sel]
-        plus = device.to_device(lists['cell_plus'][sel].astype(numpy.int32))
-        local = device.to_device(lists['local_plus'][sel].astype(numpy.int32))
-        other = device.to_device(packed.astype(numpy.int32))
-        cellpos = device.to_device(numpy.ascontiguousarray(
-            positions[mesh.cell_edges].T.reshape(-1)))
-    if len(cache) >= 32:
-        cache.clear()
-    out = InteriorFacetLists(plus, local, other, count, positions, cellpos)
-    cache[key] = (None if everywhere else markers, version, out)
-    return out
-
-
 def _form_degree(form, form_compiler_parameters=None):
     from . import forms
     q = forms._quadrature_degree(form.metadata)
@@ -2256,236 +2162,36 @@ def cell_indicator(form, share=0.5, out=None, form_compiler_parameters=None):
     return out
 
 
-def facet_map_host(mesh, layout, rank, markers=None,
-                   subdomain_id='everywhere'):
-    '''The facet contribution map of one (facet selection, space layout) pair
-    as numpy int32 arrays (targets, ptr, src).  The lanes of
-    flow_form_facet_matrix / flow_form_facet_vector write the element entries
-    of facet k of the selection (facet_lists' order) to scratch[(i*NL + j)*nf
-    + k] (rank 2) or scratch[i*nf + k] (rank 1), NL = layout.nloc -- ALL the
-    dofs of the owning cell, not only those on the edge.  targets: the sorted
-    unique indices of the nonzeros of the layout's CSR pattern (rank 2) or of
-    the dofs (rank 1) that any listed facet's cell touches; target t sums
-    scratch[src[e]], e in [ptr[t], ptr[t+1]), ascending by facet position,
-    then by ij (i).  Every scratch entry appears exactly once.'''
-    sel = _facet_selection(mesh, markers, subdomain_id)
-    nf, nl = len(sel), layout.nloc
-    if nf == 0:
-        return (numpy.zeros(0, numpy.int32), numpy.zeros(1, numpy.int32),
-                numpy.zeros(0, numpy.int32))
-    cd = layout.cell_dofs[mesh.bfacet_cell[sel]].astype(numpy.int64)  # (nf, nl)
-    if rank == 1:
-        tgt = cd.T.reshape(-1)                          # [i][k]
-    else:
-        N = layout.N
-        key = (cd[:, :, None] * N + cd[:, None, :]).transpose(1, 2, 0)
-        key = key.reshape(-1)                           # [i*nl + j][k]
-        rowptr = layout.pattern('rowptr').astype(numpy.int64)
-        ukey = numpy.repeat(numpy.arange(N, dtype=numpy.int64),
-                            numpy.diff(rowptr)) * N + layout.pattern('cols')
-        tgt = numpy.searchsorted(ukey, key)
-        assert (ukey[tgt] == key).all()
-    assert len(tgt) < 2**31
-    scr = numpy.arange(len(tgt), dtype=numpy.int64)
-    order = numpy.lexsort((scr // nf, scr % nf, tgt))   # (target, k, ij)
-    st = tgt[order]
-    first = numpy.nonzero(numpy.concatenate([[True], st[1:] != st[:-1]]))[0]
-    return (st[first].astype(numpy.int32),
-            numpy.concatenate([first, [len(st)]]).astype(numpy.int32),
-            order.astype(numpy.int32))
-
-
-def facet_map(mesh, layout, rank, markers=None, subdomain_id='everywhere'):
-    '''facet_map_host on the device: (targets, ptr, src, number of targets),
-    None arrays for an empty selection.  Cached on the mesh next to the
-    facet_lists entry and against the markers' version in the same way: a time
-    loop uploads nothing, re-marking rebuilds.  The SAME tuple is returned
-    while the entry holds.'''
-    everywhere = subdomain_id in (None, 'everywhere')
-    if markers is None and not everywhere:
-        raise ValueError('ds(%r) needs markers: Measure(\'ds\', domain=mesh, '
-                         'subdomain_data=markers)' % (subdomain_id,))
-    if markers is not None and markers.mesh is not mesh:
-        raise ValueError('the facet markers belong to another mesh')
-    cache = mesh._cache.setdefault('facet_maps', {})
-    key = (None if everywhere else id(markers),
-           None if everywhere else subdomain_id, id(layout), rank,
-           str(device.get()))
-    version = None if everywhere else markers.version
-    held = cache.get(key)
-    if held is not None and held[0] is (None if everywhere else markers) \
-            and held[1] == version and held[2] is layout:
-        return held[3]
-    targets, ptr, src = facet_map_host(mesh, layout, rank, markers,
-                                       subdomain_id)
-    nt = len(targets)
-    if nt:
-        fmap = (device.to_device(targets), device.to_device(ptr),
-                device.to_device(src), nt)
-    else:
-        fmap = (None, None, None, 0)
-    if len(cache) >= 32:
-        cache.clear()
-    # (markers and layout are kept alive with the entry: their ids stay unique)
-    cache[key] = (None if everywhere else markers, version, layout, fmap)
-    return fmap
-
-
-def _facet_arguments(mesh, lay, rank, fs, markers, subdomain_id, out):
-    '''One ds part of rank 1 | 2 into `out` (N | nnz doubles, zero outside
-    the map's targets): the element launch and the gather launch.'''
-    cells, local, nf = facet_lists(mesh, markers, subdomain_id)
-    if nf == 0:
+def _list_launch(fn, head, mesh, lists, count, lmap, per_item, out, tail=()):
+    '''The element launch over a list and the gather launch, one C call `fn`
+    of the shape (*head, count, *lists, nt, targets, ptr, src, scratch, out,
+    *tail, stream).  head: the mesh, space and form structs by reference;
+    lists: [(device int32 array of `count` entries, its label)] -- the cells,
+    or the cells and the local facet indices; lmap: the contribution map
+    (targets, ptr, src, nt) of the list; per_item: element entries per item
+    of the list; out: (buffer, its length, its label), written at the map's
+    targets only.  An empty list launches nothing.'''
+    if count == 0:
         return
-    targets, ptr, src, nt = facet_map(mesh, lay, rank, markers, subdomain_id)
-    n = lay.nloc**rank * nf
-    lib = _hip.lib()
-    fn = lib.flow_form_facet_matrix if rank == 2 else lib.flow_form_facet_vector
+    targets, ptr, src, nt = lmap
+    n = per_item * count
+    buf, length, label = out
     _hip.check(fn(
-        ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay)),
-        ctypes.byref(fs), nf, _hip.i32(cells, nf, 'facet cells'),
-        _hip.i32(local, nf, 'facet local indices'), nt,
+        *head, count, *[_hip.i32(a, count, what) for a, what in lists], nt,
         _hip.i32(targets, nt, 'map targets'), _hip.i32(ptr, nt + 1, 'map ptr'),
         _hip.i32(src, n, 'map src'), _hip.f64(scratch(mesh, n), n, 'scratch'),
-        _hip.f64(out, lay.nnz if rank == 2 else lay.N, 'out'), _hip.stream()))
+        _hip.f64(buf, length, label), *tail, _hip.stream()))
 
 
-# -- cell subdomains: dx(k) (forms.cell_subdomains) ----------------------------
-def is_cell_subdomain(part):
-    '''Whether a part is a dx(k) part: cells, and a subdomain id.'''
-    return part.integral_type == 'cell' \
-        and part.subdomain_id not in (None, 'everywhere')
-
-
-def _check_cell_markers(mesh, markers, subdomain_id):
-    if markers is None:
-        raise ValueError('dx(%r) needs markers: Measure(\'dx\', domain=mesh, '
-                         'subdomain_data=markers)' % (subdomain_id,))
-    if markers.mesh is not mesh:
-        raise ValueError('the cell markers belong to another mesh')
-    if getattr(markers, 'dim', None) != 2:
-        raise ValueError('dx(%r) takes a cell MeshFunction (dim 2) as '
-                         'subdomain_data' % (subdomain_id,))
-
-
-def _cell_selection(mesh, markers, subdomain_id):
-    '''The cells dx(subdomain_id) selects, ascending.'''
-    if subdomain_id in (None, 'everywhere'):
-        return numpy.arange(mesh.num_cells())
-    return numpy.nonzero(markers.array() == subdomain_id)[0]
-
-
-def cell_lists(mesh, markers=None, subdomain_id='everywhere'):
-    '''The cells a dx(k) integral runs over: a device int32 array of the
-    cells whose marker equals subdomain_id, ascending, and their count.
-    Cached on the mesh against the markers' version like facet_lists: a time
-    loop uploads nothing, re-marking re-selects.  An empty selection holds no
-    device array; for 'everywhere' nothing is built, (None, number of cells)
-    -- the whole-mesh entry points take no list.'''
-    if subdomain_id in (None, 'everywhere'):
-        return None, mesh.num_cells()
-    _check_cell_markers(mesh, markers, subdomain_id)
-    cache = mesh._cache.setdefault('cell_lists', {})
-    key = (id(markers), subdomain_id, str(device.get()))
-    held = cache.get(key)
-    if held is not None and held[0] is markers and held[1] == markers.version:
-        return held[2:]
-    sel = _cell_selection(mesh, markers, subdomain_id)
-    cells = device.to_device(sel.astype(numpy.int32)) if len(sel) else None
-    if len(cache) >= 32:
-        cache.clear()
-    # (the markers are kept alive with the entry: their id stays unique)
-    held = (markers, markers.version, cells, len(sel))
-    cache[key] = held
-    return held[2:]
-
-
-def cell_map_host(mesh, layout, rank, markers=None, subdomain_id='everywhere'):
-    '''The cell contribution map of one (cell selection, space layout, rank)
-    as numpy int32 arrays (targets, ptr, src), of the shape of facet_map_host.
-    The lanes of flow_form_cells_matrix / flow_form_cells_vector write the
-    element entries of cell k of the selection (cell_lists' order) to
-    scratch[(i*NL + j)*nsel + k] (rank 2) or scratch[i*nsel + k] (rank 1), NL
-    = layout.nloc.  targets: the sorted unique indices of the nonzeros of the
-    layout's CSR pattern (rank 2) or of the dofs (rank 1) that a selected
-    cell touches; target t sums scratch[src[e]], e in [ptr[t], ptr[t+1]).
-    ORDER: the sources of a target stand in the order in which the space's
-    own map lists them (cptr / csrc, rank 2; vptr / vsrc, rank 1), restricted
-    to the selected cells -- the space's map is filtered: the cell of each
-    source is decoded, unselected cells are dropped, the rest re-encoded with
-    the cell's position in the list.  A selection that holds every cell
-    therefore gives the bits of plain dx.  Every scratch entry appears exactly
-    once.'''
-    sel = _cell_selection(mesh, markers, subdomain_id)
-    nsel, nc = len(sel), mesh.num_cells()
-    if nsel == 0:
-        return (numpy.zeros(0, numpy.int32), numpy.zeros(1, numpy.int32),
-                numpy.zeros(0, numpy.int32))
-    if rank == 2:
-        ptr, src = layout.pattern('cptr'), layout.pattern('csrc')
-    else:
-        ptr, src = layout.vmap('vptr'), layout.vmap('vsrc')
-    src = src.astype(numpy.int64)
-    position = numpy.full(nc, -1, dtype=numpy.int64)
-    position[sel] = numpy.arange(nsel)
-    pos = position[src % nc]
-    keep = pos >= 0
-    # (kept sources before each row of the space's map: the new row pointers)
-    before = numpy.concatenate([[0], numpy.cumsum(keep)])[ptr]
-    count = numpy.diff(before)
-    targets = numpy.nonzero(count)[0]
-    new_src = (src[keep] // nc) * nsel + pos[keep]
-    assert len(new_src) == layout.nloc**rank * nsel < 2**31
-    return (targets.astype(numpy.int32),
-            numpy.concatenate([before[targets], [len(new_src)]]).astype(
-                numpy.int32),
-            new_src.astype(numpy.int32))
-
-
-def cell_map(mesh, layout, rank, markers=None, subdomain_id='everywhere'):
-    '''cell_map_host on the device: (targets, ptr, src, number of targets),
-    None arrays for an empty selection.  Cached on the mesh against the
-    markers' version like facet_map; the SAME tuple is returned while the
-    entry holds.'''
-    _check_cell_markers(mesh, markers, subdomain_id)
-    cache = mesh._cache.setdefault('cell_maps', {})
-    key = (id(markers), subdomain_id, id(layout), rank, str(device.get()))
-    held = cache.get(key)
-    if held is not None and held[0] is markers \
-            and held[1] == markers.version and held[2] is layout:
-        return held[3]
-    targets, ptr, src = cell_map_host(mesh, layout, rank, markers,
-                                      subdomain_id)
-    nt = len(targets)
-    if nt:
-        cmap = (device.to_device(targets), device.to_device(ptr),
-                device.to_device(src), nt)
-    else:
-        cmap = (None, None, None, 0)
-    if len(cache) >= 32:
-        cache.clear()
-    # (markers and layout are kept alive with the entry: their ids stay unique)
-    cache[key] = (markers, markers.version, layout, cmap)
-    return cmap
-
-
-def _cell_arguments(mesh, lay, rank, fs, markers, subdomain_id, out):
-    '''One dx(k) part of rank 1 | 2 into `out` (N | nnz doubles, zero outside
-    the map's targets): the element launch over the cell list and the gather
-    launch.'''
-    cells, nsel = cell_lists(mesh, markers, subdomain_id)
-    if nsel == 0:
-        return
-    targets, ptr, src, nt = cell_map(mesh, lay, rank, markers, subdomain_id)
-    n = lay.nloc**rank * nsel
-    lib = _hip.lib()
-    fn = lib.flow_form_cells_matrix if rank == 2 else lib.flow_form_cells_vector
-    _hip.check(fn(
-        ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay)),
-        ctypes.byref(fs), nsel, _hip.i32(cells, nsel, 'cell list'), nt,
-        _hip.i32(targets, nt, 'map targets'), _hip.i32(ptr, nt + 1, 'map ptr'),
-        _hip.i32(src, n, 'map src'), _hip.f64(scratch(mesh, n), n, 'scratch'),
-        _hip.f64(out, lay.nnz if rank == 2 else lay.N, 'out'), _hip.stream()))
+def _selection_lists(mesh, part):
+    '''(lists, count) of a ds or dx(k) part as _list_launch takes them:
+    facet_lists | cell_lists with the labels of their arrays.'''
+    if part.integral_type == 'cell':
+        cells, nsel = cell_lists(mesh, part.subdomain_data, part.subdomain_id)
+        return [(cells, 'cell list')], nsel
+    cells, local, nf = facet_lists(mesh, part.subdomain_data,
+                                   part.subdomain_id)
+    return [(cells, 'facet cells'), (local, 'facet local indices')], nf
 
 
 def _selection_map(mesh, lay, rank, part):
@@ -2495,9 +2201,21 @@ def _selection_map(mesh, lay, rank, part):
 
 
 def _selection_arguments(mesh, lay, rank, fs, part, out):
-    '''One ds or dx(k) part of rank 1 | 2 into `out`.'''
-    fn = _cell_arguments if part.integral_type == 'cell' else _facet_arguments
-    fn(mesh, lay, rank, fs, part.subdomain_data, part.subdomain_id, out)
+    '''One ds or dx(k) part of rank 1 | 2 into `out` (N | nnz doubles, zero
+    outside the map's targets): flow_form_facet_matrix / _vector over the
+    facet lists, flow_form_cells_matrix / _vector over the cell list.'''
+    lib = _hip.lib()
+    if part.integral_type == 'cell':
+        fn = lib.flow_form_cells_matrix if rank == 2 \
+            else lib.flow_form_cells_vector
+    else:
+        fn = lib.flow_form_facet_matrix if rank == 2 \
+            else lib.flow_form_facet_vector
+    _list_launch(
+        fn, (ctypes.byref(mesh_struct(mesh)), ctypes.byref(space_struct(lay)),
+             ctypes.byref(fs)), mesh, *_selection_lists(mesh, part),
+        _selection_map(mesh, lay, rank, part), lay.nloc**rank,
+        (out, lay.nnz if rank == 2 else lay.N, 'out'))
 
 
 def form_load_vector(expr, V, form_compiler_parameters=None):

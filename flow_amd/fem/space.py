@@ -21,6 +21,7 @@ Layout decisions:
 import numpy
 
 from . import reference
+from . import selection
 
 # CSR-stream tiling (must match flow_amd/csrc/csr_stream.h)
 SPMV_ROWS_PER_BLOCK = 256
@@ -441,33 +442,19 @@ class RectLayout(object):
         '''ops.facet_map_host for this pattern: (targets, ptr, src) of the
         facets of the selection, whose lanes write scratch[(i*nloc_cols +
         j)*nf + k]; sources ascend by facet position, then by ij.'''
-        from . import ops
-        sel = ops._facet_selection(self.mesh, markers, subdomain_id)
+        sel = selection._facet_selection(self.mesh, markers, subdomain_id)
         return self._list_map(self.mesh.bfacet_cell[sel])
 
     def cell_map_host(self, markers=None, subdomain_id='everywhere'):
         '''ops.cell_map_host for this pattern: (targets, ptr, src) of the
         selected cells (ascending), whose lanes write scratch[(i*nloc_cols +
         j)*nsel + k]; sources ascend by cell, as cptr / csrc list them.'''
-        from . import ops
-        sel = ops._cell_selection(self.mesh, markers, subdomain_id)
+        sel = selection._cell_selection(self.mesh, markers, subdomain_id)
         return self._list_map(sel)
 
     def _list_map(self, cells):
-        n = len(cells)
-        if n == 0:
-            return (numpy.zeros(0, numpy.int32), numpy.zeros(1, numpy.int32),
-                    numpy.zeros(0, numpy.int32))
         tgt = self._targets(cells).transpose(1, 2, 0).reshape(-1)  # [ij][k]
-        assert len(tgt) < 2**31
-        scr = numpy.arange(len(tgt), dtype=numpy.int64)
-        order = numpy.lexsort((scr // n, scr % n, tgt))     # (target, k, ij)
-        st = tgt[order]
-        first = numpy.nonzero(
-            numpy.concatenate([[True], st[1:] != st[:-1]]))[0]
-        return (st[first].astype(numpy.int32),
-                numpy.concatenate([first, [len(st)]]).astype(numpy.int32),
-                order.astype(numpy.int32))
+        return selection.by_target(tgt, len(cells))
 
 
 def transpose_permutation(rowptr, cols, other_rowptr, other_cols):
