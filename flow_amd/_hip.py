@@ -45,6 +45,30 @@ class Operator(ctypes.Structure):
         ]
 
 
+class MixedS(ctypes.Structure):
+    '''flow_mixed: the blocks of a Taylor-Hood matrix for flow_mixed_apply.'''
+    _fields_ = [
+        ('nv', ctypes.c_int),
+        ('np', ctypes.c_int),
+        ('nvtiles', ctypes.c_int),
+        ('nptiles', ctypes.c_int),
+        ('vrowptr', ctypes.c_void_p),
+        ('vcols', ctypes.c_void_p),
+        ('uu', ctypes.c_void_p * 4),
+        ('uprowptr', ctypes.c_void_p),
+        ('upcols', ctypes.c_void_p),
+        ('up', ctypes.c_void_p * 2),
+        ('prowptr', ctypes.c_void_p),
+        ('pcols', ctypes.c_void_p),
+        ('pp', ctypes.c_void_p),
+        ('purowptr', ctypes.c_void_p),
+        ('pucols', ctypes.c_void_p),
+        ('pu', ctypes.c_void_p * 2),
+        ('vtiles', ctypes.c_void_p),
+        ('ptiles', ctypes.c_void_p),
+        ]
+
+
 class CoarseS(ctypes.Structure):
     _fields_ = [
         ('n', ctypes.c_int),
@@ -544,6 +568,7 @@ SYMBOLS = {
                                         _VP, ctypes.c_size_t, _I, _VP],
     'flow_block_gram': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, ctypes.c_size_t,
                         _VP, _VP, _VP],
+    'flow_mixed_apply': [_P(MixedS), _VP, _VP, _VP],
     'flow_stats_update': [_I, _I, _I, _P(StatsFreq), _D, _D, _D, _VP, _VP,
                           ctypes.c_size_t, _VP],
     'flow_stats_merge': [_I, _I, _I, _I, _D, _D, _VP, _VP, ctypes.c_size_t,

@@ -129,6 +129,39 @@ struct StreamTile {
   }
 };
 
+// The same tile with a SECOND value plane over the same pattern (the two planes
+// of a coupling pair of a mixed operator, mixed_kernels.hip): load() fetches
+// the column pairs once and the value pairs of both planes; gather() is the
+// tile's own, and plane(p) is the StreamTile of plane p -- its park() and sum()
+// are StreamTile's, so each plane has the bits of a product on its own.
+struct StreamTilePlanes : StreamTile {
+  double2 w[kPairs];   // the second plane's value pairs
+
+  __device__ __forceinline__ void load(int r0, int r1, const int* __restrict__ rowptr,
+                                       const int* __restrict__ cols,
+                                       const double* __restrict__ vals0,
+                                       const double* __restrict__ vals1) {
+    StreamTile::load(r0, r1, rowptr, cols, vals0);
+    // (the pairs of StreamTile::load: base aligned down, trailing odd element)
+    const double2* __restrict__ w2p = reinterpret_cast<const double2*>(vals1 + ka);
+    const int npair = (k1 - ka + 1) >> 1;
+#pragma unroll
+    for (int j = 0; j < kPairs; ++j) {
+      const int p = threadIdx.x + j * kBlock;
+      w[j] = p < npair ? w2p[p] : make_double2(0.0, 0.0);
+    }
+  }
+
+  __device__ __forceinline__ StreamTile plane(int p) const {
+    StreamTile t = *this;
+    if (p) {
+#pragma unroll
+      for (int j = 0; j < kPairs; ++j) t.v[j] = w[j];
+    }
+    return t;
+  }
+};
+
 // The products of the rows [r0, r1) with x go through LDS (prod, kTile doubles),
 // then lane i sums row r0 + i.  Returns that row's sum (0 for a lane without a
 // row).
@@ -241,10 +274,15 @@ struct StreamTile2 {
         const double2 axx = vxx[j], axy = vxy[j], ayx = vyx[j], ayy = vyy[j];
         const double u0 = g.u0[j], u1 = g.u1[j];
         const double w0 = g.w0[j], w1 = g.w1[j];
-        prod0[2 * p] = axx.x * u0 + axy.x * u1;
-        prod1[2 * p] = ayx.x * u0 + ayy.x * u1;
-        prod0[2 * p + 1] = axx.y * w0 + axy.y * w1;
-        prod1[2 * p + 1] = ayx.y * w0 + ayy.y * w1;
+        // a x u + b x v as spmv_stream_block2_kernel is compiled: the second
+        // product rounded, the first fused into the sum.  Written out, because
+        // the compiler's own contraction of a * u + b * v picks either product
+        // depending on the kernel around it (it fused the other one in
+        // mixed_kernels.hip), and the bits must not.
+        prod0[2 * p] = fma(axx.x, u0, axy.x * u1);
+        prod1[2 * p] = fma(ayx.x, u0, ayy.x * u1);
+        prod0[2 * p + 1] = fma(axx.y, w0, axy.y * w1);
+        prod1[2 * p + 1] = fma(ayx.y, w0, ayy.y * w1);
       }
     }
   }

@@ -30,7 +30,7 @@ from .forms import (                                            # noqa: F401
     cell_subdomains,
     vector_arguments, vector_derivatives, sym, tr, transpose, Identity, outer,
     interior_facets, jump, avg, FacetArea,
-    mixed_arguments, TestFunctions, TrialFunctions, split,
+    mixed_arguments, TestFunctions, TrialFunctions, split, mixed_gmres,
     )
 from .space import RectLayout, rect_layout                      # noqa: F401
 from .mixed import MixedMatrix                                  # noqa: F401

@@ -1143,6 +1143,19 @@ class mixed_arguments(_Switch):
     enabled = False
 
 
+class mixed_gmres(_Switch):
+    '''The switch of solve(a == L, w, bcs) for NON-symmetric forms on a
+    Taylor-Hood space (Oseen, Picard steps of Navier-Stokes, a Stokes form
+    written with +q*div(u)): flexible GMRES with a block-triangular
+    preconditioner over the one-launch block product (fem/mixed.py: fgmres,
+    BlockTriangularPreconditioner, MixedMatrix.apply_fused).  Off by default:
+    such a solve stays the NotImplementedError it was.  `mixed_gmres(True)`
+    switches it on at once, for the process; `.previous` is the setting it
+    replaced, and as a context manager it restores that on exit.  It implies
+    no other switch.'''
+    enabled = False
+
+
 _MIXED_MISMATCH = (
     'an argument of a mixed space together with an argument of another space '
     'in one form: the test and the trial function of a mixed form both come '

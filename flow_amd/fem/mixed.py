@@ -25,10 +25,15 @@ of space.RectLayout.  Everything numerical is a call into libflow_hip.so.
 Unknowns are numbered velocity x, velocity y, pressure: 2 Nv + Np.
 
 solve(a == L, w, bcs) runs preconditioned MINRES (the loop of stokes._minres
-over an abstract operator and preconditioner) and therefore takes SYMMETRIC
-forms only; a non-symmetric mixed form is a NotImplementedError there -- there
-is no flexible Krylov loop here that takes a block preconditioner yet --
-while assemble_system and MixedMatrix.to_scipy() work for it.
+over an abstract operator and preconditioner) for SYMMETRIC forms.  A
+non-symmetric mixed form (Oseen, a Picard step of Navier-Stokes, +q*div(u))
+is a NotImplementedError unless forms.mixed_gmres(True) is on: then it runs
+right-preconditioned flexible GMRES (fgmres) with a block-triangular
+preconditioner (BlockTriangularPreconditioner: ILU(0) or Jacobi on uu, a
+signed approximate Schur diagonal on the pressure) over the product of all
+blocks in one launch (MixedMatrix.apply_fused: flow_mixed_apply, csrc/
+mixed_kernels.hip).  assemble_system and MixedMatrix.to_scipy() work for such
+a form either way.
 '''
 import ctypes
 
@@ -38,7 +43,7 @@ import torch
 from . import ops
 from . import selection
 from .function import Function, Vector
-from .space import rect_layout
+from .space import rect_layout, csr_stream_rowblocks
 from .. import _hip
 from .. import device
 
@@ -111,6 +116,7 @@ class MixedMatrix(object):
         self.up = list(up) if up is not None else [None, None]
         self.pu = list(pu) if pu is not None else [None, None]
         self._tmp = None
+        self._fused = None
 
     @property
     def size(self):
@@ -162,6 +168,54 @@ class MixedMatrix(object):
             _hip.fill(yp, 0.0)
         return y
 
+    def fused(self):
+        '''The flow_mixed struct of the present blocks (include/flow_hip.h)
+        with the velocity and pressure tiles of fused_tiles; cached.'''
+        if self._fused is None:
+            mesh = self.space.mesh()
+            layv, layp = self.W.layout, self.P.layout
+            Rup = rect_layout(mesh, self.W.degree, self.P.degree)
+            Rpu = rect_layout(mesh, self.P.degree, self.W.degree)
+            vt, pt = fused_tiles(Rup, True), fused_tiles(Rpu, True)
+            s = _hip.MixedS()
+            s.nv, s.np = layv.N, layp.N
+            s.nvtiles, s.nptiles = vt.numel() - 1, pt.numel() - 1
+            s.vtiles = _hip.i32(vt, None, 'vtiles')
+            s.ptiles = _hip.i32(pt, None, 'ptiles')
+            s.vrowptr = _hip.i32(layv.dev('rowptr'), layv.N + 1, 'rowptr')
+            s.vcols = _hip.i32(layv.dev('cols'), layv.nnz, 'cols')
+            s.prowptr = _hip.i32(layp.dev('rowptr'), layp.N + 1, 'rowptr')
+            s.pcols = _hip.i32(layp.dev('cols'), layp.nnz, 'cols')
+            s.uprowptr = _hip.i32(Rup.dev('rowptr'), layv.N + 1, 'rowptr')
+            s.upcols = _hip.i32(Rup.dev('cols'), Rup.nnz, 'cols')
+            s.purowptr = _hip.i32(Rpu.dev('rowptr'), layp.N + 1, 'rowptr')
+            s.pucols = _hip.i32(Rpu.dev('cols'), Rpu.nnz, 'cols')
+            if self.uu is not None:
+                assert self.uu.kind == 2 and self.uu.layout is layv
+                for p in range(4):
+                    s.uu[p] = self.uu.operator().vals[p]
+            if self.pp is not None:
+                assert self.pp.kind == 0 and self.pp.layout is layp
+                s.pp = self.pp.operator().vals[0]
+            for c in range(2):
+                if self.up[c] is not None:
+                    assert self.up[c].layout is Rup
+                    s.up[c] = self.up[c].operator().vals[0]
+                if self.pu[c] is not None:
+                    assert self.pu[c].layout is Rpu
+                    s.pu[c] = self.pu[c].operator().vals[0]
+            self._fused = s
+        return self._fused
+
+    def apply_fused(self, x, y):
+        '''y = A x in one launch (flow_mixed_apply): every entry has the bits
+        apply() leaves there.  y overlapping x is a ValueError.'''
+        assert x.numel() == self.size and y.numel() == self.size
+        _hip.check(_hip.lib().flow_mixed_apply(
+            ctypes.byref(self.fused()), _hip.f64(x, self.size, 'x'),
+            _hip.f64(y, self.size, 'y'), _hip.stream()))
+        return y
+
     def __mul__(self, x):
         '''A * w for a Vector or a Function of WP: a new Vector.'''
         ops._no_strips('MixedMatrix * vector')
@@ -192,6 +246,32 @@ class MixedMatrix(object):
         A.eliminate_zeros()
         A.sort_indices()
         return A
+
+
+def _tile_cap():
+    '''Nonzeros a tile of flow_mixed_apply may hold in each of its patterns:
+    the caps of the CSR-stream kernels of kind 0 and kind 2 (the header's
+    constant without a built library).'''
+    try:
+        return min(_hip.spmv_tile_nnz(0), _hip.spmv_tile_nnz(2))
+    except (OSError, _hip.HipError):
+        return _hip.SPMV_NNZ_PER_BLOCK
+
+
+def fused_tiles(R, dev=False):
+    '''Row tiles of flow_mixed_apply over the rows of the RectLayout R: at
+    most 256 consecutive rows that stay within the tile cap both in the
+    square pattern of R's row layout and in R's own -- the velocity tiles for
+    R = RectLayout(kv, kp), the pressure tiles for RectLayout(kp, kv).  Held
+    on R (dev: the device copy).'''
+    if 'mixed_tiles_host' not in R._dev:
+        R._dev['mixed_tiles_host'] = csr_stream_rowblocks(
+            [R.rows.pattern('rowptr'), R.rowptr], nnz_per_block=_tile_cap())
+    if not dev:
+        return R._dev['mixed_tiles_host']
+    if 'mixed_tiles' not in R._dev:
+        R._dev['mixed_tiles'] = device.to_device(R._dev['mixed_tiles_host'])
+    return R._dev['mixed_tiles']
 
 
 # -- assembly ---------------------------------------------------------------------
@@ -626,30 +706,274 @@ def _schur_diagonal(A, pmask):
     return d
 
 
-def _form_diagonal(prec_form, bcs, form_compiler_parameters):
+def _form_diagonal(prec_form, bcs, form_compiler_parameters, signed=False):
     '''The absolute lumped rows of the pp block of a rank-2 mixed form (the
     reference's mu*inner(grad(u), grad(v))*dx - p*q*dx idiom; its sign is
-    ignored), eliminated with the same conditions: Dirichlet rows 1.'''
+    ignored), eliminated with the same conditions: Dirichlet rows 1.
+    signed (the GMRES path): the lumped rows as written, with their sign.'''
     M, _ = assemble_system(prec_form, None, bcs, form_compiler_parameters)
     if M.pp is None:
         raise ValueError("'preconditioner_form' has no pressure-pressure "
                          'term (p*q*dx) to precondition the pressure with')
     npr = M.P.N
-    d = torch.abs(M.pp.apply(device.zeros(npr) + 1.0, device.empty(npr)))
-    if not bool((d > 0.0).all()):
+    d = M.pp.apply(device.zeros(npr) + 1.0, device.empty(npr))
+    if not bool((torch.abs(d) > 0.0).all()):
         raise ValueError("'preconditioner_form': a lumped pressure row is "
                          'zero')
+    return d if signed else torch.abs(d)
+
+
+# -- flexible GMRES ---------------------------------------------------------------
+def fgmres(apply_A, precondition, b, x, rtol, atol=0.0, maxit=1000,
+           restart=30):
+    '''Right-preconditioned flexible GMRES(restart) (Saad, Alg. 9.6) over
+    apply_A(x, y) and precondition(v, z) on device vectors of one length: the
+    preconditioned vectors Z_j are kept and x is updated from them, as
+    flow_gmres_solve does, so the preconditioner may change from one
+    application to the next (sweeps in reduced precision).  x holds the
+    initial guess and receives the solution.
+    Host-looped.  The basis V and Z are column-major device stores with an
+    even leading dimension (16-byte aligned columns); an Arnoldi step
+    orthogonalises by classical Gram-Schmidt with a second pass: per pass one
+    flow_multi_dot launch over the basis and one read-back, and one
+    flow_combine for the subtraction; one more dot gives the norm.  Givens
+    rotations run on the host.
+    Stopping: within a cycle the rotated residual estimate is watched; at a
+    restart and on exit the TRUE residual |b - A x|_2 is computed and tested
+    against max(rtol |b|_2, atol), flow_gmres_solve's rule for right
+    preconditioning.  Every kernel has a fixed summation order: the same call
+    gives the same bits.  Returns (iterations, true residual norm); raises
+    _hip.NotConverged.'''
+    lib = _hip.lib()
+    n = b.numel()
+    m = max(1, int(restart))
+    ld = n + (n & 1)
+    V = device.zeros((m + 1) * ld)
+    Z = device.zeros(m * ld)
+    assert V.data_ptr() % 16 == 0 and Z.data_ptr() % 16 == 0
+    col = lambda S, j: S[j * ld:j * ld + n]   # noqa: E731
+    w, w1 = device.zeros(n), device.zeros(n)
+    dwork = device.empty((m + 1) * _hip.MULTI_DOT_BLOCKS)
+    dots = device.empty(m + 1)
+
+    def project(k, y, out):
+        '''out = y - V[:, :k] (V[:, :k]^T y); returns the k coefficients.'''
+        _hip.check(lib.flow_multi_dot(
+            n, k, _hip.f64(V, (k - 1) * ld + n, 'basis'), ld,
+            _hip.f64(y, n, 'y'), _hip.f64(dwork, k * _hip.MULTI_DOT_BLOCKS),
+            _hip.f64(dots, k), _hip.stream()))
+        h = device.to_host(dots[:k]).numpy().astype(numpy.float64)
+        combine(V, k, -h, y, out)
+        return h
+
+    def combine(S, k, coef, base, out):
+        '''out = base + S[:, :k] coef (flow_combine; out overlaps nothing).'''
+        C = device.to_device(numpy.ascontiguousarray(coef, numpy.float64))
+        _hip.check(lib.flow_combine(
+            n, k, _hip.f64(S, (k - 1) * ld + n, 'columns'), ld, 1,
+            _hip.f64(C, k, 'coefficients'), _hip.f64(base, n, 'base'),
+            _hip.f64(out, n, 'out'), ld, _hip.stream()))
+
+    def residual(dst):
+        apply_A(x, w)
+        ops.copy(dst, b)
+        ops.axpby(-1.0, w, 1.0, dst)
+        return numpy.sqrt(max(ops.dot(dst, dst), 0.0))
+
+    tol = max(rtol * numpy.sqrt(max(ops.dot(b, b), 0.0)), atol)
+    its = 0
+    beta = residual(col(V, 0))
+    while beta > tol:
+        if its >= maxit:
+            raise _hip.NotConverged(
+                'FGMRES did not converge in %d iterations (|b - A x| = %.3e > '
+                '%.3e)' % (its, beta, tol))
+        ops.axpby(0.0, col(V, 0), 1.0 / beta, col(V, 0))
+        H = numpy.zeros((m + 1, m))
+        g = numpy.zeros(m + 1)
+        g[0] = beta
+        cs, sn = numpy.zeros(m), numpy.zeros(m)
+        k = 0
+        while k < m and its < maxit:
+            j = k
+            precondition(col(V, j), col(Z, j))
+            apply_A(col(Z, j), w)
+            h = project(j + 1, w, w1)
+            h = h + project(j + 1, w1, col(V, j + 1))
+            vn = col(V, j + 1)
+            hn = numpy.sqrt(max(ops.dot(vn, vn), 0.0))
+            H[:j + 1, j] = h
+            H[j + 1, j] = hn
+            for i in range(j):
+                t = cs[i] * H[i, j] + sn[i] * H[i + 1, j]
+                H[i + 1, j] = -sn[i] * H[i, j] + cs[i] * H[i + 1, j]
+                H[i, j] = t
+            d = numpy.hypot(H[j, j], H[j + 1, j])
+            if d == 0.0:
+                break    # (A Z_j lies in the span and adds nothing: singular)
+            cs[j], sn[j] = H[j, j] / d, H[j + 1, j] / d
+            H[j, j], H[j + 1, j] = d, 0.0
+            g[j + 1] = -sn[j] * g[j]
+            g[j] = cs[j] * g[j]
+            k += 1
+            its += 1
+            if hn == 0.0 or abs(g[k]) <= tol:
+                break
+            ops.axpby(0.0, vn, 1.0 / hn, vn)
+        if k == 0:
+            raise _hip.NotConverged(
+                'FGMRES broke down after %d iterations (|b - A x| = %.3e > '
+                '%.3e)' % (its, beta, tol))
+        y = numpy.zeros(k)
+        for i in range(k - 1, -1, -1):
+            y[i] = (g[i] - H[i, i + 1:k].dot(y[i + 1:])) / H[i, i]
+        combine(Z, k, y, x, w1)
+        ops.copy(x, w1)
+        beta = residual(col(V, 0))
+    return its, beta
+
+
+class BlockTriangularPreconditioner(object):
+    '''The block upper triangular preconditioner [[F~, up], [0, diag(sdiag)]]
+    of an eliminated MixedMatrix A for fgmres:
+        z_p = r_p / sdiag;  z_u = F~^-1 (r_u - up z_p).
+    velocity 'ilu0' (default): one application of Ilu0(A.uu), the ILU(0)
+    factors of the two diagonal planes of uu; 'jacobi': A.uu.diag_inv().
+    sdiag: the signed approximate Schur diagonal on the device
+    (_signed_schur_diagonal, or the lumped rows of a preconditioner form),
+    Dirichlet rows 1.  Dirichlet rows are identity rows: the eliminated uu has
+    unit rows there and the coupling planes are zero on them.'''
+
+    def __init__(self, A, velocity='ilu0', sdiag=None):
+        if velocity not in ('ilu0', 'jacobi'):
+            raise ValueError("preconditioner %r under GMRES: 'ilu0' or "
+                             "'jacobi'" % (velocity,))
+        if A.uu is None:
+            raise ValueError('the form has no velocity-velocity block: '
+                             'nothing to precondition the velocity with')
+        from .ilu import Ilu0
+        self.A = A
+        self.velocity = velocity
+        self.nv, self.n2 = A.W.N, A.W.size()
+        if sdiag is None:
+            sdiag = _signed_schur_diagonal(A, None)
+        self.sinv = torch.reciprocal(sdiag)
+        self.ru = device.empty(self.n2)
+        self.tmp = device.empty(self.nv)
+        if velocity == 'ilu0':
+            self.ilu = Ilu0(A.uu)
+            self.work = device.empty(self.n2)
+        else:
+            self.dinv = A.uu.diag_inv()
+
+    def apply(self, v, z):
+        n2, nv = self.n2, self.nv
+        zp = z[n2:]
+        ops.vmul(v[n2:], self.sinv, zp)
+        ru = ops.copy(self.ru, v[:n2])
+        for r in range(2):
+            if self.A.up[r] is not None:
+                self.A.up[r].apply(zp, self.tmp)
+                ops.axpby(-1.0, self.tmp, 1.0, ru[r * nv:(r + 1) * nv])
+        if self.velocity == 'jacobi':
+            ops.vmul(ru, self.dinv, z[:n2])
+        else:
+            _hip.check(_hip.lib().flow_ilu0_solve(
+                ctypes.byref(self.ilu.struct), _hip.f64(ru, n2),
+                _hip.f64(z[:n2], n2), _hip.f64(self.work, n2),
+                _hip.stream()))
+        return z
+
+
+def _signed_schur_diagonal(A, pmask):
+    '''diag(pp) - sum_s diag(pu[s] diag(uu_ss)^-1 up[s]) of the eliminated A,
+    with its true sign: every entry of the plane pu[s] times its mirror entry
+    of up[s] (_transpose_perm: the permutation symmetric_part uses), that
+    plane applied to the inverse diagonal of uu's plane (s, s), summed.  A form
+    written with -q*div(u) gives a negative, one with +q*div(u) a positive
+    diagonal.  Rows with a zero and Dirichlet rows 1.'''
+    nv, npr = A.W.N, A.P.N
+    dinv = A.uu.diag_inv()
+    if A.pp is not None:
+        lay = A.pp.layout
+        d = A.pp.vals[lay.dev('diag_idx').long()].contiguous()
+    else:
+        d = device.zeros(npr)
+    tmp = device.empty(npr)
+    for s in range(2):
+        B, C = A.up[s], A.pu[s]
+        if B is None or C is None:
+            continue
+        Rup, Rpu = B.layout, C.layout
+        perm = _transpose_perm(Rpu, Rup).long()
+        both = RectMatrix(Rpu)
+        both.vals[:Rpu.nnz] = C.vals[:Rpu.nnz] * B.vals[perm]
+        both.apply(dinv[s * nv:(s + 1) * nv], tmp)
+        ops.axpby(-1.0, tmp, 1.0, d)
+    one = torch.ones_like(d)
+    d = torch.where(d != 0.0, d, one)
+    if pmask is not None:
+        d = torch.where(device.to_device(pmask) != 0, one, d)
     return d
+
+
+def solver_route(symmetric, prm):
+    '''Which loop solve() runs for a form that is symmetric (structurally, or
+    by 'symmetric': True) or not: 'minres'; 'fgmres' with mixed_gmres(True)
+    for a non-symmetric form, or where 'linear_solver' is 'gmres'; 'refuse'
+    for a non-symmetric form with the switch off.'''
+    from . import forms
+    if forms.mixed_gmres.enabled and (
+            not symmetric or prm.get('linear_solver') == 'gmres'):
+        return 'fgmres'
+    return 'minres' if symmetric else 'refuse'
+
+
+def _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters):
+    '''solve() for mixed_gmres(True): assemble_system (no symmetrisation of a
+    non-symmetric form), BlockTriangularPreconditioner, fgmres.'''
+    velocity = prm.get('preconditioner', 'ilu0')
+    if velocity not in ('ilu0', 'jacobi'):
+        raise ValueError("preconditioner %r under GMRES: 'ilu0' or 'jacobi'"
+                         % (velocity,))
+    ks = dict(prm.get('krylov_solver') or {})
+    masks = {}
+    A, b = assemble_system(a, L, bcs, form_compiler_parameters, masks)
+    if A.uu is None:
+        raise ValueError('the form has no velocity-velocity block')
+    if prm.get('preconditioner_form') is not None:
+        sdiag = _form_diagonal(prm['preconditioner_form'], bcs,
+                               form_compiler_parameters, signed=True)
+    else:
+        sdiag = _signed_schur_diagonal(A, masks['p'])
+    M = BlockTriangularPreconditioner(A, velocity, sdiag)
+    # (the one-launch product: bit-equal to A.apply and faster, README)
+    its, res = fgmres(A.apply_fused, M.apply, b.data, w.data,
+                      ks.get('relative_tolerance', 1.0e-12),
+                      ks.get('absolute_tolerance', 0.0),
+                      int(ks.get('maximum_iterations', 1000)),
+                      int(ks.get('restart', 30)))
+    return ops.SolveInfo(its, res, 'fgmres+' + velocity)
 
 
 def solve(a, L, w, bcs=None, solver_parameters=None,
           form_compiler_parameters=None):
     '''solve(a == L, w, bcs) with w = Function(WP): assemble_system, then
-    preconditioned MINRES from w's values into w.  The form must be symmetric
-    -- structurally (forms.is_symmetric_form: over all its parts) or by
-    solver_parameters['symmetric'] = True --, else NotImplementedError: there
-    is no flexible Krylov loop that takes a block preconditioner yet
-    (assemble_system and to_scipy() still work for such a form).
+    preconditioned MINRES from w's values into w.  MINRES takes a symmetric
+    form -- structurally (forms.is_symmetric_form: over all its parts) or by
+    solver_parameters['symmetric'] = True.  Any other form is a
+    NotImplementedError unless forms.mixed_gmres(True) is on (assemble_system
+    and to_scipy() work for it either way); with that switch it goes to
+    assemble_system without symmetrisation, BlockTriangularPreconditioner and
+    fgmres over apply_fused, and 'linear_solver': 'gmres' sends a symmetric
+    form there too.  There: 'preconditioner' 'ilu0' (default) | 'jacobi'
+    ('two_level' is a ValueError); 'preconditioner_form', whose pp block's
+    SIGNED lumped rows as written precondition the pressure (-p*q*dx, or
+    -(1/nu)*p*q*dx for Oseen, for the reference's sign convention; default:
+    _signed_schur_diagonal); 'krylov_solver' also takes 'restart' (30), and
+    the tolerances are on the true residual |b - A x|_2; the method reported
+    is 'fgmres+ilu0' or 'fgmres+jacobi'; a matrix without a uu block is a
+    ValueError.
     A structurally symmetric form is solved on the bitwise symmetric matrix
     of assemble_system; a form that only 'symmetric': True vouches for is NOT
     symmetrised (its blocks need not have mirror blocks), so MINRES then runs
@@ -671,12 +995,15 @@ def solve(a, L, w, bcs=None, solver_parameters=None,
                          'trial function')
     prm = dict(solver_parameters or {})
     symmetric = prm.get('symmetric') is True or forms.is_symmetric_form(a)
-    if not symmetric:
+    route = solver_route(symmetric, prm)
+    if route == 'refuse':
         raise NotImplementedError(
             'solve of a non-symmetric form on a mixed space: MINRES needs a '
-            'symmetric form, and there is no flexible Krylov loop that takes '
-            'a block preconditioner yet; assemble_system(a, L, bcs) and '
-            'to_scipy() work for it')
+            'symmetric form; flexible GMRES with a block preconditioner '
+            'takes it once fem.mixed_gmres(True) is on; assemble_system(a, '
+            'L, bcs) and to_scipy() work for it either way')
+    if route == 'fgmres':
+        return _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters)
     ks = dict(prm.get('krylov_solver') or {})
     masks = {}
     A, b = assemble_system(a, L, bcs, form_compiler_parameters, masks)

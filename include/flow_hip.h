@@ -1947,6 +1947,61 @@ int flow_block_gram(int n, int ma, const double* X, size_t ldx, int mb,
                     const double* Y, size_t ldy, double* work, double* out,
                     void* stream);
 
+/* ---- the matrix of a form on a Taylor-Hood space (flow_amd/fem/mixed.py):
+ * MixedMatrix ------------------------------------------------------------------
+ * A linear operator by blocks over the unknowns velocity x, velocity y,
+ * pressure (2 nv + np):
+ *   uu     2x2 blocks over the velocity pattern (nv rows): four value planes,
+ *          plane 2 r + s = (test component r, trial component s), as the
+ *          planes of a kind-2 flow_operator;
+ *   up[r]  (test component r, trial p): nv x np, the two planes over ONE
+ *          rectangular pattern (space.RectLayout(kv, kp));
+ *   pp     np x np over the pressure pattern: one plane;
+ *   pu[s]  (test q, trial component s): np x nv, the two planes over ONE
+ *          rectangular pattern (space.RectLayout(kp, kv)).
+ * Any block may be absent: its value pointer is NULL (the four uu planes are
+ * present or absent together); the pattern of an absent block is not read.
+ * Value planes and cols as for flow_operator: every plane 16-byte aligned and
+ * readable up to index nnz, cols 8-byte aligned and readable at nnz.
+ * vtiles (nvtiles + 1) / ptiles (nptiles + 1): row tiles of the velocity and of
+ * the pressure rows, each of at most FLOW_SPMV_ROWS_PER_BLOCK consecutive rows
+ * holding no more nonzeros than flow_spmv_tile_nnz(kind) in EACH pattern the
+ * tile touches: a velocity tile the velocity pattern (kind 2) and the up
+ * pattern (kind 0), a pressure tile the pressure pattern and the pu pattern
+ * (kind 0).  Built on the host over both row pointers. */
+typedef struct {
+  int nv, np;              /* dofs of one velocity component, of the pressure */
+  int nvtiles, nptiles;
+  const int* vrowptr;      /* nv+1 */
+  const int* vcols;
+  const double* uu[4];
+  const int* uprowptr;     /* nv+1 */
+  const int* upcols;
+  const double* up[2];
+  const int* prowptr;      /* np+1 */
+  const int* pcols;
+  const double* pp;
+  const int* purowptr;     /* np+1 */
+  const int* pucols;
+  const double* pu[2];
+  const int* vtiles;       /* nvtiles+1 */
+  const int* ptiles;       /* nptiles+1 */
+} flow_mixed;
+
+/* y = A x for all blocks in ONE launch of nvtiles + nptiles workgroups; x and
+ * y hold 2 nv + np doubles.  A velocity tile does the uu product of both
+ * components and then the two up planes (columns and x_p loaded once), a
+ * pressure tile the pp row sum and then the two pu planes (columns loaded
+ * once); y_u = s_uu + s_up per component, y_p = (s_pp + s_pu0) + s_pu1, a row
+ * sum being the products of the row added in ascending k.  Every entry of y
+ * has the bits that one flow_operator_apply per block, the results added in
+ * that order by flow_axpby(1, t, 1, y), leaves there, for every subset of
+ * present blocks (rows that no present block touches: 0.0).  No atomics: two
+ * calls give the same bits.  Only a tile's own columns are dereferenced.  y
+ * overlapping x is refused (code 2); a refusal launches nothing. */
+int flow_mixed_apply(const flow_mixed* A, const double* x, double* y,
+                     void* stream);
+
 /* ---- running time statistics of a field (flow_amd/fem/statistics.py):
  * fem.Statistics ---------------------------------------------------------------
  * A store of planes of ld doubles each (ld >= n and even, the store 16-byte
