@@ -20,6 +20,8 @@
 
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 namespace flow {
 
 // ---------------------------------------------------------------------------
@@ -240,6 +242,109 @@ __global__ __launch_bounds__(kBlock) void mass_cheb_kernel(
   }
 }
 
+// The last step (MODE 2) of a correction of flow_mass_correct: the solve runs
+// around the caller's vectors, so what flow_mass_solve_increment leaves to
+// passes before and behind it happens where the rows are in registers anyway.
+//   base    the start of the solve, never formed: `ui`, on identity rows `xbc`
+//   xread   the increment before this correction (nullptr: zero) -- the first
+//           correction reads the caller's start vector, the later ones x
+//   x       the increment after it (the solver's own vector)
+//   x_out   base + x, the y the norm of the stopping test is taken of
+//   inc_out x_out - ui (nullptr: not wanted), what a time loop files as the
+//           increment it found
+// Every correction that runs writes all three for its rows, so they hold the
+// last correction's values however the solve ends.  The expressions are those
+// of mass_cheb_kernel<float2, 2, .> / add_to_x, operand for operand.
+struct MassOut {
+  const double* xread;
+  const double* ui;
+  const double* xbc;
+  double* x_out;
+  double* inc_out;
+};
+
+template <bool PACKED>
+__global__ __launch_bounds__(kBlock) void mass_cheb_out_kernel(
+    int n, const int* __restrict__ rowptr, const int* __restrict__ cols,
+    const void* __restrict__ vals, const int* __restrict__ rowblocks,
+    const unsigned char* __restrict__ mask, const float2* __restrict__ g,
+    const float2* __restrict__ rho_in, float c1, float c2,
+    const float2* __restrict__ acc, double* x, MassOut o,
+    double* __restrict__ zz_part, double* __restrict__ xx_part,
+    const double* __restrict__ stop) {
+  __shared__ float2 prod[kTile16];
+  if (stopped(stop)) return;
+  int r, r1;
+  float2 own, rho_old, acc_old;
+  vzero(own);
+  vzero(rho_old);
+  vzero(acc_old);
+  XRow xr;
+  double u0 = 0.0, u1 = 0.0;
+  auto early = [&](int row, bool has) {
+    if (!has) return;
+    own = g[row];
+    rho_old = rho_in[row];
+    acc_old = acc[row];
+    if (o.xread) {
+      xr.x0 = o.xread[row];
+      xr.x1 = o.xread[n + row];
+    }
+    u0 = o.ui[row];
+    u1 = o.ui[n + row];
+    xr.b0 = mask[row] ? u0 : o.xbc[row];
+    xr.b1 = mask[n + row] ? u1 : o.xbc[n + row];
+  };
+  float2 s = PACKED
+                 ? fp16_tile_row_sum(
+                       rowptr,
+                       PackedStream{static_cast<const unsigned*>(vals), cols},
+                       rowblocks, g, prod, r, r1, early)
+                 : fp16_tile_row_sum(
+                       rowptr,
+                       Cols32Stream<__half>{static_cast<const __half*>(vals), cols},
+                       rowblocks, g, prod, r, r1, early);
+  double2 dots = make_double2(0.0, 0.0);
+  if (r < r1) {
+    apply_mask(mask, n, r, own, s);
+    const float2 rho = vaxpby(1.f, rho_old, -1.f, s);
+    const float2 d = vaxpby(c1, own, c2, rho);
+    const float2 z = vaxpby(1.f, acc_old, 1.f, d);
+    const double x0 = xr.x0 + static_cast<double>(z.x);
+    const double x1 = xr.x1 + static_cast<double>(z.y);
+    x[r] = x0;
+    x[n + r] = x1;
+    const double y0 = xr.b0 + x0;
+    const double y1 = xr.b1 + x1;
+    o.x_out[r] = y0;
+    o.x_out[n + r] = y1;
+    if (o.inc_out) {
+      o.inc_out[r] = y0 - u0;
+      o.inc_out[n + r] = y1 - u1;
+    }
+    dots = make_double2(
+        static_cast<double>(z.x) * z.x + static_cast<double>(z.y) * z.y,
+        y0 * y0 + y1 * y1);
+  }
+  const double zz = block_sum(dots.x);
+  const double xx = block_sum(dots.y);
+  if (threadIdx.x == 0) {
+    zz_part[blockIdx.x] = zz;
+    xx_part[blockIdx.x] = xx;
+  }
+}
+
+// x[dofs[i]] = 0: a start vector of the increment vanishes on the identity rows
+// (len: the vector's length; an index outside it is skipped)
+__global__ void mass_zero_rows_kernel(int nbc, const int* __restrict__ dofs,
+                                      long long len, double* __restrict__ x) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nbc;
+       i += gridDim.x * blockDim.x) {
+    const int d = dofs[i];
+    if (d >= 0 && d < len) x[d] = 0.0;
+  }
+}
+
 // One workgroup: z.z and x.x from the partials of the last product; the
 // stopping test  contraction |z_k| <= max(rtol |x_{k+1}|, atol)  (x already
 // holds x_{k+1} = x_k + z_k, the iterate the test accepts: |B r_{k+1}| <=
@@ -364,7 +469,8 @@ struct MassTiles {
 template <class V, bool PACKED>
 int correction(const flow_mass* M, const MassTiles& T, double* x,
                const double* xbase, double* zz_part, double* xx_part,
-               const double* stop, hipStream_t st) {
+               const double* stop, hipStream_t st,
+               const MassOut* out = nullptr) {
   const flow_operator* A = M->A;
   const int n = A->n;
   // (PACKED: the packed stream and the tiles' base columns take the places of
@@ -398,6 +504,18 @@ int correction(const flow_mass* M, const MassTiles& T, double* x,
                        nod, n, nod, nod, stop, 0, 0x7fffffff);
   }
   ch.next(&c1, &c2);
+  if constexpr (std::is_same<V, float2>::value) {
+    if (out) {
+      // (flow_mass_correct: the solve around the caller's vectors)
+      hipLaunchKernelGGL((mass_cheb_out_kernel<PACKED>),
+                         dim3(T.nblocks[products - 1]), blk, 0, st, n, A->rowptr,
+                         cols, v16, T.rowblocks[products - 1], A->rowmask,
+                         d[(products - 2) & 1], rho, c1, c2, acc, x, *out, zz_part,
+                         xx_part, stop);
+      FLOW_CHECK_LAUNCH();
+      return FLOW_OK;
+    }
+  }
   hipLaunchKernelGGL((mass_cheb_kernel<V, 2, PACKED>),
                      dim3(T.nblocks[products - 1]), blk, 0, st, n, A->rowptr, cols,
                      v16, T.rowblocks[products - 1], A->rowmask,
@@ -450,10 +568,16 @@ static int mass_check(const flow_mass* M) {
 // xbase != nullptr: the INCREMENT form -- b is the defect g = b' - M xbase of
 // the start xbase, x the increment; x_is_zero: it is zero on entry, the first
 // correction then needs no product with M
+// out != nullptr (flow_mass_correct, kind 4): xbase is not used -- the base is
+// out->ui with out->xbc on the identity rows --, x is only ever WRITTEN by the
+// first correction, which reads the increment it starts from at out->xread
+// (nullptr with x_is_zero), and every correction leaves out->x_out and
+// out->inc_out behind (mass_cheb_out_kernel)
 static int mass_solve(const flow_mass* M, const double* b, double* x,
                       const double* xbase, bool x_is_zero, double rtol,
                       double atol, int maxit, int first_check, double* work,
-                      int* iters_host, double* resid_host, hipStream_t st) {
+                      int* iters_host, double* resid_host, hipStream_t st,
+                      const MassOut* out = nullptr) {
   const flow_operator* A = M->A;
   double* S = work + 3 * kRedBlocks;
   double* zz_part = work + FLOW_REDUCE_WORK;
@@ -462,7 +586,17 @@ static int mass_solve(const flow_mass* M, const double* b, double* x,
   const double c2 = M->contraction * M->contraction;
   int rc;
   if ((rc = fill(kNumSlots, 0.0, S, st))) return rc;
+  bool first = true;
   auto one = [&]() -> int {
+    // the increment this correction starts from: x, but for the first
+    // correction of a solve around the caller's vectors
+    MassOut o = {};
+    if (out) {
+      o = *out;
+      if (!first) o.xread = x;
+    }
+    const double* xr = out ? o.xread : x;
+    first = false;
     if (x_is_zero) {
       hipLaunchKernelGGL(mass_rho0_kernel, dim3(grid_for(A->n)), dim3(kBlock), 0,
                          st, A->n, A->kind == 4 ? 2 : 1, b, M->dinv, M->work16,
@@ -471,7 +605,7 @@ static int mass_solve(const flow_mass* M, const double* b, double* x,
     } else if (A->kind == 4) {
       hipLaunchKernelGGL(mass_residual_pair_kernel, dim3(A->nblocks), dim3(kBlock),
                          0, st, A->n, A->rowptr, A->cols, A->vals[0], A->rowblocks,
-                         A->rowmask, x, A->n, b, M->dinv,
+                         A->rowmask, xr, A->n, b, M->dinv,
                          reinterpret_cast<float2*>(M->work16), stop);
     } else {
       hipLaunchKernelGGL(mass_residual_kernel, dim3(A->nblocks), dim3(kBlock), 0, st,
@@ -480,10 +614,11 @@ static int mass_solve(const flow_mass* M, const double* b, double* x,
     }
     const MassTiles T = default_tiles(M);
     if (A->kind == 4) {
+      const MassOut* op = out ? &o : nullptr;
       rc = M->packed16 ? correction<float2, true>(M, T, x, xbase, zz_part, xx_part,
-                                                  stop, st)
+                                                  stop, st, op)
                        : correction<float2, false>(M, T, x, xbase, zz_part,
-                                                   xx_part, stop, st);
+                                                   xx_part, stop, st, op);
     } else {
       rc = M->packed16 ? correction<float, true>(M, T, x, xbase, zz_part, xx_part,
                                                  stop, st)
@@ -505,18 +640,24 @@ static int mass_solve(const flow_mass* M, const double* b, double* x,
     base.pod(0x6d73ull);      // "ms"
     key_operator(base, A);
     base.obj(M).pod(b).pod(x).pod(xbase).pod(work).pod(rtol).pod(atol);
+    // (the caller's vectors of flow_mass_correct are arguments of the launches)
+    base.obj(out);
   }
   auto one_replayed = [&]() -> int {
     if (!replay) return one();
     KeyHash key = base;
     key.pod(x_is_zero);
+    // (... and its first correction reads another vector than the later ones)
+    key.pod(out != nullptr && first);
     hipGraphExec_t graph = nullptr;
     int nodes = 0, r;
-    const bool was_zero = x_is_zero;
+    const bool was_zero = x_is_zero, was_first = first;
     if ((r = replay_prepare(key.h, kReplayMass, st, one, &graph, &nodes))) return r;
     x_is_zero = was_zero;     // (a capture has run `one` without launching)
+    first = was_first;
     if (!graph) return one();
     x_is_zero = false;
+    first = false;
     return replay_launch(graph, nodes, st);
   };
   double state[kNumSlots];
@@ -870,6 +1011,59 @@ extern "C" int flow_mass_solve_increment(const flow_mass* M, const double* g,
                      static_cast<int>(N), xbase, delta, x);
   FLOW_CHECK_LAUNCH();
   return rc;
+}
+
+// The increment solve around the caller's vectors: what the sequence
+//   start = ui, start[bc_dofs] = bc values, delta0[bc_dofs] = 0,
+//   flow_mass_solve_increment(g, start, delta0) -> x_out, inc_out = x_out - ui
+// computes, bit for bit, without forming `start`, without copying delta0 into
+// the solver's increment and without the passes behind the solve.
+extern "C" int flow_mass_correct(const flow_mass* M, const double* g,
+                                 const double* ui, const double* xbc,
+                                 double* delta0, int nbc, const int* bc_dofs,
+                                 double* x_out, double* inc_out, double rtol,
+                                 double atol, int maxit, int first_check,
+                                 double* work, size_t work_len, int* iters_host,
+                                 double* resid_host, void* stream) {
+  int rc = mass_check(M);
+  if (rc) return rc;
+  FLOW_REQUIRE(M->A->kind == 4 && M->A->rowmask != nullptr,
+               "flow_mass_correct: operator kind 4 (one plane, two components, "
+               "identity rows by mask)");
+  FLOW_REQUIRE(g && ui && x_out && work && iters_host && resid_host,
+               "solver pointers");
+  FLOW_REQUIRE(nbc >= 0 && (nbc == 0 || (bc_dofs && xbc)),
+               "flow_mass_correct: identity rows need bc_dofs and xbc");
+  FLOW_REQUIRE(x_out != ui && x_out != g && x_out != xbc && x_out != delta0 &&
+                   x_out != inc_out,
+               "flow_mass_correct: x_out is a vector of its own");
+  FLOW_REQUIRE(inc_out == nullptr ||
+                   (inc_out != ui && inc_out != g && inc_out != xbc &&
+                    inc_out != delta0),
+               "flow_mass_correct: inc_out is a vector of its own");
+  FLOW_REQUIRE(rtol >= 0.0 && atol >= 0.0 && maxit >= 1 && first_check >= 0,
+               "solver tolerances");
+  const size_t N = 2 * static_cast<size_t>(M->A->n);
+  const size_t head = FLOW_REDUCE_WORK + 2 * static_cast<size_t>(M->nblocks16);
+  FLOW_REQUIRE(work_len >= head + (head & 1) + N, "mass solve workspace too small");
+  hipStream_t st = as_stream(stream);
+  double* delta = work + head + (head & 1);
+  FLOW_REQUIRE(delta != x_out && delta != inc_out && delta != ui && delta != g &&
+                   delta != delta0,
+               "flow_mass_correct: the workspace is a vector of its own");
+  if (delta0 && nbc > 0) {
+    hipLaunchKernelGGL(mass_zero_rows_kernel, dim3(grid_for(nbc)), dim3(kBlock), 0,
+                       st, nbc, bc_dofs, static_cast<long long>(N), delta0);
+    FLOW_CHECK_LAUNCH();
+  }
+  MassOut out;
+  out.xread = delta0;
+  out.ui = ui;
+  out.xbc = xbc ? xbc : ui;
+  out.x_out = x_out;
+  out.inc_out = inc_out;
+  return mass_solve(M, g, delta, nullptr, delta0 == nullptr, rtol, atol, maxit,
+                    first_check, work, iters_host, resid_host, st, &out);
 }
 
 // y[i] = a[i] + b[i] on the rows [lo, hi) of ncomp components (stride n)

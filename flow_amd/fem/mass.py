@@ -188,6 +188,59 @@ class MassSolver(object):
                              'defect correction (increment) + chebyshev%d/fp16'
                              % self.struct.steps)
 
+    def correct(self, g, ui, xbc, bc_dofs, x, rtol, atol=0.0, maxit=50,
+                tag=None, first_check=0, delta0=None, inc_out=None):
+        '''solve_increment around the caller's vectors (flow_mass_correct,
+        kind 4): x = start + increment and inc_out = x - ui (if given), where
+        start = ui with the boundary values on the identity rows -- read from
+        `xbc`, a vector of A.size that carries them on the rows `bc_dofs` (int32,
+        the rows A masks) --, M increment = g.  Bit for bit what
+        `start = copy(ui); start[bc_dofs] = values; delta0[bc_dofs] = 0;
+        solve_increment(g, start, x, delta0=delta0); inc_out = x - ui`
+        gives, without those passes; delta0 is zeroed on bc_dofs in place.'''
+        assert self.ncomp == 2
+        n = self.A.size
+        nbc = 0 if bc_dofs is None else bc_dofs.numel()
+        head = _hip.REDUCE_WORK + 2 * self.struct.nblocks16
+        wk = ops.work(head + 2 + n)
+        if first_check == 0 and tag is not None and tag in self.history:
+            first_check = self.history[tag]
+        its = ctypes.c_int(0)
+        res = ctypes.c_double(0.0)
+        try:
+            _hip.check(_hip.lib().flow_mass_correct(
+                ctypes.byref(self.struct), _hip.f64(g, n, 'g'),
+                _hip.f64(ui, n, 'ui'),
+                _hip.f64(xbc, n, 'xbc') if nbc > 0 else None,
+                _hip.f64(delta0, n, 'delta0') if delta0 is not None else None,
+                nbc, _hip.i32(bc_dofs, nbc, 'bc_dofs') if nbc > 0 else None,
+                _hip.f64(x, n, 'x'),
+                _hip.f64(inc_out, n, 'inc_out') if inc_out is not None else None,
+                float(rtol), float(atol), int(maxit), int(first_check),
+                _hip.f64(wk), wk.numel(), ctypes.byref(its), ctypes.byref(res),
+                _hip.stream()))
+        except _hip.NotConverged as err:
+            if not self._bound_failed(err):
+                raise
+            # as solve_increment: M increment = g by Jacobi-CG from zero,
+            # x = start + increment
+            delta = _hip.fill(device.empty(n), 0.0)
+            sol = self._fallback(err, g, delta, rtol, atol)
+            ops.copy(x, ui)
+            if nbc > 0:
+                mask = self.A.rowmask == 0
+                x[mask] = xbc[mask]
+            ops.axpby(1.0, delta, 1.0, x)
+            if inc_out is not None:
+                ops.copy(inc_out, x)
+                ops.axpby(-1.0, ui, 1.0, inc_out)
+            return sol
+        if tag is not None:
+            self.history[tag] = its.value
+        return ops.SolveInfo(its.value, res.value,
+                             'defect correction (increment) + chebyshev%d/fp16'
+                             % self.struct.steps)
+
     def solve(self, b, x, rtol, atol=0.0, maxit=50, tag=None, first_check=0):
         '''x holds the initial guess; raises _hip.NotConverged like the Krylov
         solvers.  tag: the solve recurs in a time loop under that name -- as

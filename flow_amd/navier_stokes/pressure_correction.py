@@ -276,7 +276,12 @@ solver_parameters = {
                    # solve for u1 - ui (flow_mass_solve_increment), started from
                    # the previous increments extrapolated in time ('zero': not)
                    'increment': True, 'increment_start': 'extrapolated',
-                   'start_points': 5, 'start_degree': 3},
+                   'start_points': 5, 'start_degree': 3,
+                   # the increment solve on one GPU runs around the step's own
+                   # vectors (flow_mass_correct: no start vector formed, u1 and
+                   # the filed increment written by the solver; same bits).
+                   # False: flow_mass_solve_increment and the passes around it
+                   'around_caller': True},
     }
 
 _MODES = {
@@ -1369,6 +1374,38 @@ def _compute_pressure(
     return p1
 
 
+def _correction_route(par, sharded, graphs):
+    '''Which solve the velocity correction runs with the settings `par`
+    (solver_parameters['correction']): 'around_caller' (flow_mass_correct),
+    'increment' (flow_mass_solve_increment), 'solve' (flow_mass_solve) or
+    'cg'.  sharded: the step runs on the strips of flow_amd.parallel; graphs:
+    solver loops may be replayed as HIP graphs -- their vectors then have to
+    keep their addresses from step to step, which the fresh u1 and the rotating
+    history slots of 'around_caller' do not.'''
+    if par.get('method', 'chebyshev') != 'chebyshev':
+        return 'cg'
+    if not par.get('increment', True) or par.get('extrapolate', False):
+        return 'solve'
+    if sharded or graphs or not par.get('around_caller', True):
+        return 'increment'
+    return 'around_caller'
+
+
+def _bc_full(lay, dofs, bc_dofs, bc_vals, n2):
+    '''The boundary values scattered into a vector of n2 entries (zero
+    elsewhere), made once per set of conditions: `bc_vals` is the same tensor
+    while they are unchanged (_bc_arrays).'''
+    key = ('bc_full', dofs.tobytes())
+    held = lay._dev.get(key)
+    if held is None or held[0] is not bc_vals or held[1].numel() != n2:
+        full = _zeros(n2)
+        _hip.check(_hip.lib().flow_bc_set_values(
+            bc_dofs.numel(), _hip.i32(bc_dofs), _hip.f64(bc_vals),
+            _hip.f64(full), _hip.stream()))
+        held = lay._dev[key] = (bc_vals, full)
+    return held[1]
+
+
 def _compute_velocity_correction(
         ui, u, u_bcs, p1, p0, v, mu, rho, dt, rotational_form, tol, verbose
         ):
@@ -1428,8 +1465,15 @@ def _compute_velocity_correction(
     # (increment form on one GPU: the start lives in a buffer of the layout --
     # the solver's loop only sees it and its own workspace, the same addresses
     # every call --, the result base + increment is written to a fresh u1)
+    # ('around_caller': no start vector at all -- the solver reads ui and, on
+    # the Dirichlet rows, the boundary values where it needs the start)
+    direct = _correction_route(par, parallel.active(),
+                               _hip.graphs_possible()) == 'around_caller'
     apart = increment and not parallel.active()
-    if apart:
+    if direct:
+        start = None
+        u1 = Function(W, device.empty(n2))
+    elif apart:
         start = ops.copy(_persistent(lay, 'correction_start', n2), ui.data)
         u1 = Function(W, device.empty(n2))
     else:
@@ -1450,9 +1494,10 @@ def _compute_velocity_correction(
         ops.axpby(r, hist['u_out'], 1.0, start)
         ops.axpby(-r, hist['ui'], 1.0, start)
     if nbc > 0:
-        _hip.check(lib.flow_bc_set_values(
-            nbc, _hip.i32(bc_dofs), _hip.f64(bc_vals), _hip.f64(start), st
-            ))
+        if not direct:
+            _hip.check(lib.flow_bc_set_values(
+                nbc, _hip.i32(bc_dofs), _hip.f64(bc_vals), _hip.f64(start), st
+                ))
         if increment:
             # (the increment vanishes on the Dirichlet rows: the start carries
             # the boundary values)
@@ -1485,13 +1530,29 @@ def _compute_velocity_correction(
                         key='correction_increments', power=2,
                         degree=par.get('start_degree')):
                     d0 = None
-                elif nbc > 0:
+                elif nbc > 0 and not direct:
                     _hip.check(lib.flow_bc_set_values(
                         nbc, _hip.i32(bc_dofs),
                         _hip.f64(lay._dev[('bc_zeros', nbc)]), _hip.f64(d0),
                         st))
             ui_keep = ui.data
-            if parallel.active():
+            if direct:
+                # the solver zeroes d0 on the Dirichlet rows itself, writes u1
+                # and files u1 - ui in the history's own vector
+                slot = None
+                if par.get('increment_start') == 'extrapolated':
+                    slot = start_vectors.increment_slot(
+                        lay, n2, key='correction_increments')
+                sol = solver.correct(
+                    b, ui_keep,
+                    _bc_full(lay, dofs, bc_dofs, bc_vals, n2) if nbc > 0 else None,
+                    bc_dofs if nbc > 0 else None, u1.data, tol,
+                    maxit=min(par['maxit'], 100), tag='correction', delta0=d0,
+                    inc_out=slot)
+                if slot is not None:
+                    start_vectors.file_increment(
+                        lay, dt, slot, key='correction_increments')
+            elif parallel.active():
                 # (on the strips: one collective per correction, the deep halo
                 # of the defect; u1 comes back valid on own + ghost rows)
                 sol = parallel.mass_solve(
@@ -1501,7 +1562,7 @@ def _compute_velocity_correction(
                 sol = solver.solve_increment(
                     b, start, u1.data, tol, maxit=min(par['maxit'], 100),
                     tag='correction', delta0=d0)
-            if par.get('increment_start') == 'extrapolated':
+            if par.get('increment_start') == 'extrapolated' and not direct:
                 d0 = lay._dev['correction_d0_scratch']
                 ops.copy(d0, u1.data)
                 ops.axpby(-1.0, ui_keep, 1.0, d0)

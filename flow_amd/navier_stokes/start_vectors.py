@@ -343,6 +343,43 @@ def remember_increment(lay, dt, dx, key='newton_increments'):
     hist.insert(0, (keep, dt, tr.level))
 
 
+def increment_slot(lay, n, key='newton_increments'):
+    '''The vector remember_increment would copy an increment of n entries
+    into, handed out BEFORE the solve so that the solver writes there itself:
+    this time level's earlier attempt (a repeated step replaces it), the oldest
+    entry beyond KEEP_POINTS -- never read by extrapolated_increment, which
+    takes KEEP_POINTS entries at the most --, or a new vector.  None without a
+    trajectory.  Ask after extrapolated_increment (a repeated step starts from
+    the vector handed out here) and file it with file_increment; a slot that
+    is not filed is simply dropped.'''
+    st = lay._dev.get('start_vector_state')
+    if st is None or (st.current is None and not st.unresolved):
+        return None
+    tr = _resolve(st)
+    hist = tr.entries(key)
+    hist[:] = [h for h in hist if h[0].numel() == n]
+    if hist and hist[0][2] == tr.level:
+        return hist[0][0]
+    if len(hist) >= KEEP_POINTS + 1:
+        return hist.pop()[0]
+    return device.empty(n)
+
+
+def file_increment(lay, dt, slot, key='newton_increments'):
+    '''remember_increment for an increment that already lies in the vector
+    increment_slot handed out: no copy.'''
+    st = lay._dev.get('start_vector_state')
+    if st is None or (st.current is None and not st.unresolved):
+        return
+    tr = _resolve(st)
+    hist = tr.entries(key)
+    if hist and hist[0][2] == tr.level:
+        assert hist[0][0] is slot
+        hist[0] = (slot, dt, tr.level)
+        return
+    hist.insert(0, (slot, dt, tr.level))
+
+
 def newton_key(it):
     '''Key of the increment history of Newton iteration `it`: the first three
     iterations of a time loop's calls have one each (a developed vortex street

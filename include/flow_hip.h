@@ -619,6 +619,28 @@ int flow_mass_solve_increment(const flow_mass* M, const double* g,
                               double* work, size_t work_len, int* iters_host,
                               double* resid_host, void* stream);
 
+/* The increment solve of a time loop's velocity correction AROUND THE CALLER'S
+ * VECTORS (kind 4 only).  Computes, bit for bit, what
+ *     start = ui;  start[bc_dofs] = bc values;  delta0[bc_dofs] = 0;
+ *     flow_mass_solve_increment(M, g, start, delta0, x_out, ...);
+ *     inc_out = x_out - ui
+ * computes, with these passes gone: `start` is never formed (the rows read ui,
+ * the identity rows xbc: the boundary values scattered into a vector of op
+ * size, read on those rows only); delta0 is read where it lies by the first
+ * correction (zeroed on the rows bc_dofs IN PLACE first: nbc entries, which
+ * must be the rows A masks); the last Chebyshev step of every correction
+ * stores x_out = start + increment and inc_out = x_out - ui (or NULL) next to
+ * the increment, so nothing runs behind the solve, however it ends.
+ * delta0 NULL: the increment starts from zero.  x_out, inc_out: vectors of
+ * their own.  Errors, counts, *resid_host and work as
+ * flow_mass_solve_increment. */
+int flow_mass_correct(const flow_mass* M, const double* g, const double* ui,
+                      const double* xbc, double* delta0, int nbc,
+                      const int* bc_dofs, double* x_out, double* inc_out,
+                      double rtol, double atol, int maxit, int first_check,
+                      double* work, size_t work_len, int* iters_host,
+                      double* resid_host, void* stream);
+
 /* ---- K12: Krylov drivers -------------------------------------------------
  * Device-resident loops.  Convergence is decided ON THE DEVICE: the kernel
  * that computes the solver scalars compares the residual norm with the target
