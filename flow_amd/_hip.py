@@ -571,6 +571,7 @@ SYMBOLS = {
     'flow_block_gram': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, ctypes.c_size_t,
                         _VP, _VP, _VP],
     'flow_mixed_apply': [_P(MixedS), _VP, _VP, _VP],
+    'flow_mixed_upper_rhs': [_P(MixedS), _VP, _VP, _VP, _VP, _VP],
     'flow_stats_update': [_I, _I, _I, _P(StatsFreq), _D, _D, _D, _VP, _VP,
                           ctypes.c_size_t, _VP],
     'flow_stats_merge': [_I, _I, _I, _I, _D, _D, _VP, _VP, ctypes.c_size_t,

@@ -31,6 +31,30 @@
 // never -0.0 (it starts from +0.0), so 0.0 + s has the bits of s: an absent
 // block may be skipped or added as 0.0 alike.  Every entry of y therefore has
 // the bits MixedMatrix.apply leaves there, for every subset of present blocks.
+//
+// flow_mixed_upper_rhs is the first half of the block upper triangular
+// preconditioner (mixed.py, BlockTriangularPreconditioner) over the same tiles,
+// also in ONE launch: z_p = r_p * sinv and ru = r_u - up z_p.  The composed
+// sequence is a vmul, a copy of r_u and, per coupling plane, a
+// flow_operator_apply into a temporary and an axpby(-1, tmp, 1, ru): six
+// launches, each plane streamed in a launch of its own.  Here
+//
+//   pressure tile  z_p[i] = r_p[i] * sinv[i];
+//   velocity tile  the two planes up0, up1 through StreamTilePlanes, the column
+//                  pairs loaded once; r_p and sinv are both gathered at the
+//                  tile's columns and multiplied in the lane, so the operand
+//                  z_p[col] never comes from memory and no velocity tile waits
+//                  for a pressure tile; ru[c nv + i] = r[c nv + i] - s_c.
+//
+// Bits: vmul_kernel leaves 1.0 * r_p[i] * sinv[i], one rounded multiply, and
+// the lane's r_p[col] * sinv[col] is the same multiply of the same operands, so
+// the parked products are those of flow_operator_apply on the stored z_p; the
+// row sum is the tile structs' sum in ascending k; axpby(-1, tmp, 1, ru) is
+// -1 * tmp + 1 * ru, whose two products are exact, fused or not: one rounded
+// subtraction ru - tmp.  A component whose plane is absent keeps the bits of
+// r (the copy).  Every entry of z_p and ru therefore has the bits the composed
+// sequence leaves, for every subset of present planes.  No atomics, and no LDS
+// beyond the two planes declared for the product.
 #include "csr_stream.h"
 #include "multi_dot.h"
 
@@ -129,6 +153,61 @@ __global__ __launch_bounds__(kBlock) void mixed_apply_kernel(
 static_assert(2 * kTileM * sizeof(double) <= 32768,
               "two LDS planes (16 KB with two pairs per lane)");
 
+__device__ __forceinline__ void upper_rhs_velocity_tile(
+    const flow_mixed& A, int r0, int r1, const double* __restrict__ sinv,
+    const double* __restrict__ r, double* __restrict__ ru,
+    double* __restrict__ prod0, double* __restrict__ prod1) {
+  const int nv = A.nv;
+  const int row = r0 + threadIdx.x;
+  // (block-uniform)
+  const bool up0 = A.up[0] != nullptr, up1 = A.up[1] != nullptr;
+  StreamTilePlanes c;
+  StreamTile::Gathered g, gs;
+  if (up0 || up1)   // (an absent plane: the other's values, loaded and unused)
+    c.load(r0, r1, A.uprowptr, A.upcols, up0 ? A.up[0] : A.up[1],
+           up1 ? A.up[1] : A.up[0]);
+  double b0 = 0.0, b1 = 0.0;
+  if (row < r1) {
+    b0 = r[row];
+    b1 = r[nv + row];
+  }
+  if (up0 || up1) {
+    g = c.gather(A.upcols, r + 2 * static_cast<size_t>(nv));
+    gs = c.gather(A.upcols, sinv);
+#pragma unroll
+    for (int j = 0; j < kPairs; ++j) {   // z_p at the columns: vmul's multiply
+      g.x0[j] = g.x0[j] * gs.x0[j];
+      g.x1[j] = g.x1[j] * gs.x1[j];
+    }
+    if (up0) c.plane(0).park(g, prod0);
+    if (up1) c.plane(1).park(g, prod1);
+    __syncthreads();
+    if (up0) b0 = b0 - c.sum(prod0);
+    if (up1) b1 = b1 - c.sum(prod1);
+  }
+  if (row < r1) {
+    ru[row] = b0;
+    ru[nv + row] = b1;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void mixed_upper_rhs_kernel(
+    flow_mixed A, const double* __restrict__ sinv, const double* __restrict__ r,
+    double* __restrict__ z_p, double* __restrict__ ru) {
+  __shared__ double prod0[kTileM];
+  __shared__ double prod1[kTileM];
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
+  if (tile < A.nvtiles) {
+    upper_rhs_velocity_tile(A, A.vtiles[tile], A.vtiles[tile + 1], sinv, r, ru,
+                            prod0, prod1);
+  } else {
+    const int pt = tile - A.nvtiles;
+    const int i = A.ptiles[pt] + threadIdx.x;
+    if (i < A.ptiles[pt + 1])
+      z_p[i] = 1.0 * r[2 * static_cast<size_t>(A.nv) + i] * sinv[i];
+  }
+}
+
 bool plane_ok(const double* p) { return p == nullptr || aligned16(p); }
 
 }  // namespace
@@ -167,6 +246,33 @@ extern "C" int flow_mixed_apply(const flow_mixed* A, const double* x, double* y,
   FLOW_REQUIRE(!overlap(y, n, x, n), "mixed product: y overlaps x");
   hipLaunchKernelGGL(mixed_apply_kernel, dim3(A->nvtiles + A->nptiles), dim3(kBlock),
                      0, as_stream(stream), *A, x, y);
+  FLOW_CHECK_LAUNCH();
+  return FLOW_OK;
+}
+
+extern "C" int flow_mixed_upper_rhs(const flow_mixed* A, const double* sinv,
+                                    const double* r, double* z_p, double* ru,
+                                    void* stream) {
+  FLOW_REQUIRE(A != nullptr, "mixed operator is NULL");
+  FLOW_REQUIRE(A->nv > 0 && A->np > 0, "mixed operator sizes");
+  FLOW_REQUIRE(A->nvtiles > 0 && A->nptiles > 0 && A->vtiles && A->ptiles,
+               "mixed operator tiles");
+  FLOW_REQUIRE(!(A->up[0] || A->up[1]) || (A->uprowptr && A->upcols),
+               "mixed operator: up pattern");
+  FLOW_REQUIRE(plane_ok(A->up[0]) && plane_ok(A->up[1]),
+               "value planes must be 16-byte aligned");
+  FLOW_REQUIRE((reinterpret_cast<size_t>(A->upcols) & 7) == 0,
+               "cols must be 8-byte aligned");
+  FLOW_REQUIRE(sinv && r && z_p && ru, "mixed upper rhs pointers");
+  const size_t n2 = 2 * static_cast<size_t>(A->nv);
+  const size_t np = static_cast<size_t>(A->np);
+  FLOW_REQUIRE(!overlap(ru, n2, r, n2 + np), "mixed upper rhs: ru overlaps r");
+  FLOW_REQUIRE(!overlap(z_p, np, r, n2 + np), "mixed upper rhs: z_p overlaps r");
+  FLOW_REQUIRE(!overlap(ru, n2, sinv, np) && !overlap(z_p, np, sinv, np),
+               "mixed upper rhs: an output overlaps sinv");
+  FLOW_REQUIRE(!overlap(ru, n2, z_p, np), "mixed upper rhs: ru overlaps z_p");
+  hipLaunchKernelGGL(mixed_upper_rhs_kernel, dim3(A->nvtiles + A->nptiles),
+                     dim3(kBlock), 0, as_stream(stream), *A, sinv, r, z_p, ru);
   FLOW_CHECK_LAUNCH();
   return FLOW_OK;
 }

@@ -31,6 +31,7 @@ from .forms import (                                            # noqa: F401
     vector_arguments, vector_derivatives, sym, tr, transpose, Identity, outer,
     interior_facets, jump, avg, FacetArea,
     mixed_arguments, TestFunctions, TrialFunctions, split, mixed_gmres,
+    mixed_derivatives,
     )
 from .space import RectLayout, rect_layout                      # noqa: F401
 from .mixed import MixedMatrix                                  # noqa: F401

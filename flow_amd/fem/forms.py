@@ -408,6 +408,14 @@ def s_gateaux(n, u, k, V):
     u, i, d) becomes ('arg', k, d, V, i), component i of the vector argument.'''
     op = n[0]
     if op == 'field':
+        if is_mixed_space(V):
+            # (u a Function of a Taylor-Hood space, mixed_derivatives: its
+            # fields are the views u.split() makes afresh at every call, known
+            # by their owner; the leaves are those of TrialFunctions(V))
+            own = getattr(n[1], 'mixed_owner', None)
+            if own is None or own[0] is not u:
+                return ZERO
+            return ('arg', k, n[3], V, n[2] if own[1] == 0 else 2)
         if n[1] is u and V.dim == 2:
             return ('arg', k, n[3], V, n[2])
         if n[1] is u and n[2] == 0:
@@ -1153,6 +1161,20 @@ class mixed_gmres(_Switch):
     switches it on at once, for the process; `.previous` is the setting it
     replaced, and as a context manager it restores that on exit.  It implies
     no other switch.'''
+    enabled = False
+
+
+class mixed_derivatives(_Switch):
+    '''The switch of derivative() with respect to a Function w of a
+    Taylor-Hood space and of solve(F == 0, w, bcs) there (mixed Newton:
+    fem/mixed.py, MixedNewtonAssembler, newton_solve).  Off by default: both
+    stay the NotImplementedError they were.  `mixed_derivatives(True)`
+    switches them on at once, for the process; `.previous` is the setting it
+    replaced, and as a context manager it restores that on exit.  It implies
+    no other switch: the forms need mixed_arguments(True) and
+    vector_arguments(True), the linear solves of Newton's method
+    mixed_gmres(True), ds parts facet_arguments(True), dx(k) parts
+    cell_subdomains(True).'''
     enabled = False
 
 
@@ -2057,7 +2079,9 @@ def derivative(F, u, du=None):
     vector_derivatives(True): or one of a vector space), part by part: a form of
     rank + 1 whose new argument has the number of arguments F already has (0:
     the test, 1: the trial function of u's space).  du: that argument, given
-    explicitly.  See the module docstring for the rules and the refusals.'''
+    explicitly.  See the module docstring for the rules and the refusals.
+    With mixed_derivatives(True) u may be a Function of a Taylor-Hood space:
+    _mixed_derivative.'''
     if not isinstance(F, Form):
         raise TypeError('derivative takes a form (got %r)' % (type(F),))
     if _sum_rank(F) >= 2:
@@ -2067,6 +2091,8 @@ def derivative(F, u, du=None):
         raise TypeError('derivative with respect to a Function (got %r)'
                         % (type(u),))
     V = u.function_space()
+    if is_mixed_space(V) and mixed_derivatives.enabled:
+        return _mixed_derivative(F, u, du)
     plain = hasattr(V, 'layout') and hasattr(V, 'dim') \
         and V.component is None
     vector = plain and V.dim == 2 and vector_derivatives.enabled
@@ -2103,6 +2129,53 @@ def derivative(F, u, du=None):
             raise ValueError(
                 'derivative: du must be the %s(V) of the space of u'
                 % ('TestFunction', 'TrialFunction')[k])
+    return _derived_parts(F, u, k, V)
+
+
+def _mixed_derivative(F, w, du):
+    '''derivative(F, w, du) for w a Function of a Taylor-Hood space WP
+    (mixed_derivatives(True)): the fields of F that are views of w (w.split(),
+    w.sub(i), split(w)) become the leaves of TrialFunctions(WP) -- or of
+    TestFunctions(WP) for a rank-0 F --, so the result is a mixed form like a
+    hand-written one.  A deep copy, or a view of another Function, is a
+    coefficient and differentiates to zero.'''
+    WP = w.function_space()
+    if not getattr(w, '_mixed', False):
+        raise ValueError('derivative: w was made before mixed_arguments(True) '
+                         'and is no Function of the Taylor-Hood space')
+    found = F.arguments()
+    k = len(found)
+    if sorted(found) != list(range(k)):
+        raise ValueError('derivative: the form holds a trial function without '
+                         'a test function')
+    for W in found.values():
+        if not (is_mixed_space(W) and W.same_as(WP)):
+            raise ValueError(
+                'derivative: w and the arguments of the form live on '
+                'different spaces or meshes')
+    if du is not None:
+        name = ('TestFunctions', 'TrialFunctions')[k]
+        ok = isinstance(du, (tuple, list)) and len(du) == 2 \
+            and all(isinstance(e, FormExpr) for e in du)
+        if ok:
+            leaves = list(du[0].comps) if du[0].shape == (2,) else [None]
+            leaves.append(du[1].comps if du[1].shape == () else None)
+            ok = len(leaves) == 3 and all(
+                isinstance(c, tuple) and len(c) == 5
+                and c[:3] == ('arg', k, 0) and is_mixed_space(c[3])
+                and c[3].same_as(WP) and c[4] == i
+                for i, c in enumerate(leaves))
+        if not ok:
+            raise ValueError(
+                'derivative: du must be the pair %s(W) of the space of w'
+                % name)
+    return _derived_parts(F, w, k, WP)
+
+
+def _derived_parts(F, u, k, V):
+    '''The parts of derivative(F, u): s_gateaux of every part of F in the
+    direction of argument number k of V, with the degree, measure and
+    subdomain of the part it came from.'''
     parts = []
     for sign, part in F.terms():
         if part.integral_type == 'interior_facet':
@@ -2587,9 +2660,11 @@ def argument_programs(table, rank, facet=False):
 
 
 def depends_on(n, u):
-    '''Whether the scalar tree n reads the Function u.'''
+    '''Whether the scalar tree n reads the Function u -- itself, or through
+    a view u.split() / u.sub(i) of a Function of a Taylor-Hood space.'''
     if n[0] == 'field':
-        return n[1] is u
+        own = getattr(n[1], 'mixed_owner', None)
+        return n[1] is u or (own is not None and own[0] is u)
     return n[0] in NONLEAF and any(
         depends_on(c, u) for c in n[1:] if isinstance(c, tuple))
 

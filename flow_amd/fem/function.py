@@ -287,6 +287,11 @@ class Function(_FormOperand):
     # True for a Function of a Taylor-Hood space (made while
     # forms.mixed_arguments(True) was on; what it is does not change after)
     _mixed = False
+    # (w, i) on the views w.split() / w.sub(i) of a Function w of a
+    # Taylor-Hood space: i = 0 the velocity, 1 the pressure view; None on
+    # every other Function, deep copies included (forms.derivative and
+    # forms.depends_on recognise a field of w by it)
+    mixed_owner = None
 
     def __init__(self, V, data=None):
         if _mixed_enabled(V):
@@ -377,7 +382,11 @@ class Function(_FormOperand):
             parts = (self.data[:W.size()], self.data[W.size():])
             if deepcopy:
                 parts = tuple(_hip.clone(x) for x in parts)
-            return Function(W, parts[0]), Function(P, parts[1])
+            views = Function(W, parts[0]), Function(P, parts[1])
+            if not deepcopy:
+                for i, view in enumerate(views):
+                    view.mixed_owner = (self, i)
+            return views
         assert self._V.dim == 2
         n = self._V.N
         S = self._V.collapse()

@@ -34,6 +34,13 @@ signed approximate Schur diagonal on the pressure) over the product of all
 blocks in one launch (MixedMatrix.apply_fused: flow_mixed_apply, csrc/
 mixed_kernels.hip).  assemble_system and MixedMatrix.to_scipy() work for such
 a form either way.
+
+With forms.mixed_derivatives(True), solve(F == 0, w, bcs) on WP is Newton's
+method (newton_solve): MixedNewtonAssembler holds J = derivative(F, w) and F,
+assembles the blocks of J that do not read w once, and every step solves
+J delta = F by fgmres over apply_fused with the block-triangular preconditioner
+whose first half runs in one launch (BlockTriangularPreconditioner.
+apply_fused: flow_mixed_upper_rhs).
 '''
 import ctypes
 
@@ -320,11 +327,15 @@ def _rect_part(part, block, q, scheme, R, mesh):
     return out
 
 
-def assemble_form(form, rank, form_compiler_parameters=None):
+def assemble_form(form, rank, form_compiler_parameters=None, only=None):
     '''ops.assemble of a form (or signed sum) of arguments on a Taylor-Hood
     space: a MixedMatrix (rank 2) or a Vector of 2 Nv + Np (rank 1), part by
     part -- the programs of a part are compiled while the kernels of the part
-    before run -- and, within a block, added in the order written.'''
+    before run -- and, within a block, added in the order written.  only: the
+    names of the blocks to assemble (MixedMatrix.blocks() naming; the others
+    come out absent) -- a block's launches and sum do not depend on the
+    others, so it has the bits it has in the whole matrix
+    (MixedNewtonAssembler skips its frozen blocks so).'''
     from . import forms
     if not forms.vector_arguments.enabled:
         raise NotImplementedError(
@@ -337,6 +348,7 @@ def assemble_form(form, rank, form_compiler_parameters=None):
     Rpu = rect_layout(mesh, P.degree, W.degree)
     names = ['uu', 'pp'] + (['up0', 'up1', 'pu0', 'pu1'] if rank == 2 else [])
     sums = {k: ops._Sum() for k in names}
+    want = (lambda k: True) if only is None else (lambda k: k in only)
     for sign, part in form.terms():
         ops._check_part_mesh(part, mesh)
         _, table = part.argument_table()
@@ -346,25 +358,25 @@ def assemble_form(form, rank, form_compiler_parameters=None):
         corner = table.velocity()
         present = [b for row in corner for b in row] if rank == 2 \
             else list(corner)
-        if any(b is not None for b in present):
+        if want('uu') and any(b is not None for b in present):
             sums['uu'].add(sign, ops._block_part(part, corner, rank, q, scheme,
                                                  layv, mesh), True)
         pblock = table[2][2] if rank == 2 else table[2]
-        if pblock is not None:
+        if want('pp') and pblock is not None:
             ops._scalar_part(part, pblock, rank, q, scheme, layp, mesh,
                              sums['pp'], sign)
         if rank == 1:
             continue
         for c in range(2):
-            if table[c][2] is not None:
+            if want('up%d' % c) and table[c][2] is not None:
                 sums['up%d' % c].add(
                     sign, _rect_part(part, table[c][2], q, scheme, Rup, mesh),
                     True)
-            if table[2][c] is not None:
+            if want('pu%d' % c) and table[2][c] is not None:
                 sums['pu%d' % c].add(
                     sign, _rect_part(part, table[2][c], q, scheme, Rpu, mesh),
                     True)
-    if all(s.total is None for s in sums.values()):
+    if only is None and all(s.total is None for s in sums.values()):
         raise ValueError('an empty sum of forms has no rank')
     if rank == 1:
         out = device.zeros(WP.size())
@@ -884,6 +896,48 @@ class BlockTriangularPreconditioner(object):
                 _hip.stream()))
         return z
 
+    def apply_fused(self, v, z):
+        '''apply() with its first half -- the vmul, the copy and per coupling
+        plane a product and an axpby -- in one launch (flow_mixed_upper_rhs,
+        csrc/mixed_kernels.hip), then the unchanged ILU or Jacobi step: every
+        entry of z has the bits apply() leaves there.  v overlapping z is a
+        ValueError.'''
+        n2 = self.n2
+        upper_rhs(self.A, self.sinv, v, z[n2:], self.ru)
+        if self.velocity == 'jacobi':
+            ops.vmul(self.ru, self.dinv, z[:n2])
+        else:
+            _hip.check(_hip.lib().flow_ilu0_solve(
+                ctypes.byref(self.ilu.struct), _hip.f64(self.ru, n2),
+                _hip.f64(z[:n2], n2), _hip.f64(self.work, n2),
+                _hip.stream()))
+        return z
+
+    def refresh(self, sdiag=None):
+        '''The same object for new values in the planes of A (a Newton step:
+        the buffers of A are held): Ilu0.refactor or a new inverse diagonal,
+        and the signed Schur diagonal again unless sdiag gives one.'''
+        if sdiag is None:
+            sdiag = _signed_schur_diagonal(self.A, None)
+        self.sinv = torch.reciprocal(sdiag)
+        if self.velocity == 'ilu0':
+            self.ilu.refactor(self.A.uu)
+        else:
+            self.dinv = self.A.uu.diag_inv()
+        return self
+
+
+def upper_rhs(A, sinv, r, zp, ru):
+    '''z_p = r_p * sinv and ru = r_u - up z_p of the MixedMatrix A in one
+    launch (flow_mixed_upper_rhs): r of 2 Nv + Np, sinv and zp of Np, ru of
+    2 Nv doubles.  An output overlapping an input is a ValueError.'''
+    n2, npr = A.W.size(), A.P.N
+    _hip.check(_hip.lib().flow_mixed_upper_rhs(
+        ctypes.byref(A.fused()), _hip.f64(sinv, npr, 'sinv'),
+        _hip.f64(r, n2 + npr, 'r'), _hip.f64(zp, npr, 'z_p'),
+        _hip.f64(ru, n2, 'ru'), _hip.stream()))
+    return zp, ru
+
 
 def _signed_schur_diagonal(A, pmask):
     '''diag(pp) - sum_s diag(pu[s] diag(uu_ss)^-1 up[s]) of the eliminated A,
@@ -1021,3 +1075,287 @@ def solve(a, L, w, bcs=None, solver_parameters=None,
                       ks.get('absolute_tolerance', 0.0),
                       int(ks.get('maximum_iterations', 1000)))
     return ops.SolveInfo(its, res, 'minres')
+
+
+# -- Newton's method on WP: solve(F == 0, w, bcs) -----------------------------------
+BLOCK_NAMES = ('uu', 'pp', 'up0', 'up1', 'pu0', 'pu1')
+
+# The rule of adoption (README): the Newton path runs
+# BlockTriangularPreconditioner.apply_fused where its measured median is not
+# above apply's (tools/mixed_newton_lab.py), else apply.
+NEWTON_FUSED_PRECONDITIONER = True
+
+
+def _table_blocks(table):
+    '''{block name: [scalar tables]} of a rank-2 MixedTable: the four tables
+    of the velocity corner under 'uu'.'''
+    out = {k: [] for k in BLOCK_NAMES}
+    for r in range(2):
+        for s in range(2):
+            if table[r][s] is not None:
+                out['uu'].append(table[r][s])
+        if table[r][2] is not None:
+            out['up%d' % r].append(table[r][2])
+        if table[2][r] is not None:
+            out['pu%d' % r].append(table[2][r])
+    if table[2][2] is not None:
+        out['pp'].append(table[2][2])
+    return out
+
+
+def _reads(tree, WP, w):
+    '''forms.depends_on(tree, w); w None: whether the tree reads a view of
+    any Function of the space WP.'''
+    from . import forms
+    if w is not None:
+        return forms.depends_on(tree, w)
+    if tree[0] == 'field':
+        own = getattr(tree[1], 'mixed_owner', None)
+        return own is not None and own[0].function_space().same_as(WP)
+    return tree[0] in forms.NONLEAF and any(
+        _reads(c, WP, None) for c in tree[1:] if isinstance(c, tuple))
+
+
+def block_dependence(J, WP, w=None):
+    '''{block name: whether a part of the rank-2 mixed form J has a term of
+    that block that reads w} over the blocks J has a term for.'''
+    from . import forms
+    out = {}
+    for _, part in J.terms():
+        _, table = part.argument_table()
+        if not isinstance(table, forms.MixedTable):
+            raise NotImplementedError(forms._MIXED_MISMATCH)
+        for name, tabs in _table_blocks(table).items():
+            for tab in tabs:
+                reads = any(c is not None and _reads(c, WP, w)
+                            for row in tab for c in row)
+                out[name] = out.get(name, False) or reads
+    return out
+
+
+class MixedNewtonAssembler(object):
+    '''(J, F) of Newton's method on the Taylor-Hood space WP at the current
+    values of the fields: a MixedMatrix and a vector of 2 Nv + Np whose
+    buffers live as long as the object.  Every block of J has the bits of
+    assemble(J) and every component of F those of assemble(F): the launches
+    are assemble_form's -- the velocity corner through ops._block_part, pp
+    through ops._scalar_part, the coupling planes through _rect_part --, their
+    results copied into the held planes.
+    `frozen`: the blocks of J (MixedMatrix.blocks() naming) none of whose
+    parts reads w (forms.depends_on; w None: a view of any Function of WP) --
+    for Navier-Stokes up0, up1, pu0, pu1 and any pp.  A frozen block is
+    assembled by the first assemble() and not again; system() applies the
+    boundary conditions to it once.  `route` is 'by_parts': every part is
+    assembled on its own; there is no fused element kernel here.'''
+    route = 'by_parts'
+    fused = False
+
+    def __init__(self, J, F, WP, form_compiler_parameters=None, w=None):
+        from . import forms
+        if not forms.vector_arguments.enabled:
+            raise NotImplementedError(
+                'forms on a mixed space need vector_arguments(True) as well')
+        self.space = WP
+        self.J, self.F = J, F
+        self.params = form_compiler_parameters
+        for form in (J, F):
+            for _, part in form.terms():
+                ops._check_part_mesh(part, WP.mesh())
+        reads = block_dependence(J, WP, w)
+        self.frozen = tuple(k for k in BLOCK_NAMES
+                            if k in reads and not reads[k])
+        self._live = tuple(k for k in BLOCK_NAMES if reads.get(k))
+        self.A = None
+        self.b = device.empty(WP.size())
+        self._system = None
+
+    @staticmethod
+    def _block(A, name):
+        return {'uu': A.uu, 'pp': A.pp}[name] if len(name) == 2 else \
+            (A.up if name[:2] == 'up' else A.pu)[int(name[2])]
+
+    def assemble(self):
+        '''(MixedMatrix, device vector): the held J and F, without boundary
+        conditions.'''
+        if self.A is None:
+            # (the first call: all blocks; the result's planes are the held
+            # ones from here on)
+            self.A = assemble_form(self.J, 2, self.params)
+        elif self._live:
+            fresh = assemble_form(self.J, 2, self.params, only=self._live)
+            for name in self._live:
+                _hip.copy(self._block(self.A, name).vals,
+                          self._block(fresh, name).vals)
+        _hip.copy(self.b, assemble_form(self.F, 1, self.params).data)
+        return self.A, self.b
+
+    def system(self, um, pm):
+        '''The held J with the conditions of the device masks um (2 Nv bytes)
+        and pm (Np bytes) applied homogeneously, as assemble_system applies
+        them: symmetric_bc_blocks on uu, symmetric_bc_matrix on pp (absent
+        and a pressure condition: unit diagonal on its rows),
+        flow_bc_rect_mask on the coupling planes.  Into held planes of its
+        own; a frozen block only the first time.  After assemble().'''
+        A = self.A
+        W, P = A.W, A.P
+        nv = W.N
+        first = self._system is None
+        if first:
+            uu = None if A.uu is None else ops.Matrix(W.layout, 2)
+            pp = None
+            if A.pp is not None or bool(pm.any()):
+                pp = ops.Matrix(P.layout, 0)
+            self._system = MixedMatrix(
+                self.space, uu, pp,
+                [None if B is None else RectMatrix(B.layout) for B in A.up],
+                [None if B is None else RectMatrix(B.layout) for B in A.pu])
+            self._pp_zero = None if A.pp is not None or pp is None \
+                else ops.Matrix(P.layout, 0)
+        S = self._system
+        todo = lambda k: first or k in self._live   # noqa: E731
+        if A.uu is not None and todo('uu'):
+            ops.symmetric_bc_blocks(A.uu, um, S.uu)
+        if A.pp is not None and todo('pp'):
+            ops.symmetric_bc_matrix(A.pp, pm, S.pp)
+        elif first and S.pp is not None and A.pp is None:
+            ops.symmetric_bc_matrix(self._pp_zero, pm, S.pp)
+        ums = [um[r * nv:(r + 1) * nv] for r in range(2)]
+        for c in range(2):
+            if A.up[c] is not None and todo('up%d' % c):
+                _hip.copy(S.up[c].vals, A.up[c].vals)
+                _rect_mask(S.up[c], ums[c], pm)
+            if A.pu[c] is not None and todo('pu%d' % c):
+                _hip.copy(S.pu[c].vals, A.pu[c].vals)
+                _rect_mask(S.pu[c], pm, ums[c])
+        return S
+
+
+def newton_solve(F, w, bcs=None, J=None, solver_parameters=None,
+                 form_compiler_parameters=None):
+    '''solve(F == 0, w, bcs, J) with w a Function of the Taylor-Hood space WP
+    (forms.mixed_derivatives(True)): ops.newton_solve's loop -- its order,
+    stopping rule, 'newton_solver' keys and defaults (ops.newton_parameters),
+    'report' and 'error_on_nonconvergence' -- over MixedNewtonAssembler.
+    w[dof] = g first (mixed_bcs); per iteration (J, F) at w, the conditions
+    applied homogeneously (MixedNewtonAssembler.system, F[dof] = 0), r =
+    |F|_2, stop where r < absolute_tolerance or r / r0 < relative_tolerance,
+    else J delta = F from a zero start by fgmres over apply_fused with
+    BlockTriangularPreconditioner -- the ILU(0) factors refactored and the
+    signed Schur diagonal recomputed every step (unless 'preconditioner_form'
+    gives one) -- and w -= relaxation_parameter * delta.
+    'newton_solver' also takes 'preconditioner' ('ilu0' | 'jacobi';
+    'two_level' is the ValueError of the linear solve) and
+    'preconditioner_form', and its 'krylov_solver' 'restart', with the
+    meanings of solve(a == L) under mixed_gmres.  Needs mixed_gmres(True).  A
+    singular pressure is the user's to pin.  Returns an ops.NewtonInfo with
+    `frozen` (MixedNewtonAssembler.frozen), route 'by_parts' and method
+    'fgmres+ilu0' | 'fgmres+jacobi'.  Not on strips.'''
+    from . import forms
+    from ..message import info as say
+    prm = dict(solver_parameters or {})
+    given = dict(prm.get('newton_solver') or {})
+    velocity = given.pop('preconditioner', 'ilu0')
+    prec_form = given.pop('preconditioner_form', None)
+    if 'newton_solver' in prm:
+        prm['newton_solver'] = given
+    ns, _ = ops.newton_parameters(prm)
+    if velocity not in ('ilu0', 'jacobi'):
+        raise ValueError("preconditioner %r under GMRES: 'ilu0' or 'jacobi'"
+                         % (velocity,))
+    if not isinstance(F, forms.Form) or F.rank != 1:
+        raise ValueError('solve(F == 0, w): F must be a form of rank 1, '
+                         'linear in the test functions')
+    WP = w.function_space()
+    V = F.arguments()[0]
+    if not forms.is_mixed_space(V) or not V.same_as(WP) \
+            or not getattr(w, '_mixed', False):
+        raise ValueError('solve writes into a Function of the space of the '
+                         'test functions')
+    for _, part in F.terms():
+        if part.integral_type == 'interior_facet':
+            raise NotImplementedError(
+                'solve(F == 0) on a mixed space: dS parts are not supported '
+                '(test functions under dS)')
+    if not any(forms.depends_on(p.integrand.comps, w) for _, p in F.terms()):
+        raise ValueError('solve(F == 0, w): the form does not depend on w')
+    if J is None:
+        J = forms.derivative(F, w)
+    elif not isinstance(J, forms.Form) or J.rank != 2 \
+            or not all(forms.is_mixed_space(S) and S.same_as(WP)
+                       for S in J.arguments().values()):
+        raise ValueError('J must be a bilinear form (rank 2) on the space of '
+                         'w')
+    if not forms.mixed_gmres.enabled:
+        raise NotImplementedError(
+            'solve(F == 0) on a mixed space: the Jacobian is not symmetric and '
+            'its linear solves are flexible GMRES with a block preconditioner, '
+            'which fem.mixed_gmres(True) switches on')
+    asm = MixedNewtonAssembler(J, F, WP, form_compiler_parameters, w)
+    ks = ns['krylov_solver']
+    held = mixed_bcs(bcs, WP)
+    W, P = WP.taylor_hood()
+    if held is None:
+        dofs = None
+        um = device.to_device(numpy.zeros(W.size(), dtype=numpy.uint8))
+        pm = device.to_device(numpy.zeros(P.size(), dtype=numpy.uint8))
+        pmask = None
+    else:
+        dofs, vals = device.to_device(held[0]), device.to_device(held[1])
+        um, pm = device.to_device(held[2]), device.to_device(held[3])
+        pmask = held[3]
+        ops._set_values(dofs, vals, w.data)
+        zero = device.zeros(dofs.numel())
+    sform = None
+    if prec_form is not None:
+        sform = _form_diagonal(prec_form, bcs, form_compiler_parameters,
+                               signed=True)
+    delta = device.empty(WP.size())
+    M = None
+    out = ops.NewtonInfo(False, 'fgmres+' + velocity, asm.route)
+    out.frozen = asm.frozen
+    rtol, atol = ns['relative_tolerance'], ns['absolute_tolerance']
+    maxit = int(ns['maximum_iterations'])
+    r0 = None
+    while True:
+        asm.assemble()
+        A = asm.system(um, pm)
+        b = asm.b
+        if dofs is not None:
+            ops._set_values(dofs, zero, b)
+        r = ops.vector_norm(b)
+        r0 = r if r0 is None else r0
+        out.residuals.append(r)
+        rel = r / r0 if r0 > 0.0 else 0.0
+        if ns['report']:
+            say('Newton iteration %d: r (abs) = %.3e (tol = %.3e) r (rel) = '
+                '%.3e (tol = %.3e)' % (out.iterations, r, atol, rel, rtol))
+        if r < atol or rel < rtol:
+            out.converged = True
+            break
+        if out.iterations >= maxit:
+            break
+        if A.uu is None:
+            raise ValueError('the form has no velocity-velocity block')
+        sdiag = sform if sform is not None \
+            else _signed_schur_diagonal(A, pmask)
+        if M is None:
+            M = BlockTriangularPreconditioner(A, velocity, sdiag)
+        else:
+            M.refresh(sdiag)
+        _hip.fill(delta, 0.0)
+        its, _ = fgmres(
+            A.apply_fused,
+            M.apply_fused if NEWTON_FUSED_PRECONDITIONER else M.apply,
+            b, delta, ks.get('relative_tolerance', 1.0e-12),
+            ks.get('absolute_tolerance', 0.0),
+            int(ks.get('maximum_iterations', 1000)),
+            int(ks.get('restart', 30)))
+        out.linear_iterations.append(its)
+        ops.axpby(-float(ns['relaxation_parameter']), delta, 1.0, w.data)
+        out.iterations += 1
+    if not out.converged and ns['error_on_nonconvergence']:
+        raise _hip.NotConverged(
+            'Newton solver did not converge: %d iterations, |F| = %.3e '
+            '(absolute tolerance %.3e), |F| / |F0| = %.3e (relative '
+            'tolerance %.3e)' % (out.iterations, r, atol, rel, rtol))
+    return out

@@ -1308,6 +1308,12 @@ def solve(equation, u, bcs=None, J=None, solver_parameters=None,
     if isinstance(equation.rhs, numbers.Real):
         if isinstance(u, Function) and forms.is_mixed_space(
                 u.function_space()):
+            if forms.mixed_derivatives.enabled:
+                # (Newton on a Taylor-Hood space: fem/mixed.py)
+                from . import mixed
+                return mixed.newton_solve(equation.lhs, u, bcs, J,
+                                          solver_parameters,
+                                          form_compiler_parameters)
             raise NotImplementedError(
                 'solve(F == 0) on a mixed space: Newton\'s method takes '
                 'scalar and vector spaces only')
@@ -1401,7 +1407,11 @@ class NewtonInfo(object):
     residual needed a 'vector' job and no block of a fused row was split into
     several programs -- block_jobs_fused), `method` (of the linear solves),
     `route` (NewtonAssembler.route: 'by_parts' where a ds or dx(k) part is
-    gathered on its own, else 'fused' | 'pair').'''
+    gathered on its own, else 'fused' | 'pair'), `frozen` (on a Taylor-Hood
+    space, mixed.newton_solve: the blocks of the Jacobian, in
+    MixedMatrix.blocks() naming, that do not read the unknown and were
+    assembled once; () elsewhere).'''
+    frozen = ()
 
     def __init__(self, fused, method, route=None):
         self.iterations = 0

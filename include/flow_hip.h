@@ -2024,6 +2024,23 @@ typedef struct {
 int flow_mixed_apply(const flow_mixed* A, const double* x, double* y,
                      void* stream);
 
+/* The first half of the block upper triangular preconditioner [[F, up], [0,
+ * diag(s)]] in ONE launch over the tiles of flow_mixed_apply: r holds 2 nv + np
+ * doubles, sinv (np) the inverse of the pressure diagonal;
+ *   z_p[i]        = r_p[i] * sinv[i]                            (np doubles)
+ *   ru[c nv + i]  = r[c nv + i] - sum_k up[c][k] (r_p[col_k] * sinv[col_k])
+ * for both components (2 nv doubles).  Only the up planes and their pattern
+ * are read; an absent plane leaves its component of ru equal to r's.  A
+ * velocity tile forms the gathered operand itself, one rounded multiply, and
+ * reads no entry of z_p.  Every entry has the bits of the composed sequence
+ * flow_vmul(1, r_p, sinv, z_p), a copy of r_u, and per plane
+ * flow_operator_apply(up[c], z_p, t) and flow_axpby(-1, t, 1, ru_c).  No
+ * atomics: two calls give the same bits.  ru or z_p overlapping r, sinv or
+ * each other is refused (code 2); a refusal launches nothing. */
+int flow_mixed_upper_rhs(const flow_mixed* A, const double* sinv,
+                         const double* r, double* z_p, double* ru,
+                         void* stream);
+
 /* ---- running time statistics of a field (flow_amd/fem/statistics.py):
  * fem.Statistics ---------------------------------------------------------------
  * A store of planes of ld doubles each (ld >= n and even, the store 16-byte
