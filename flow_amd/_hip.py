@@ -564,6 +564,7 @@ SYMBOLS = {
     'flow_multi_dot': [_I, _I, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP],
     'flow_combine': [_I, _I, _VP, ctypes.c_size_t, _I, _VP, _VP, _VP,
                      ctypes.c_size_t, _VP],
+    'flow_deflate': [_I, _I, _VP, ctypes.c_size_t, _VP, _VP, _VP, _VP],
     'flow_operator_apply_block': [_P(Operator), _I, _VP, ctypes.c_size_t, _VP,
                                   ctypes.c_size_t, _VP],
     'flow_operator_apply_block_chunk': [_P(Operator), _I, _VP, ctypes.c_size_t,

@@ -48,6 +48,9 @@ from .recovery import (                                         # noqa: F401
     )
 from .snapshots import Snapshots                                # noqa: F401
 from .eigen import Eigenmodes, eigensolve, vector_eigenmodes    # noqa: F401
+from .nullspace import (                                        # noqa: F401
+    VectorSpaceBasis, constant_nullspace, rigid_body_modes,
+    )
 from .statistics import Statistics                              # noqa: F401
 from .distance import Distance, wall_distance                   # noqa: F401
 from .isolines import Isolines, isolines                        # noqa: F401

@@ -983,7 +983,29 @@ def solver_route(symmetric, prm):
     return 'minres' if symmetric else 'refuse'
 
 
-def _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters):
+def _validate_nullspace(ns, WP, bcs):
+    '''nullspace.validate with the Dirichlet dofs of mixed_bcs: the checks of
+    nullspace= that need no device.'''
+    from . import nullspace
+    held = mixed_bcs(bcs, WP)
+    nullspace.validate(ns, WP, None if held is None else held[0])
+
+
+def _deflated(ns, A, b, x, precondition, prm):
+    '''What a linear solve with nullspace=ns runs before its loop: the |A z|
+    check, b projected (its Z^T b and b . b left on the device: the slots of
+    VectorSpaceBasis.project_rhs), the start vector x projected (None: a zero
+    start), and the preconditioner wrapped so that every preconditioned
+    vector is projected.  Returns (wrapped preconditioner, slots).'''
+    from . import nullspace
+    nullspace.check_null(ns, A, prm.get('nullspace_check'))
+    slots = ns.project_rhs(b)
+    if x is not None:
+        ns.deflate(x)
+    return nullspace.deflated_preconditioner(ns, precondition), slots
+
+
+def _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters, nullspace=None):
     '''solve() for mixed_gmres(True): assemble_system (no symmetrisation of a
     non-symmetric form), BlockTriangularPreconditioner, fgmres.'''
     velocity = prm.get('preconditioner', 'ilu0')
@@ -992,6 +1014,8 @@ def _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters):
                          % (velocity,))
     ks = dict(prm.get('krylov_solver') or {})
     masks = {}
+    if nullspace is not None:
+        _validate_nullspace(nullspace, a.arguments()[0], bcs)
     A, b = assemble_system(a, L, bcs, form_compiler_parameters, masks)
     if A.uu is None:
         raise ValueError('the form has no velocity-velocity block')
@@ -1001,17 +1025,25 @@ def _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters):
     else:
         sdiag = _signed_schur_diagonal(A, masks['p'])
     M = BlockTriangularPreconditioner(A, velocity, sdiag)
+    precondition, slots = M.apply, None
+    if nullspace is not None:
+        # (the true residual of fgmres is then taken against the projected b)
+        precondition, slots = _deflated(nullspace, A, b.data, w.data, M.apply,
+                                        prm)
     # (the one-launch product: bit-equal to A.apply and faster, README)
-    its, res = fgmres(A.apply_fused, M.apply, b.data, w.data,
+    its, res = fgmres(A.apply_fused, precondition, b.data, w.data,
                       ks.get('relative_tolerance', 1.0e-12),
                       ks.get('absolute_tolerance', 0.0),
                       int(ks.get('maximum_iterations', 1000)),
                       int(ks.get('restart', 30)))
-    return ops.SolveInfo(its, res, 'fgmres+' + velocity)
+    info = ops.SolveInfo(its, res, 'fgmres+' + velocity)
+    if slots is not None:
+        info.rhs_defect = nullspace.defect(slots)
+    return info
 
 
 def solve(a, L, w, bcs=None, solver_parameters=None,
-          form_compiler_parameters=None):
+          form_compiler_parameters=None, nullspace=None):
     '''solve(a == L, w, bcs) with w = Function(WP): assemble_system, then
     preconditioned MINRES from w's values into w.  MINRES takes a symmetric
     form -- structurally (forms.is_symmetric_form: over all its parts) or by
@@ -1039,7 +1071,13 @@ def solve(a, L, w, bcs=None, solver_parameters=None,
     diag(B diag(uu)^-1 B^T)); 'krylov_solver': 'relative_tolerance' (1e-12,
     on the preconditioned residual), 'absolute_tolerance' (0),
     'maximum_iterations' (1000).  A singular pressure (all-Dirichlet velocity,
-    nothing pinned) is the user's to pin.  Returns an ops.SolveInfo; raises
+    nothing pinned) takes nullspace=fem.constant_nullspace(WP) (fem/
+    nullspace.py; the checks and rhs_defect: ops.solve's docstring): b and
+    the start vector are projected once, and every preconditioned vector of
+    the loop -- z_new of minres, the output of precondition in fgmres -- by a
+    wrapped preconditioner; minres and fgmres themselves are unchanged, and
+    fgmres tests the true residual against the projected b.  The left and the
+    right nullspace must coincide.  Returns an ops.SolveInfo; raises
     _hip.NotConverged.'''
     from . import forms
     WP = a.arguments()[0]
@@ -1057,9 +1095,12 @@ def solve(a, L, w, bcs=None, solver_parameters=None,
             'takes it once fem.mixed_gmres(True) is on; assemble_system(a, '
             'L, bcs) and to_scipy() work for it either way')
     if route == 'fgmres':
-        return _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters)
+        return _solve_fgmres(a, L, w, bcs, prm, form_compiler_parameters,
+                             nullspace)
     ks = dict(prm.get('krylov_solver') or {})
     masks = {}
+    if nullspace is not None:
+        _validate_nullspace(nullspace, WP, bcs)
     A, b = assemble_system(a, L, bcs, form_compiler_parameters, masks)
     if prm.get('preconditioner_form') is not None:
         pdiag = _form_diagonal(prm['preconditioner_form'], bcs,
@@ -1070,11 +1111,18 @@ def solve(a, L, w, bcs=None, solver_parameters=None,
         pdiag = _schur_diagonal(A, masks['p'])
     M = BlockPreconditioner(A, prm.get('preconditioner', 'jacobi'), pdiag,
                             masks['u'])
-    its, res = minres(A.apply, M.apply, b.data, w.data,
+    precondition, slots = M.apply, None
+    if nullspace is not None:
+        precondition, slots = _deflated(nullspace, A, b.data, w.data, M.apply,
+                                        prm)
+    its, res = minres(A.apply, precondition, b.data, w.data,
                       ks.get('relative_tolerance', 1.0e-12),
                       ks.get('absolute_tolerance', 0.0),
                       int(ks.get('maximum_iterations', 1000)))
-    return ops.SolveInfo(its, res, 'minres')
+    info = ops.SolveInfo(its, res, 'minres')
+    if slots is not None:
+        info.rhs_defect = nullspace.defect(slots)
+    return info
 
 
 # -- Newton's method on WP: solve(F == 0, w, bcs) -----------------------------------
@@ -1231,7 +1279,7 @@ class MixedNewtonAssembler(object):
 
 
 def newton_solve(F, w, bcs=None, J=None, solver_parameters=None,
-                 form_compiler_parameters=None):
+                 form_compiler_parameters=None, nullspace=None):
     '''solve(F == 0, w, bcs, J) with w a Function of the Taylor-Hood space WP
     (forms.mixed_derivatives(True)): ops.newton_solve's loop -- its order,
     stopping rule, 'newton_solver' keys and defaults (ops.newton_parameters),
@@ -1247,12 +1295,20 @@ def newton_solve(F, w, bcs=None, J=None, solver_parameters=None,
     'two_level' is the ValueError of the linear solve) and
     'preconditioner_form', and its 'krylov_solver' 'restart', with the
     meanings of solve(a == L) under mixed_gmres.  Needs mixed_gmres(True).  A
-    singular pressure is the user's to pin.  Returns an ops.NewtonInfo with
+    singular pressure takes nullspace=fem.constant_nullspace(WP): every
+    step's J delta = F goes through the deflated solve of solve(a == L)
+    (solver_parameters['nullspace_check'] as there), so delta has no
+    component along the basis and w keeps the pressure mean it started with;
+    the info's rhs_defect is the largest |Z^T F| / |F| over the steps.
+    Returns an ops.NewtonInfo with
     `frozen` (MixedNewtonAssembler.frozen), route 'by_parts' and method
     'fgmres+ilu0' | 'fgmres+jacobi'.  Not on strips.'''
     from . import forms
     from ..message import info as say
     prm = dict(solver_parameters or {})
+    ns_prm = {}
+    if nullspace is not None and 'nullspace_check' in prm:
+        ns_prm['nullspace_check'] = prm.pop('nullspace_check')
     given = dict(prm.get('newton_solver') or {})
     velocity = given.pop('preconditioner', 'ilu0')
     prec_form = given.pop('preconditioner_form', None)
@@ -1290,6 +1346,8 @@ def newton_solve(F, w, bcs=None, J=None, solver_parameters=None,
             'solve(F == 0) on a mixed space: the Jacobian is not symmetric and '
             'its linear solves are flexible GMRES with a block preconditioner, '
             'which fem.mixed_gmres(True) switches on')
+    if nullspace is not None:
+        _validate_nullspace(nullspace, WP, bcs)
     asm = MixedNewtonAssembler(J, F, WP, form_compiler_parameters, w)
     ks = ns['krylov_solver']
     held = mixed_bcs(bcs, WP)
@@ -1343,13 +1401,23 @@ def newton_solve(F, w, bcs=None, J=None, solver_parameters=None,
         else:
             M.refresh(sdiag)
         _hip.fill(delta, 0.0)
+        precondition = M.apply_fused if NEWTON_FUSED_PRECONDITIONER \
+            else M.apply
+        slots = None
+        if nullspace is not None:
+            precondition, slots = _deflated(nullspace, A, b, None,
+                                            precondition, ns_prm)
+            # (the |A z| check: on the first Jacobian only)
+            ns_prm = {'nullspace_check': False}
         its, _ = fgmres(
-            A.apply_fused,
-            M.apply_fused if NEWTON_FUSED_PRECONDITIONER else M.apply,
+            A.apply_fused, precondition,
             b, delta, ks.get('relative_tolerance', 1.0e-12),
             ks.get('absolute_tolerance', 0.0),
             int(ks.get('maximum_iterations', 1000)),
             int(ks.get('restart', 30)))
+        if slots is not None:
+            out.rhs_defect = max(out.rhs_defect or 0.0,
+                                 nullspace.defect(slots))
         out.linear_iterations.append(its)
         ops.axpby(-float(ns['relaxation_parameter']), delta, 1.0, w.data)
         out.iterations += 1

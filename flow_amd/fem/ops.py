@@ -575,6 +575,10 @@ class StartChooser(object):
 
 
 class SolveInfo(object):
+    # |Z^T b| / |b| before the projection, of a solve with nullspace= (else
+    # None)
+    rhs_defect = None
+
     def __init__(self, iterations, residual, method):
         self.iterations = iterations
         self.residual = residual
@@ -1280,8 +1284,25 @@ def apply_identity_rows(bc, A=None, b=None):
 _KRYLOV_METHODS = ('cg', 'gmres', 'bicgstab')
 
 
+def _solve_cg_nullspace(A, b, u, ns, prm, ks):
+    '''The CG route of solve(a == L, ..., nullspace=ns) on a scalar or vector
+    space, after nullspace.validate: b projected, the native CG untouched, u
+    projected; the returned SolveInfo carries rhs_defect.'''
+    from . import nullspace
+    nullspace.check_null(ns, A, prm.get('nullspace_check'))
+    slots = ns.project_rhs(b.data)
+    ns.deflate(u.data)
+    info = krylov_solve(
+        'cg', A, b.data, u.data, ks.get('relative_tolerance', 1.0e-12),
+        atol=ks.get('absolute_tolerance', 0.0),
+        maxit=int(ks.get('maximum_iterations', 1000)), check_every=10)
+    ns.deflate(u.data)
+    info.rhs_defect = ns.defect(slots)
+    return info
+
+
 def solve(equation, u, bcs=None, J=None, solver_parameters=None,
-          form_compiler_parameters=None):
+          form_compiler_parameters=None, nullspace=None):
     '''solve(F == 0, u, bcs, J=None): Newton's method, newton_solve below
     (J: the Jacobian, derivative(F, u) by default; for a linear equation it
     must stay None).
@@ -1298,8 +1319,22 @@ def solve(equation, u, bcs=None, J=None, solver_parameters=None,
     without a warning (it may not converge: NotConverged).  'krylov_solver':
     'relative_tolerance' (1e-12), 'absolute_tolerance' (0),
     'maximum_iterations' (1000).  There is no direct solver.  A pure Neumann
-    problem is singular: pin a value.  Raises _hip.NotConverged (a
-    RuntimeError).  Not on strips.'''
+    problem is singular: pass its nullspace.  Raises _hip.NotConverged (a
+    RuntimeError).  Not on strips.
+    nullspace: a fem.VectorSpaceBasis (fem/nullspace.py: constant_nullspace,
+    rigid_body_modes) of the singular operator, orthonormal; None: nothing
+    changes.  The left and the right nullspace must coincide (one basis
+    serves both; not checked).  Scalar and vector spaces: the CG route only
+    (a symmetric form, Jacobi) -- b is projected, the native CG runs
+    untouched, u is projected; the ILU(0) routes and Newton's method on these
+    spaces are a NotImplementedError.  Taylor-Hood spaces: MINRES, FGMRES and
+    Newton's method (fem/mixed.py).  Before the solve: the basis must be
+    orthonormal, live on the space of the unknown, vanish on the Dirichlet
+    dofs, and satisfy |A z|_inf <= sqrt(eps) |A|_inf |z|_inf (the threshold:
+    solver_parameters['nullspace_check']; False skips it) -- each a
+    ValueError.  The returned info carries rhs_defect = |Z^T b| / |b| from
+    before the projection: an inconsistent right-hand side (the integral of f
+    not 0) shows there.'''
     from . import forms
     _no_strips('solve')
     if not isinstance(equation, forms.Equation):
@@ -1313,10 +1348,14 @@ def solve(equation, u, bcs=None, J=None, solver_parameters=None,
                 from . import mixed
                 return mixed.newton_solve(equation.lhs, u, bcs, J,
                                           solver_parameters,
-                                          form_compiler_parameters)
+                                          form_compiler_parameters, nullspace)
             raise NotImplementedError(
                 'solve(F == 0) on a mixed space: Newton\'s method takes '
                 'scalar and vector spaces only')
+        if nullspace is not None:
+            raise NotImplementedError(
+                'nullspace= with Newton\'s method on a scalar or vector '
+                'space (Taylor-Hood spaces take it)')
         return newton_solve(equation.lhs, u, bcs, J, solver_parameters,
                             form_compiler_parameters)
     if J is not None:
@@ -1333,7 +1372,7 @@ def solve(equation, u, bcs=None, J=None, solver_parameters=None,
         # (symmetric forms only: preconditioned MINRES, fem/mixed.py)
         from . import mixed
         return mixed.solve(a, L, u, bcs, solver_parameters,
-                           form_compiler_parameters)
+                           form_compiler_parameters, nullspace)
     if not isinstance(u, Function) or not u.function_space().same_as(V):
         raise ValueError('solve writes into a Function of the space of the '
                          'trial function')
@@ -1343,7 +1382,20 @@ def solve(equation, u, bcs=None, J=None, solver_parameters=None,
     if method in ('default', 'iterative'):
         method = 'cg' if symmetric else 'gmres'
     ks = dict(prm.get('krylov_solver') or {})
+    if nullspace is not None and method != 'cg':
+        raise NotImplementedError(
+            'nullspace= on a scalar or vector space takes the CG route (a '
+            "symmetric form with Jacobi); %r%s is not built for a singular "
+            'matrix' % (method, '' if symmetric else ' with ILU(0)'))
+    if nullspace is not None:
+        from . import nullspace as nsp
+        from .bcs import collect
+        held = [] if bcs is None else (
+            list(bcs) if isinstance(bcs, (list, tuple)) else [bcs])
+        nsp.validate(nullspace, V, collect(held, V.size())[0])
     A, b = assemble_system(a, L, bcs, form_compiler_parameters)
+    if nullspace is not None:
+        return _solve_cg_nullspace(A, b, u, nullspace, prm, ks)
     ilu = None
     if method != 'cg' and not symmetric:
         from .ilu import Ilu0
@@ -1410,8 +1462,11 @@ class NewtonInfo(object):
     gathered on its own, else 'fused' | 'pair'), `frozen` (on a Taylor-Hood
     space, mixed.newton_solve: the blocks of the Jacobian, in
     MixedMatrix.blocks() naming, that do not read the unknown and were
-    assembled once; () elsewhere).'''
+    assembled once; () elsewhere), `rhs_defect` (with nullspace=: the largest
+    |Z^T F| / |F| over the linear solves, taken before the projection; else
+    None).'''
     frozen = ()
+    rhs_defect = None
 
     def __init__(self, fused, method, route=None):
         self.iterations = 0

@@ -1932,6 +1932,27 @@ int flow_combine(int n, int m, const double* X, size_t ldx, int r,
                  const double* C, const double* base, double* out, size_t ldo,
                  void* stream);
 
+/* ---- deflation against a nullspace basis (flow_amd/fem/nullspace.py):
+ * fem.VectorSpaceBasis ------------------------------------------------------------
+ * x <- x - sum_{j < k} Z_j (Z_j^T x) in place, Z_j = Z + j*ldz the columns of a
+ * store with the conventions of flow_multi_dot (ldz >= n and even, Z and x
+ * 16-byte aligned), 1 <= k <= 8.  Two launches, no temporary, no host
+ * synchronisation, no atomics: the first leaves per-block partial sums of all k
+ * products around one load of x in work (k * FLOW_MULTI_DOT_BLOCKS doubles) with
+ * the lane order, block shape and grid of flow_multi_dot; in the second every
+ * block adds the partials of each column in ascending block order and then
+ * updates its entries, x[i] = fma(-c_j, Z_j[i], x[i]) for j ascending.  coef (k
+ * doubles of DEVICE memory, or NULL) receives c: coef[j] has the bits
+ * flow_multi_dot(n, k, Z, ldz, x, ...) leaves in out[j], and x the bits of that
+ * call followed by flow_combine(n, k, Z, ldz, 1, -c, x, out, ...).  Neither
+ * depends on k or on a column's place among the others beyond their order, and
+ * two calls give the same bits.  work, coef, Z and x must not overlap one
+ * another (refused, code 2; a refusal launches nothing).  n == 0 or k == 0:
+ * nothing is launched.  For a basis that is orthonormal this is the orthogonal
+ * projection onto its complement. */
+int flow_deflate(int n, int k, const double* Z, size_t ldz, double* x,
+                 double* work, double* coef, void* stream);
+
 /* ---- block kernels of the eigensolver (flow_amd/fem/eigen.py): fem.Eigenmodes --
  * X and Y are column-major stores with the conventions above: column j at
  * X + j*ldx, ld >= n and even, the store 16-byte aligned, the padding (entries
